@@ -34,11 +34,26 @@ settled: the first milliseconds of a run are 10-30 % slower.
 
 Other BASELINE configurations: --config C3 (8192-pt FFT, 50 % overlap fused into the read, batch
 4096, 512 bins) and --config C5 (65536-pt FFT, fp16 IQ, 512 bins, the per-GPU share of a sharded
-frame) emit the same JSON shape with their own workload string and roofline convention.  The default
-run (C2, one GPU) ALSO measures C3 (20 steps) and C5 (200 steps: a C5 step is one 0.29 ms frame), in the same process, after the
-headline, and reports them inside the one JSON line as `other_configs` (--no-other-configs skips them), followed by
-`other_configs.sink`: the PCIe-INCLUSIVE rates of the drop-in path (work() -> FIFO -> H2D -> kernels, and plain fosphor_process()
-calls of 1 Mi host samples), 2 s each, as MSamples/s and as a fraction of the Gen5 x16 link -- reported, never `value`.
+frame) emit the same JSON shape with their own workload string and roofline convention.
+
+A plain run does only what the headline needs: set-up (placement tuning included), pre-conditioning, warm-up, the timed
+steps, --dump-outputs if given, the JSON line.  Everything else it measures runs only with --full (each part can still be
+switched off there with its --no-* option):
+  - config.placement.untuned_value, the rate of the allocations as they came, before the placement tuning;
+  - the informational K2/K3 and isolated-K1 passes (roofline.k2_ms_per_launch / k3_ms_per_launch / isolated) and
+    config.strict_ordering_value, all after the timed region;
+  - roofline.traffic_twin (C2);
+  - cpu_baseline (C2, one GPU);
+  - other_configs (C2, one GPU): C3 (20 steps) and C5 (200 steps: a C5 step is one 0.29 ms frame), in the same process, after
+    the headline, followed by `other_configs.sink`: the PCIe-INCLUSIVE rates of the drop-in path (work() -> FIFO -> H2D ->
+    kernels, and plain fosphor_process() calls of 1 Mi host samples), 2 s each, as MSamples/s and as a fraction of the Gen5
+    x16 link -- reported, never `value`.
+
+--dump-outputs DIR: after the timed steps (before anything else runs on the instance) rank 0 writes what a caller of the timed
+path receives after its last step -- waterfall, histogram, spectrum (live and max-hold) and hitcount (the last batch's) -- as
+DIR/<name>.npy in float32 (hitcount: float64, exact).  The inputs depend only on the arguments (seeded on the device), so two
+builds can be compared array for array.  Where the arrays together exceed DUMP_BUDGET_BYTES (C3, C5) every array keeps the same
+fixed, seeded sample of its FFT-bin columns, in ascending order.
 
 roofline: the dominant kernel is K1 (fft_bin), bound by the HBM read of the IQ stream (8 B per
 sample, 4 B for fp16 IQ).  K1s of consecutive sub-launches run on alternating streams and overlap
@@ -61,6 +76,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 HBM_PEAK_GBS = 8000.0		# MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s
 ACHIEVABLE_GBS = 6290.0		# measured float4 copy on MI355X (guide), informational
+DUMP_BUDGET_BYTES = 60_000_000	# --dump-outputs: all arrays of one run together (npy headers stay well inside 64 MB)
 
 # name -> geometry.  spb = spectra per batch, bps = default batches per step, over = overlap_cc ratio
 CONFIGS = {
@@ -98,13 +114,39 @@ def parse():
                     help="batch mode, NOT for headline runs: instances (= sets of allocations) tried before the run; the fastest over 48 untimed steps is kept")
     ap.add_argument("--no-extra-passes", action="store_true", help="skip the informational K2/K3 and isolated-K1 passes")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default C2 run on one GPU: do not measure C3 / C5 afterwards (other_configs in the JSON line)")
+                    help="--full C2 run on one GPU: do not measure C3 / C5 afterwards (other_configs in the JSON line)")
     ap.add_argument("--other-steps", type=int, default=20, help="steps of the other_configs pass (C3; C5 runs ten times as many)")
     ap.add_argument("--sink-seconds", type=float, default=2.0, help="seconds of each PCIe-inclusive leg of other_configs.sink")
     ap.add_argument("--strict-ordering", action="store_true", help="keep stream ordering between calls (default: relaxed, "
                     "the input ring is never rewritten)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: untuned placement rate, K2/K3 and isolated-K1 passes, strict "
+                         "ordering rate, traffic twin, cpu_baseline and other_configs (see the docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path computed in its last step to DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(f, directory):
+    """--dump-outputs: waterfall, histogram, spectrum and hitcount of instance `f` as float32 / float64 .npy files.  If they
+    exceed DUMP_BUDGET_BYTES together, each keeps the same seeded sample of its FFT-bin columns (a function of N alone)."""
+    import numpy as np
+    arrays = {"waterfall": f.waterfall, "histogram": f.histogram, "spectrum": f.spectrum,
+              "hitcount": f.hitcount.astype(np.float64)}
+    n = f.n							# the FFT-bin axis: last for [rows][N], middle for spectrum [2][N][2]
+    per_column = sum(a.nbytes // n for a in arrays.values())
+    if per_column * n > DUMP_BUDGET_BYTES:
+        cols = np.sort(np.random.default_rng(20240607).choice(n, DUMP_BUDGET_BYTES // per_column, replace=False))
+        arrays = {k: (a[:, cols] if k == "spectrum" else a[..., cols]) for k, a in arrays.items()}
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), np.ascontiguousarray(a))
+    sys.stderr.write("bench.py: wrote %s to %s (%.1f MB)\n" % (", ".join(sorted(arrays)), directory,
+                                                               sum(a.nbytes for a in arrays.values()) / 1e6))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -287,7 +329,7 @@ def measure(name, args, ctx, steps, warmup, light=False, batches_per_step=0):
     hop = n_fft // over
     # unexpanded stream of one step: (F*spb - 1) * hop + n_fft samples (overlap_cc_impl.cc:64-79)
     step_stream = (F * spb - 1) * hop + n_fft if over > 1 else F * samples_per_batch
-    extra = not (args.no_extra_passes or light)
+    extra = args.full and not (args.no_extra_passes or light)
     precondition = args.precondition if not light else min(args.precondition, 0.25)
 
     # synthetic white complex Gaussian IQ, sigma 0.05 per component, resident in HBM;
@@ -362,8 +404,8 @@ def measure(name, args, ctx, steps, warmup, light=False, batches_per_step=0):
     # Placement (untimed, once): on MI355X the FFT kernel's memory traffic runs in one of two states -- 98 or 109 us per 512 MiB of IQ --
     # decided by the allocations involved (the IQ buffer against the instance's intermediate sets).  The library
     # re-allocates its sets until the traffic runs at 6 TB/s (fosphor_amd_tune_placement); if none does, the IQ ring is the unlucky side
-    # and is allocated again (same distribution, the generator's next numbers).  The rate of the allocations AS THEY CAME is measured
-    # first and reported beside the headline (placement.untuned_value).
+    # and is allocated again (the same samples, regenerated from the seed).  The rate of the allocations AS THEY CAME is measured
+    # first and reported beside the headline (placement.untuned_value, --full).
     placement = None
     if cfg["log2n"] == 10 and bins <= 256 and not args.no_placement_tuning and not light and F >= 16:	# (a launch long enough for its time to be bandwidth)
         sub_t = min(F, 64)
@@ -374,7 +416,8 @@ def measure(name, args, ctx, steps, warmup, light=False, batches_per_step=0):
             t_w = time.perf_counter()
             while time.perf_counter() - t_w < min(precondition, 0.3):
                 run_steps(4); sync()
-            placement["untuned_value"] = timed(max(8, min(steps, 40)))	# MSamples/s before any re-allocation (untimed extra pass)
+            if args.full:
+                placement["untuned_value"] = timed(max(8, min(steps, 40)))	# MSamples/s before any re-allocation (untimed extra pass)
             state["pos"] = 0
 
         def tune(inst):
@@ -389,6 +432,7 @@ def measure(name, args, ctx, steps, warmup, light=False, batches_per_step=0):
                     break
                 old = iq
                 iq = torch.empty_like(old)
+                g.manual_seed(7 + rank)		# a new allocation, the same samples: the inputs depend on the arguments alone
                 iq.normal_(0.0, 0.05, generator=g)
                 torch.cuda.synchronize()
                 del old
@@ -467,6 +511,9 @@ def measure(name, args, ctx, steps, warmup, light=False, batches_per_step=0):
         exchange_check = {"hit_counts_per_column": per_column,
                           "every_spectrum_counted_once_on_every_rank": all(int(e[1].item()) == 1 for e in every),
                           "replicated_state_bit_identical_across_ranks": all(int(e[0].item()) == int(every[0][0].item()) for e in every)}
+    # what the last timed step left, before any pass below changes the instance's state
+    if args.dump_outputs and rank == 0 and not light:
+        dump_outputs(f, args.dump_outputs)
 
     ms_all, n_all, iso, twin_ms = [0.0] * 3, [0] * 3, None, None
     if extra:
@@ -505,7 +552,7 @@ def measure(name, args, ctx, steps, warmup, light=False, batches_per_step=0):
 
     # the practical ceiling for K1 on this chip: its memory traffic (same loads, order, prefetch depth, stores)
     # without its arithmetic, measured live on the same buffers
-    if mode == "batch" and name == "C2" and not args.no_traffic_twin and not light:
+    if mode == "batch" and name == "C2" and args.full and not args.no_traffic_twin and not light:
         try:
             sub = min(F, 64)
             twin_ms = f.traffic_twin(iq[:sub * samples_per_batch], sub, spb, reps=50)
@@ -765,7 +812,7 @@ def main():
 
     out = measure(args.config, args, ctx, args.steps, args.warmup)
 
-    if world == 1 and args.config == "C2" and not args.no_other_configs and args.mode in ("auto", "batch") \
+    if world == 1 and args.config == "C2" and args.full and not args.no_other_configs and args.mode in ("auto", "batch") \
             and not args.bins and not args.batches_per_step:
         # The other single-GPU BASELINE configurations, in the same process, so that the driver's clock has seen them too
         # (each: its own instance and input ring, a short pre-conditioning, `--other-steps` timed steps of bench.py --config Cx)
@@ -800,7 +847,7 @@ def main():
             out["invalid"] = guard
             sys.stderr.write("bench.py: %s\n" % guard)
     if rank == 0 and out is not None:
-        if world == 1 and not args.no_cpu_baseline and args.config == "C2":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.config == "C2":
             out["cpu_baseline"] = cpu_baseline((args.bins or CONFIGS["C2"]["bins"]), args.cpu_seconds)
         # RCCL prints a version banner through C stdio, which would otherwise be flushed after this line
         import ctypes

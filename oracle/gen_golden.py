@@ -44,6 +44,17 @@ def written_rows(wf, pos0, batch):
     return idx, wf[idx]
 
 
+def save_fixture(name, arrays):
+    """<name>.npz, or -- if that would exceed gc.MAX_FIXTURE_BYTES -- call 0 there and call k in <name>.c<k>.npz
+    (gc.load_fixture merges them)."""
+    path = os.path.join(OUT, name + ".npz")
+    np.savez_compressed(path, **arrays)
+    if os.path.getsize(path) > gc.MAX_FIXTURE_BYTES:
+        for c in sorted({k.split("_")[0] for k in arrays}):
+            part = {k: v for k, v in arrays.items() if k.split("_")[0] == c}
+            np.savez_compressed(path if c == "c0" else os.path.join(OUT, "%s.%s.npz" % (name, c)), **part)
+
+
 def run_case(name, spec, portable=True):
     r = RefKernels(portable=portable)
     if "power_range" in spec:
@@ -116,7 +127,7 @@ def main(argv):
                 arrays[pre + "wf_row_sample"] = c["wf_rows"][::97]
                 if hc is not None:
                     arrays[pre + "hc"] = hc
-        np.savez_compressed(os.path.join(OUT, name + ".npz"), **arrays)
+        save_fixture(name, arrays)
         meta[name] = m
         print("%-22s %d call(s)  %.1fs" % (name, len(res), time.time() - t0), flush=True)
 
@@ -137,6 +148,15 @@ def main(argv):
         y = RefKernels.fft(x, gc.hann512(), n=512)
         np.savez_compressed(os.path.join(OUT, "fft512.npz"), x=x, win=gc.hann512(), fft=y)
         meta["fft512"] = {"sha_fft": sha(y)}
+
+    if not argv or "crosscheck" in argv:
+        # digests of what the reference kernels make of tests/test_oracle_golden.py's cross-check input
+        r = RefKernels(portable=True)
+        calls = []
+        for x in gc.crosscheck_calls():
+            assert r.process(x) == 0
+            calls.append({f: sha(getattr(r, f)) for f in gc.CROSSCHECK_FIELDS})
+        meta["ref_crosscheck"] = calls
 
     if not argv or "cmap" in argv:
         # palettes straight from the reference's gl_cmap_gen.c (oracle/_ref/libcmap_ref.so)
@@ -191,4 +211,4 @@ def main(argv):
 
 
 if __name__ == "__main__":
-    main([a for a in sys.argv[1:] if a in gc.CASES or a in ("fft512", "cmap", "axis", "geom", "glibc")])
+    main([a for a in sys.argv[1:] if a in gc.CASES or a in ("fft512", "crosscheck", "cmap", "axis", "geom", "glibc")])

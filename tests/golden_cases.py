@@ -8,11 +8,25 @@ Every case is reference geometry: N=1024, 128 bins, 1024 waterfall rows.
 A case = optional setup + a list of process() calls; inputs are deterministic functions of
 numpy default_rng seeds, and are ALSO stored in the small fixtures.
 """
+import glob
+import os
+
 import numpy as np
 
 from oracle_lib import add_tone, gaussian_iq
 
 N = 1024
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+MAX_FIXTURE_BYTES = 1 << 20		# a case whose file would be larger is stored one call per file
+
+
+def load_fixture(name):
+    """The stored arrays of case `name`: tests/golden/<name>.npz, merged with <name>.c<k>.npz where the case is stored one
+    call per file."""
+    z = dict(np.load(os.path.join(GOLD, name + ".npz")))
+    for p in sorted(glob.glob(os.path.join(GOLD, name + ".c*.npz"))):
+        z.update(np.load(p))
+    return z
 
 
 def blackman_harris(n=N):
@@ -97,6 +111,16 @@ FFT512_SEED = 512
 
 def fft512_input():
     return gaussian_iq(4 * 512, FFT512_SEED, sigma=1.0)
+
+
+# Restatement vs reference kernels on an input no other fixture uses: two calls, 16 and 32 spectra
+CROSSCHECK_FIELDS = ("fft_out", "waterfall", "histogram", "spectrum")
+
+
+def crosscheck_calls():
+    rng = np.random.default_rng(12345)
+    x = (rng.standard_normal((48 * N, 2)) * 0.3).astype(np.float32)
+    return [x[:16 * N], x[16 * N:]]
 
 
 # Frequency-axis cases for the label formatter (axis.c:63-162): (center Hz, span Hz, n_div)

@@ -201,7 +201,7 @@ def test_bin_exact(amd, torch_cuda, oracle_built, n_bins, power):
 @pytest.mark.parametrize("name", [n for n in gc.CASES if gc.CASES[n]["store"] == "full"])
 def test_process_matches_reference_fixture(amd, torch_cuda, name):
     spec = gc.CASES[name]
-    z = np.load(os.path.join(GOLD, name + ".npz"))
+    z = gc.load_fixture(name)
     f = amd.Fosphor()
     if "power_range" in spec:
         f.set_power_range(*spec["power_range"])

@@ -40,7 +40,7 @@ def test_restatement_matches_reference_fixture(name, oracle_built):
     spec = gc.CASES[name]
     if name == "c8_b8192" and os.environ.get("FOSPHOR_SKIP_SLOW"):
         pytest.skip("slow")
-    z = np.load(os.path.join(GOLD, name + ".npz"))
+    z = gc.load_fixture(name)
     o = make_oracle(spec)
     calls = spec["calls"]()
     for k, x in enumerate(calls):
@@ -149,17 +149,20 @@ def test_restatement_threads_agree(oracle_built):
         assert digest(getattr(a, f)) == digest(getattr(b, f))
 
 
-@pytest.mark.skipif(not have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 def test_reference_kernels_live_crosscheck(oracle_built):
-    """Where the compiled reference kernels exist, run them again on a fresh random input
-    (not a stored fixture) against the restatement: bit-exact."""
-    rng = np.random.default_rng(12345)
-    x = (rng.standard_normal((48 * 1024, 2)) * 0.3).astype(np.float32)
-    r, o = RefKernels(portable=True), Oracle()
-    for blk in (x[:16 * 1024], x[16 * 1024:]):
-        assert r.process(blk) == 0 and o.process(blk) == 0
-        for f in ("fft_out", "waterfall", "histogram", "spectrum"):
-            assert np.array_equal(bits(getattr(r, f)), bits(getattr(o, f))), f
+    """The restatement on an input no other fixture uses, bit-exact against the reference kernels: against the digests
+    they produced (golden_meta.json "ref_crosscheck", oracle/gen_golden.py) and, where the compiled reference kernels
+    exist, against a live run of them as well."""
+    r = RefKernels(portable=True) if have_ref() else None
+    o = Oracle()
+    for k, blk in enumerate(gc.crosscheck_calls()):
+        assert o.process(blk) == 0
+        for f in gc.CROSSCHECK_FIELDS:
+            assert sha(getattr(o, f)) == META["ref_crosscheck"][k][f], f
+        if r is not None:
+            assert r.process(blk) == 0
+            for f in gc.CROSSCHECK_FIELDS:
+                assert np.array_equal(bits(getattr(r, f)), bits(getattr(o, f))), f
 
 
 GLIBC_CELL_BUDGET_PER_MI = 8

@@ -13,7 +13,7 @@ for v in "$@"; do
              "SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT" \
              "SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_INST_LEVEL_LDS"; do
     i=$((i+1))
-    timeout 200 rocprofv3 --pmc $grp --kernel-trace -f csv -d $out/k$v/p$i -o p -- python3 bench.py --config C3 --steps 3 --warmup 1 --precondition 0.02 --no-cpu-baseline --no-other-configs > /dev/null 2> $out/k${v}_p$i.log
+    timeout 200 rocprofv3 --pmc $grp --kernel-trace -f csv -d $out/k$v/p$i -o p -- python3 bench.py --full --config C3 --steps 3 --warmup 1 --precondition 0.02 --no-cpu-baseline --no-other-configs > /dev/null 2> $out/k${v}_p$i.log
   done
   python3 tools/pmc_summary.py $(find $out/k$v -name "*counter_collection.csv") | grep -i "k1w\|kernel |" | cut -c1-700 > $out/k$v.md
   cat $out/k$v.md

@@ -1,15 +1,15 @@
 #!/bin/bash
 # Run ON the GPU box (gpurun -- 'bash tools/r04_ceiling_run.sh'): the ceiling probes of DESIGN_HISTORY.md 4a, raw bench lines kept.
-# Every line is `bench.py --steps 40 --warmup 8 --no-cpu-baseline` on C2 (256 bins, batch mode), two repetitions each.
+# Every line is `bench.py --full --steps 40 --warmup 8 --no-cpu-baseline` on C2 (256 bins, batch mode), two repetitions each.
 OUT=gpurun_out/r04_ceiling
 mkdir -p $OUT
 run() {		# label, lib ('' = product), env...
 	local label=$1 lib=$2; shift 2
 	for rep in 1 2; do
 		if [ -n "$lib" ]; then
-			env FOSPHOR_AMD_LIB=$PWD/build/ab/lib_$lib.so "$@" python3 bench.py --steps 40 --warmup 8 --no-cpu-baseline > $OUT/${label}_$rep.json 2> $OUT/${label}_$rep.err
+			env FOSPHOR_AMD_LIB=$PWD/build/ab/lib_$lib.so "$@" python3 bench.py --full --steps 40 --warmup 8 --no-cpu-baseline > $OUT/${label}_$rep.json 2> $OUT/${label}_$rep.err
 		else
-			env "$@" python3 bench.py --steps 40 --warmup 8 --no-cpu-baseline > $OUT/${label}_$rep.json 2> $OUT/${label}_$rep.err
+			env "$@" python3 bench.py --full --steps 40 --warmup 8 --no-cpu-baseline > $OUT/${label}_$rep.json 2> $OUT/${label}_$rep.err
 		fi
 		python3 tools/bline.py "$label" $OUT/${label}_$rep.json
 	done
