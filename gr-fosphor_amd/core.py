@@ -18,6 +18,9 @@ MULT_BATCH = 16			# private.h:24
 MAX_BATCH = 1024		# private.h:25
 
 
+IQ_FORMATS = {"fp32": 0, "fp16": 1, "sc16": 2}	# FOSPHOR_AMD_IQ_* (include/fosphor_amd.h)
+
+
 def _ptr(x):
     """Device pointer of a torch tensor / anything with data_ptr(), or a raw integer."""
     if hasattr(x, "data_ptr"):
@@ -29,11 +32,25 @@ class Fosphor:
     """One fosphor instance (struct fosphor).  Reference geometry by default."""
 
     def __init__(self, n_bins=128, wf_rows=1024, fft_len_log=FFT_LEN_LOG, t0r=0.0, t0d=0.0, alpha=0.0,
-                 device=-1, max_spectra=1024, max_batches=0, stream=None, iq_fp16=False):
+                 device=-1, max_spectra=1024, max_batches=0, stream=None, iq_fp16=False, iq_format=None):
+        """iq_format: "fp32" (default), "fp16" (fft_len_log 16 only; iq_fp16=True says the same) or "sc16" (interleaved
+        int16, value i * 2**-15) -- or the FOSPHOR_AMD_IQ_* number; the library refuses formats it does not know."""
         self.L = _lib.load()
+        if iq_format is None:
+            fmt = 1 if iq_fp16 else 0
+        elif isinstance(iq_format, str):
+            if iq_format not in IQ_FORMATS:
+                raise ValueError("iq_format must be one of %s" % ", ".join(IQ_FORMATS))
+            fmt = IQ_FORMATS[iq_format]
+        else:
+            fmt = int(iq_format)
+        if iq_fp16 and fmt != 1:
+            raise ValueError("iq_fp16=True contradicts iq_format=%r" % (iq_format,))
         cfg = _lib.Config(fft_len_log, n_bins, wf_rows, t0r, t0d, alpha, device, max_spectra, max_batches,
-                          C.c_void_p(stream) if stream else None, 1 if iq_fp16 else 0)
-        self.iq_fp16 = bool(iq_fp16)
+                          C.c_void_p(stream) if stream else None, fmt)
+        self.iq_format = fmt
+        self.iq_fp16 = fmt == 1
+        self.iq_sc16 = fmt == 2
         self.h = self.L.fosphor_amd_init(C.byref(cfg))
         if not self.h:
             raise RuntimeError("fosphor_amd_init failed (see stderr); no CPU fallback exists")
@@ -53,8 +70,17 @@ class Fosphor:
 
     # ---- reference API ---------------------------------------------------
     def process(self, samples):
-        """fosphor_process: host interleaved fp32 (re, im); returns 0 / -EINVAL / -EIO."""
-        x = np.ascontiguousarray(samples, dtype=np.float16 if self.iq_fp16 else np.float32).reshape(-1)
+        """fosphor_process: host interleaved (re, im) in the instance's format -- fp32 (fp16); on sc16 instances an int16 numpy
+        array only, flat of even length or (n, 2) (TypeError otherwise: floats are never converted silently).
+        Returns 0 / -EINVAL / -EIO."""
+        if self.iq_sc16:
+            if not isinstance(samples, np.ndarray) or samples.dtype != np.int16:
+                raise TypeError("an sc16 instance takes an int16 numpy array, got %s" % getattr(samples, "dtype", type(samples).__name__))
+            if not (samples.ndim == 1 and samples.size % 2 == 0) and not (samples.ndim == 2 and samples.shape[1] == 2):
+                raise TypeError("sc16 samples must be flat (re, im, ...) of even length or of shape (n, 2), got %s" % (samples.shape,))
+            x = np.ascontiguousarray(samples).reshape(-1)
+        else:
+            x = np.ascontiguousarray(samples, dtype=np.float16 if self.iq_fp16 else np.float32).reshape(-1)
         return self.L.fosphor_process(self.h, x.ctypes.data, x.size // 2)
 
     def draw(self, render=None):
@@ -78,20 +104,26 @@ class Fosphor:
         self.L.fosphor_set_frequency_range(self.h, float(center), float(span))
 
     # ---- device-resident data path -----------------------------------------
+    def _dev(self, d_samples):
+        """Device pointer of the samples; on sc16 instances a torch tensor must be int16 (ValueError otherwise)."""
+        if self.iq_sc16 and hasattr(d_samples, "data_ptr") and hasattr(d_samples, "dtype") and str(d_samples.dtype) != "torch.int16":
+            raise ValueError("an sc16 instance reads int16 samples, got a %s tensor" % d_samples.dtype)
+        return _ptr(d_samples)
+
     def process_device(self, d_samples, n_batches, batch):
-        return self.L.fosphor_amd_process_device(self.h, _ptr(d_samples), int(n_batches), int(batch))
+        return self.L.fosphor_amd_process_device(self.h, self._dev(d_samples), int(n_batches), int(batch))
 
     def process_device_overlap(self, d_samples, n_batches, batch, overlap):
         """overlap_cc(wlen=N, overlap) fused into the read (unexpanded stream in HBM)."""
-        return self.L.fosphor_amd_process_device_overlap(self.h, _ptr(d_samples), int(n_batches), int(batch), int(overlap))
+        return self.L.fosphor_amd_process_device_overlap(self.h, self._dev(d_samples), int(n_batches), int(batch), int(overlap))
 
     def finish(self):
         return self.L.fosphor_amd_finish(self.h)
 
     def accumulate_device(self, d_samples, n_local, t_offset, total_batch, overlap=1):
         if overlap > 1:
-            return self.L.fosphor_amd_accumulate_device_overlap(self.h, _ptr(d_samples), n_local, t_offset, total_batch, overlap)
-        return self.L.fosphor_amd_accumulate_device(self.h, _ptr(d_samples), n_local, t_offset, total_batch)
+            return self.L.fosphor_amd_accumulate_device_overlap(self.h, self._dev(d_samples), n_local, t_offset, total_batch, overlap)
+        return self.L.fosphor_amd_accumulate_device(self.h, self._dev(d_samples), n_local, t_offset, total_batch)
 
     def merge(self, total_batch):
         return self.L.fosphor_amd_merge(self.h, total_batch)
@@ -183,7 +215,7 @@ class Fosphor:
 
     # ---- kernel-level hooks -------------------------------------------------
     def fft_device(self, d_in, d_out, n_spectra):
-        return self.L.fosphor_amd_fft(self.h, _ptr(d_in), _ptr(d_out), n_spectra)
+        return self.L.fosphor_amd_fft(self.h, self._dev(d_in), _ptr(d_out), n_spectra)
 
     def bin_device(self, d_fft, d_bin, d_pwr, n):
         return self.L.fosphor_amd_bin(self.h, _ptr(d_fft), _ptr(d_bin), _ptr(d_pwr), n)

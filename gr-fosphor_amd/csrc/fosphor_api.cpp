@@ -62,7 +62,8 @@ struct fosphor
 	int tw_len, tw_off[8];
 	float t0r, t0d, alpha;
 	int max_spectra, max_batches;
-	int iq_half;				/* device IQ is fp16 pairs (N = 65536 only) */
+	int iq_format;				/* FOSPHOR_AMD_IQ_*: fp32, fp16 (N = 65536 only) or sc16 pairs */
+	size_t sample_bytes;			/* bytes per sample of that format: 8, 4, 4 */
 	size_t stage_samples;			/* capacity of one host staging slot, samples */
 
 	/* reference-visible settings (private.h:44-54) */
@@ -438,12 +439,13 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 		fprintf(stderr, "[!] fosphor_amd: fft_len_log=%d not supported (10, 13 or 16)\n", self->log2n);
 		goto error;
 	}
-	self->iq_half = (cfg && cfg->iq_format == FOSPHOR_AMD_IQ_FP16);
-	if (cfg && cfg->iq_format != FOSPHOR_AMD_IQ_FP32 && cfg->iq_format != FOSPHOR_AMD_IQ_FP16) {
-		fprintf(stderr, "[!] fosphor_amd: iq_format=%d unknown\n", cfg->iq_format);
+	self->iq_format = cfg ? cfg->iq_format : FOSPHOR_AMD_IQ_FP32;
+	if (self->iq_format != FOSPHOR_AMD_IQ_FP32 && self->iq_format != FOSPHOR_AMD_IQ_FP16 && self->iq_format != FOSPHOR_AMD_IQ_SC16) {
+		fprintf(stderr, "[!] fosphor_amd: iq_format=%d unknown\n", self->iq_format);
 		goto error;
 	}
-	if (self->iq_half && self->log2n != 16) {
+	self->sample_bytes = self->iq_format == FOSPHOR_AMD_IQ_FP32 ? sizeof(float2) : 4;
+	if (self->iq_format == FOSPHOR_AMD_IQ_FP16 && self->log2n != 16) {
 		fprintf(stderr, "[!] fosphor_amd: fp16 IQ is only implemented for fft_len_log=16\n");
 		goto error;
 	}
@@ -901,7 +903,7 @@ static void fill_k1(struct fosphor *self, K1Params *k1, const void *d_iq, int to
 		k1->dbg_k1h = dbg;
 	}
 #endif
-	k1->iq_half = self->iq_half;
+	k1->iq_format = self->iq_format;
 	k1->n_cus = self->n_cus;
 	{
 		const int sc = self->share_cus;
@@ -914,6 +916,8 @@ static void fill_k1(struct fosphor *self, K1Params *k1, const void *d_iq, int to
 	}
 	if (k1->variant == 1 && (k1->hop & 1))
 		k1->variant = 2;		/* 16-byte IQ loads of variant 1 need an even hop */
+	if (k1->variant == 1 && self->iq_format == FOSPHOR_AMD_IQ_SC16 && ((uintptr_t)d_iq & 7))
+		k1->variant = 2;		/* ... and its 8-byte sc16 loads an 8-byte aligned start (variant 2 loads one 4-byte sample per lane) */
 }
 
 /* A batch longer than 1024 spectra is counted as ONE chunk where that still gives the chip enough work-groups
@@ -1161,7 +1165,7 @@ static int wf_leave(struct fosphor *self, hipStream_t ks)
 static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch, int hop = 0, int device_call = 0)
 {
 	const int total = n_batches * batch;
-	const size_t sample_bytes = self->iq_half ? 4 : sizeof(float2);
+	const size_t sample_bytes = self->sample_bytes;
 	const int hop_samples = hop ? hop : self->n;
 	hipStream_t st2 = self->overlap ? self->stream2 : self->stream;
 	/* third stream: only the 16-bit count path has a second hit-count set */
@@ -1297,9 +1301,15 @@ error:
 	return -EIO;
 }
 
+/* sc16 samples are dwords: a device pointer to them must be 4-byte aligned (fp32 / fp16 callers are not checked here) */
+static int misaligned(const struct fosphor *self, const void *d_samples)
+{
+	return self->iq_format == FOSPHOR_AMD_IQ_SC16 && ((uintptr_t)d_samples & 3);
+}
+
 extern "C" int fosphor_amd_process_device(struct fosphor *self, const void *d_samples, int n_batches, int batch)
 {
-	if (!self || !d_samples || n_batches < 1 || batch < 16 || (batch & 15))
+	if (!self || !d_samples || n_batches < 1 || batch < 16 || (batch & 15) || misaligned(self, d_samples))
 		return -EINVAL;
 	if ((long long)n_batches * batch > self->max_spectra || n_batches > self->max_batches)
 		return -EINVAL;
@@ -1313,7 +1323,7 @@ extern "C" int fosphor_amd_process_device(struct fosphor *self, const void *d_sa
 extern "C" int fosphor_amd_process_device_overlap(struct fosphor *self, const void *d_samples,
                                                   int n_batches, int batch, int overlap)
 {
-	if (!self || !d_samples || n_batches < 1 || batch < 16 || (batch & 15))
+	if (!self || !d_samples || n_batches < 1 || batch < 16 || (batch & 15) || misaligned(self, d_samples))
 		return -EINVAL;
 	if (overlap < 1 || overlap > self->n || (self->n % overlap))
 		return -EINVAL;
@@ -1325,7 +1335,7 @@ extern "C" int fosphor_amd_process_device_overlap(struct fosphor *self, const vo
 extern "C" int fosphor_process(struct fosphor *self, void *samples, int len)
 {
 	int k;
-	const size_t sample_bytes = self->iq_half ? 4 : sizeof(float2);
+	const size_t sample_bytes = self->sample_bytes;
 
 	/* cl.c:882-886 */
 	if (len <= 0 || (len & ((16 * self->n) - 1)))
@@ -1380,7 +1390,7 @@ error:
 extern "C" int fosphor_amd_upload_pinned(struct fosphor *self, const void *samples, int len)
 {
 	int k;
-	const size_t sample_bytes = self->iq_half ? 4 : sizeof(float2);
+	const size_t sample_bytes = self->sample_bytes;
 
 	/* cl.c:882-886 for one batch; beyond it a whole number of 1024-spectrum batches in one call (applied one after the other like so
 	 * many calls, one upload and one set of launches: what the host spends per call -- ~250 us -- is then spent per 64 MiB, not per 8) */
@@ -1579,7 +1589,7 @@ extern "C" int fosphor_amd_fft(struct fosphor *self, const void *d_in, void *d_o
 {
 	K1Params k1;
 	int saved_state;
-	if (!self || !d_in || !d_out || n_spectra < 4 || (n_spectra & 3) || n_spectra > self->max_spectra)
+	if (!self || !d_in || !d_out || n_spectra < 4 || (n_spectra & 3) || n_spectra > self->max_spectra || misaligned(self, d_in))
 		return -EINVAL;
 	if (sync_all(self))				/* scratch sets may still be read by a queued K2 */
 		return -EIO;
@@ -1629,7 +1639,7 @@ static int accumulate(struct fosphor *self, const void *d_samples, int n_local, 
 	hipStream_t st2;
 
 	if (!self || !d_samples || n_local < 16 || (n_local & 15) || (t_offset & 15) ||
-	    t_offset < 0 || t_offset + n_local > total_batch || n_local > self->max_spectra)
+	    t_offset < 0 || t_offset + n_local > total_batch || n_local > self->max_spectra || misaligned(self, d_samples))
 		return -EINVAL;
 	const int did_prep = self->win_dirty || self->thr_dirty || self->state == ST_BOOTING;
 	if (prepare(self))
@@ -1649,7 +1659,7 @@ static int accumulate(struct fosphor *self, const void *d_samples, int n_local, 
 		int sub_c = (int)(self->sub_samples / per_chunk);
 		if (sub_c < 1) sub_c = 1;
 		if (chunked && cpb > sub_c) {
-			const size_t sample_bytes = self->iq_half ? 4 : sizeof(float2);
+			const size_t sample_bytes = self->sample_bytes;
 			/* K2 counts G consecutive 1024-spectrum chunks per work-group (16-bit counters hold 65535 spectra): 1 / G of the
 			 * slab traffic, as long as enough work-groups are left to keep the bin-index reads in flight */
 			int G = 1;
@@ -2065,7 +2075,8 @@ extern "C" int fosphor_amd_traffic_twin(struct fosphor *self, const void *d_samp
 	hipEvent_t e0 = nullptr, e1 = nullptr;
 	const int total = n_batches * batch;
 	float ms = 0.0f;
-	if (!self || !d_samples || !ms_out || reps < 1 || total < 16 || total > self->max_spectra || self->log2n != 10 || self->bins16)
+	if (!self || !d_samples || !ms_out || reps < 1 || total < 16 || total > self->max_spectra || self->log2n != 10 || self->bins16 ||
+	    self->iq_format != FOSPHOR_AMD_IQ_FP32)
 		return -EINVAL;
 	if (fosphor_amd_finish(self) < 0 || prepare(self))
 		return -EIO;
@@ -2105,7 +2116,8 @@ extern "C" int fosphor_amd_tune_placement(struct fosphor *self, const void *d_sa
                                           float *us_before, float *us_after)
 {
 	const int total = n_batches * batch;
-	if (!self || !d_samples || total < 16 || total > self->max_spectra || self->log2n != 10 || self->bins16 || max_tries < 1)
+	if (!self || !d_samples || total < 16 || total > self->max_spectra || self->log2n != 10 || self->bins16 || max_tries < 1 ||
+	    self->iq_format != FOSPHOR_AMD_IQ_FP32)
 		return -EINVAL;
 	if (fosphor_amd_finish(self) < 0)
 		return -EIO;

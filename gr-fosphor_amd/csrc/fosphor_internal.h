@@ -43,7 +43,7 @@ struct K1Params {
 	float2       *fft_out;		/* test hook, or nullptr */
 	long long    *dbg;		/* K1_TIMING builds: [waves][8] cycle accumulators, or nullptr */
 	float2       *scratch;		/* variant 4: [64 clusters][N] intermediate spectrum between the two stages */
-	int   iq_half;			/* variant 4: the IQ stream is fp16 (re, im) pairs, 4 B per sample */
+	int   iq_format;		/* FOSPHOR_AMD_IQ_*: 0 fp32 pairs (8 B per sample), 1 fp16 pairs (variant 4 only), 2 int16 pairs (4 B) */
 	uint32_t *sync;			/* variant 4: cluster counters [64][64] */
 	uint32_t *sync_err;		/* ... its error word (host-mapped): set when a bounded cluster wait times out */
 	int   dbg_k1h;			/* measurement only (FOSPHOR_AMD_DBG_K1H): 1 no cluster waits, 2 no IQ loads, 4 no row / bin stores,

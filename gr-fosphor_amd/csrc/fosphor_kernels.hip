@@ -522,6 +522,22 @@ static __device__ __forceinline__ float max_f32(float a, float b)
 #endif
 
 typedef float v4f __attribute__((ext_vector_type(4)));
+typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+
+/* IQ formats (K1Params::iq_format, FOSPHOR_AMD_IQ_*).  The FFT kernels' text sits in k1*.inc and is compiled twice: as the fp32 / fp16
+ * entry points (k1_fft_bin, ..., k1h_fused: K1_SC16 = 0, the code of those kernels is exactly what it was before sc16 existed) and as the
+ * sc16 ones (k1_fft_bin_sc16, ...: K1_SC16 = 1, K1_IQ the IQ as uint32_t, one dword per sample).  An sc16 sample (re in the low, im in
+ * the high half) is widened where it is loaded: (float)(short) v * 2^-15 is exact (int16 -> float is exact, and a power-of-two scale of
+ * a value >= 2^-15 in magnitude stays normal), so everything behind the load computes on the very floats an fp32 instance fed those
+ * values would -- no conversion pass, no fp32 copy in memory. */
+constexpr int kIqFp32 = 0, kIqFp16 = 1, kIqSc16 = 2;
+static __device__ __forceinline__ v2f widen_sc16(uint32_t v)
+{
+	return v2f{ (float)(short)(v & 0xffffu) * 0x1p-15f, (float)(short)(v >> 16) * 0x1p-15f };
+}
+/* one sample, non-temporal (read-once) */
+static __device__ __forceinline__ v2f ld_sample(const float2 *src) { return __builtin_nontemporal_load(reinterpret_cast<const v2f *>(src)); }
+static __device__ __forceinline__ v2f ld_sample(const uint32_t *src) { return widen_sc16(__builtin_nontemporal_load(src)); }
 
 /* 8 x (64 lanes x 16 B) = 1 KiB per instruction, read-once: non-temporal.  `src` points at this
  * lane's pair: elements (2L, 2L+1) + 128k land in x[2k], x[2k+1].  (Ablation on MI355X: with
@@ -535,337 +551,25 @@ static __device__ __forceinline__ void load_iq16(v2f (&x)[16], const float2 *__r
 		x[2 * k + 1] = v2f{ q.z, q.w };
 	}
 }
+/* sc16: the same lane-to-sample map at half the bytes, 8 x (64 lanes x 8 B): `src` 8-byte aligned (even hop, 8-byte aligned base) */
+static __device__ __forceinline__ void load_iq16(v2f (&x)[16], const uint32_t *__restrict__ src)
+{
+#pragma unroll
+	for (int k = 0; k < 8; k++) {
+		const u2v q = __builtin_nontemporal_load(reinterpret_cast<const u2v *>(src + 128 * k));
+		x[2 * k]     = widen_sc16(q.x);
+		x[2 * k + 1] = widen_sc16(q.y);
+	}
+}
 #define K1_LANE_SRC(lane) (2 * (lane))
 
-template <bool WRITE_FFT, bool NB256 = false>	/* NB256: 256 bins -- the saturating conversion of the bin byte IS the clamp at n_bins - 1 */
-__global__ __launch_bounds__(256, K1_WAVES_PER_SIMD)
-void k1_fft_bin(const K1Params p)
-{
-	__shared__ v2f   lds[4][kN];			/* 8 KiB exchange slab per wave */
-	__shared__ v2f   tw4_tab[512];			/* pass-4 twiddles, shared by the block */
-	__shared__ float win_tab[kN];			/* window, shared by the block */
-	/* exact-bin thresholds (n_bins <= 256 in this kernel): the rare path that consults them would otherwise wait for its two table
-	 * loads BEHIND the next spectrum's IQ, already requested from HBM -- loads return in order */
-	__shared__ double thr_tab[264];
-#if K1_DBG_EPI & 32
-	__shared__ uint32_t dbg_cnt[256 * 32];		/* probe: the counter image of a 64-column slab */
-#endif
-
-	const int lane   = threadIdx.x & 63;
-	const int wv     = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);	/* tile, spectrum index, row predicate: SGPRs */
-	const int ntiles = p.total / p.tile;
-	const int stride = gridDim.x * 4;		/* waves in the grid */
-#if K1_TIMING
-	const long long t_wave_start = wall_clock64();	/* 100 MHz, common to all CUs */
-#endif
-	int tile = blockIdx.x * 4 + wv;
-	const v2f *twg = reinterpret_cast<const v2f *>(p.tw);
-
-	for (int i = threadIdx.x; i < kN; i += 256)
-		win_tab[i] = p.win[i];
-	for (int i = threadIdx.x; i < 512; i += 256)
-		tw4_tab[i] = twg[kTw4Off + i];
-	for (int i = threadIdx.x; i <= p.n_bins && i < 264; i += 256)
-		thr_tab[i] = p.thr[i];
-	__syncthreads();				/* the only block-wide barrier */
-
-	if (tile >= ntiles)
-		return;					/* whole wave leaves */
-
-	v2f *buf = lds[wv];
-
-	/* ---- per-lane constants, loaded once per wave -------------------------- */
-	v2f tw2[7];
-	v2f tw3[7];
-#pragma unroll
-	for (int n = 0; n < 7; n++) {
-		tw2[n] = twg[kTw2Off + (lane & 7) * 7 + n];	/* k = i & 7  (both virtual items) */
-		tw3[n] = twg[kTw3Off + lane * 7 + n];		/* k = i & 63 = lane               */
-	}
-	const v2f s12 = { F_SQRT_1_2, F_SQRT_1_2 };
-
-	/* ---- swizzled LDS addressing -------------------------------------------
-	 * element e lives at phys(e) = e ^ ((e >> 3) & 15): every access below is
-	 * bank-conflict free for ds_read_b64 (32-lane groups, 64 banks) and
-	 * ds_write_b64 (16-lane groups, 32 banks).  The closed forms per access
-	 * pattern are derived in DESIGN_HISTORY.md ("LDS exchange").                    */
-	const int rd_even = lane ^ ((lane >> 3) & 7);		/* e = lane + 64m, m even */
-	const int rd_odd  = rd_even ^ 8;			/*                 m odd  */
-	const int st1     = (8 * lane) ^ (lane & 15);		/* pass 1: e = 8i + jj, i = lane (+64v)   */
-	const int st1a    = (16 * lane) ^ ((2 * lane) & 15);		/* pass 1, i = 2 lane     */
-	const int st1b    = (16 * lane + 8) ^ ((2 * lane + 1) & 15);	/* pass 1, i = 2 lane + 1 */
-	(void)st1; (void)st1a; (void)st1b;
-	const int st2     = ((64 * (lane >> 3)) + (lane & 7)) ^ (lane & 8);	/* pass 2: e = 64(i>>3)+(i&7)+8jj */
-
-	const BinConst bk = { p.binA, p.binC, p.amb, p.kappa, p.n_bins, p.thr };
-	const float vmax_init = -1000.0f / F_HALF_LOG10_2;	/* display.cl:91, in log2 units */
-
-	v2f xn[16];
-	load_iq16(xn, p.iq + (size_t)tile * p.tile * p.hop + K1_LANE_SRC(lane));
-#if K1_TIMING
-	long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-	long long tprev = __builtin_readcyclecounter();
-#endif
-
-	/* persistent wave: tiles tile, tile + stride, ... (per-lane constants stay in registers) */
-	for (; tile < ntiles; tile += stride) {
-	const int t0 = tile * p.tile;
-
-	/* live partial and running max of this tile, in log2(|X|^2) units */
-	float live[16], vmax[16];
-#pragma unroll
-	for (int m = 0; m < 16; m++) {
-		live[m] = 0.0f;
-		vmax[m] = vmax_init;
-	}
-
-	/* The bin dwords of a quad of spectra are stored one window multiply LATER than they are complete: the wait for the prefetched IQ at
-	 * the top of a spectrum is an s_waitcnt vmcnt(0) (the number of stores behind the loads varies, so the compiler cannot count them out),
-	 * and stores issued behind those loads -- at the end of the previous spectrum -- made every fourth spectrum wait for its own stores'
-	 * acknowledgements.  Stores issued AHEAD of the next prefetch are older than the loads the wave waits for next. */
-	uint32_t pack[16];
-#pragma unroll
-	for (int m = 0; m < 16; m++)
-		pack[m] = 0;
-	int pend_row = -1;			/* row of p.bins the bytes in pack belong to, or -1 (uniform) */
-	auto flush_pack = [&]() {
-		uint32_t *dst = p.bins + (size_t)pend_row * kN + lane;
-		if (K1_DBG_EPI & 16) {
-			uint32_t any = 0;			/* keep the values alive without the stores */
-#pragma unroll
-			for (int m = 0; m < 16; m++)
-				any |= pack[m];
-			if (any == 0xdeadbeefu)
-				dst[0] = any;
-		} else {
-#pragma unroll
-			for (int m = 0; m < 16; m++)
-				dst[64 * m] = pack[m];
-		}
-#pragma unroll
-		for (int m = 0; m < 16; m++)
-			pack[m] = 0;
-		pend_row = -1;
-	};
-
-	for (int g0 = 0; g0 < p.tile; g0 += 4) {
-#pragma unroll 1
-		for (int u = 0; u < 4; u++) {
-			const int t = t0 + g0 + u;
-			v2f x[16];
-
-			K1_STAMP(7);		/* loop overhead + stores of the previous iteration */
-			/* window (fft.cl:415-417); taps fetched as pairs */
-#pragma unroll
-			for (int k = 0; k < 8; k++) {	/* x[2k], x[2k+1] = elements 2L + 128k, 2L + 1 + 128k */
-				const v2f w = *reinterpret_cast<const v2f *>(&win_tab[2 * lane + 128 * k]);
-				x[2 * k]     = mul_bcast_lo(xn[2 * k], w);
-				x[2 * k + 1] = mul_bcast_hi(xn[2 * k + 1], w);
-			}
-
-			if (K1_LATE_BINS && u == 0 && pend_row >= 0)
-				flush_pack();		/* the previous quad's bin dwords: behind the wait above, ahead of the prefetch below */
-			/* prefetch the next spectrum this wave will process */
-			{
-				const bool last = (g0 + u + 1 == p.tile);
-				const int t_next = last ? (tile + stride) * p.tile : t + 1;
-				if (!last || tile + stride < ntiles)
-					load_iq16(xn, p.iq + (size_t)t_next * p.hop + K1_LANE_SRC(lane));
-			}
-
-			K1_STAMP(0);		/* window (includes waiting for the prefetched IQ) + prefetch issue */
-			/* ---- pass 1: radix 8, p = 1, no twiddle (fft.cl:419-420) --------
-			 * This lane is virtual work-items i = 2L + v (elements i + 128j = x[2j + v], as the 16-byte
-			 * loads deliver them).  Item i stores its outputs at e = 8i + jj; which lane runs which
-			 * item is free. */
-#pragma unroll
-			for (int v = 0; v < 2; v++) {
-				v2f r[8];
-#pragma unroll
-				for (int j = 0; j < 8; j++)
-					r[j] = x[v + 2 * j];
-				dft8(r, s12);
-#pragma unroll
-				for (int jj = 0; jj < 8; jj++)
-					buf[(v ? st1b : st1a) ^ jj] = r[R8_PERM(jj)];
-			}
-			wave_lds_sync();
-#pragma unroll
-			for (int m = 0; m < 16; m++)
-				x[m] = buf[((m & 1) ? rd_odd : rd_even) + 64 * m];
-			wave_lds_sync();
-
-			K1_STAMP(1);		/* pass 1 + exchange */
-			/* ---- pass 2: radix 8, p = 8 (fft.cl:422-423) ------------------- */
-#pragma unroll
-			for (int v = 0; v < 2; v++) {
-				v2f r[8];
-				{
-					v2f in7[7], out7[7];
-#pragma unroll
-					for (int j = 1; j < 8; j++)
-						in7[j - 1] = x[v + 2 * j];
-					c_mul_n<7>(out7, in7, tw2);
-					r[0] = x[v];
-#pragma unroll
-					for (int j = 1; j < 8; j++)
-						r[j] = out7[j - 1];
-				}
-				dft8(r, s12);
-#pragma unroll
-				for (int jj = 0; jj < 8; jj++)
-					buf[(st2 ^ (9 * jj)) + 512 * v] = r[R8_PERM(jj)];
-			}
-			wave_lds_sync();
-#pragma unroll
-			for (int m = 0; m < 16; m++)
-				x[m] = buf[((m & 1) ? rd_odd : rd_even) + 64 * m];
-			wave_lds_sync();
-
-			K1_STAMP(2);		/* pass 2 + exchange */
-			/* ---- pass 3: radix 8, p = 64 (fft.cl:425-426) ------------------
-			 * Virtual item i = lane + 64v stores its outputs at e = 512v + lane + 64jj, and the
-			 * pass-4 butterflies of this lane read exactly e = lane + 64m: with both items of a
-			 * pair in the same lane the third exchange is the identity x[jj + 8v] = out_v[jj] --
-			 * no LDS round trip (fft.cl:347-349 + 435-438 collapse to register renaming). */
-			{
-				v2f y[16];
-#pragma unroll
-				for (int v = 0; v < 2; v++) {
-					v2f r[8];
-					{
-						v2f in7[7], out7[7];
-#pragma unroll
-						for (int j = 1; j < 8; j++)
-							in7[j - 1] = x[v + 2 * j];
-						c_mul_n<7>(out7, in7, tw3);
-						r[0] = x[v];
-#pragma unroll
-						for (int j = 1; j < 8; j++)
-							r[j] = out7[j - 1];
-					}
-					dft8(r, s12);
-#pragma unroll
-					for (int jj = 0; jj < 8; jj++)
-						y[jj + 8 * v] = r[R8_PERM(jj)];
-				}
-#pragma unroll
-				for (int m = 0; m < 16; m++)
-					x[m] = y[m];
-			}
-
-			K1_STAMP(3);		/* pass 3 + exchange */
-			/* ---- pass 4: radix 2, p = 512 (fft.cl:428-458) ------------------
-			 * butterfly on elements (j, j + 512), j = lane + 64c, twiddle k = j.
-			 * Results: X[j] -> x[c], X[j + 512] -> x[c + 8], i.e. column lane + 64m. */
-			{
-				v2f in8[8], w8[8], out8[8];
-#pragma unroll
-				for (int c = 0; c < 8; c++) { in8[c] = x[c + 8]; w8[c] = tw4_tab[lane + 64 * c]; }	/* k = lane + 64c */
-				c_mul_n<8>(out8, in8, w8);
-#pragma unroll
-				for (int c = 0; c < 8; c++) {
-					v2f a = x[c];
-					v2f b = out8[c];
-					DFT2(a, b);
-					x[c] = a;
-					x[c + 8] = b;
-				}
-			}
-
-			K1_STAMP(4);		/* pass 4 */
-			if (WRITE_FFT) {
-#pragma unroll
-				for (int m = 0; m < 16; m++)
-					reinterpret_cast<v2f *>(p.fft_out)[(size_t)t * kN + lane + 64 * m] = x[m];
-			}
-
-			/* ---- epilogue: log-power, exact bin (display.cl:136,161-168) ---- */
-			float    l2[16];
-			uint32_t amb = 0;
-			const float top = (float)(bk.nb - 1);
-#pragma unroll
-			for (int m = 0; m < 16; m++) {
-				uint32_t ab;
-				const float r = bin_fast(x[m].x, x[m].y, bk, &l2[m], &ab);
-				amb = amb > ab ? amb : ab;			/* v_max_u32: NaN / inf propagate */
-				if (!(K1_DBG_EPI & 8))
-					pack[m] = NB256 ? __builtin_amdgcn_cvt_pk_u8_f32(r, (uint32_t)u, pack[m]) : pack_bin(r, top, (uint32_t)u, pack[m]);
-				else
-					pack[m] ^= __float_as_uint(r);
-			}
-			if (!K1_DBG_NO_EXACT && amb > __float_as_uint(bk.amb)) {
-				/* rare (a few % of spectra have one such sample): find the samples, decide them
-				 * against the exact thresholds, patch their bin byte and log-power */
-#pragma unroll
-				for (int m = 0; m < 16; m++) {
-					const float v = __builtin_fmaf(bk.A, l2[m], bk.C);
-					const float r = __builtin_rintf(v);
-					const float a = __builtin_fmaf(__builtin_fabsf(l2[m]), bk.kappa, __builtin_fabsf(v - r));
-					if (!(a <= bk.amb)) {
-						const int guess = (int)__builtin_amdgcn_fmed3f(r, 0.0f, top);
-						float nl2;
-#if K1_THR_LDS
-						const uint32_t nbn = bin_exact(x[m].x, x[m].y, l2[m], guess,
-						                               (const __attribute__((address_space(3))) double *)thr_tab, bk.nb, &nl2);
-#else
-						const uint32_t nbn = bin_exact(x[m].x, x[m].y, l2[m], guess, bk.thr, bk.nb, &nl2);
-#endif
-						pack[m] = (pack[m] & ~(0xffu << (8 * u))) | (nbn << (8 * u));
-						l2[m] = nl2;
-					}
-				}
-			}
-
-#pragma unroll
-			for (int m = 0; m < 16; m++) {
-				/* Horner form of display.cl:149-150, in place (v_fma with the accumulator as destination:
-				 * the compiler's v_fmac into the dying l2 register costs a v_mov per column) */
-				if (K1_DBG_EPI & 4) { live[m] = l2[m]; continue; }
-				asm("v_fma_f32 %0, %0, %1, %2" : "+v"(live[m]) : "s"(p.w), "v"(l2[m]));
-				vmax[m] = max_f32(vmax[m], l2[m]);		/* display.cl:139 */
-			}
-#if K1_DBG_EPI & 32
-#pragma unroll
-			for (int m = 0; m < 16; m++)
-				atomicAdd(&dbg_cnt[((pack[m] >> (8 * u)) & 0xffu) * 32 + (lane & 31)], (lane & 32) ? 0x10000u : 1u);
-#endif
-			if (t >= p.wf_first) {				/* uniform: one scalar branch */
-				float *wf_row = p.wf + (size_t)((p.wf_pos0 + t) & p.wf_mask) * kN + lane;
-#pragma unroll
-				for (int m = 0; m < 16; m++)
-					wf_row[64 * m] = l2[m] * F_HALF_LOG10_2;	/* display.cl:142-146 */
-			}
-			K1_STAMP(6);		/* epilogue */
-		}
-
-		K1_STAMP(5);			/* 4th epilogue (the first three land in 7) */
-		/* 4 spectra x 1 column per dword, coalesced 256 B per instruction: stored at the top of the next quad (or below) */
-		pend_row = (t0 + g0) >> 2;
-		if (!K1_LATE_BINS)
-			flush_pack();
-	}
-	if (pend_row >= 0)
-		flush_pack();
-
-	/* leave the log2 domain: pwr = log10|X| = l2 * log10(2)/2; an untouched max is exactly -1000 */
-	float2 *pp = p.partial + (size_t)tile * kN + lane;
-#pragma unroll
-	for (int m = 0; m < 16; m++)
-		pp[64 * m] = make_float2(live[m] * F_HALF_LOG10_2,
-		                         (vmax[m] == vmax_init) ? -1000.0f : vmax[m] * F_HALF_LOG10_2);
-	}	/* tile loop */
-#if K1_TIMING
-	if (p.dbg && lane == 0) {
-		const int w = blockIdx.x * 4 + wv;
-		for (int i = 0; i < 8; i++)
-			p.dbg[w * 8 + i] = tacc[i];
-		/* wave lifetime on the common clock replaces the two near-empty phase slots */
-		p.dbg[w * 8 + 3] = t_wave_start;
-		p.dbg[w * 8 + 5] = wall_clock64();
-	}
-#endif
-}
+#define K1_ENTRY(name) name
+#define K1_SC16 0
+#define K1_IQ p.iq
+#include "k1_fft_bin.inc"
+#undef K1_ENTRY
+#undef K1_SC16
+#undef K1_IQ
 
 /* ------------------------------------------------------------------------ */
 /* K1's memory traffic without K1's arithmetic (measurement hook)             */
@@ -947,200 +651,20 @@ static __device__ __forceinline__ void load_iq8(v2f (&x)[8], const float2 *__res
 	for (int j = 0; j < 8; j++)		/* elements i + 128 j */
 		x[j] = __builtin_nontemporal_load(reinterpret_cast<const v2f *>(src + 128 * j));
 }
-
-template <bool WRITE_FFT>
-__global__ __launch_bounds__(128, K1V2_WAVES_PER_SIMD)
-void k1v2_fft_bin(const K1Params p)
+static __device__ __forceinline__ void load_iq8(v2f (&x)[8], const uint32_t *__restrict__ src)
 {
-	__shared__ v2f   buf[kN];			/* 8 KiB exchange slab of the work-group's spectrum */
-	__shared__ v2f   tw4_tab[512];
-	__shared__ float win_tab[kN];
-
-	const int lane   = threadIdx.x & 63;
-	const int w      = threadIdx.x >> 6;		/* wave = virtual-item half */
-	const int i0     = threadIdx.x;			/* virtual work-item i = lane + 64w */
-	const int ntiles = p.total / p.tile;
-	const int stride = gridDim.x;
-	int tile = blockIdx.x;
-	const v2f *twg = reinterpret_cast<const v2f *>(p.tw);
-
-	for (int i = threadIdx.x; i < kN; i += 128)
-		win_tab[i] = p.win[i];
-	for (int i = threadIdx.x; i < 512; i += 128)
-		tw4_tab[i] = twg[kTw4Off + i];
-	__syncthreads();
-
-	/* per-lane twiddles: k = i & 7 and k = i & 63 do not depend on w */
-	v2f tw2[7];
-	v2f tw3[7];
 #pragma unroll
-	for (int n = 0; n < 7; n++) {
-		tw2[n] = twg[kTw2Off + (lane & 7) * 7 + n];
-		tw3[n] = twg[kTw3Off + lane * 7 + n];
-	}
-	const v2f s12 = { F_SQRT_1_2, F_SQRT_1_2 };
-
-	/* swizzled addressing, as in k1_fft_bin with v = w */
-	const int rd_even = lane ^ ((lane >> 3) & 7);
-	const int rd_w    = w ? (rd_even ^ 8) : rd_even;		/* e = lane + 64(w + 2j): parity of m is w */
-	const int st1     = ((8 * lane) ^ (lane & 15)) + 512 * w;
-	const int st2     = (((64 * (lane >> 3)) + (lane & 7)) ^ (lane & 8)) + 512 * w;
-	const int st3     = 512 * w;					/* + (odd jj ? rd_odd : rd_even) + 64 jj */
-	const int rd_odd  = rd_even ^ 8;
-
-	const BinConst bk = { p.binA, p.binC, p.amb, p.kappa, p.n_bins, p.thr };
-	const float vmax_init = -1000.0f / F_HALF_LOG10_2;
-	const float top = (float)(bk.nb - 1);
-
-	v2f xn[8];
-	if (tile < ntiles)
-		load_iq8(xn, p.iq + (size_t)tile * p.tile * p.hop + i0);
-
-	for (; tile < ntiles; tile += stride) {		/* uniform over the work-group */
-	const int t0 = tile * p.tile;
-
-	float live[8], vmax[8];
-#pragma unroll
-	for (int q = 0; q < 8; q++) {
-		live[q] = 0.0f;
-		vmax[q] = vmax_init;
-	}
-
-	for (int g0 = 0; g0 < p.tile; g0 += 4) {
-		uint32_t pack[8];
-#pragma unroll
-		for (int q = 0; q < 8; q++)
-			pack[q] = 0;
-
-#pragma unroll 1
-		for (int u = 0; u < 4; u++) {
-			const int t = t0 + g0 + u;
-			v2f r[8];
-
-			/* window (fft.cl:415-417) */
-#pragma unroll
-			for (int j = 0; j < 8; j += 2) {
-				v2f ww;
-				ww.x = win_tab[i0 + 128 * j];
-				ww.y = win_tab[i0 + 128 * (j + 1)];
-				r[j]     = mul_bcast_lo(xn[j], ww);
-				r[j + 1] = mul_bcast_hi(xn[j + 1], ww);
-			}
-			{	/* prefetch the next spectrum of this work-group */
-				const bool last = (g0 + u + 1 == p.tile);
-				const int t_next = last ? (tile + stride) * p.tile : t + 1;
-				if (!last || tile + stride < ntiles)
-					load_iq8(xn, p.iq + (size_t)t_next * p.hop + i0);
-			}
-
-			/* pass 1 (fft.cl:419-420) */
-			dft8(r, s12);
-#pragma unroll
-			for (int jj = 0; jj < 8; jj++)
-				buf[st1 ^ jj] = r[R8_PERM(jj)];
-			__syncthreads();
-#pragma unroll
-			for (int j = 0; j < 8; j++)
-				r[j] = buf[rd_w + 64 * (w + 2 * j)];
-			__syncthreads();
-
-			/* pass 2 (fft.cl:422-423) */
-#pragma unroll
-			for (int j = 1; j < 8; j++)
-				r[j] = c_mul(r[j], tw2[j - 1]);
-			dft8(r, s12);
-#pragma unroll
-			for (int jj = 0; jj < 8; jj++)
-				buf[st2 ^ (9 * jj)] = r[R8_PERM(jj)];
-			__syncthreads();
-#pragma unroll
-			for (int j = 0; j < 8; j++)
-				r[j] = buf[rd_w + 64 * (w + 2 * j)];
-			__syncthreads();
-
-			/* pass 3 (fft.cl:425-426) */
-#pragma unroll
-			for (int j = 1; j < 8; j++)
-				r[j] = c_mul(r[j], tw3[j - 1]);
-			dft8(r, s12);
-#pragma unroll
-			for (int jj = 0; jj < 8; jj++)
-				buf[st3 + ((jj & 1) ? rd_odd : rd_even) + 64 * jj] = r[R8_PERM(jj)];
-			__syncthreads();
-
-			/* pass 4 (fft.cl:428-458): butterflies c = 4w + q on elements (j, j+512), j = lane + 64c.
-			 * x[q] = X[lane + 64(4w+q)], x[q+4] = X[lane + 64(8+4w+q)] */
-			v2f x[8];
-#pragma unroll
-			for (int q = 0; q < 4; q++) {
-				const int c = 4 * w + q;		/* parity of c is parity of q */
-				v2f a = buf[((q & 1) ? rd_odd : rd_even) + 64 * c];
-				v2f b = buf[((q & 1) ? rd_odd : rd_even) + 64 * (c + 8)];
-				b = c_mul(b, tw4_tab[lane + 64 * c]);
-				DFT2(a, b);
-				x[q] = a;
-				x[q + 4] = b;
-			}
-			__syncthreads();		/* the slab is rewritten by the next spectrum's pass 1 */
-
-			if (WRITE_FFT) {
-#pragma unroll
-				for (int q = 0; q < 4; q++) {
-					reinterpret_cast<v2f *>(p.fft_out)[(size_t)t * kN + lane + 64 * (4 * w + q)] = x[q];
-					reinterpret_cast<v2f *>(p.fft_out)[(size_t)t * kN + lane + 64 * (8 + 4 * w + q)] = x[q + 4];
-				}
-			}
-
-			/* epilogue (display.cl:136,161-168), as in k1_fft_bin */
-			float    l2[8];
-			uint32_t amb = 0;
-#pragma unroll
-			for (int q = 0; q < 8; q++) {
-				uint32_t ab;
-				const float rr = bin_fast(x[q].x, x[q].y, bk, &l2[q], &ab);
-				amb = amb > ab ? amb : ab;
-				pack[q] = pack_bin(rr, top, (uint32_t)u, pack[q]);
-			}
-			if (amb > __float_as_uint(bk.amb)) {
-#pragma unroll
-				for (int q = 0; q < 8; q++) {
-					const float v = __builtin_fmaf(bk.A, l2[q], bk.C);
-					const float rr = __builtin_rintf(v);
-					const float a = __builtin_fmaf(__builtin_fabsf(l2[q]), bk.kappa, __builtin_fabsf(v - rr));
-					if (!(a <= bk.amb)) {
-						const int guess = (int)__builtin_amdgcn_fmed3f(rr, 0.0f, top);
-						float nl2;
-						const uint32_t nbn = bin_exact(x[q].x, x[q].y, l2[q], guess, ThrScalar{ bk.thr }, bk.nb, &nl2);
-						pack[q] = (pack[q] & ~(0xffu << (8 * u))) | (nbn << (8 * u));
-						l2[q] = nl2;
-					}
-				}
-			}
-
-			const bool store_row = (t >= p.wf_first);
-			float *wf_row = p.wf + (size_t)((p.wf_pos0 + t) & p.wf_mask) * kN + lane + 256 * w;
-#pragma unroll
-			for (int q = 0; q < 8; q++) {
-				live[q] = __builtin_fmaf(live[q], p.w, l2[q]);
-				vmax[q] = max_f32(vmax[q], l2[q]);
-				if (store_row)
-					wf_row[64 * (q & 3) + 512 * (q >> 2)] = l2[q] * F_HALF_LOG10_2;
-			}
-		}
-
-		uint32_t *dst = p.bins + (size_t)((t0 + g0) >> 2) * kN + lane + 256 * w;
-#pragma unroll
-		for (int q = 0; q < 8; q++)
-			dst[64 * (q & 3) + 512 * (q >> 2)] = pack[q];
-	}
-
-	float2 *pp = p.partial + (size_t)tile * kN + lane + 256 * w;
-#pragma unroll
-	for (int q = 0; q < 8; q++)
-		pp[64 * (q & 3) + 512 * (q >> 2)] = make_float2(live[q] * F_HALF_LOG10_2,
-			(vmax[q] == vmax_init) ? -1000.0f : vmax[q] * F_HALF_LOG10_2);
-	}	/* tile loop */
+	for (int j = 0; j < 8; j++)
+		x[j] = ld_sample(src + 128 * j);
 }
+
+#define K1_ENTRY(name) name
+#define K1_SC16 0
+#define K1_IQ p.iq
+#include "k1v2_fft_bin.inc"
+#undef K1_ENTRY
+#undef K1_SC16
+#undef K1_IQ
 
 /* ------------------------------------------------------------------------ */
 /* K1 general N: N/8 threads per spectrum                                    */
@@ -1155,160 +679,18 @@ void k1v2_fft_bin(const K1Params p)
  * involves address bits 0..6).  Bin indices are 16-bit, 2 spectra per dword. */
 static __device__ __forceinline__ int swz(int e) { return e ^ ((e >> 3) & 15); }
 
-template <int LOG2N, bool WRITE_FFT>
-__global__ __launch_bounds__((1 << LOG2N) / 8)
-void k1big_fft_bin(const K1Params p)
-{
-	constexpr int N = 1 << LOG2N, T = N / 8, NP8 = LOG2N / 3;
-	static_assert(LOG2N % 3 == 1, "plan: radix-8 passes then one radix-2 pass");
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-	v2f *buf = reinterpret_cast<v2f *>(smem_raw);
-
-	const int i = threadIdx.x;
-	const int ntiles = p.total / p.tile;
-	/* the whole twiddle table sits behind the exchange slab in LDS: read from global memory it was 21 B per sample of L2 traffic,
-	 * against 8 B per sample of IQ.  The reference's layout, 7 per item and pass, then the radix-2 pass's */
-	constexpr int TWLEN = ((N / 2 - 8) / 7) * 7 + N / 2;	/* (8 + 64 + ... + N/16) * 7 + N/2 */
-	v2f *tws = buf + N;
-	float *wins = reinterpret_cast<float *>(tws + TWLEN);	/* and the window behind it: 160 KiB in all at N = 8192 */
-	for (int k = i; k < TWLEN; k += T)
-		tws[k] = reinterpret_cast<const v2f *>(p.tw)[k];
-	for (int k = i; k < N; k += T)
-		wins[k] = p.win[k];
-	__syncthreads();
-	const v2f *twg = tws;
-	const v2f s12 = { F_SQRT_1_2, F_SQRT_1_2 };
-	const BinConst bk = { p.binA, p.binC, p.amb, p.kappa, p.n_bins, p.thr };
-	const float vmax_init = -1000.0f / F_HALF_LOG10_2;
-	const float top = (float)(bk.nb - 1);
-
-	for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-	const int t0 = tile * p.tile;
-	float live[8], vmax[8];
-#pragma unroll
-	for (int q = 0; q < 8; q++) { live[q] = 0.0f; vmax[q] = vmax_init; }
-
-	for (int g0 = 0; g0 < p.tile; g0 += 2) {
-		uint32_t pack[8];
-#pragma unroll
-		for (int q = 0; q < 8; q++) pack[q] = 0;
-
-#pragma unroll 1
-		for (int u = 0; u < 2; u++) {
-			const int t = t0 + g0 + u;
-			const float2 *src = p.iq + (size_t)t * p.hop;
-			v2f r[8];
-
-			/* window (fft.cl:415-417) */
-#pragma unroll
-			for (int j = 0; j < 8; j++) {
-				const v2f xv = __builtin_nontemporal_load(reinterpret_cast<const v2f *>(src + i + T * j));
-				const float wv = wins[i + T * j];
-				r[j] = v2f{ xv.x * wv, xv.y * wv };
-			}
-
-			/* radix-8 passes p = 1, 8, 64, ... (fft.cl:278-350) */
-			int pp = 1;
-#pragma unroll
-			for (int q8 = 0; q8 < NP8; q8++) {
-				const int k = i & (pp - 1);
-				if (q8 > 0) {
-					const v2f *tw = twg + p.tw_off[q8 - 1] + k * 7;
-#pragma unroll
-					for (int j = 1; j < 8; j++)
-						r[j] = c_mul(r[j], tw[j - 1]);
-				}
-				dft8(r, s12);
-				const int j0 = ((i - k) << 3) + k;
-#pragma unroll
-				for (int jj = 0; jj < 8; jj++)
-					buf[swz(j0 + jj * pp)] = r[R8_PERM(jj)];
-				__syncthreads();
-				if (q8 + 1 < NP8) {
-#pragma unroll
-					for (int j = 0; j < 8; j++)
-						r[j] = buf[swz(i + T * j)];
-					__syncthreads();
-				}
-				pp <<= 3;
-			}
-
-			/* final radix-2 pass, p = N/2 (fft.cl:428-458): butterflies jb = i + T c on (jb, jb + N/2) */
-			v2f x[8];
-#pragma unroll
-			for (int c = 0; c < 4; c++) {
-				const int jb = i + T * c;
-				v2f a = buf[swz(jb)];
-				v2f b = buf[swz(jb + N / 2)];
-				b = c_mul(b, twg[p.tw_off[NP8 - 1] + jb]);
-				DFT2(a, b);
-				x[c] = a;		/* column jb */
-				x[c + 4] = b;		/* column jb + N/2 */
-			}
-			__syncthreads();		/* slab free for the next spectrum */
-
-			if (WRITE_FFT) {
-#pragma unroll
-				for (int c = 0; c < 4; c++) {
-					reinterpret_cast<v2f *>(p.fft_out)[(size_t)t * N + i + T * c] = x[c];
-					reinterpret_cast<v2f *>(p.fft_out)[(size_t)t * N + i + T * c + N / 2] = x[c + 4];
-				}
-			}
-
-			/* epilogue (display.cl:136,161-168), as in the 1024-point kernels, 16-bit bin indices */
-			float l2[8];
-			uint32_t bn[8];
-			uint32_t amb = 0;
-#pragma unroll
-			for (int q = 0; q < 8; q++) {
-				uint32_t ab;
-				const float rr = bin_fast(x[q].x, x[q].y, bk, &l2[q], &ab);
-				amb = amb > ab ? amb : ab;
-				bn[q] = (uint32_t)(int)__builtin_amdgcn_fmed3f(rr, 0.0f, top);
-			}
-			if (amb > __float_as_uint(bk.amb)) {
-#pragma unroll
-				for (int q = 0; q < 8; q++) {
-					const float v = __builtin_fmaf(bk.A, l2[q], bk.C);
-					const float rr = __builtin_rintf(v);
-					const float a = __builtin_fmaf(__builtin_fabsf(l2[q]), bk.kappa, __builtin_fabsf(v - rr));
-					if (!(a <= bk.amb)) {
-						float nl2;
-						bn[q] = bin_exact(x[q].x, x[q].y, l2[q], (int)bn[q], ThrScalar{ bk.thr }, bk.nb, &nl2);
-						l2[q] = nl2;
-					}
-				}
-			}
-			const bool store_row = (t >= p.wf_first);
-			float *wf_row = p.wf + (size_t)((p.wf_pos0 + t) & p.wf_mask) * N + i;
-#pragma unroll
-			for (int q = 0; q < 8; q++) {
-				const int col_off = T * (q & 3) + (N / 2) * (q >> 2);
-				pack[q] |= bn[q] << (16 * u);
-				live[q] = __builtin_fmaf(live[q], p.w, l2[q]);
-				vmax[q] = max_f32(vmax[q], l2[q]);
-				if (store_row)
-					wf_row[col_off] = l2[q] * F_HALF_LOG10_2;
-			}
-		}
-		uint32_t *dst = p.bins + (size_t)((t0 + g0) >> 1) * N + i;
-#pragma unroll
-		for (int q = 0; q < 8; q++)
-			dst[T * (q & 3) + (N / 2) * (q >> 2)] = pack[q];
-	}
-	float2 *pp2 = p.partial + (size_t)tile * N + i;
-#pragma unroll
-	for (int q = 0; q < 8; q++)
-		pp2[T * (q & 3) + (N / 2) * (q >> 2)] = make_float2(live[q] * F_HALF_LOG10_2,
-			(vmax[q] == vmax_init) ? -1000.0f : vmax[q] * F_HALF_LOG10_2);
-	}
-}
+#define K1_ENTRY(name) name
+#define K1_SC16 0
+#define K1_IQ p.iq
+#include "k1big_fft_bin.inc"
+#undef K1_ENTRY
+#undef K1_SC16
+#undef K1_IQ
 
 /* Buffer addressing for the 8192- and 65536-point kernels: every global access of their loops is `scalar base (descriptor) + ONE 32-bit per-lane
  * offset + a scalar offset` -- buffer_load / buffer_store ... offen -- where the per-lane offset is fixed for the kernel's lifetime and
  * everything that changes (spectrum, row, column block c) is scalar arithmetic.  With plain pointers the compiler folded the
  * column-block constants into 64-bit per-lane adds (240 of them per spectrum) and spilled.  Arrays addressed this way are < 4 GiB. */
-typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 static __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base)
 {
@@ -1413,402 +795,13 @@ static __device__ __forceinline__ void wg_barrier_lds()
 
 constexpr int kK1wIdxStores = 16;	/* index stores a thread issues per ODD spectrum (one dword per column and pair of spectra): the immediate of the
 					 * hand-written wait for the IQ requested before them */
-template <int SHIFT>
-__global__ __launch_bounds__(512, 2)
-void k1w_fft_bin(const K1Params p)
-{
-	constexpr int N = 8192, TH = 512;
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-	/* two 64 KiB slabs; a spectrum's exchanges use A, B, A (the half one: its first 32 KiB) and the next spectrum's B, A, B */
-	v2f *slab0 = reinterpret_cast<v2f *>(smem_raw);
-	v2f *slab1 = slab0 + N;
-	/* behind the slabs: the exact-bin thresholds (n_bins + 1 <= 513 doubles): the rare path that consults them must not wait behind the IQ
-	 * in flight (a table load through the vector memory path returns in order), and while one wave is in it the other seven wait at the
-	 * next barrier */
-	typedef const __attribute__((address_space(3))) double *lds_cdp;
-	double *thr_g = reinterpret_cast<double *>(slab0 + 2 * N);
-	const lds_cdp thr_l = (lds_cdp)thr_g;
-
-	const int th = threadIdx.x;
-	const int ntiles = p.total / p.tile;
-	const v2f *twg = reinterpret_cast<const v2f *>(p.tw);
-	const v2f two = { 2.0f, 2.0f };
-	const BinConst bk = { p.binA, p.binC, p.amb, p.kappa, p.n_bins, p.thr };
-	const float vmax_init = -1000.0f / F_HALF_LOG10_2;
-	const float top = (float)(bk.nb - 1);
-
-	/* ---- per-thread constants ------------------------------------------------ */
-	const int hh = th >> 8, kk = th & 255;		/* item th = kk + 256 hh of the pass p = 256 */
-	const int hu = __builtin_amdgcn_readfirstlane(th >> 8);	/* = hh, as a scalar (wave-uniform: waves 0-3 / 4-7), for the whole kernel: taken inside the spectrum
-								 * loop it kept th >> 8 alive in a vector register -- the one the general-hop form spilled */
-	const v2f w16c = twg[p.tw_off[0]], w8c = twg[p.tw_off[0] + 1], w163c = twg[p.tw_off[0] + 2];	/* W16, W8, W16^3: the first pass */
-	v2f wab[8];			/* taps of elements th + 512 j and th + 512 (j + 8): the pair of a first-pass stage-A butterfly */
-	v2f tw16[8], tw256[8];		/* w^8, w^4, w^2, w^2 W8, w, w W16, w W8, w W16^3 for k = th & 15, th & 255 */
-	v2f twr[8];			/* radix-2 twiddles k = kk + 256 (8 hh + c) */
-#pragma unroll
-	for (int j = 0; j < 8; j++) {
-		wab[j] = v2f{ p.win[th + 512 * j], p.win[th + 512 * (j + 8)] };
-		twr[j] = twg[p.tw_off[3] + kk + 256 * (8 * hh + j)];
-	}
-	for (int e = th; e <= p.n_bins && e < 520; e += TH)
-		thr_g[e] = p.thr[e];
-	__syncthreads();
-#pragma unroll
-	for (int n = 0; n < 8; n++) {
-		tw16[n]  = twg[p.tw_off[1] + (th & 15) * 8 + n];
-		tw256[n] = twg[p.tw_off[2] + kk * 8 + n];
-	}
-
-	/* ---- LDS addressing (8-byte elements, phys(e) = e ^ ((e >> 4) & 31)) ----
-	 * loads of every pass: e = th + 512 j -> phys = rd + 512 j
-	 * stores: pass p = 1    e = 16 th + m                          -> st1 ^ m
-	 *         pass p = 16   e = 256 (th >> 4) + (th & 15) + 16 m   -> st2 ^ ((m ^ 16 (m & 1)) | 32 (m >> 1))
-	 *         half exchange (plain layout [m''][th]: lane-contiguous both ways)  stores m'' 512 + th, loads m'' 512 + (th ^ 256) */
-	const int rd  = th ^ ((th >> 4) & 31);
-	const int st1 = (32 * (th >> 1)) | ((16 * (th & 1)) ^ (th & 31));
-	const int st2 = (256 * (th >> 4)) | ((th & 15) ^ (16 * ((th >> 4) & 1)));
-
-	/* SHIFT = 16 / R for hop = N / R, R = 2, 4, 8, 16: the next window's row j is this window's row j + SHIFT of the same thread;
-	 * SHIFT = 16: any other hop, every row is requested again */
-	const uint32_t iq_vo = 8u * (uint32_t)th;		/* element th + 512 j of a window at 8 th + 4096 j (scalar descriptor + one lane offset) */
-	auto ld_iq = [&](__amdgpu_buffer_rsrc_t rs, int j) __attribute__((always_inline)) -> v2f {
-		return bld_v2f<kAuxNT>(rs, iq_vo, 4096u * (uint32_t)j);
-	};
-
-	v2f q[16];			/* raw IQ of the spectrum to be processed next: rows th + 512 j */
-	/* column of xo[m]: cb + 256 (m & 7) + 4096 (m >> 3), cb = kk + 2048 hh.  ONE register carries it through the spectrum loop, as the
-	 * byte offset 2 cb of the column's short in an index row (the kernel has no register to spare: tools/check_k1w_loads.py); the rare
-	 * users of cb itself (waterfall rows, the bytes of 9th bits, the tile's partials) take it back out of it where they run */
-	const uint32_t cb2 = 2u * ((uint32_t)kk + 2048u * (uint32_t)hh);
-#define K1W_CB() ({ uint32_t _c; asm volatile("v_lshrrev_b32 %0, 1, %1" : "=v"(_c) : "v"(cb2)); _c; })
-
-	/* Epilogue of columns [M0, M1) of spectrum tp, whose FFT is in xo: log-power, exact 16-bit bin, live / max, waterfall row
-	 * (display.cl:136-150,161-168).  Per column, nothing carried from column to column: it is cut into three pieces that
-	 * run between the LDS stores of the NEXT spectrum's exchanges and the barrier behind them, i.e. while this wave
-	 * would otherwise wait for the slowest one. */
-#ifndef K1W_P1
-#define K1W_P1 6		/* the three epilogue pieces: columns [0, P1), [P1, P2), [P2, 16) of a thread (A/B builds) */
-#define K1W_P2 11
-#endif
-#define K1W_COL(m) (256 * ((m) & 7) + 4096 * ((m) >> 3))
-#define K1W_EPI(M0, M1, tp) do { \
-		if (K1W_P(4)) break; \
-		if (K1W_PRIO) __builtin_amdgcn_s_setprio(0); \
-		const bool _row = ((tp) >= p.wf_first); \
-		float *_wfr = p.wf + (size_t)((p.wf_pos0 + (tp)) & p.wf_mask) * N; \
-		/* index stores (512 bins: 9 bits), 1.125 B per sample instead of the 2 B of a 16-bit index (round 6): \
-		 *   low bytes   one SHORT per column and PAIR of spectra, [t / 2][column] (even spectrum in the low byte) \
-		 *   9th bits    one BYTE per column and EIGHT spectra, [t / 8][column] behind the shorts (bit u = spectrum 8 (t / 8) + u) \
-		 * A vector-memory instruction costs a CU 8-17 cycles whatever it carries (tools/ubench/vmem_rate.hip: 8.2 for 64 dense shorts, \
-		 * 10.8 for 64 dwords), and with a store per sample the index stores were a quarter of this kernel's time: the low bytes of an \
-		 * even spectrum wait in four registers (four columns each) for the odd one's, the 9th bits of eight spectra in four more \
-		 * (tiles are multiples of 8: launch_k1).  Scalar base (SALU) + ONE lane offset + immediate; column cb + K1W_COL(m) of a row: \
-		 * shorts at 2 cb + 512 (m & 7) + 8192 (m >> 3), bytes at cb + 256 (m & 7) + 4096 (m >> 3) */ \
-		const char *_blo = reinterpret_cast<const char *>(p.bins) + (size_t)((tp) >> 1) * (N * 2); \
-		const char *_bhi = reinterpret_cast<const char *>(p.bins) + (size_t)p.total * N + (size_t)((tp) >> 3) * N; \
-		const uint32_t _bo2 = cb2; \
-		const uint32_t _sh = (uint32_t)(tp) & 7u;		/* uniform */ \
-		if ((M0) == 0 && _sh == 0) { hi9[0] = 0; hi9[1] = 0; hi9[2] = 0; hi9[3] = 0; } \
-		float _l2[(M1) - (M0)]; uint32_t _bn[(M1) - (M0)]; uint32_t _amb = 0; \
-		_Pragma("unroll") \
-		for (int m = (M0); m < (M1); m++) { \
-			uint32_t ab; \
-			const float rr = bin_fast(xo[m].x, xo[m].y, bk, &_l2[m - (M0)], &ab); \
-			_amb = _amb > ab ? _amb : ab;		/* v_max_u32: NaN / inf order above every finite measure */ \
-			_bn[m - (M0)] = (uint32_t)(int)__builtin_amdgcn_fmed3f(rr, 0.0f, top); \
-		} \
-		/* ONE branch per piece (a compare + exec save + branch per sample cost 9 % of this kernel): rare -- find the samples again \
-		 * and decide them against the exact thresholds */ \
-		if (!K1_DBG_NO_EXACT && _amb > __float_as_uint(bk.amb)) { \
-			_Pragma("unroll") \
-			for (int m = (M0); m < (M1); m++) { \
-				const float v = __builtin_fmaf(bk.A, _l2[m - (M0)], bk.C); \
-				const float a = __builtin_fmaf(__builtin_fabsf(_l2[m - (M0)]), bk.kappa, __builtin_fabsf(v - __builtin_rintf(v))); \
-				if (!(a <= bk.amb)) { \
-					float nl2; \
-					_bn[m - (M0)] = bin_exact(xo[m].x, xo[m].y, _l2[m - (M0)], (int)_bn[m - (M0)], thr_l, bk.nb, &nl2); \
-					_l2[m - (M0)] = nl2; \
-				} \
-			} \
-		} \
-		_Pragma("unroll") \
-		for (int m = (M0); m < (M1); m++)		/* the 9th bit joins its column's byte: bit (t & 7) */ \
-			hi9[m >> 2] = (__builtin_amdgcn_ubfe(_bn[m - (M0)], 8, 1) << (8 * (m & 3) + _sh)) | hi9[m >> 2]; \
-		if (!((tp) & 1)) {		/* (uniform: ONE branch per piece) even spectrum: keep the low bytes, four columns per register */ \
-			_Pragma("unroll") \
-			for (int m = (M0); m < (M1); m++) \
-				held[m >> 2] = __builtin_amdgcn_perm(_bn[m - (M0)], held[m >> 2], \
-				                                     (m & 3) == 0 ? 0x03020104u : (m & 3) == 1 ? 0x03020400u : (m & 3) == 2 ? 0x03040100u : 0x04020100u); \
-		} else if (!K1W_P(8)) {		/* odd spectrum: the short of both */ \
-			_Pragma("unroll") \
-			for (int m = (M0); m < (M1); m++) { \
-				const char *_sb = _blo + 8192 * (m >> 3); \
-				const uint32_t _d = __builtin_amdgcn_perm(_bn[m - (M0)], held[m >> 2], 0x0c0c0400u | (uint32_t)(m & 3)); \
-				switch (m & 7) { \
-				case 0:  asm volatile("global_store_short %0, %1, %2" :: "v"(_bo2), "v"(_d), "s"(_sb) : "memory"); break; \
-				case 1:  asm volatile("global_store_short %0, %1, %2 offset:512" :: "v"(_bo2), "v"(_d), "s"(_sb) : "memory"); break; \
-				case 2:  asm volatile("global_store_short %0, %1, %2 offset:1024" :: "v"(_bo2), "v"(_d), "s"(_sb) : "memory"); break; \
-				case 3:  asm volatile("global_store_short %0, %1, %2 offset:1536" :: "v"(_bo2), "v"(_d), "s"(_sb) : "memory"); break; \
-				case 4:  asm volatile("global_store_short %0, %1, %2 offset:2048" :: "v"(_bo2), "v"(_d), "s"(_sb) : "memory"); break; \
-				case 5:  asm volatile("global_store_short %0, %1, %2 offset:2560" :: "v"(_bo2), "v"(_d), "s"(_sb) : "memory"); break; \
-				case 6:  asm volatile("global_store_short %0, %1, %2 offset:3072" :: "v"(_bo2), "v"(_d), "s"(_sb) : "memory"); break; \
-				default: asm volatile("global_store_short %0, %1, %2 offset:3584" :: "v"(_bo2), "v"(_d), "s"(_sb) : "memory"); break; \
-				} \
-			} \
-			if (_sh == 7) {		/* (uniform) the eighth spectrum: the bytes of 9th bits, scalar base + one lane offset + immediate like the shorts; \
-						 * byte 0 / 2 of a register as it is (global_store_byte / _d16_hi), byte 1 / 3 of its copy shifted by 8 */ \
-				const uint32_t cb = K1W_CB(); \
-				_Pragma("unroll") \
-				for (int m = (M0); m < (M1); m++) { \
-					const char *_hb = _bhi + 4096 * (m >> 3); \
-					const uint32_t _hv = (m & 1) ? (hi9[m >> 2] >> 8) : hi9[m >> 2]; \
-					if (m & 2) { \
-						switch (m & 7) { \
-						case 2:  asm volatile("global_store_byte_d16_hi %0, %1, %2 offset:512" :: "v"(cb), "v"(_hv), "s"(_hb) : "memory"); break; \
-						case 3:  asm volatile("global_store_byte_d16_hi %0, %1, %2 offset:768" :: "v"(cb), "v"(_hv), "s"(_hb) : "memory"); break; \
-						case 6:  asm volatile("global_store_byte_d16_hi %0, %1, %2 offset:1536" :: "v"(cb), "v"(_hv), "s"(_hb) : "memory"); break; \
-						default: asm volatile("global_store_byte_d16_hi %0, %1, %2 offset:1792" :: "v"(cb), "v"(_hv), "s"(_hb) : "memory"); break; \
-						} \
-					} else { \
-						switch (m & 7) { \
-						case 0:  asm volatile("global_store_byte %0, %1, %2" :: "v"(cb), "v"(_hv), "s"(_hb) : "memory"); break; \
-						case 1:  asm volatile("global_store_byte %0, %1, %2 offset:256" :: "v"(cb), "v"(_hv), "s"(_hb) : "memory"); break; \
-						case 4:  asm volatile("global_store_byte %0, %1, %2 offset:1024" :: "v"(cb), "v"(_hv), "s"(_hb) : "memory"); break; \
-						default: asm volatile("global_store_byte %0, %1, %2 offset:1280" :: "v"(cb), "v"(_hv), "s"(_hb) : "memory"); break; \
-						} \
-					} \
-				} \
-			} \
-		} \
-		_Pragma("unroll") \
-		for (int m = (M0); m < (M1); m++) { \
-			live[m] = __builtin_fmaf(live[m], p.w, _l2[m - (M0)]); \
-			vmax[m] = max_f32(vmax[m], _l2[m - (M0)]); \
-		} \
-		if (_row) {		/* uniform, rare (the last wf_rows spectra of a call): one branch per piece instead of one per sample; the row \
-					 * values are recomputed from the log-powers, which the live / max updates above kept alive anyway */ \
-			float *_wf = _wfr + K1W_CB(); \
-			_Pragma("unroll") \
-			for (int m = (M0); m < (M1); m++) \
-				_wf[K1W_COL(m)] = _l2[m - (M0)] * F_HALF_LOG10_2; \
-		} \
-		if (K1W_PRIO) __builtin_amdgcn_s_setprio(2); \
-	} while (0)
-
-	if (K1W_PRIO) __builtin_amdgcn_s_setprio(2);
-#if K1W_TIMING
-	uint32_t wacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-	uint32_t wprev = (uint32_t)__builtin_readcyclecounter();
-#endif
-	for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-	const int t0 = tile * p.tile;
-	float live[16], vmax[16];
-	uint32_t held[4] = { 0, 0, 0, 0 };		/* low bytes of the tile's last even spectrum's bin indices, four columns per register */
-	uint32_t hi9[4] = { 0, 0, 0, 0 };		/* 9th bits of the indices of up to eight spectra, one byte per column, four columns per register */
-#pragma unroll
-	for (int m = 0; m < 16; m++) { live[m] = 0.0f; vmax[m] = vmax_init; }
-
-	{
-		const __amdgpu_buffer_rsrc_t src = make_rsrc(p.iq + (size_t)t0 * p.hop);
-#pragma unroll
-		for (int j = 0; j < 16; j++)
-			q[j] = ld_iq(src, j);
-	}
-
-	v2f xo[16];			/* FFT of the previous spectrum of the tile, its epilogue still to do */
-#pragma unroll
-	for (int m = 0; m < 16; m++) xo[m] = v2f{ 0.0f, 0.0f };
-
-#pragma unroll 1
-	for (int g = 0; g < p.tile; g++) {
-		const int t = t0 + g;
-		const bool have_prev = g > 0;			/* uniform */
-		/* The two waves of a SIMD (waves w and w + 4 of the work-group) run their epilogue pieces on opposite sides of the barrier:
-		 * one computes while the other waits for its LDS loads, instead of all eight moving from LDS to VALU and back together */
-		const bool late = hu != 0;
-		v2f x[16];
-		{ v2f *sw = slab0; slab0 = slab1; slab1 = sw; }		/* (the first spectrum starts on the second slab) */
-
-		/* x[j] = element th + 512 j (the window multiply of fft.cl:415-417 rides on the first pass) */
-		/* ---- pass 1: p = 1, item th, outputs e = 16 th + m -> slab0.  Before the next spectrum's IQ is requested: the requests then
-		 * land in the registers this pass has just consumed (requested first, they needed sixteen more and a copy at the end of the loop) ---- */
-		/* the IQ requested one iteration ago has arrived once at most the index stores issued BEHIND the requests are outstanding: the
-		 * sixteen of an odd spectrum's epilogue, which ran in the previous iteration if that one's g was even and >= 2 (more, if waterfall
-		 * rows or fft_out went out as well: the wait is then longer than needed, not shorter) */
-#define K1W_Q16 "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]), "+v"(q[4]), "+v"(q[5]), "+v"(q[6]), "+v"(q[7]), \
-		"+v"(q[8]), "+v"(q[9]), "+v"(q[10]), "+v"(q[11]), "+v"(q[12]), "+v"(q[13]), "+v"(q[14]), "+v"(q[15])
-		/* (ONE statement, the choice inside it: two statements under an if made the compiler copy q -- before the wait) */
-		/* (kK1wIdxStores: ONE constant for the wait's immediate and for what K1W_EPI issues per odd spectrum -- a change of the index
-		 * format that packs the stores must change both; tools/check_k1w_loads.py counts the stores of the compiled loop against it) */
-		static_assert(kK1wIdxStores == 16, "the counted wait below and K1W_EPI's index stores (one dword per column and pair of spectra) go together");
-		asm volatile("s_cmp_eq_u32 %16, 0\n\ts_cbranch_scc1 1f\n\ts_waitcnt vmcnt(%17)\n\ts_branch 2f\n1:\ts_waitcnt vmcnt(0)\n2:"
-		             : K1W_Q16 : "s"(__builtin_amdgcn_readfirstlane((!K1W_P(8) && (g & 1) && g >= 3) ? 1 : 0)), "n"(kK1wIdxStores) : "scc");
-#undef K1W_Q16
-#pragma unroll
-		for (int j = 0; j < 16; j++)
-			x[j] = q[j];
-		K1W_STAMP(0);			/* radix 2 of the previous spectrum, loop overhead, wait for the IQ */
-		pass16_first<true>(x, wab, w16c, w8c, w163c, two);
-		K1W_STAMP(1);
-
-		/* raw IQ of the next spectrum of this tile: shared rows move down, the new ones are requested now.  UNCONDITIONALLY (behind the
-		 * tile's last spectrum: of that spectrum again, unused): a load inside a branch whose result merges with an older value at the
-		 * join makes the compiler wait for it right there */
-		{
-			const int tn = (g + 1 < p.tile) ? t + 1 : t;
-			const __amdgpu_buffer_rsrc_t src = make_rsrc(p.iq + (size_t)tn * p.hop);
-			/* (moves the compiler cannot sink: left to it, they went behind the requests -- whose results then needed registers of their
-			 * own, a copy at the end of the loop and, for that copy, a wait for every store issued in between) */
-#pragma unroll
-			for (int j = 0; j < 16 - SHIFT; j++)
-				asm volatile("v_mov_b64 %0, %1" : "=v"(q[j]) : "v"(q[j + SHIFT]));
-			/* The requests are made by hand, and so is the wait for them at the top of the next iteration: loads and stores leave the
-			 * vmcnt queue IN ORDER, and the wait the compiler places for loads it knows about -- vmcnt(0) -- also sat through the
-			 * acknowledgement of every index store issued since (a third of this kernel's time: probe builds without the stores / without
-			 * the requests, profiles/r05_c3.md) */
-#pragma unroll
-			for (int j = 16 - SHIFT; j < 16; j++)
-				if (!K1W_P(16))
-					asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen nt" : "=v"(q[j]) : "v"(iq_vo), "s"(src), "s"(4096u * (uint32_t)j));
-		}
-
-#pragma unroll
-		for (int m = 0; m < 16; m++)
-			if (!K1W_P(1)) slab0[st1 ^ m] = x[R16_PERM(m)];
-		if (have_prev && !late) K1W_EPI(0, K1W_P1, t - 1);
-		K1W_STAMP(2);			/* IQ requests, stores (until done), early piece */
-		wg_barrier_lds();
-		K1W_STAMP(3);			/* barrier */
-#if K1W_READ_FIRST
-		/* the reads are requested BEFORE the late piece: a late wave's piece then runs while its operands travel (and while the early
-		 * wave of its SIMD, whose reads were requested at the same moment, has nothing to compute yet) */
-#pragma unroll
-		for (int j = 0; j < 16; j++)
-			if (!K1W_P(2)) x[j] = slab0[rd + 512 * j];
-		if (have_prev && late) K1W_EPI(0, K1W_P1, t - 1);
-		K1W_STAMP(4);			/* late piece */
-#else
-		if (have_prev && late) K1W_EPI(0, K1W_P1, t - 1);
-		K1W_STAMP(4);			/* late piece */
-#pragma unroll
-		for (int j = 0; j < 16; j++)
-			if (!K1W_P(2)) x[j] = slab0[rd + 512 * j];
-#endif
-		K1W_STAMP(5);			/* reads (until all have arrived) */
-
-		/* ---- pass 2: p = 16, k = th & 15, outputs e = 256 (th >> 4) + (th & 15) + 16 m -> slab1 ---- */
-		pass16_ab<true>(x, tw16[0], tw16[1], two);
-		pass16_cd<true>(x, tw16[2], tw16[3], tw16[4], tw16[5], tw16[6], tw16[7], two);
-		K1W_STAMP(6);			/* pass 2 */
-#pragma unroll
-		for (int m = 0; m < 16; m++)
-			if (!K1W_P(1)) slab1[st2 ^ ((m ^ (16 * (m & 1))) | (32 * (m >> 1)))] = x[R16_PERM(m)];
-		if (have_prev && !late) K1W_EPI(K1W_P1, K1W_P2, t - 1);
-		K1W_STAMP(7);
-		wg_barrier_lds();
-		K1W_STAMP(8);
-#if K1W_READ_FIRST
-#pragma unroll
-		for (int j = 0; j < 16; j++)
-			if (!K1W_P(2)) x[j] = slab1[rd + 512 * j];
-		if (have_prev && late) K1W_EPI(K1W_P1, K1W_P2, t - 1);
-		K1W_STAMP(9);
-#else
-		if (have_prev && late) K1W_EPI(K1W_P1, K1W_P2, t - 1);
-		K1W_STAMP(9);
-#pragma unroll
-		for (int j = 0; j < 16; j++)
-			if (!K1W_P(2)) x[j] = slab1[rd + 512 * j];
-#endif
-		K1W_STAMP(10);
-
-		/* ---- pass 3: p = 256, k = kk: X3[4096 hh + kk + 256 m] = x[R16_PERM(m)]; the half this thread's butterflies do not need goes to
-		 * thread th ^ 256 through slab0 ([m''][th]: m'' = m - 8 (1 - hh)) ---- */
-		pass16_ab<true>(x, tw256[0], tw256[1], two);
-		pass16_cd<true>(x, tw256[2], tw256[3], tw256[4], tw256[5], tw256[6], tw256[7], two);
-		K1W_STAMP(11);			/* pass 3 */
-		if (hu == 0) {			/* uniform per wave (waves 0-3 / 4-7): a scalar branch */
-#pragma unroll
-			for (int c = 0; c < 8; c++)
-				if (!K1W_P(1)) slab0[512 * c + th] = x[R16_PERM(8 + c)];
-		} else {
-#pragma unroll
-			for (int c = 0; c < 8; c++)
-				if (!K1W_P(1)) slab0[512 * c + th] = x[R16_PERM(c)];
-		}
-		if (have_prev && !late) K1W_EPI(K1W_P2, 16, t - 1);
-		K1W_STAMP(12);
-		wg_barrier_lds();
-		K1W_STAMP(13);
-		/* ---- radix 2, p = 4096 (fft.cl:428-458; o_pass_radix2_fma): (jb, jb + 4096), jb = kk + 256 (8 hh + c) ->
-		 * xo[c] = X[jb], xo[c + 8] = X[jb + 4096] ---- */
-		{
-			v2f o[8];
-#if K1W_READ_FIRST
-#pragma unroll
-			for (int c = 0; c < 8; c++)
-				o[c] = K1W_P(2) ? x[c] : slab0[512 * c + (th ^ 256)];
-			if (have_prev && late) K1W_EPI(K1W_P2, 16, t - 1);
-			K1W_STAMP(14);
-#else
-			if (have_prev && late) K1W_EPI(K1W_P2, 16, t - 1);
-			K1W_STAMP(14);
-#pragma unroll
-			for (int c = 0; c < 8; c++)
-				o[c] = K1W_P(2) ? x[c] : slab0[512 * c + (th ^ 256)];
-#endif
-			K1W_STAMP(15);
-			/* (step by step, like bf8; the two forms differ in where a and b come from) */
-#define K1W_R2(A, B) do { \
-				v2f u[8], pa[8]; \
-				_Pragma("unroll") \
-				for (int c = 0; c < 8; c++) \
-					asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" : "=v"(u[c]) : "v"(B), "v"(twr[c]), "v"(A)); \
-				_Pragma("unroll") \
-				for (int c = 0; c < 8; c++) \
-					asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(pa[c]) : "v"(B), "v"(twr[c]), "v"(u[c])); \
-				_Pragma("unroll") \
-				for (int c = 0; c < 8; c++) \
-					asm volatile("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(xo[c + 8]) : "v"(A), "s"(two), "v"(pa[c])); \
-				_Pragma("unroll") \
-				for (int c = 0; c < 8; c++) \
-					xo[c] = pa[c]; \
-			} while (0)
-			if (hu == 0)			/* X3[jb] is this item's output m = c, X3[jb + 4096] item th + 256's */
-				K1W_R2(x[R16_PERM(c)], o[c]);
-			else				/* X3[jb] is item th - 256's output m = 8 + c, X3[jb + 4096] this item's */
-				K1W_R2(o[c], x[R16_PERM(8 + c)]);
-#undef K1W_R2
-		}
-
-		if (p.fft_out) {		/* (tests) */
-#pragma unroll
-			for (int m = 0; m < 16; m++)
-				reinterpret_cast<v2f *>(p.fft_out)[(size_t)t * N + K1W_CB() + K1W_COL(m)] = xo[m];
-		}
-	}
-	/* the last iteration's requests (made unconditionally, see above) still own their registers: nothing may reuse them before they have landed */
-	asm volatile("s_waitcnt vmcnt(0)" : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]), "+v"(q[4]), "+v"(q[5]), "+v"(q[6]), "+v"(q[7]),
-	             "+v"(q[8]), "+v"(q[9]), "+v"(q[10]), "+v"(q[11]), "+v"(q[12]), "+v"(q[13]), "+v"(q[14]), "+v"(q[15]));
-	K1W_EPI(0, 16, t0 + p.tile - 1);		/* the tile's last spectrum */
-
-	float2 *pp2 = p.partial + (size_t)tile * N + K1W_CB();
-#pragma unroll
-	for (int m = 0; m < 16; m++)
-		pp2[K1W_COL(m)] = make_float2(live[m] * F_HALF_LOG10_2,
-			(vmax[m] == vmax_init) ? -1000.0f : vmax[m] * F_HALF_LOG10_2);
-	}
-#if K1W_TIMING
-	if (p.dbg && (th & 255) == 0) {
-#pragma unroll
-		for (int i = 0; i < 16; i++)
-			p.dbg[((size_t)blockIdx.x * 2 + (th >> 8)) * 16 + i] = wacc[i];
-	}
-#endif
-#undef K1W_EPI
-#undef K1W_CB
-#undef K1W_COL
-}
+#define K1_ENTRY(name) name
+#define K1_SC16 0
+#define K1_IQ p.iq
+#include "k1w_fft_bin.inc"
+#undef K1_ENTRY
+#undef K1_SC16
+#undef K1_IQ
 
 /* ------------------------------------------------------------------------ */
 /* K1 for N = 65536: radix-16 plan, two stages, the intermediate in the XCD's L2 */
@@ -1926,533 +919,34 @@ template <int NWV> struct K1hGeom {
 						/* (exchange, two twiddle tables, staged input, thresholds) */
 };
 
-template <bool HALF, bool WRITE_FFT, int NWV>
-__global__ __launch_bounds__(64 * NWV, 2)
-void k1h_fused(const K1Params p)
-{
-	constexpr int N = 65536;
-	typedef K1hGeom<NWV> G;
-	constexpr int NT = 64 * NWV, kMem = G::kMem, kRpm = G::kRpm, kXLen = G::kXLen, kInLen = G::kInLen;
-	/* Every wait on another work-group is bounded (a poll is ~1 us: seconds, far beyond any legitimate wait): a protocol failure
-	 * ends the kernel with an error word the host turns into -EIO, it does not hang the GPU. */
-	constexpr uint32_t kSpinLimit = 4u << 20;
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-	v2f *xa_all = reinterpret_cast<v2f *>(smem_raw);		/* stage A: one private exchange region per wave ... */
-	v2f *xb = xa_all;						/* ... stage B: the work-group's exchange array, in the same memory */
-	v2f *twa_t = xa_all + kXLen;					/* pass-2 twiddles [k2 16][8 of kTwRow] */
-	v2f *tw3_t = twa_t + 16 * kTwRow;				/* pass-3 twiddles of this member's 32 offsets [32][8 of kTwRow] */
-	uint32_t *inb = reinterpret_cast<uint32_t *>(tw3_t + kRpm * kTwRow);	/* fp16 IQ of the next two spectra (two buffers of kInLen dwords) */
-	/* the exact-bin thresholds: the rare path that consults them must not wait for the loads and stores in flight (LDS reads have
-	 * their own counter) */
-	typedef const __attribute__((address_space(3))) double *lds_cdp;
-	double *thr_g = reinterpret_cast<double *>(inb + 2 * kInLen);
-	const lds_cdp thr_l = (lds_cdp)thr_g;
+#define K1_ENTRY(name) name
+#define K1_SC16 0
+#define K1_IQ p.iq
+#include "k1h_fused.inc"
+#undef K1_ENTRY
+#undef K1_SC16
+#undef K1_IQ
 
-	const int tid = threadIdx.x;
-	/* Cluster formation.  A work-group takes a ticket from the counter of the XCD it actually runs on (XCC_ID):
-	 * tickets 8c .. 8c + 7 of an XCD are cluster c of that XCD, whatever the dispatcher did.  A cluster works once
-	 * its 8 members are resident; complete clusters claim tiles until none is left, and a cluster still forming
-	 * when the tiles run out (another kernel holds the CUs its members need) is abandoned as a whole: progress
-	 * never depends on a work-group that is not resident. */
-	__shared__ int sh_ticket, sh_tile;
-	uint32_t xcc;
-	asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-	xcc &= 7;
-	uint32_t *next_tile = p.sync + 63 * 64 + 56;		/* (on the last cluster's line; tickets sit at word 48) */
-	const int ntiles = p.total / p.tile;
-	if (tid == 0) {
-		uint32_t *tick = p.sync + xcc * 8 * 64 + 48;		/* on the line of the XCD's first cluster */
-		const uint32_t tk = __hip_atomic_fetch_add(tick, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		int ok = 0;
-		if (tk < 64) {
-			/* the cluster's state: 0 forming, 1 complete (set by the holder of its 8th ticket: all 8 are resident),
-			 * 2 abandoned (set by a member that saw the tiles run out first) -- one compare-and-swap decides */
-			uint32_t *state = p.sync + ((int)xcc * 8 + (int)(tk / kMem)) * 64 + 24;
-			uint32_t st = 0;
-			if ((tk % kMem) == kMem - 1) {
-				__hip_atomic_compare_exchange_strong(state, &st, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				st = __hip_atomic_load(state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			} else {
-				uint32_t spins = 0;
-				while ((st = __hip_atomic_load(state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
-					const bool tiles_left = (int)__hip_atomic_load(next_tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ntiles;
-					if (!tiles_left || ++spins > kSpinLimit) {	/* (a cluster that never fills is abandoned, never waited for) */
-						if (tiles_left)
-							*p.sync_err = 0x80000004u;	/* ... but with work left that is a failed call, not a quiet exit */
-						uint32_t expect = 0;
-						__hip_atomic_compare_exchange_strong(state, &expect, 2u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					}
-					__builtin_amdgcn_s_sleep(8);
-				}
-			}
-			ok = (st == 1);
-		}
-		sh_ticket = ok ? (int)tk : -1;
-	}
-	__syncthreads();
-	/* The counters reset themselves: the last work-group to leave the kernel (an exit ticket, drawn behind everything else a work-group
-	 * does with them) zeroes the whole array for the next launch -- no memset queued per frame (4.6 us each on this runtime). */
-	auto leave = [&]() {
-		__syncthreads();
-		if (tid == 0)
-			sh_ticket = (int)__hip_atomic_fetch_add(p.sync + 63 * 64 + 60, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		__syncthreads();
-		if (sh_ticket == (int)gridDim.x - 1)
-			for (int e = tid; e < 64 * 64; e += NT)
-				__hip_atomic_store(p.sync + e, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	};
-	if (sh_ticket < 0) {
-		leave();
-		return;
-	}
-	/* (everything that is the same for the whole work-group is forced into SGPRs: addresses are then a scalar base plus ONE
-	 * 32-bit per-lane offset -- global_load / global_store ... s[base:base+1] -- instead of a 64-bit vector add per access) */
-	const int ticket = __builtin_amdgcn_readfirstlane(sh_ticket);
-	const int member = ticket % kMem;
-	const int gc = (int)xcc * 8 + ticket / kMem;			/* cluster: up to 8 per XCD */
-	uint32_t *c_a = p.sync + gc * 64;				/* stage A done */
-	uint32_t *c_t = p.sync + gc * 64 + 16;				/* (round << 20) | tile, published by member 0 */
-	uint32_t *c_b = p.sync + gc * 64 + 32;				/* stage B has read the intermediate */
-	v2f *wint = reinterpret_cast<v2f *>(p.scratch) + (size_t)gc * N;	/* the cluster's intermediate: [offset / 32][residue][offset % 32] */
-	const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(wint);
-
-	const int lane = tid & 63;
-	const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-	const v2f *twg = reinterpret_cast<const v2f *>(p.tw);
-	const v2f two = { 2.0f, 2.0f };
-	const BinConst bk = { p.binA, p.binC, p.amb, p.kappa, p.n_bins, p.thr };
-	const float vmax_init = -1000.0f / F_HALF_LOG10_2;
-	const float top = (float)(bk.nb - 1);
-
-	/* ---- per-thread constants -------------------------------------------------------------------------------------
-	 * stage A: residue q = 32 member + 4 wave + (lane >> 4); pass-1 item a = lane & 15 reads m = a + 16 j; after the
-	 *          exchange the same lane is pass-2 item k2 = lane & 15 (twiddle index k2)
-	 * stage B: offset kk = 32 member + (tid & 31); pass-3 item a3 = tid >> 5 reads residues q = a3 + 16 j3 (twiddle
-	 *          index kk); after the exchange the same thread is pass-4 item jj3 = tid >> 5 (twiddle index kk + 256 jj3)
-	 *          and owns columns kk + 256 jj3 + 4096 jj4 */
-	const int sa = lane >> 4, ia = lane & 15;
-	const int qa = kRpm * member + 4 * wv + sa;
-	const int kkl = tid % kRpm, ib = tid / kRpm;
-	const int kk = kRpm * member + kkl;
-	const int col0 = kk + 256 * ib;
-	const unsigned ucol0 = (unsigned)col0;				/* the one per-lane offset of every output access */
-	/* the intermediate is [offset / kRpm][residue][offset % kRpm].  32 offsets per block: see the stores below; 16: a row is one 128-byte run */
-	const unsigned wst0 = kRpm == 32 ? 8u * (unsigned)(qa * 32 + (ia ^ ((qa & 1) << 4)))		/* stage-A stores of even / odd jj (byte offsets) */
-	                                 : 8u * (unsigned)(qa * 16 + ia);
-	const unsigned wst1 = wst0 ^ 128u;
-	const unsigned wld = kRpm == 32 ? 8u * (unsigned)(ib * 32 + (kkl ^ ((ib & 1) << 4)))		/* stage-B loads */
-	                                : 8u * (unsigned)(ib * 16 + kkl);
-	const __amdgpu_buffer_rsrc_t rs_wf = make_rsrc(p.wf), rs_part = make_rsrc(p.partial);
-
-	const v2f w16c = twg[p.tw_off[0]], w8c = twg[p.tw_off[0] + 1], w163c = twg[p.tw_off[0] + 2];	/* W16, W8, W16^3: the first pass */
-	v2f wab[HALF ? 8 : 1];						/* wab[j]: the window taps of this thread's pass-1 inputs j and j + 8, the pair of
-									 * a stage-A butterfly (fp32 IQ, not a BASELINE configuration at this length: read
-									 * where they are used -- its 32 staging registers leave no room for them) */
-#pragma unroll
-	for (int j = 0; j < (HALF ? 8 : 1); j++)
-		wab[j] = v2f{ p.win[qa + 256 * (ia + 16 * j)], p.win[qa + 256 * (ia + 16 * (j + 8))] };
-	v2f tw4[8];							/* pass 4: w^8, w^4, w^2, w^2 W8, w, w W16, w W8, w W16^3 of k = kk + 256 ib */
-#pragma unroll
-	for (int j = 0; j < 8; j++)
-		tw4[j] = twg[p.tw_off[3] + (kk + 256 * ib) * 8 + j];
-	for (int e = tid; e <= p.n_bins && e < kThrMax; e += NT)
-		thr_g[e] = p.thr[e];
-	for (int e = tid; e < 16 * 8; e += NT)
-		twa_t[(e >> 3) * kTwRow + (e & 7)] = twg[p.tw_off[1] + e];
-	for (int e = tid; e < kRpm * 8; e += NT)
-		tw3_t[(e >> 3) * kTwRow + (e & 7)] = twg[p.tw_off[2] + (kRpm * member) * 8 + e];
-	__syncthreads();
-
-	v2f *xa = xa_all + wv * kXaWave;
-	const int ea_w = sa * 272 + ia;			/* + 17 jj : pass-1 outputs [residue][jj][a] */
-	const int ea_r = sa * 272 + ia * 17;		/* + j2    : pass-2 inputs of item k2 = ia */
-	const int eb_w = kkl * 257 + ib;		/* + 16 jj3: pass-3 outputs [offset][jj3][a3] */
-	const int eb_r = kkl * 257 + ib * 16;		/* + j4    : pass-4 inputs of item jj3 = ib */
-
-	if (K1H_PRIO && wv >= NWV / 2)
-		__builtin_amdgcn_s_setprio(2);
-	uint32_t done = 0;						/* spectra this cluster has finished */
-	uint32_t round = 0;						/* tiles this cluster has taken */
-
-	typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-	/* fp16 IQ: the work-group fetches its 32 residues of a spectrum as whole 128-byte runs STRAIGHT INTO LDS (buffer_load_dwordx4 ... lds:
-	 * no staging registers, no ds_write pass) -- one wave-instruction lands 64 x 16 B = 8 rows x 128 B back to back, so rows cannot be
-	 * padded; the 16-byte piece pc of row m sits at slot 8 m + (pc ^ (m & 7)) instead (the permutation is applied to the per-lane SOURCE
-	 * address and again to the read address; a wave's reads meet two-way conflicts at most).  A wave then finds the rows of its four
-	 * residues in LDS (a wave gathering its own 16-byte pieces straight from memory touches every line eight times over: measured
-	 * +205 us per frame against +37).  Two buffers: spectrum u of a tile in buffer u & 1.
-	 * fp32 IQ (not a BASELINE configuration at this length) is gathered per lane where it is used. */
-	/* (16 residues per member: rows of 64 B, one wave-instruction lands 16 of them; piece pc of row m at slot 4 m + (pc ^ ((m >> 2) & 3)):
-	 * the 64 lanes of a read -- 16 rows x the 4 dwords of one piece -- then fall into 64 different banks) */
-	constexpr int kRowsPerDma = 256 / kRpm;			/* rows one wave-instruction lands: 8 / 16 */
-	const uint32_t iq_vo = kRpm == 32 ? 1024u * (unsigned)(lane >> 3) + 16u * (unsigned)((lane & 7) ^ ((lane >> 3) & 7))
-	                                  : 1024u * (unsigned)(lane >> 2) + 16u * (unsigned)((lane & 3) ^ ((lane >> 4) & 3));
-	const int in_rd  = kRpm == 32 ? ia * 32 + ((wv ^ (ia & 7)) << 2) + sa	/* + kRpm * 16 j: row m = ia + 16 j, residue 4 wave + sa (dwords) */
-	                              : ia * 16 + ((wv ^ ((ia >> 2) & 3)) << 2) + sa;
-	const uint32_t inb_lds = (uint32_t)(size_t)(__attribute__((address_space(3))) void *)inb;
-	if (PROBE_K1H(p) & 2)			/* (measurement only: noise-like input that is never loaded) */
-		for (int e = tid; e < 2 * kInLen; e += NT)
-			inb[e] = ((0x211fu + 977u * e) & 0x3fffu) | 0x20000000u | (((0x2c11u + 131u * e) & 0x3fffu) << 16) | ((e & 1u) << 15) | ((e & 2u) << 30);
-	auto fetch_iq = [&](int t, int buf) {		/* row groups g = wave, wave + NWV - 1, ... (256 dwords each) into buffer `buf`; the last wave
-							 * requests nothing: it polls the cluster counters, and a poll returns behind whatever
-							 * its wave has in flight */
-		constexpr int kFetchWaves = K1H_SPOLL ? NWV : NWV - 1;	/* (K1H_SPOLL: nobody polls through the vector path, every wave fetches) */
-		if (!HALF || (PROBE_K1H(p) & 2) || wv >= kFetchWaves)
-			return;
-		if (PROBE_K1H(p) & 32) t = gc;	/* (measurement only: the same rows again and again) */
-		/* global_load_lds_dwordx4 by hand: the compiler parks every LDS read and every __syncthreads() that follows an LDS-DMA it
-		 * knows about behind s_waitcnt vmcnt(0) -- the request would be waited for at the very next barrier instead of an iteration
-		 * later.  Whoever reads the buffer is behind an explicit `s_waitcnt vmcnt(..)` of the requesting wave and a barrier. */
-		const uint32_t *src = reinterpret_cast<const uint32_t *>(p.iq) + (size_t)t * p.hop + kRpm * member;
-#pragma unroll 1
-		for (int g = wv; g < kRpm; g += kFetchWaves) {
-			const uint32_t *sk = src + 256 * kRowsPerDma * g;				/* 8 / 16 rows of 1 KiB */
-			const uint32_t la = inb_lds + 4u * (unsigned)(buf * kInLen + 256 * g);
-			uint32_t keep;
-			asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 " K1H_IQ_MOD "\n\ts_mov_b32 m0, %0"
-			             : "=&s"(keep) : "v"(iq_vo), "s"(sk), "s"(la) : "memory");
-		}
-	};
-
-	v2f ra[16];				/* stage A of the spectrum AFTER the one stage B is working on */
-	/* pass 1 (p = 1: no twiddles) of spectrum t and the 16 x 16 transpose inside the wave */
-	auto stage_a1 = [&](int t, int buf) {
-		if (PROBE_K1H(p) & 64) return;		/* (measurement only: stage B alone) */
-		const __amdgpu_buffer_rsrc_t rs_f = make_rsrc(p.iq + (size_t)t * p.hop);
-#pragma unroll
-		for (int jo = 0; jo < 16; jo++) {
-			const int j = K1H_PAIR(jo);
-			v2f xv;
-			if (HALF) {
-				const uint32_t raw = inb[buf * kInLen + in_rd + 16 * kRpm * j];
-				const h2 h = __builtin_bit_cast(h2, raw);
-				xv = v2f{ (float)h.x, (float)h.y };		/* v_cvt_f32_f16: exact */
-			} else if (PROBE_K1H(p) & 2) {
-				xv = v2f{ 0.01f * (float)(((tid * 37 + j * 11) & 63) - 32), 0.01f * (float)(((tid * 29 + j * 7) & 63) - 31) };
-			} else {
-				xv = bld_v2f<kAuxNT>(rs_f, 8u * (unsigned)(qa + 256 * ia), 32768u * j);
-			}
-			ra[j] = xv;
-		}
-		/* first pass (p = 1), the window of fft.cl:415-417 on its stage-A butterflies */
-		if constexpr (HALF) {
-			pass16_first<K1H_SC, false>(ra, wab, w16c, w8c, w163c, two);
-		} else {
-			v2f wl[8];
-#pragma unroll
-			for (int j = 0; j < 8; j++)
-				wl[j] = v2f{ p.win[qa + 256 * (ia + 16 * j)], p.win[qa + 256 * (ia + 16 * (j + 8))] };
-			pass16_first<K1H_SC, false>(ra, wl, w16c, w8c, w163c, two);
-		}
-	};
-	/* ... and the 16 x 16 transpose inside the wave that follows it */
-	auto stage_a1x = [&]() {
-		if (PROBE_K1H(p) & 64) return;
-#pragma unroll
-		for (int jj = 0; jj < 16; jj++)
-			xa[ea_w + 17 * jj] = ra[R16_PERM(jj)];
-		wave_lds_sync();
-#pragma unroll
-		for (int jo = 0; jo < 16; jo++)
-			ra[K1H_PAIR(jo)] = xa[ea_r + K1H_PAIR(jo)];
-		wave_lds_sync();
-	};
-	/* pass 2, p = 16, k = ia */
-#ifndef K1H_TW_REGS
-#define K1H_TW_REGS 0		/* 1: the pass-2 / pass-3 twiddles of a thread (fixed for its lifetime) in registers instead of 16 LDS reads per spectrum.
-				 * Measured (round 5): the kernel ALONE 2.6 % faster (15 850 against 16 270 cycles per spectrum, K1H_TIMING builds) -- and the
-				 * path 10 % slower (209 against 231 GSamples/s, three interleaved runs each): 233 instead of 209 VGPRs leave the scan / merge
-				 * kernels of the previous frame no registers on a CU this kernel occupies, and the frame's tail no longer runs beside it */
-#endif
-#if K1H_TW_REGS
-	v2f twa_r[8], tw3_r[8];
-#pragma unroll
-	for (int j = 0; j < 8; j++) {
-		twa_r[j] = twa_t[ia * kTwRow + j];
-		tw3_r[j] = tw3_t[kkl * kTwRow + j];
-	}
-#else
-	const v2f *twa_r = twa_t + ia * kTwRow;
-	const v2f *tw3_r = tw3_t + kkl * kTwRow;
-#endif
-	auto stage_a2_ab = [&]() { if (PROBE_K1H(p) & 64) return; pass16_ab<K1H_SC, false>(ra, twa_r[0], twa_r[1], two); };
-	auto stage_a2_cd = [&]() { if (PROBE_K1H(p) & 64) return; pass16_cd<K1H_SC, false>(ra, twa_r[2], twa_r[3], twa_r[4], twa_r[5], twa_r[6], twa_r[7], two); };
-	auto stage_a2 = [&]() { stage_a2_ab(); stage_a2_cd(); };
-
-#if K1H_TIMING
-	long long hacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-	long long hprev = __builtin_readcyclecounter();
-#endif
-	uint32_t *bins_lo = p.bins;					/* [total / 4][N] dwords: 4 spectra x low 8 bits */
-	uint32_t *bins_hi = p.bins + (size_t)(p.total >> 2) * N;	/* [total / tile][N] dwords: bit u = 9th bit of the tile's spectrum u */
-
-	for (;;) {
-	/* member 0 claims the cluster's next tile */
-	if (tid == 0) {
-		uint32_t v;
-		if (member == 0) {
-			v = __hip_atomic_fetch_add(next_tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			if (v > 0xfffffu) v = 0xfffffu;
-			__hip_atomic_store(c_t, ((round + 1) << 20) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		} else {
-			uint32_t spins = 0;
-			while (((v = __hip_atomic_load(c_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 20) != round + 1) {
-				if (++spins > kSpinLimit) { *p.sync_err = 0x80000001u; v = 0xfffffu; break; }	/* fail the call, not the GPU */
-				__builtin_amdgcn_s_sleep(2);
-			}
-			v &= 0xfffffu;
-		}
-		sh_tile = (int)v;
-	}
-	__syncthreads();				/* (also: every read of the exchange array by the previous tile's last spectrum is done) */
-	const int tile = __builtin_amdgcn_readfirstlane(sh_tile);
-	round++;
-	if (tile >= ntiles)
-		break;
-	const int t0 = tile * p.tile;
-	float live[16], vmax[16];
-	uint32_t plo[16], phi[16];
-#pragma unroll
-	for (int c = 0; c < 16; c++) { live[c] = 0.0f; vmax[c] = vmax_init; plo[c] = 0; phi[c] = 0; }
-	auto epilogue = [&](v2f (&r)[16], const int t, const int u) {
-		if (WRITE_FFT) {
-#pragma unroll
-			for (int c = 0; c < 16; c++)
-				bst_v2f<0>(r[R16_PERM(c)], make_rsrc(reinterpret_cast<v2f *>(p.fft_out) + (size_t)t * N), 8u * ucol0, 32768u * c);
-		}
-
-		/* epilogue (display.cl:136-150,161-168), 9-bit bin indices: low byte into the quad's dword, 9th bit into the tile's */
-		const bool store_row = (t >= p.wf_first) && !(PROBE_K1H(p) & 4);
-		const uint32_t wf_so = (uint32_t)((p.wf_pos0 + t) & p.wf_mask) * (uint32_t)(N * 4);
-		const int sh8 = 8 * (u & 3);
-		/* four samples at a time: fast path, ONE branch for the four (rare: some sample is not provably exact -- find it again and
-		 * decide it against the exact thresholds), then the updates and stores */
-#pragma unroll
-		for (int g = 0; g < 4; g++) {
-			float l2g[4]; uint32_t bng[4]; uint32_t amb = 0;
-#pragma unroll
-			for (int k = 0; k < 4; k++) {
-				const v2f x = r[R16_PERM(4 * g + k)];
-				uint32_t ab;
-				const float rr = bin_fast(x.x, x.y, bk, &l2g[k], &ab);
-				amb = amb > ab ? amb : ab;		/* v_max_u32: NaN / inf order above every finite measure */
-				bng[k] = (uint32_t)(int)__builtin_amdgcn_fmed3f(rr, 0.0f, top);
-			}
-			if (amb > __float_as_uint(bk.amb) && !(PROBE_K1H(p) & 16)) {
-#pragma unroll
-				for (int k = 0; k < 4; k++) {
-					const v2f x = r[R16_PERM(4 * g + k)];
-					const float v = __builtin_fmaf(bk.A, l2g[k], bk.C);
-					const float a = __builtin_fmaf(__builtin_fabsf(l2g[k]), bk.kappa, __builtin_fabsf(v - __builtin_rintf(v)));
-					if (!(a <= bk.amb)) {
-						float nl2;
-						bng[k] = bin_exact(x.x, x.y, l2g[k], (int)bng[k], thr_l, bk.nb, &nl2);
-						l2g[k] = nl2;
-					}
-				}
-			}
-#pragma unroll
-			for (int k = 0; k < 4; k++) {
-				const int c = 4 * g + k;
-				const uint32_t bn = bng[k];
-				const float l2v = l2g[k];
-				plo[c] |= (bn & 0xffu) << sh8;
-				phi[c] |= (bn >> 8) << u;
-				live[c] = __builtin_fmaf(live[c], p.w, l2v);
-				vmax[c] = max_f32(vmax[c], l2v);
-				/* rows and bin indices are streamed out non-temporally: plain stores allocate in the XCD's L2 and push the cluster's
-				 * intermediate out of it */
-				if (store_row)
-					__builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(l2v * F_HALF_LOG10_2), rs_wf, 4u * ucol0, wf_so + 16384u * c, K1H_OUT_AUX);
-			}
-		}
-		if ((u & 3) == 3 && !(PROBE_K1H(p) & 4)) {
-			const __amdgpu_buffer_rsrc_t rs_lo = make_rsrc(bins_lo + (size_t)(t >> 2) * N);
-#pragma unroll
-			for (int c = 0; c < 16; c++) {
-				__builtin_amdgcn_raw_buffer_store_b32(plo[c], rs_lo, 4u * ucol0, 16384u * c, K1H_OUT_AUX);
-				plo[c] = 0;
-			}
-		}
-	};
-	/* the tile's first spectrum: nothing to hide its stage A behind.  Input buffers: spectrum u of the tile in buffer u & 1 */
-	fetch_iq(t0, 0);
-	if (1 < p.tile)
-		fetch_iq(t0 + 1, 1);
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	wg_barrier_lds();
-	stage_a1(t0, 0);
-	stage_a1x();
-	wg_barrier_lds();				/* every wave has its rows out of buffer 0 */
-	if (2 < p.tile)
-		fetch_iq(t0 + 2, 0);
-	stage_a2();
-
-	/* The loop is skewed: while spectrum u's blocks travel to the L2 (stores), to the other members (cluster wait) and back (loads),
-	 * the same threads run stage A of spectrum u + 1 -- its first pass between the stores and the arrival at the cluster barrier,
-	 * its second between the loads of the intermediate and their use. */
-#pragma unroll 1
-	for (int u = 0; u < p.tile; u++) {
-		const int t = t0 + u;
-		const bool more = (u + 1 < p.tile);
-
-		K1H_STAMP(0);		/* loop overhead, tile claim (first spectrum of a tile) */
-		/* (every member has read the previous spectrum out of the intermediate: the last wave looked before its epilogue)
-		 * every read of the stage-B exchange array is done -- stage A writes the same memory */
-		if (K1H_SPOLL) {
-			/* every member has read the previous spectrum out of the intermediate? */
-			if (!(PROBE_K1H(p) & 1)) {
-				uint32_t spins = 0;
-				while ((int)(sload_fresh(c_b) - (uint32_t)kMem * done) < 0) {
-					if (++spins > kSpinLimit) { if (lane == 0) *p.sync_err = 0x80000002u; break; }
-					__builtin_amdgcn_s_sleep(1);
-				}
-			}
-		} else {
-			wg_barrier_lds();
-		}
-		K1H_STAMP(1);		/* top barrier: waiting for the work-group's slowest wave (K1H_SPOLL: this wave's own look at the counter) */
-		if (!(PROBE_K1H(p) & (8 | 512))) {
-			/* w[256 q + kk], kk = ia + 16 jj2, at [kk >> 5][q][(kk & 31) ^ 16 (q & 1)]: 16 lanes x 8 B = 128-byte runs; odd residues
-			 * keep their two halves swapped so that one store instruction (one jj for every lane) is spread over both halves of the
-			 * 256-byte rows -- both values of the address bit that picks an L2 channel -- instead of one */
-#pragma unroll
-			for (int jj = 0; jj < 16; jj++) {
-				if (kRpm == 32) bst_v2f<0>(ra[R16_PERM(jj)], rs_w, (jj & 1) ? wst1 : wst0, 65536u * (jj >> 1));
-				else            bst_v2f<0>(ra[R16_PERM(jj)], rs_w, wst0, 32768u * jj);	/* (one instruction: four residues = 512 B in a row) */
-			}
-		}
-		if (more)
-			stage_a1(t + 1, (u + 1) & 1);			/* (while the stores travel) */
-		K1H_STAMP(2);		/* intermediate stores issued + first pass of the next spectrum */
-		/* this wave's blocks are in the L2 (and the input rows it requested most of an iteration ago in LDS) */
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		K1H_STAMP(3);		/* waiting for the stores' acknowledgements (and the IQ requested an iteration ago) */
-		wg_barrier_lds();
-		if (tid == 0)
-			__hip_atomic_fetch_add(c_a, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		K1H_STAMP(4);		/* barrier + arrival */
-		if (more) {
-			if (K1H_SPLIT != 3)
-				stage_a1x();				/* (while the arrivals travel) */
-			if (K1H_SPLIT == 0)
-				stage_a2_ab();				/* second pass, stages A and B (C and D: beside the loads below) */
-			else if (K1H_SPLIT == 2)
-				stage_a2();
-		}
-
-		K1H_STAMP(5);		/* transpose (+ what of the second pass runs here) */
-		if (tid == 0 && !(PROBE_K1H(p) & 1)) {
-			uint32_t spins = 0;
-			while ((int)(__hip_atomic_load(c_a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (uint32_t)kMem * (done + 1)) < 0) {
-				if (++spins > kSpinLimit) { *p.sync_err = 0x80000003u; break; }
-				__builtin_amdgcn_s_sleep(1);
-			}
-		}
-		wg_barrier_lds();
-		asm volatile("" ::: "memory");
-		K1H_STAMP(6);		/* cluster barrier: poll + work-group barrier */
-
-		/* ================= stage B: offsets kk = 32 member .. + 31 ================= */
-		v2f r[16];
-		if (!(PROBE_K1H(p) & (8 | 256))) {
-			/* residues q = ib + 16 j3 (q & 1 = ib & 1); sc1: the loads miss the CU's L1 by construction and are served by the L2 */
-#pragma unroll
-			for (int jo = 0; jo < 16; jo++)
-				r[K1H_PAIR(jo)] = bld_v2f<kAuxSC1>(rs_w, wld, (uint32_t)(2048 * kRpm) * member + (uint32_t)(128 * kRpm) * K1H_PAIR(jo));
-		} else {
-#pragma unroll
-			for (int j = 0; j < 16; j++)
-				r[j] = ra[j];
-		}
-		if (more) {						/* (while the loads travel) */
-			if (K1H_SPLIT == 0)
-				stage_a2_cd();
-			else if (K1H_SPLIT == 1)
-				stage_a2();
-			else if (K1H_SPLIT == 3) {
-				stage_a1x();
-				stage_a2();
-			}
-		}
-		K1H_STAMP(7);		/* loads of the intermediate issued + second pass of the next spectrum */
-		if (!(PROBE_K1H(p) & 128))	/* (128, measurement only: stage A alone -- no stage-B arithmetic, exchange or epilogue; the barriers stay) */
-		pass16_ab<K1H_SC, false>(r, tw3_r[0], tw3_r[1], two);				/* pass 3, p = 256, k = kk */
-#if K1H_TIMING
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-		K1H_STAMP(8);		/* third pass, stages A and B: includes the wait for the loads */
-		/* spectrum u + 3 is requested into the buffer spectrum u + 1 has been read out of by every wave (two barriers ago); it is
-		 * waited for by the `vmcnt(0)` of the NEXT iteration.  Requested only now that the loads of the intermediate have been used:
-		 * loads return in order, and these come from HBM */
-		if (u + 3 < p.tile)
-			fetch_iq(t + 3, (u + 1) & 1);
-		if (!(PROBE_K1H(p) & 128)) {
-		pass16_cd<K1H_SC, false>(r, tw3_r[2], tw3_r[3], tw3_r[4], tw3_r[5], tw3_r[6], tw3_r[7], two);
-#pragma unroll
-		for (int jj = 0; jj < 16; jj++)
-			xb[eb_w + 16 * jj] = r[R16_PERM(jj)];
-		} else {
-			asm volatile("s_waitcnt vmcnt(0)" :: "v"(r[0]), "v"(r[15]) : "memory");
-		}
-		K1H_STAMP(9);		/* IQ request + third pass, stages C and D + exchange stores */
-		wg_barrier_lds();
-		if (tid == 0)							/* everybody's loads of the intermediate have landed */
-			__hip_atomic_fetch_add(c_b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		done++;
-		K1H_STAMP(10);		/* exchange barrier */
-		if (!(PROBE_K1H(p) & 128)) {
-#pragma unroll
-		for (int jo = 0; jo < 16; jo++)
-			r[K1H_PAIR(jo)] = xb[eb_r + K1H_PAIR(jo)];
-		pass16_ab<K1H_SC, false>(r, tw4[0], tw4[1], two);					/* pass 4, p = 4096, k = kk + 256 ib */
-		pass16_cd<K1H_SC, false>(r, tw4[2], tw4[3], tw4[4], tw4[5], tw4[6], tw4[7], two);
-		}
-
-		K1H_STAMP(11);		/* exchange loads + fourth pass */
-		/* every member has read this spectrum out of the intermediate?  (they said so about a pass ago.)  Asked here because this
-		 * wave has nothing in flight now: behind the epilogue's stores the answer would wait for them.  (Round 5, K1H_TIMING build: the
-		 * ~2000 cycles this wave spends here per spectrum are the spread between the cluster's members, not a round trip -- requesting
-		 * the counter one pass EARLIER and looking at the answer here returned "not yet" and cost 50 us per frame on top.) */
-		if (!K1H_SPOLL && tid == NT - 64 && !(PROBE_K1H(p) & 1)) {
-			uint32_t spins = 0;
-			while ((int)(__hip_atomic_load(c_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (uint32_t)kMem * done) < 0) {
-				if (++spins > kSpinLimit) { *p.sync_err = 0x80000002u; break; }
-				__builtin_amdgcn_s_sleep(1);
-			}
-		}
-
-		K1H_STAMP(12);		/* "everyone has read the intermediate" poll (last wave only) */
-		if (!(PROBE_K1H(p) & 128))
-		epilogue(r, t, u);
-		K1H_STAMP(13);		/* epilogue */
-	}
-	if (!(PROBE_K1H(p) & 4)) {
-		const __amdgpu_buffer_rsrc_t rs_hi = make_rsrc(bins_hi + (size_t)tile * N);
-#pragma unroll
-		for (int c = 0; c < 16; c++)
-			__builtin_amdgcn_raw_buffer_store_b32(phi[c], rs_hi, 4u * ucol0, 16384u * c, K1H_OUT_AUX);
-	}
-#pragma unroll
-	for (int c = 0; c < 16; c++)
-		bst_v2f<0>(v2f{ live[c] * F_HALF_LOG10_2, (vmax[c] == vmax_init) ? -1000.0f : vmax[c] * F_HALF_LOG10_2 },
-		           rs_part, 8u * ucol0, (uint32_t)tile * (uint32_t)(N * 8) + 32768u * c);
-	}
-#if K1H_TIMING
-	if (p.dbg && lane == 0 && (wv == 0 || wv == NWV / 2 - 1 || wv == NWV - 1)) {
-		const int slot = (wv == 0) ? 0 : (wv == NWV / 2 - 1) ? 1 : 2;
-		for (int i = 0; i < 16; i++)
-			p.dbg[((size_t)blockIdx.x * 3 + slot) * 16 + i] = hacc[i];
-	}
-#endif
-	leave();
-}
+/* The sc16 entry points: the same kernel text, K1_SC16 = 1 (compiled behind every fp32 / fp16 kernel, which therefore keep their
+ * place and code in the listing) */
+#define K1_ENTRY(name) name##_sc16
+#define K1_SC16 1
+#define K1_IQ reinterpret_cast<const uint32_t *>(p.iq)
+#include "k1_fft_bin.inc"
+#include "k1v2_fft_bin.inc"
+#include "k1big_fft_bin.inc"
+#include "k1w_fft_bin.inc"
+#include "k1h_fused.inc"
+#undef K1_ENTRY
+#undef K1_SC16
+#undef K1_IQ
 
 template <int NWV>
 static hipError_t launch_k1h_form(const K1Params &p0, hipStream_t s)
 {
 	typedef void (*k1h_fn)(const K1Params);
-	static const k1h_fn fn[4] = { k1h_fused<false, false, NWV>, k1h_fused<true, false, NWV>, k1h_fused<false, true, NWV>, k1h_fused<true, true, NWV> };
+	static const k1h_fn fn[6] = { k1h_fused<false, false, NWV>, k1h_fused<true, false, NWV>, k1h_fused<false, true, NWV>, k1h_fused<true, true, NWV>,
+	                              k1h_fused_sc16<true, false, NWV>, k1h_fused_sc16<true, true, NWV> };
 	constexpr size_t lds = K1hGeom<NWV>::kLds;
 	/* (the attribute belongs to the function object of the CURRENT device: once per device, not once per process) */
 	static unsigned long long attr_dev = 0;
@@ -2460,7 +954,7 @@ static hipError_t launch_k1h_form(const K1Params &p0, hipStream_t s)
 	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
 		return hipErrorInvalidDevice;
 	if (!(attr_dev >> dev & 1)) {
-		for (int i = 0; i < 4; i++) {
+		for (int i = 0; i < 6; i++) {
 			const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 			if (e != hipSuccess)
 				return e;
@@ -2469,7 +963,8 @@ static hipError_t launch_k1h_form(const K1Params &p0, hipStream_t s)
 	}
 	/* (the counters in p0.sync are zero: cleared at allocation, and by the last work-group of every launch) */
 	/* 32 clusters: 8 work-groups of 8 waves, one per CU -- or 16 work-groups of 4 waves, two per CU */
-	hipLaunchKernelGGL(fn[(p0.iq_half ? 1 : 0) | (p0.fft_out ? 2 : 0)], dim3(256 * 8 / NWV), dim3(64 * NWV), lds, s, p0);
+	const int which = p0.iq_format == kIqSc16 ? 4 + (p0.fft_out ? 1 : 0) : (p0.iq_format == kIqFp16 ? 1 : 0) | (p0.fft_out ? 2 : 0);
+	hipLaunchKernelGGL(fn[which], dim3(256 * 8 / NWV), dim3(64 * NWV), lds, s, p0);
 	return hipGetLastError();
 }
 
@@ -2486,6 +981,9 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 {
 	if (p.variant == 4)
 		return launch_k1h(p, s);
+	if (p.iq_format != kIqFp32 && p.iq_format != kIqSc16)
+		return hipErrorInvalidValue;		/* (fp16: the 65536-point kernel only) */
+	const bool sc16 = p.iq_format == kIqSc16;
 	const int tiles = p.total / p.tile;
 	if (p.variant == 3) {
 		static unsigned long long attr_dev = 0;		/* (the attribute belongs to the function object of the CURRENT device: once per device) */
@@ -2494,7 +992,11 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 			constexpr int N = 1024;
 			constexpr int lds = (N + ((N / 2 - 8) / 7) * 7 + N / 2) * 8 + N * 4;		/* exchange slab + the reference's twiddles + window */
 			const int blocks = tiles < 4096 ? tiles : 4096;
-			if (p.fft_out)
+			if (sc16 && p.fft_out)
+				hipLaunchKernelGGL((k1big_fft_bin_sc16<10, true>), dim3(blocks), dim3(N / 8), lds, s, p);
+			else if (sc16)
+				hipLaunchKernelGGL((k1big_fft_bin_sc16<10, false>), dim3(blocks), dim3(N / 8), lds, s, p);
+			else if (p.fft_out)
 				hipLaunchKernelGGL((k1big_fft_bin<10, true>), dim3(blocks), dim3(N / 8), lds, s, p);
 			else
 				hipLaunchKernelGGL((k1big_fft_bin<10, false>), dim3(blocks), dim3(N / 8), lds, s, p);
@@ -2505,12 +1007,13 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 		/* N = 8192: 16 points per thread, tables in registers, overlap reuse in registers (k1w_fft_bin); any hop */
 		constexpr int ldsw = 2 * 8192 * 8 + 520 * 8;	/* two slabs + the exact-bin thresholds */
 		typedef void (*k1w_fn)(const K1Params);
-		static const k1w_fn fns[5] = { k1w_fft_bin<8>, k1w_fft_bin<4>, k1w_fft_bin<2>, k1w_fft_bin<1>, k1w_fft_bin<16> };
+		static const k1w_fn fns[10] = { k1w_fft_bin<8>, k1w_fft_bin<4>, k1w_fft_bin<2>, k1w_fft_bin<1>, k1w_fft_bin<16>,
+		                                k1w_fft_bin_sc16<8>, k1w_fft_bin_sc16<4>, k1w_fft_bin_sc16<2>, k1w_fft_bin_sc16<1>, k1w_fft_bin_sc16<16> };
 		int dev = 0;
 		if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
 			return hipErrorInvalidDevice;
 		if (!(attr_dev >> dev & 1)) {
-			for (int i = 0; i < 5; i++) {
+			for (int i = 0; i < 10; i++) {
 				hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fns[i]), hipFuncAttributeMaxDynamicSharedMemorySize, ldsw);
 				if (e != hipSuccess)
 					return e;
@@ -2524,13 +1027,17 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 		const int all_cus = p.n_cus > 0 ? p.n_cus : 256;
 		const int cus = (p.cus > 0 && p.cus < all_cus && tiles % p.cus == 0) ? p.cus : all_cus;
 		const int bw = tiles < cus ? tiles : cus;
-		hipLaunchKernelGGL(fns[which], dim3(bw), dim3(512), ldsw, s, p);
+		hipLaunchKernelGGL(fns[which + (sc16 ? 5 : 0)], dim3(bw), dim3(512), ldsw, s, p);
 		return hipGetLastError();
 	}
 	if (p.variant == 2) {
 		const int maxb = 256 * 2 * K1V2_WAVES_PER_SIMD;	/* resident 2-wave work-groups on 256 CUs */
 		int blocks = tiles < maxb ? tiles : maxb;
-		if (p.fft_out)
+		if (sc16 && p.fft_out)
+			hipLaunchKernelGGL(k1v2_fft_bin_sc16<true>, dim3(blocks), dim3(128), 0, s, p);
+		else if (sc16)
+			hipLaunchKernelGGL(k1v2_fft_bin_sc16<false>, dim3(blocks), dim3(128), 0, s, p);
+		else if (p.fft_out)
 			hipLaunchKernelGGL(k1v2_fft_bin<true>, dim3(blocks), dim3(128), 0, s, p);
 		else
 			hipLaunchKernelGGL(k1v2_fft_bin<false>, dim3(blocks), dim3(128), 0, s, p);
@@ -2542,7 +1049,14 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 	                                   return (v > 0 && v < kK1MaxBlocks) ? v : kK1MaxBlocks; }();
 	if (blocks > max_blocks)
 		blocks = max_blocks;		/* persistent: 2 work-groups per CU */
-	if (p.fft_out)
+	if (sc16) {
+		if (p.fft_out)
+			hipLaunchKernelGGL((k1_fft_bin_sc16<true, false>), dim3(blocks), dim3(256), 0, s, p);
+		else if (p.n_bins == 256)
+			hipLaunchKernelGGL((k1_fft_bin_sc16<false, true>), dim3(blocks), dim3(256), 0, s, p);
+		else
+			hipLaunchKernelGGL((k1_fft_bin_sc16<false, false>), dim3(blocks), dim3(256), 0, s, p);
+	} else if (p.fft_out)
 		hipLaunchKernelGGL((k1_fft_bin<true, false>), dim3(blocks), dim3(256), 0, s, p);
 	else
 		if (p.n_bins == 256)

@@ -32,6 +32,13 @@ extern "C" {
  * wf_rows 1024 (cl.c:528), t0r 16, t0d 1024, alpha 0.002 (cl.c:714-716). */
 #define FOSPHOR_AMD_IQ_FP32 0	/* interleaved float (re, im), 8 B per sample: the reference's format */
 #define FOSPHOR_AMD_IQ_FP16 1	/* interleaved IEEE half (re, im), 4 B per sample; fft_len_log = 16 only */
+#define FOSPHOR_AMD_IQ_SC16 2	/* interleaved little-endian int16 (re, im), 4 B per sample (UHD "sc16"); every fft_len_log.
+				 * The sample value is (re * 2^-15, im * 2^-15): full scale is +-1.0, -32768 is exactly -1.0.  The
+				 * widening is exact, so an sc16 instance leaves every buffer bit-identical to an fp32 instance of the
+				 * same geometry fed float(i) * 2^-15 through the same calls.  Device pointers to sc16 samples must
+				 * be 4-byte aligned (-EINVAL otherwise, nothing is launched); at fft_len_log = 10 an 8-byte aligned
+				 * pointer with an even hop runs the faster kernel.  fosphor_amd_traffic_twin and
+				 * fosphor_amd_tune_placement return -EINVAL on sc16 instances (they time the fp32 kernel). */
 
 struct fosphor_amd_config
 {
@@ -43,14 +50,16 @@ struct fosphor_amd_config
 	int   max_spectra;	/* capacity of one launch (all batches together); 0 = 1024 */
 	int   max_batches;	/* most batches in one launch; 0 = max(8, max_spectra/1024) */
 	void *stream;		/* hipStream_t to run on; NULL = create a private one */
-	int   iq_format;	/* FOSPHOR_AMD_IQ_*: format of every sample buffer handed to this instance */
+	int   iq_format;	/* FOSPHOR_AMD_IQ_*: format of every sample buffer handed to this instance (fosphor_process,
+				 * process_device*, accumulate_device*, process_pinned, upload_pinned, the fosphor_amd_fft hook);
+				 * lengths, batches and hops are counted in samples whatever the format */
 };
 
 /* fosphor_init with explicit geometry.  NULL on failure (message on stderr). */
 struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg);
 
 /* Process IQ that is ALREADY in device memory: n_batches consecutive batches of
- * `batch` spectra each (batch % 16 == 0), interleaved fp32 (re, im).
+ * `batch` spectra each (batch % 16 == 0), in the instance's iq_format (fp32 (re, im) by default).
  * Semantics are identical to n_batches successive fosphor_process() calls of
  * batch*N samples each (cl.c:870-968) -- every batch gets its own histogram /
  * live / max-hold update in order -- but the FFT+binning of all batches runs
@@ -113,7 +122,7 @@ int fosphor_amd_get_buffers_nohc(struct fosphor *self, struct fosphor_amd_buffer
 int fosphor_amd_read(struct fosphor *self, int which, void *host, uint64_t bytes);
 
 /* Kernel-level test hook: windowed forward FFT only (the fft1D_1024 contract,
- * fft.cl:397-466): d_in, d_out are float2[n_spectra][N] device buffers; n_spectra a multiple of 4
+ * fft.cl:397-466): d_in, d_out are float2[n_spectra][N] device buffers (d_in in the instance's iq_format); n_spectra a multiple of 4
  * (of 8 at fft_len_log = 13), at most max_spectra; -EINVAL otherwise. */
 int fosphor_amd_fft(struct fosphor *self, const void *d_in, void *d_out, int n_spectra);
 

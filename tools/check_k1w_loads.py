@@ -6,7 +6,9 @@ The kernel requests the next spectrum's IQ with `buffer_load_dwordx2` written as
 only correct if NOTHING reads or writes those registers between a request and the wait: a register-allocator copy in between would copy
 stale data.  This script compiles the kernels to assembly and checks exactly that, for every instantiation:
 
-    python3 tools/check_k1w_loads.py [kernels.s]        (without an argument: runs hipcc -S itself)
+    python3 tools/check_k1w_loads.py [--sc16] [kernels.s]        (without a file: runs hipcc -S itself)
+
+--sc16 checks the sc16 entry points (k1w_fft_bin_sc16: one `buffer_load_dword` per row) instead, and requires ScratchSize 0.
 
 Exit status 0 and one line per kernel if the property holds."""
 import os
@@ -34,9 +36,12 @@ def regs(line):
     return out
 
 
-def check(path):
+def check(path, sc16=False):
     src = open(path).read().splitlines()
-    starts = [i for i, l in enumerate(src) if re.match(r"^_ZN11fosphor_amd11k1w_fft_binILi\d+EEEvNS_8K1ParamsE:", l)]
+    sym = r"^_ZN11fosphor_amd16k1w_fft_bin_sc16ILi\d+EEEvNS_8K1ParamsE:" if sc16 else r"^_ZN11fosphor_amd11k1w_fft_binILi\d+EEEvNS_8K1ParamsE:"
+    req = r"buffer_load_dword " if sc16 else r"buffer_load_dwordx[24] "
+    req_dst = r"buffer_load_dword v(\d+)()," if sc16 else r"buffer_load_dwordx[24] v\[(\d+):(\d+)\]"
+    starts = [i for i, l in enumerate(src) if re.match(sym, l)]
     if not starts:
         raise SystemExit("no k1w_fft_bin instantiation found in %s" % path)
     report = []
@@ -60,13 +65,13 @@ def check(path):
         tail = max(i for i, _ in back)
         header = min(h for _, h in back)
         label = body[header].split(":")[0]
-        loads = [i for i in range(w, tail) if re.search(r"buffer_load_dwordx[24] ", body[i])]
+        loads = [i for i in range(w, tail) if re.search(req, body[i])]
         if not loads:
             raise SystemExit("%s: no IQ request inside the loop" % name)
         dests, bad = set(), []
         for ld in loads:		# a register is in flight from ITS request to the wait
-            m = re.search(r"buffer_load_dwordx[24] v\[(\d+):(\d+)\]", body[ld])
-            d = set(range(int(m.group(1)), int(m.group(2)) + 1))
+            m = re.search(req_dst, body[ld])
+            d = set(range(int(m.group(1)), int(m.group(2) or m.group(1)) + 1))
             dests |= d
             for i in list(range(ld + 1, tail + 1)) + list(range(header, w)):
                 l = body[i].strip()
@@ -115,6 +120,8 @@ def check(path):
         if hot_spills:
             raise SystemExit("%s: %d basic block(s) of the spectrum loop spill or reload outside the fft_out test path" % (name, hot_spills))
         scratch = next((int(m.group(1)) for l in src[st:end + 200] for m in [re.search(r";\s*ScratchSize:\s*(\d+)", l)] if m), -1)
+        if sc16 and scratch != 0:
+            raise SystemExit("%s: ScratchSize %d bytes per lane (the sc16 forms must not spill at all)" % (name, scratch))
         if scratch > 64:
             raise SystemExit("%s: ScratchSize %d bytes per lane (budget: 64, all of it outside the spectrum loop)" % (name, scratch))
         report.append("%s: %d requests -> v%d..v%d, untouched until the wait (loop %s, %d lines); vmcnt(%d) = %d index stores per wave; "
@@ -124,11 +131,14 @@ def check(path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1:
-        lines = check(sys.argv[1])
+    args = sys.argv[1:]
+    sc16 = "--sc16" in args
+    args = [a for a in args if a != "--sc16"]
+    if args:
+        lines = check(args[0], sc16)
     else:
         with tempfile.TemporaryDirectory() as d:
             out = os.path.join(d, "kernels.s")
             compile_asm(out)
-            lines = check(out)
+            lines = check(out, sc16)
     print("\n".join(lines))
