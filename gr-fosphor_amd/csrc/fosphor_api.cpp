@@ -9,6 +9,7 @@
  *
  * There is no CPU fallback: without a HIP device fosphor_init() fails loudly.
  */
+#include <assert.h>
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>
@@ -745,6 +746,12 @@ static void prof_end(struct fosphor *self, hipStream_t st)
 	self->ev_used += 2;
 }
 
+/* The stream K2 / K3 and the exchanges run on: a second stream when the two-stream pipeline is on, else the main one */
+static hipStream_t count_stream(const struct fosphor *self)
+{
+	return self->overlap ? self->stream2 : self->stream;
+}
+
 static int sync_all(struct fosphor *self)
 {
 	int rv = 0;
@@ -833,6 +840,7 @@ static int pick_tile(const struct fosphor *self, int total, int batch)
 		return 4;
 	}
 	if (self->log2n == 13) {
+		assert(batch % 16 == 0);	/* (every entry point asks for it: the fallback tile of 8 divides the batch) */
 		/* one work-group per CU walks whole tiles; inside a tile the overlapped half of a window is reused from registers,
 		 * so long tiles fetch less (tile 64 at 50 % overlap: 65 half-windows for 64 spectra) and leave fewer partial rows;
 		 * every CU gets a tile (measured, 16384 spectra per launch: tile 16 / 32 / 64 -> 279 / 288 / 289 GSamples/s) */
@@ -960,12 +968,48 @@ extern "C" int fosphor_amd_plan_piece_batches(int log2n, int overlap, int n_batc
 	return sub_b;
 }
 
+/* The count-kernel fields every K2 launch sets alike: `total` spectra of the current set's bin indices / tile partials in batches of
+ * `batch`, counted `chunk` spectra per work-group; the first of them is spectrum t_offset of a batch of weight_batch (live-sum weights) */
+static void fill_k2(const struct fosphor *self, K2Params *k2, int total, int batch, int chunk, int tile, int t_offset, int weight_batch)
+{
+	memset(k2, 0, sizeof(*k2));
+	k2->bins = self->d_bins; k2->partial = self->d_partial;
+	k2->n = self->n; k2->bins16 = self->bins16 && self->log2n != 13; k2->bins8p1 = (self->log2n == 13);
+	k2->bins9 = (self->log2n == 16); k2->total = total;
+	k2->batch = batch; k2->chunk = chunk; k2->tile = tile; k2->n_bins = self->n_bins;
+	k2->w = 1.0f - self->alpha;
+	k2->log2_w = (float)log2((double)(1.0f - self->alpha));
+	k2->t_offset = t_offset; k2->weight_batch = weight_batch;
+#ifdef FOSPHOR_AMD_PROBES
+	{
+		static const int dbg_same = getenv("FOSPHOR_AMD_DBG_SAME") != NULL;
+		k2->dbg_same = dbg_same;
+	}
+#endif
+}
+
+/* The per-chunk float partials of n_batches batches of cpb chunks each, reduced into live-sum / max slot lslot; sum16: the chunks'
+ * 16-bit count slabs in d_slab16 added into the 32-bit hit counts of slot slot0 as well (k2c_sum) */
+static hipError_t launch_chunk_sum(struct fosphor *self, int n_batches, int cpb, int slot0, int lslot, int sum16, hipStream_t st)
+{
+	K2bParams k2b;
+	memset(&k2b, 0, sizeof(k2b));
+	k2b.chunk_sum = self->d_chunk_sum; k2b.chunk_max = self->d_chunk_max;
+	k2b.live_sum = self->d_live_sum + (size_t)lslot * self->n;
+	k2b.vmax = self->d_vmax + (size_t)lslot * self->n;
+	k2b.n_batches = n_batches; k2b.cpb = cpb; k2b.n = self->n;
+	if (!sum16)
+		return launch_k2b(k2b, st);
+	k2b.hc16 = self->d_slab16; k2b.hc = self->d_hc + (size_t)slot0 * self->n_bins * self->n; k2b.n_bins = self->n_bins;
+	return launch_k2c(k2b, st);
+}
+
 /* K2 (+K2b) for n_batches batches of `batch` spectra whose bin indices / tile partials are in
  * d_bins / d_partial; results land in slot `slot0`.. of hc / live_sum / vmax. */
 static int run_count(struct fosphor *self, int n_batches, int batch, int tile, int slot0,
                      int t_offset, int weight_batch, hipStream_t st, int use16 = 0, int hset = 0)
 {
-	K2Params k2; K2bParams k2b;
+	K2Params k2;
 	const int one_chunk = use16 && count_one_chunk(self, batch, n_batches);
 	const int chunk = (batch <= 1024 || one_chunk) ? batch : gcd_int(batch, 1024);
 	const int cpb = batch / chunk;
@@ -977,8 +1021,7 @@ static int run_count(struct fosphor *self, int n_batches, int batch, int tile, i
 	const int sum16 = (!use16 || batch > 1024) && chunk == 1024 && cpb > 1 && self->d_slab16 &&
 	                  n_batches * cpb <= self->slab_chunks && !self->kn_no_sum16;
 
-	memset(&k2, 0, sizeof(k2));
-	k2.bins = self->d_bins; k2.partial = self->d_partial;
+	fill_k2(self, &k2, n_batches * batch, batch, chunk, tile, t_offset, weight_batch);
 	k2.hc = self->d_hc + (size_t)slot0 * cells;
 	k2.hc16 = (use16 && (batch <= 1024 || one_chunk) && self->rise_ok(batch))
 	          ? (uint16_t *)self->d_hc + (size_t)hset * self->max_batches * cells : NULL;
@@ -990,18 +1033,6 @@ static int run_count(struct fosphor *self, int n_batches, int batch, int tile, i
 	if (sum16)
 		k2.hc16 = self->d_slab16, k2.rowmask = NULL;
 	const int lslot = slot0 + hset * self->max_batches;	/* live-sum / max slot */
-	k2.n = self->n; k2.bins16 = self->bins16 && self->log2n != 13; k2.bins8p1 = (self->log2n == 13);
-	k2.bins9 = (self->log2n == 16); k2.total = n_batches * batch;
-	k2.batch = batch; k2.chunk = chunk; k2.tile = tile; k2.n_bins = self->n_bins;
-	k2.w = 1.0f - self->alpha;
-	k2.log2_w = (float)log2((double)(1.0f - self->alpha));
-	k2.t_offset = t_offset; k2.weight_batch = weight_batch;
-#ifdef FOSPHOR_AMD_PROBES
-	{
-		static const int dbg_same = getenv("FOSPHOR_AMD_DBG_SAME") != NULL;
-		k2.dbg_same = dbg_same;
-	}
-#endif
 	if (cpb == 1) {
 		k2.chunk_sum = self->d_live_sum + (size_t)lslot * self->n;
 		k2.chunk_max = self->d_vmax + (size_t)lslot * self->n;
@@ -1014,19 +1045,8 @@ static int run_count(struct fosphor *self, int n_batches, int batch, int tile, i
 	prof_begin(self, 1, st);
 	HIP_TRY(launch_k2(k2, n_batches * cpb, st), "launch count");
 	self->k2_stream_last = st;
-	if (cpb > 1) {
-		memset(&k2b, 0, sizeof(k2b));
-		k2b.chunk_sum = self->d_chunk_sum; k2b.chunk_max = self->d_chunk_max;
-		k2b.live_sum = self->d_live_sum + (size_t)lslot * self->n;
-		k2b.vmax = self->d_vmax + (size_t)lslot * self->n;
-		k2b.n_batches = n_batches; k2b.cpb = cpb; k2b.n = self->n;
-		if (sum16) {
-			k2b.hc16 = k2.hc16; k2b.hc = k2.hc; k2b.n_bins = self->n_bins;
-			HIP_TRY(launch_k2c(k2b, st), "launch chunk sum");
-		} else {
-			HIP_TRY(launch_k2b(k2b, st), "launch chunk reduce");
-		}
-	}
+	if (cpb > 1)
+		HIP_TRY(launch_chunk_sum(self, n_batches, cpb, slot0, lslot, sum16, st), sum16 ? "launch chunk sum" : "launch chunk reduce");
 	prof_end(self, st);
 	return 0;
 error:
@@ -1160,6 +1180,76 @@ static int wf_leave(struct fosphor *self, hipStream_t ks)
 	return 0;
 }
 
+/* measurement only, probe builds (results are wrong): FOSPHOR_AMD_DBG_SKIP bit 0 = no K1, bit 1 = no count / merge, bit 2 = no K3,
+ * bit 3 = no K2 (bits 1-3: device-resident calls); FOSPHOR_AMD_DBG_NOWAIT: an FFT launch does not wait for the count kernel that
+ * still reads its intermediate set */
+#ifdef FOSPHOR_AMD_PROBES
+static int dbg_skip(void)
+{
+	static const int v = [] { const char *e = getenv("FOSPHOR_AMD_DBG_SKIP"); return e ? atoi(e) : 0; }();
+	return v;
+}
+static int dbg_nowait(void)
+{
+	static const int v = getenv("FOSPHOR_AMD_DBG_NOWAIT") != NULL;
+	return v;
+}
+#else
+static int dbg_skip(void) { return 0; }
+static int dbg_nowait(void) { return 0; }
+#endif
+
+/* One FFT launch ("piece") of sub_total spectra from d_iq on FFT stream ks; its first spectrum is spectrum t of the waterfall ring's
+ * time frame (its row goes to ring position wf_pos + t), and rows are stored for the spectra from first_row on (same frame).  The
+ * piece writes the next intermediate set of the rotation once the count kernel that read that set last is done, and the count
+ * stream waits for the piece.  Returns the set (k1_set_release() behind the count kernel that reads it), -1 on error. */
+static int k1_piece(struct fosphor *self, hipStream_t ks, const void *d_iq, int t, int sub_total, int tile, int first_row, int hop)
+{
+	K1Params k1;
+	const int set = self->pp;
+	int wf_first = first_row - t > 0 ? first_row - t : 0;
+	const int stores_rows = wf_first < sub_total;
+
+	self->pp = (self->pp + 1) % self->n_sets;
+	self->d_bins = self->d_bins_pp[set];
+	self->d_partial = self->d_partial_pp[set];
+	if (self->overlap && self->set_used[set] && !dbg_nowait())
+		HIP_TRY(hipStreamWaitEvent(ks, self->ev_set_free[set], 0), "wait for intermediate set");
+	if (!stores_rows)
+		wf_first = sub_total;
+	fill_k1(self, &k1, d_iq, sub_total, tile, (self->wf_pos + t) & (self->wf_rows - 1), wf_first, hop);
+	if (stores_rows && wf_enter(self, ks))
+		return -1;
+	prof_begin(self, 0, ks);
+	if (!(dbg_skip() & 1))
+		HIP_TRY(launch_k1(k1, ks), "launch fft_bin");
+	prof_end(self, ks);
+	if (self->log2n == 13) {
+		if (k1.cus) self->k1w_shared++; else self->k1w_full++;
+	}
+	if (stores_rows && wf_leave(self, ks))
+		return -1;
+	if (self->overlap) {
+		HIP_TRY(hipEventRecord(self->ev_k1_done[set], ks), "record K1 done");
+		HIP_TRY(hipStreamWaitEvent(count_stream(self), self->ev_k1_done[set], 0), "K2 waits for K1");
+	}
+	return set;
+error:
+	return -1;
+}
+
+/* ... behind the count kernel (queued on the count stream) that read intermediate set `set`: the set is free again */
+static int k1_set_release(struct fosphor *self, int set)
+{
+	if (self->overlap) {
+		HIP_TRY(hipEventRecord(self->ev_set_free[set], count_stream(self)), "record set free");
+		self->set_used[set] = 1;
+	}
+	return 0;
+error:
+	return -EIO;
+}
+
 /* n_batches consecutive batches of `batch` spectra.  device_call: the samples are the caller's device buffer
  * (fosphor_amd_process_device*), which may be cut into sub-launches whose K1s alternate between two streams. */
 static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch, int hop = 0, int device_call = 0)
@@ -1167,21 +1257,12 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 	const int total = n_batches * batch;
 	const size_t sample_bytes = self->sample_bytes;
 	const int hop_samples = hop ? hop : self->n;
-	hipStream_t st2 = self->overlap ? self->stream2 : self->stream;
+	hipStream_t st2 = count_stream(self);
 	/* third stream: only the 16-bit count path has a second hit-count set */
 	const int three = self->overlap && self->pipe3 && batch <= 1024 && self->rise_ok(batch);
 	hipStream_t st3 = three ? self->stream3 : st2;
 	const int did_prep = self->win_dirty || self->thr_dirty || self->state == ST_BOOTING;
-	const int wf_first_global = total > self->wf_rows ? total - self->wf_rows : 0;
-	int sub_b, n_sub, use_alt, used_alt = 0;
-	/* measurement only, probe builds (results are wrong): FOSPHOR_AMD_DBG_SKIP bit 0 = no K1, bit 1 = no count / merge, bit 2 = no K3,
-	 * bit 3 = no K2; FOSPHOR_AMD_DBG_NOWAIT: an FFT launch does not wait for the count kernel that still reads its intermediate set */
-#ifdef FOSPHOR_AMD_PROBES
-	static const int dbg_skip = [] { const char *e = getenv("FOSPHOR_AMD_DBG_SKIP"); return e ? atoi(e) : 0; }();
-	static const int dbg_nowait = getenv("FOSPHOR_AMD_DBG_NOWAIT") != NULL;
-#else
-	constexpr int dbg_skip = 0, dbg_nowait = 0;
-#endif
+	int sub_b, n_sub, use_alt;
 
 	if (prepare(self))
 		return -EIO;
@@ -1213,47 +1294,16 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 		const int nb = (n_batches - b0 < sub_b) ? n_batches - b0 : sub_b;
 		const int t0 = b0 * batch, sub_total = nb * batch;
 		const int tile = pick_tile(self, sub_total, batch);
-		hipStream_t ks = self->stream;
-		K1Params k1;
-		int set, hset = 0, wf_first, stores_rows;
+		hipStream_t ks = use_alt ? self->k1_streams[self->k1_seq++ % self->n_k1_streams] : self->stream;
+		const int set = k1_piece(self, ks, (const char *)d_iq + (size_t)t0 * hop_samples * sample_bytes, t0, sub_total, tile,
+		                         total - self->wf_rows, hop);
+		int hset = 0;
 
-		if (use_alt) {
-			ks = self->k1_streams[self->k1_seq++ % self->n_k1_streams];
-			used_alt = 1;
-		}
-		set = self->pp;
-		self->pp = (self->pp + 1) % self->n_sets;
-		self->d_bins = self->d_bins_pp[set];
-		self->d_partial = self->d_partial_pp[set];
-		if (self->overlap && self->set_used[set] && !dbg_nowait)
-			HIP_TRY(hipStreamWaitEvent(ks, self->ev_set_free[set], 0), "wait for intermediate set");
-		wf_first = wf_first_global - t0;
-		if (wf_first < 0) wf_first = 0;
-		stores_rows = wf_first < sub_total;
-		if (!stores_rows) wf_first = sub_total;
-		fill_k1(self, &k1, (const char *)d_iq + (size_t)t0 * hop_samples * sample_bytes, sub_total, tile,
-		        (self->wf_pos + t0) & (self->wf_rows - 1), wf_first, hop);
-		if (stores_rows && wf_enter(self, ks))
+		if (set < 0)
 			return -EIO;
-		prof_begin(self, 0, ks);
-		if (!(dbg_skip & 1))
-			HIP_TRY(launch_k1(k1, ks), "launch fft_bin");
-		prof_end(self, ks);
-		if (self->log2n == 13) {
-			if (k1.cus) self->k1w_shared++; else self->k1w_full++;
-		}
-		if (stores_rows && wf_leave(self, ks))
-			return -EIO;
-
-		if (self->overlap) {
-			HIP_TRY(hipEventRecord(self->ev_k1_done[set], ks), "record K1 done");
-			HIP_TRY(hipStreamWaitEvent(st2, self->ev_k1_done[set], 0), "K2 waits for K1");
-		}
-		if (dbg_skip & 2) {
-			if (self->overlap) {
-				HIP_TRY(hipEventRecord(self->ev_set_free[set], st2), "record set free");
-				self->set_used[set] = 1;
-			}
+		if (dbg_skip() & 2) {
+			if (k1_set_release(self, set))
+				return -EIO;
 			continue;
 		}
 		if (three) {
@@ -1264,17 +1314,15 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 		} else if (drain_h_sets(self, st2)) {
 			return -EIO;
 		}
-		if (!(dbg_skip & 8) && run_count(self, nb, batch, tile, 0, 0, batch, st2, 1, hset))
+		if (!(dbg_skip() & 8) && run_count(self, nb, batch, tile, 0, 0, batch, st2, 1, hset))
 			return -EIO;
-		if (self->overlap) {
-			HIP_TRY(hipEventRecord(self->ev_set_free[set], st2), "record set free");
-			self->set_used[set] = 1;
-		}
+		if (k1_set_release(self, set))
+			return -EIO;
 		if (three) {
 			HIP_TRY(hipEventRecord(self->ev_k2_done[hset], st2), "record K2 done");
 			HIP_TRY(hipStreamWaitEvent(st3, self->ev_k2_done[hset], 0), "K3 waits for K2");
 		}
-		if (!(dbg_skip & 4) && run_merge(self, nb, batch, 0, st3, 1, hset))
+		if (!(dbg_skip() & 4) && run_merge(self, nb, batch, 0, st3, 1, hset))
 			return -EIO;
 		if (self->overlap && self->log2n == 13) {
 			HIP_TRY(hipEventRecord(self->ev_tail, st3), "record tail");
@@ -1286,7 +1334,7 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 		}
 		self->last_batches = nb;
 	}
-	if (used_alt && !self->relaxed) {
+	if (use_alt && !self->relaxed) {
 		/* what the caller queues on `stream` next (e.g. refilling the sample buffer) follows every K1 */
 		if (k1_streams_join(self))
 			return -EIO;
@@ -1301,19 +1349,18 @@ error:
 	return -EIO;
 }
 
-/* sc16 samples are dwords: a device pointer to them must be 4-byte aligned (fp32 / fp16 callers are not checked here) */
-static int misaligned(const struct fosphor *self, const void *d_samples)
+/* The checks of every call that reads the caller's device samples: `spectra` spectra from d_samples, their windows advancing
+ * N / overlap samples (1: back to back).  sc16 samples are dwords: a device pointer to them must be 4-byte aligned (fp32 / fp16
+ * callers are not checked here). */
+static int device_call_ok(const struct fosphor *self, const void *d_samples, long long spectra, int overlap)
 {
-	return self->iq_format == FOSPHOR_AMD_IQ_SC16 && ((uintptr_t)d_samples & 3);
+	return self && d_samples && spectra <= self->max_spectra && overlap >= 1 && overlap <= self->n && self->n % overlap == 0 &&
+	       !(self->iq_format == FOSPHOR_AMD_IQ_SC16 && ((uintptr_t)d_samples & 3));
 }
 
 extern "C" int fosphor_amd_process_device(struct fosphor *self, const void *d_samples, int n_batches, int batch)
 {
-	if (!self || !d_samples || n_batches < 1 || batch < 16 || (batch & 15) || misaligned(self, d_samples))
-		return -EINVAL;
-	if ((long long)n_batches * batch > self->max_spectra || n_batches > self->max_batches)
-		return -EINVAL;
-	return run(self, d_samples, n_batches, batch, 0, 1);
+	return fosphor_amd_process_device_overlap(self, d_samples, n_batches, batch, 1);
 }
 
 /* overlap_cc (lib/overlap_cc_impl.cc:48-79) emits wlen-sample windows whose starts advance
@@ -1323,13 +1370,21 @@ extern "C" int fosphor_amd_process_device(struct fosphor *self, const void *d_sa
 extern "C" int fosphor_amd_process_device_overlap(struct fosphor *self, const void *d_samples,
                                                   int n_batches, int batch, int overlap)
 {
-	if (!self || !d_samples || n_batches < 1 || batch < 16 || (batch & 15) || misaligned(self, d_samples))
-		return -EINVAL;
-	if (overlap < 1 || overlap > self->n || (self->n % overlap))
-		return -EINVAL;
-	if ((long long)n_batches * batch > self->max_spectra || n_batches > self->max_batches)
+	if (!device_call_ok(self, d_samples, (long long)n_batches * batch, overlap) || n_batches < 1 || n_batches > self->max_batches ||
+	    batch < 16 || (batch & 15))
 		return -EINVAL;
 	return run(self, d_samples, n_batches, batch, self->n / overlap, 1);
+}
+
+/* The kernels for the samples in staging slot k.  The slot is free again once everything queued so far (copy + kernels reading
+ * d_stage[k]) has finished: a later fosphor_amd_upload_pinned into this slot (its own stream) waits for stage_free[k]. */
+static int run_staged(struct fosphor *self, int k, int n_batches, int batch)
+{
+	int rv = run(self, self->d_stage[k], n_batches, batch);
+	if (hipEventRecord(self->stage_free[k], self->stream) != hipSuccess && !rv)
+		rv = -EIO;
+	self->stage_used[k] = 1;
+	return rv;
 }
 
 extern "C" int fosphor_process(struct fosphor *self, void *samples, int len)
@@ -1371,12 +1426,7 @@ extern "C" int fosphor_process(struct fosphor *self, void *samples, int len)
 	memcpy(self->h_stage[k], samples, sample_bytes * (size_t)len);
 	HIP_TRY(hipMemcpyAsync(self->d_stage[k], self->h_stage[k], sample_bytes * (size_t)len, hipMemcpyHostToDevice, self->stream), "H2D samples");
 	{
-		int rv = run(self, self->d_stage[k], 1, len / self->n);
-		/* the slot is free again once everything queued so far (copy + kernels reading
-		 * d_stage[k]) has finished */
-		if (hipEventRecord(self->stage_free[k], self->stream) != hipSuccess && !rv)
-			rv = -EIO;
-		self->stage_used[k] = 1;		/* a later fosphor_amd_upload_pinned into this slot (its own stream) waits for stage_free[k] */
+		const int rv = run_staged(self, k, 1, len / self->n);
 		self->stage_idx ^= 1;
 		return rv;
 	}
@@ -1453,17 +1503,12 @@ extern "C" int fosphor_amd_process_uploaded(struct fosphor *self, int *len_out)
 	const int k = self->pend_slot[self->pend_head], len = self->pend_len[self->pend_head];
 	const long long one = (long long)self->n * 1024;
 	const int n_batches = (long long)len > one ? (int)((long long)len / one) : 1;
-	int rv;
 	self->pend_head ^= 1;
 	self->pend_n--;
 	if (len_out)
 		*len_out = len;
 	HIP_TRY(hipStreamWaitEvent(self->stream, self->upload_slot[k], 0), "kernels wait for the upload");
-	rv = run(self, self->d_stage[k], n_batches, len / self->n / n_batches);
-	if (hipEventRecord(self->stage_free[k], self->stream) != hipSuccess && !rv)
-		rv = -EIO;
-	self->stage_used[k] = 1;
-	return rv;
+	return run_staged(self, k, n_batches, len / self->n / n_batches);
 error:
 	return -EIO;
 }
@@ -1585,22 +1630,28 @@ extern "C" int fosphor_amd_read(struct fosphor *self, int which, void *host, uin
 /* Test hooks                                                               */
 /* ------------------------------------------------------------------------ */
 
+/* The tables uploaded for a hook's kernel, without the boot fills, behind everything queued (the intermediate sets the hook
+ * writes may still be read by a queued K2) */
+static int prepare_hook(struct fosphor *self)
+{
+	if (sync_all(self))
+		return -EIO;
+	const int saved_state = self->state;
+	self->state = ST_READY;
+	const int rv = prepare(self);
+	self->state = saved_state;
+	return rv;
+}
+
 extern "C" int fosphor_amd_fft(struct fosphor *self, const void *d_in, void *d_out, int n_spectra)
 {
 	K1Params k1;
-	int saved_state;
-	if (!self || !d_in || !d_out || n_spectra < 4 || (n_spectra & 3) || n_spectra > self->max_spectra || misaligned(self, d_in))
-		return -EINVAL;
-	if (sync_all(self))				/* scratch sets may still be read by a queued K2 */
-		return -EIO;
-	saved_state = self->state;
-	self->state = ST_READY;			/* no boot fills for a pure FFT */
-	if (prepare(self)) { self->state = saved_state; return -EIO; }
-	self->state = saved_state;
-	/* rows are not stored (wf_first = total); bins/partials land in scratch */
 	/* (N = 8192: tiles of at least 8 spectra -- the 9th bits of the bin indices go out per eight spectra) */
-	if (self->log2n == 13 && (n_spectra & 7))
+	if (!device_call_ok(self, d_in, n_spectra, 1) || !d_out || n_spectra < 4 || (n_spectra & (self->log2n == 13 ? 7 : 3)))
 		return -EINVAL;
+	if (prepare_hook(self))
+		return -EIO;
+	/* rows are not stored (wf_first = total); bins/partials land in scratch */
 	fill_k1(self, &k1, d_in, n_spectra, self->log2n == 13 ? 8 : 4, 0, n_spectra);
 	k1.fft_out = (float2 *)d_out;
 	if (launch_k1(k1, self->stream) != hipSuccess)
@@ -1611,17 +1662,13 @@ extern "C" int fosphor_amd_fft(struct fosphor *self, const void *d_in, void *d_o
 extern "C" int fosphor_amd_bin(struct fosphor *self, const void *d_fft, void *d_bin, void *d_pwr, int n)
 {
 	K1Params k1;
-	int saved_state, force = 0;
+	int force = 0;
 	const char *e = getenv("FOSPHOR_AMD_FORCE_EXACT_BIN");
 	if (!self || !d_fft || !d_bin || !d_pwr || n < 1)
 		return -EINVAL;
 	if (e && *e == '1') force = 1;
-	if (sync_all(self))
+	if (prepare_hook(self))
 		return -EIO;
-	saved_state = self->state;
-	self->state = ST_READY;
-	if (prepare(self)) { self->state = saved_state; return -EIO; }
-	self->state = saved_state;
 	fill_k1(self, &k1, NULL, 0, 4, 0, 0);
 	if (launch_bin_hook((const float2 *)d_fft, (uint8_t *)d_bin, (float *)d_pwr, n, k1, force, self->stream) != hipSuccess)
 		return -EIO;
@@ -1632,167 +1679,76 @@ extern "C" int fosphor_amd_bin(struct fosphor *self, const void *d_fft, void *d_
 /* Multi-GPU split                                                          */
 /* ------------------------------------------------------------------------ */
 
-static int accumulate(struct fosphor *self, const void *d_samples, int n_local, int t_offset, int total_batch, int hop)
+/* Spectra [t_offset, t_offset + n_local) of a batch of total_batch spectra (a time shard of a display frame), windows advancing
+ * N / overlap samples, counted into partial slot `slot`; rows are stored for the spectra that survive in the ring */
+static int accumulate(struct fosphor *self, const void *d_samples, int n_local, int t_offset, int total_batch, int overlap)
 {
-	K1Params k1;
-	int tile, wf_first, set;
-	hipStream_t st2;
-
-	if (!self || !d_samples || n_local < 16 || (n_local & 15) || (t_offset & 15) ||
-	    t_offset < 0 || t_offset + n_local > total_batch || n_local > self->max_spectra || misaligned(self, d_samples))
+	if (!device_call_ok(self, d_samples, n_local, overlap) || n_local < 16 || (n_local & 15) || (t_offset & 15) ||
+	    t_offset < 0 || t_offset + n_local > total_batch)
 		return -EINVAL;
 	const int did_prep = self->win_dirty || self->thr_dirty || self->state == ST_BOOTING;
+	const int hop = self->n / overlap;
+	const int first_row = total_batch - self->wf_rows;	/* spectrum t_offset + t stores its row iff t_offset + t >= first_row */
+	hipStream_t st2 = count_stream(self);
+	const int cpb = n_local / 1024;
+	const int chunked = (n_local % 1024) == 0 && cpb > 1 && self->d_slab16 && cpb <= self->slab_chunks && !self->kn_no_sum16;
+	const int sub_c = self->sub_samples / (1024LL * self->n) > 1 ? (int)(self->sub_samples / (1024LL * self->n)) : 1;
+
 	if (prepare(self))
 		return -EIO;
-
-	st2 = self->overlap ? self->stream2 : self->stream;
-	{
+	if (chunked && cpb > sub_c) {
 		/* A shard of several whole 1024-spectrum chunks runs like a device-resident call: sub-launches of
 		 * sub_samples samples, K1s alternating between two streams, K2 of piece j beside K1 of piece j + 1.
 		 * Each K2 leaves its chunks' packed 16-bit count slabs and float partials at the chunks' places;
 		 * one k2c_sum at the end adds all of them into the 32-bit slot that is exchanged. */
-		const int cpb = n_local / 1024;
 		const size_t cells = (size_t)self->n_bins * self->n;
-		const int chunked = (n_local % 1024) == 0 && cpb > 1 && self->d_slab16 && cpb <= self->slab_chunks &&
-		                    !self->kn_no_sum16;
-		long long per_chunk = 1024LL * self->n;
-		int sub_c = (int)(self->sub_samples / per_chunk);
-		if (sub_c < 1) sub_c = 1;
-		if (chunked && cpb > sub_c) {
-			const size_t sample_bytes = self->sample_bytes;
-			/* K2 counts G consecutive 1024-spectrum chunks per work-group (16-bit counters hold 65535 spectra): 1 / G of the
-			 * slab traffic, as long as enough work-groups are left to keep the bin-index reads in flight */
-			int G = 1;
-			{
-				/* measured, N = 1024, 256 batches per frame: G = 1 / 2 / 4 / 8 -> 486 / 510 / 528 / 450 GSamples/s (at 8 the
-				 * count kernel's 128 work-groups no longer keep up with the FFT kernel) */
-				for (int want = self->kn_frame_group; want >= 1; want >>= 1)
-					if (want <= 32 && !(want & (want - 1)) && sub_c % want == 0 && cpb % want == 0) {
-						G = want;
-						break;
-					}
+		const int use_alt = self->overlap && self->alt && !(self->log2n == 16 && self->k1h_fused);
+		/* K2 counts G consecutive 1024-spectrum chunks per work-group (16-bit counters hold 65535 spectra): 1 / G of the
+		 * slab traffic, as long as enough work-groups are left to keep the bin-index reads in flight */
+		int G = 1;
+		/* measured, N = 1024, 256 batches per frame: G = 1 / 2 / 4 / 8 -> 486 / 510 / 528 / 450 GSamples/s (at 8 the
+		 * count kernel's 128 work-groups no longer keep up with the FFT kernel) */
+		for (int want = self->kn_frame_group; want >= 1; want >>= 1)
+			if (want <= 32 && !(want & (want - 1)) && sub_c % want == 0 && cpb % want == 0) {
+				G = want;
+				break;
 			}
-			const int use_alt = self->overlap && self->alt && !(self->log2n == 16 && self->k1h_fused);
-			int used_alt = 0;
-			if (drain_h_sets(self, st2))
+		if (drain_h_sets(self, st2) || (use_alt && (did_prep || !self->relaxed) && k1_streams_fork(self)))
+			return -EIO;
+		for (int c0 = 0; c0 < cpb; c0 += sub_c) {
+			const int nc = (cpb - c0 < sub_c) ? cpb - c0 : sub_c;
+			const int t0 = c0 * 1024, sub_total = nc * 1024;
+			const int tile = pick_tile(self, sub_total, 1024);
+			hipStream_t ks = use_alt ? self->k1_streams[self->k1_seq++ % self->n_k1_streams] : self->stream;
+			const int set = k1_piece(self, ks, (const char *)d_samples + (size_t)t0 * hop * self->sample_bytes, t_offset + t0,
+			                         sub_total, tile, first_row, hop);
+			K2Params k2;
+
+			if (set < 0)
 				return -EIO;
-			if (use_alt && (did_prep || !self->relaxed)) {
-				if (k1_streams_fork(self))
-					return -EIO;
-			}
-			for (int c0 = 0; c0 < cpb; c0 += sub_c) {
-				const int nc = (cpb - c0 < sub_c) ? cpb - c0 : sub_c;
-				const int t0 = c0 * 1024, sub_total = nc * 1024;
-				hipStream_t ks = self->stream;
-				K2Params k2;
-				int stores_rows;
-
-				if (use_alt) {
-					ks = self->k1_streams[self->k1_seq++ % self->n_k1_streams];
-					used_alt = 1;
-				}
-				set = self->pp;
-				self->pp = (self->pp + 1) % self->n_sets;
-				self->d_bins = self->d_bins_pp[set];
-				self->d_partial = self->d_partial_pp[set];
-				if (self->overlap && self->set_used[set])
-					HIP_TRY(hipStreamWaitEvent(ks, self->ev_set_free[set], 0), "wait for intermediate set");
-				tile = pick_tile(self, sub_total, 1024);
-				/* global spectrum index tau = t_offset + t0 + t stores its row iff tau >= total_batch - wf_rows */
-				wf_first = total_batch - self->wf_rows - t_offset - t0;
-				if (wf_first < 0) wf_first = 0;
-				stores_rows = wf_first < sub_total;
-				if (!stores_rows) wf_first = sub_total;
-				fill_k1(self, &k1, (const char *)d_samples + (size_t)t0 * (hop ? hop : self->n) * sample_bytes, sub_total, tile,
-				        (self->wf_pos + t_offset + t0) & (self->wf_rows - 1), wf_first, hop);
-				if (stores_rows && wf_enter(self, ks))
-					return -EIO;
-				prof_begin(self, 0, ks);
-				HIP_TRY(launch_k1(k1, ks), "launch fft_bin");
-				prof_end(self, ks);
-				if (stores_rows && wf_leave(self, ks))
-					return -EIO;
-				if (self->overlap) {
-					HIP_TRY(hipEventRecord(self->ev_k1_done[set], ks), "record K1 done");
-					HIP_TRY(hipStreamWaitEvent(st2, self->ev_k1_done[set], 0), "K2 waits for K1");
-				}
-				memset(&k2, 0, sizeof(k2));
-				k2.bins = self->d_bins; k2.partial = self->d_partial;
-				k2.hc = self->d_hc + (size_t)self->slot * cells;
-				k2.hc16 = self->d_slab16 + (size_t)(c0 / G) * cells;
-				k2.n = self->n; k2.bins16 = self->bins16 && self->log2n != 13; k2.bins8p1 = (self->log2n == 13);
-				k2.bins9 = (self->log2n == 16); k2.total = sub_total;
-				k2.batch = sub_total; k2.chunk = 1024 * G; k2.tile = tile; k2.n_bins = self->n_bins;
-				k2.w = 1.0f - self->alpha;
-				k2.log2_w = (float)log2((double)(1.0f - self->alpha));
-				k2.t_offset = t_offset + t0; k2.weight_batch = total_batch;
-				k2.chunk_sum = self->d_chunk_sum + (size_t)(c0 / G) * self->n;
-				k2.chunk_max = self->d_chunk_max + (size_t)(c0 / G) * self->n;
-				prof_begin(self, 1, st2);
-				HIP_TRY(launch_k2(k2, nc / G, st2), "launch count");
-				prof_end(self, st2);
-				if (self->overlap) {
-					HIP_TRY(hipEventRecord(self->ev_set_free[set], st2), "record set free");
-					self->set_used[set] = 1;
-				}
-			}
-			{
-				K2bParams k2b;
-				memset(&k2b, 0, sizeof(k2b));
-				k2b.chunk_sum = self->d_chunk_sum; k2b.chunk_max = self->d_chunk_max;
-				k2b.live_sum = self->d_live_sum + (size_t)self->slot * self->n;
-				k2b.vmax = self->d_vmax + (size_t)self->slot * self->n;
-				k2b.n_batches = 1; k2b.cpb = cpb / G; k2b.n = self->n;
-				k2b.hc16 = self->d_slab16;
-				k2b.hc = self->d_hc + (size_t)self->slot * cells;
-				k2b.n_bins = self->n_bins;
-				HIP_TRY(launch_k2c(k2b, st2), "launch chunk sum");
-			}
-			if (used_alt && !self->relaxed) {
-				if (k1_streams_join(self))
-					return -EIO;
-			}
-			self->wf_pos = (self->wf_pos + total_batch) & (self->wf_rows - 1);
-			self->state = ST_PENDING;
-			return 0;
+			fill_k2(self, &k2, sub_total, sub_total, 1024 * G, tile, t_offset + t0, total_batch);
+			k2.hc = self->d_hc + (size_t)self->slot * cells;
+			k2.hc16 = self->d_slab16 + (size_t)(c0 / G) * cells;
+			k2.chunk_sum = self->d_chunk_sum + (size_t)(c0 / G) * self->n;
+			k2.chunk_max = self->d_chunk_max + (size_t)(c0 / G) * self->n;
+			prof_begin(self, 1, st2);
+			HIP_TRY(launch_k2(k2, nc / G, st2), "launch count");
+			prof_end(self, st2);
+			if (k1_set_release(self, set))
+				return -EIO;
 		}
+		HIP_TRY(launch_chunk_sum(self, 1, cpb / G, self->slot, self->slot, 1, st2), "launch chunk sum");
+		if (use_alt && !self->relaxed && k1_streams_join(self))
+			return -EIO;
+	} else {
+		/* one K1 launch: same two-stream pipeline as run(): K1 on `stream`, K2 (and later the exchange and
+		 * fosphor_amd_merge's K3) on the count stream, intermediates rotating between the sets */
+		const int tile = pick_tile(self, n_local, n_local);
+		const int set = k1_piece(self, self->stream, d_samples, t_offset, n_local, tile, first_row, hop);
+		if (set < 0 || drain_h_sets(self, st2) || run_count(self, 1, n_local, tile, self->slot, t_offset, total_batch, st2) ||
+		    k1_set_release(self, set))
+			return -EIO;
 	}
-
-	/* one K1 launch: same two-stream pipeline as run(): K1 on `stream`, K2 (and later the exchange and
-	 * fosphor_amd_merge's K3) on `stream2`, intermediates rotating between the sets */
-	set = self->pp;
-	self->pp = (self->pp + 1) % self->n_sets;
-	self->d_bins = self->d_bins_pp[set];
-	self->d_partial = self->d_partial_pp[set];
-	if (self->overlap && self->set_used[set])
-		HIP_TRY(hipStreamWaitEvent(self->stream, self->ev_set_free[set], 0), "wait for intermediate set");
-
-	tile = pick_tile(self, n_local, n_local);
-	/* global spectrum index tau = t_offset + t stores its row iff tau >= total_batch - wf_rows */
-	wf_first = total_batch - self->wf_rows - t_offset;
-	if (wf_first < 0) wf_first = 0;
-	fill_k1(self, &k1, d_samples, n_local, tile, (self->wf_pos + t_offset) & (self->wf_rows - 1), wf_first, hop);
-	if (wf_enter(self, self->stream))
-		return -EIO;
-	prof_begin(self, 0, self->stream);
-	HIP_TRY(launch_k1(k1, self->stream), "launch fft_bin");
-	prof_end(self, self->stream);
-	if (wf_leave(self, self->stream))
-		return -EIO;
-
-	if (self->overlap) {
-		HIP_TRY(hipEventRecord(self->ev_k1_done[set], self->stream), "record K1 done");
-		HIP_TRY(hipStreamWaitEvent(st2, self->ev_k1_done[set], 0), "K2 waits for K1");
-	}
-	if (drain_h_sets(self, st2))
-		return -EIO;
-	if (run_count(self, 1, n_local, tile, self->slot, t_offset, total_batch, st2))
-		return -EIO;
-	if (self->overlap) {
-		HIP_TRY(hipEventRecord(self->ev_set_free[set], st2), "record set free");
-		self->set_used[set] = 1;
-	}
-
 	/* the ring advances with the data (host state), so the next frame can be accumulated
 	 * before this one is merged */
 	self->wf_pos = (self->wf_pos + total_batch) & (self->wf_rows - 1);
@@ -1805,7 +1761,7 @@ error:
 extern "C" int fosphor_amd_accumulate_device(struct fosphor *self, const void *d_samples,
                                              int n_local, int t_offset, int total_batch)
 {
-	return accumulate(self, d_samples, n_local, t_offset, total_batch, 0);
+	return accumulate(self, d_samples, n_local, t_offset, total_batch, 1);
 }
 
 /* the same with overlap_cc fused into the read (see fosphor_amd_process_device_overlap): d_samples is this rank's part
@@ -1813,9 +1769,7 @@ extern "C" int fosphor_amd_accumulate_device(struct fosphor *self, const void *d
 extern "C" int fosphor_amd_accumulate_device_overlap(struct fosphor *self, const void *d_samples,
                                                      int n_local, int t_offset, int total_batch, int overlap)
 {
-	if (!self || overlap < 1 || overlap > self->n || (self->n % overlap))
-		return -EINVAL;
-	return accumulate(self, d_samples, n_local, t_offset, total_batch, self->n / overlap);
+	return accumulate(self, d_samples, n_local, t_offset, total_batch, overlap);
 }
 
 extern "C" int fosphor_amd_set_partial_slot(struct fosphor *self, int slot)
@@ -1838,19 +1792,24 @@ extern "C" int fosphor_amd_get_partials(struct fosphor *self, struct fosphor_amd
 	return 0;
 }
 
-extern "C" int fosphor_amd_merge(struct fosphor *self, int total_batch)
+/* K3 on the partial arrays of the current slot (a batch of total_batch spectra), for the cells [cell_begin, cell_end) of the
+ * histogram (0, 0: all of them) */
+static int merge_slot(struct fosphor *self, int total_batch, int cell_begin, int cell_end)
 {
-	if (!self || total_batch < 16)
-		return -EINVAL;
-	if (prepare(self))
-		return -EIO;
-	if (run_merge(self, 1, total_batch, self->slot, self->overlap ? self->stream2 : self->stream))
+	if (prepare(self) || run_merge(self, 1, total_batch, self->slot, count_stream(self), 0, 0, cell_begin, cell_end))
 		return -EIO;
 	self->last_batches = 1;
 	self->last_slot0 = self->slot;
 	self->last_hc16 = 0;
 	self->state = ST_PENDING;
 	return 0;
+}
+
+extern "C" int fosphor_amd_merge(struct fosphor *self, int total_batch)
+{
+	if (!self || total_batch < 16)
+		return -EINVAL;
+	return merge_slot(self, total_batch, 0, 0);
 }
 
 /* ---- native exchange (RCCL over xGMI), fosphor_exchange.cpp --------------- */
@@ -1933,7 +1892,7 @@ extern "C" int fosphor_amd_exchange(struct fosphor *self, void *comm)
 	if (!self || !comm)
 		return -EINVAL;
 	const size_t cells = (size_t)self->n_bins * self->n;
-	hipStream_t st = self->overlap ? self->stream2 : self->stream;
+	hipStream_t st = count_stream(self);
 	xprof_begin(self, st);
 	const int rv = xchg_allreduce3(comm, st,
 	                               self->d_hc + (size_t)self->slot * cells, cells,
@@ -1947,14 +1906,17 @@ extern "C" int fosphor_amd_exchange(struct fosphor *self, void *comm)
  * reduce-scattered -- rank r owns cells [r C / world, (r + 1) C / world) of the [bin][x] array -- and
  * fosphor_amd_merge_sliced updates only that slice of the histogram; fosphor_amd_gather_state all-gathers the
  * slices when a complete histogram is wanted on every rank (once per draw, not once per exchange). */
+static int slice_ok(const struct fosphor *self, int world, int rank)
+{
+	return self && world >= 1 && rank >= 0 && rank < world && (size_t)self->n_bins * self->n % (size_t)world == 0;
+}
+
 extern "C" int fosphor_amd_exchange_sliced(struct fosphor *self, void *comm, int world, int rank)
 {
-	if (!self || !comm || world < 1 || rank < 0 || rank >= world)
+	if (!comm || !slice_ok(self, world, rank))
 		return -EINVAL;
 	const size_t cells = (size_t)self->n_bins * self->n;
-	if (cells % (size_t)world)
-		return -EINVAL;
-	hipStream_t st = self->overlap ? self->stream2 : self->stream;
+	hipStream_t st = count_stream(self);
 	xprof_begin(self, st);
 	const int rv = xchg_reduce_scatter(comm, st,
 	                                   self->d_hc + (size_t)self->slot * cells, cells, world, rank,
@@ -1966,32 +1928,18 @@ extern "C" int fosphor_amd_exchange_sliced(struct fosphor *self, void *comm, int
 
 extern "C" int fosphor_amd_merge_sliced(struct fosphor *self, int total_batch, int world, int rank)
 {
-	if (!self || total_batch < 16 || world < 1 || rank < 0 || rank >= world)
+	if (!slice_ok(self, world, rank) || total_batch < 16)
 		return -EINVAL;
-	const size_t cells = (size_t)self->n_bins * self->n;
-	if (cells % (size_t)world)
-		return -EINVAL;
-	if (prepare(self))
-		return -EIO;
-	const int per = (int)(cells / (size_t)world);
-	if (run_merge(self, 1, total_batch, self->slot, self->overlap ? self->stream2 : self->stream, 0, 0,
-	              per * rank, per * (rank + 1)))
-		return -EIO;
-	self->last_batches = 1;
-	self->last_slot0 = self->slot;
-	self->last_hc16 = 0;
-	self->state = ST_PENDING;
-	return 0;
+	const int per = self->n_bins * self->n / world;
+	return merge_slot(self, total_batch, per * rank, per * (rank + 1));
 }
 
 extern "C" int fosphor_amd_gather_state(struct fosphor *self, void *comm, int world, int rank)
 {
-	if (!self || !comm || world < 1 || rank < 0 || rank >= world)
+	if (!comm || !slice_ok(self, world, rank))
 		return -EINVAL;
 	const size_t cells = (size_t)self->n_bins * self->n;
-	if (cells % (size_t)world)
-		return -EINVAL;
-	hipStream_t st = self->overlap ? self->stream2 : self->stream;
+	hipStream_t st = count_stream(self);
 	if (k3_stream_enter(self, st))
 		return -EIO;
 	self->hot_valid = 0;		/* other ranks' cells arrive: the hot-row flags of the sparse merge no longer describe d_hist */
@@ -2081,26 +2029,20 @@ extern "C" int fosphor_amd_traffic_twin(struct fosphor *self, const void *d_samp
 	if (fosphor_amd_finish(self) < 0 || prepare(self))
 		return -EIO;
 	fill_k1(self, &k1, d_samples, total, pick_tile(self, total, batch), 0, total);
-	if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
+	hipError_t le = hipEventCreate(&e0);
+	if (le == hipSuccess) le = hipEventCreate(&e1);
+	for (int i = 0; i < 3 && le == hipSuccess; i++)
+		le = launch_k1_traffic_twin(k1, self->stream);
+	if (le == hipSuccess) le = hipEventRecord(e0, self->stream);
+	for (int i = 0; i < reps && le == hipSuccess; i++)
+		le = launch_k1_traffic_twin(k1, self->stream);
+	if (le == hipSuccess) le = hipEventRecord(e1, self->stream);
+	if (le == hipSuccess) le = hipEventSynchronize(e1);
+	if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
+	if (e0) (void)hipEventDestroy(e0);
+	if (e1) (void)hipEventDestroy(e1);
+	if (le != hipSuccess)
 		return -EIO;
-	{
-		hipError_t le = hipSuccess;
-		for (int i = 0; i < 3 && le == hipSuccess; i++)
-			le = launch_k1_traffic_twin(k1, self->stream);
-		if (le == hipSuccess) le = hipEventRecord(e0, self->stream);
-		for (int i = 0; i < reps && le == hipSuccess; i++)
-			le = launch_k1_traffic_twin(k1, self->stream);
-		if (le == hipSuccess) le = hipEventRecord(e1, self->stream);
-		if (le != hipSuccess) {
-			(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-			return -EIO;
-		}
-	}
-	if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
-		(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-		return -EIO;
-	}
-	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
 	*ms_out = ms / (float)reps;
 	return 0;
 }
@@ -2313,7 +2255,5 @@ extern "C" int fosphor_amd_wait_input(struct fosphor *self)
  * (after fosphor_amd_accumulate_device, before fosphor_amd_merge). */
 extern "C" void *fosphor_amd_stream2(struct fosphor *self)
 {
-	if (!self)
-		return NULL;
-	return (void *)(self->overlap ? self->stream2 : self->stream);
+	return self ? (void *)count_stream(self) : NULL;
 }

@@ -22,6 +22,8 @@
  *                  order (display.cl:217-254); live EMA + max-hold (display.cl:186-214,
  *                  257-310).
  */
+#include <atomic>
+
 #include "fosphor_internal.h"
 
 #pragma clang fp contract(off)
@@ -941,26 +943,37 @@ template <int NWV> struct K1hGeom {
 #undef K1_SC16
 #undef K1_IQ
 
-template <int NWV>
-static hipError_t launch_k1h_form(const K1Params &p0, hipStream_t s)
+typedef void (*k1_fn)(const K1Params);
+
+/* The dynamic-LDS limit of the n kernels of `fns`, raised to `lds` bytes once per device: the attribute belongs to the function object of
+ * the CURRENT device.  `done` holds a bit per device that has it (atomic: host threads may drive different devices at once; two threads
+ * on one device may both set it, which is harmless). */
+static hipError_t set_lds_once(const k1_fn *fns, int n, int lds, std::atomic<unsigned long long> &done)
 {
-	typedef void (*k1h_fn)(const K1Params);
-	static const k1h_fn fn[6] = { k1h_fused<false, false, NWV>, k1h_fused<true, false, NWV>, k1h_fused<false, true, NWV>, k1h_fused<true, true, NWV>,
-	                              k1h_fused_sc16<true, false, NWV>, k1h_fused_sc16<true, true, NWV> };
-	constexpr size_t lds = K1hGeom<NWV>::kLds;
-	/* (the attribute belongs to the function object of the CURRENT device: once per device, not once per process) */
-	static unsigned long long attr_dev = 0;
 	int dev = 0;
 	if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
 		return hipErrorInvalidDevice;
-	if (!(attr_dev >> dev & 1)) {
-		for (int i = 0; i < 6; i++) {
-			const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-			if (e != hipSuccess)
-				return e;
-		}
-		attr_dev |= 1ull << dev;
+	if (done.load() >> dev & 1)
+		return hipSuccess;
+	for (int i = 0; i < n; i++) {
+		const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fns[i]), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+		if (e != hipSuccess)
+			return e;
 	}
+	done.fetch_or(1ull << dev);
+	return hipSuccess;
+}
+
+template <int NWV>
+static hipError_t launch_k1h_form(const K1Params &p0, hipStream_t s)
+{
+	static const k1_fn fn[6] = { k1h_fused<false, false, NWV>, k1h_fused<true, false, NWV>, k1h_fused<false, true, NWV>, k1h_fused<true, true, NWV>,
+	                             k1h_fused_sc16<true, false, NWV>, k1h_fused_sc16<true, true, NWV> };
+	constexpr size_t lds = K1hGeom<NWV>::kLds;
+	static std::atomic<unsigned long long> attr_dev{0};
+	const hipError_t ae = set_lds_once(fn, 6, (int)lds, attr_dev);
+	if (ae != hipSuccess)
+		return ae;
 	/* (the counters in p0.sync are zero: cleared at allocation, and by the last work-group of every launch) */
 	/* 32 clusters: 8 work-groups of 8 waves, one per CU -- or 16 work-groups of 4 waves, two per CU */
 	const int which = p0.iq_format == kIqSc16 ? 4 + (p0.fft_out ? 1 : 0) : (p0.iq_format == kIqFp16 ? 1 : 0) | (p0.fft_out ? 2 : 0);
@@ -986,7 +999,6 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 	const bool sc16 = p.iq_format == kIqSc16;
 	const int tiles = p.total / p.tile;
 	if (p.variant == 3) {
-		static unsigned long long attr_dev = 0;		/* (the attribute belongs to the function object of the CURRENT device: once per device) */
 		if (p.log2n == 10) {
 			/* N = 1024 with 16-bit bin indices (more than 256 bins): the general kernel at 128 threads per spectrum */
 			constexpr int N = 1024;
@@ -1006,20 +1018,12 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 			return hipErrorInvalidValue;
 		/* N = 8192: 16 points per thread, tables in registers, overlap reuse in registers (k1w_fft_bin); any hop */
 		constexpr int ldsw = 2 * 8192 * 8 + 520 * 8;	/* two slabs + the exact-bin thresholds */
-		typedef void (*k1w_fn)(const K1Params);
-		static const k1w_fn fns[10] = { k1w_fft_bin<8>, k1w_fft_bin<4>, k1w_fft_bin<2>, k1w_fft_bin<1>, k1w_fft_bin<16>,
-		                                k1w_fft_bin_sc16<8>, k1w_fft_bin_sc16<4>, k1w_fft_bin_sc16<2>, k1w_fft_bin_sc16<1>, k1w_fft_bin_sc16<16> };
-		int dev = 0;
-		if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-			return hipErrorInvalidDevice;
-		if (!(attr_dev >> dev & 1)) {
-			for (int i = 0; i < 10; i++) {
-				hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fns[i]), hipFuncAttributeMaxDynamicSharedMemorySize, ldsw);
-				if (e != hipSuccess)
-					return e;
-			}
-			attr_dev |= 1ull << dev;
-		}
+		static const k1_fn fns[10] = { k1w_fft_bin<8>, k1w_fft_bin<4>, k1w_fft_bin<2>, k1w_fft_bin<1>, k1w_fft_bin<16>,
+		                               k1w_fft_bin_sc16<8>, k1w_fft_bin_sc16<4>, k1w_fft_bin_sc16<2>, k1w_fft_bin_sc16<1>, k1w_fft_bin_sc16<16> };
+		static std::atomic<unsigned long long> attr_dev{0};
+		const hipError_t ae = set_lds_once(fns, 10, ldsw, attr_dev);
+		if (ae != hipSuccess)
+			return ae;
 		/* rows of 512 samples the next window of a tile shares with this one: hop = 8192 / R, R = 2, 4, 8, 16; any other hop: none */
 		const int which = (p.hop == 4096) ? 0 : (p.hop == 2048) ? 1 : (p.hop == 1024) ? 2 : (p.hop == 512) ? 3 : 4;
 		/* one 8-wave work-group per CU -- or per CU of the share the host leaves to this kernel (K1Params.cus: the count and

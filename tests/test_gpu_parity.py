@@ -1744,3 +1744,9 @@ def test_capacity_and_argument_errors(amd, torch_cuda):
     assert L.fosphor_amd_share_stats(f.h, None, None, None) == 0
     assert L.fosphor_amd_share_stats(None, None, None, None) == -errno.EINVAL
     f.close()
+    # fosphor_amd_fft at N = 8192 takes whole groups of eight spectra (refused before anything is queued)
+    f = amd.Fosphor(fft_len_log=13, n_bins=512, max_spectra=64)
+    d = torch.zeros((16 * 8192, 2), dtype=torch.float32, device="cuda")
+    assert f.fft_device(d, torch.empty_like(d), 12) == -errno.EINVAL
+    assert f.fft_device(d, torch.empty_like(d), 16) == 0
+    f.close()
