@@ -266,6 +266,15 @@ class Fosphor:
             raise RuntimeError("fosphor_amd_share_stats -> %d" % rv)
         return a.value, b.value, c.value
 
+    def launch_stats(self):
+        """fosphor_amd_launch_stats: (FFT pieces launched by accumulate_device, chunk sums over 16-bit slabs, chunk reduces with
+        32-bit counts) since the instance was made"""
+        a, b, c = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        rv = self.L.fosphor_amd_launch_stats(self.h, C.byref(a), C.byref(b), C.byref(c))
+        if rv:
+            raise RuntimeError("fosphor_amd_launch_stats -> %d" % rv)
+        return a.value, b.value, c.value
+
     def kernel_busy(self):
         """ms during which >= 1 kernel of each kind ran (call before kernel_times)"""
         ms = (C.c_float * 3)()

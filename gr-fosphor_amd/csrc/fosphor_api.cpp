@@ -130,6 +130,7 @@ struct fosphor
 	int       n_cus;			/* hipDeviceProp_t::multiProcessorCount */
 	int       share_cus;			/* N = 8192: work-groups of an FFT launch that leaves CUs to the count / merge kernels (0: never) */
 	long long k1w_shared, k1w_full;		/* N = 8192: FFT launches made in the shared / the full-chip form (fosphor_amd_share_stats) */
+	long long acc_pieces, n_k2c, n_k2b;	/* FFT pieces launched by accumulate(); chunk sums (k2c) / chunk reduces (k2b) launched (fosphor_amd_launch_stats) */
 	uint32_t *d_hc;
 	uint32_t *d_hc_export;			/* [n_bins][N] last batch, written by K3 on the 16-bit path */
 	const uint16_t *export_src;		/* ... made from the last batch's slabs when fosphor_amd_get_buffers asks */
@@ -998,9 +999,12 @@ static hipError_t launch_chunk_sum(struct fosphor *self, int n_batches, int cpb,
 	k2b.live_sum = self->d_live_sum + (size_t)lslot * self->n;
 	k2b.vmax = self->d_vmax + (size_t)lslot * self->n;
 	k2b.n_batches = n_batches; k2b.cpb = cpb; k2b.n = self->n;
-	if (!sum16)
+	if (!sum16) {
+		self->n_k2b++;
 		return launch_k2b(k2b, st);
+	}
 	k2b.hc16 = self->d_slab16; k2b.hc = self->d_hc + (size_t)slot0 * self->n_bins * self->n; k2b.n_bins = self->n_bins;
+	self->n_k2c++;
 	return launch_k2c(k2b, st);
 }
 
@@ -1726,6 +1730,7 @@ static int accumulate(struct fosphor *self, const void *d_samples, int n_local, 
 
 			if (set < 0)
 				return -EIO;
+			self->acc_pieces++;
 			fill_k2(self, &k2, sub_total, sub_total, 1024 * G, tile, t_offset + t0, total_batch);
 			k2.hc = self->d_hc + (size_t)self->slot * cells;
 			k2.hc16 = self->d_slab16 + (size_t)(c0 / G) * cells;
@@ -1745,7 +1750,10 @@ static int accumulate(struct fosphor *self, const void *d_samples, int n_local, 
 		 * fosphor_amd_merge's K3) on the count stream, intermediates rotating between the sets */
 		const int tile = pick_tile(self, n_local, n_local);
 		const int set = k1_piece(self, self->stream, d_samples, t_offset, n_local, tile, first_row, hop);
-		if (set < 0 || drain_h_sets(self, st2) || run_count(self, 1, n_local, tile, self->slot, t_offset, total_batch, st2) ||
+		if (set < 0)
+			return -EIO;
+		self->acc_pieces++;
+		if (drain_h_sets(self, st2) || run_count(self, 1, n_local, tile, self->slot, t_offset, total_batch, st2) ||
 		    k1_set_release(self, set))
 			return -EIO;
 	}
@@ -2143,6 +2151,19 @@ extern "C" int fosphor_amd_share_stats(struct fosphor *self, long long *shared, 
 	if (shared) *shared = self->k1w_shared;
 	if (full) *full = self->k1w_full;
 	if (cus) *cus = self->share_cus;
+	return 0;
+}
+
+/* What the calls so far launched, since the instance was made: FFT pieces of fosphor_amd_accumulate_device[_overlap] (1 per call on
+ * the single-launch path, one per sub-launch otherwise), chunk sums over 16-bit slabs (k2c_sum) and chunk reduces beside 32-bit
+ * counts (k2b_reduce), the latter two by any entry point.  Host counters that only grow; nothing on the submit path reads them. */
+extern "C" int fosphor_amd_launch_stats(struct fosphor *self, long long *pieces, long long *k2c, long long *k2b)
+{
+	if (!self)
+		return -EINVAL;
+	if (pieces) *pieces = self->acc_pieces;
+	if (k2c) *k2c = self->n_k2c;
+	if (k2b) *k2b = self->n_k2b;
 	return 0;
 }
 

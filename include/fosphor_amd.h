@@ -289,6 +289,13 @@ int fosphor_amd_plan_piece_batches(int fft_len_log, int overlap, int n_batches, 
  * submitted, never on the data; results are identical (tests: test_c3_space_sharing_*).  Any pointer may be NULL. */
 int fosphor_amd_share_stats(struct fosphor *self, long long *shared, long long *full, int *cus);
 
+/* What the instance launched since it was made, for tests that must prove which path a call took: *pieces = FFT launches made by
+ * fosphor_amd_accumulate_device[_overlap] (one per call whose shard goes out in a single launch, one per sub-launch of a shard of
+ * several 1024-spectrum chunks longer than a sub-launch); *k2c = chunk sums over packed 16-bit count slabs; *k2b = chunk reduces
+ * beside 32-bit counts (the last two by any entry point).  The counters only grow and nothing reads them but this call.  Any
+ * pointer may be NULL. */
+int fosphor_amd_launch_stats(struct fosphor *self, long long *pieces, long long *k2c, long long *k2b);
+
 /* Library identification: "fosphor_amd <version> gfx950". */
 const char *fosphor_amd_version(void);
 

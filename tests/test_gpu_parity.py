@@ -1731,6 +1731,13 @@ def test_capacity_and_argument_errors(amd, torch_cuda):
     assert f.process_device(d, 0, 16) == -errno.EINVAL
     assert f.accumulate_device(d, 32, 8, 64) == -errno.EINVAL	# shard offset not on a 16-spectrum boundary
     assert f.accumulate_device(d, 32, 48, 64) == -errno.EINVAL	# shard runs past the batch
+    assert f.accumulate_device(d, 80, 0, 80) == -errno.EINVAL	# shard over capacity (n_local > max_spectra)
+    assert f.accumulate_device(d, 32, -16, 64) == -errno.EINVAL	# negative shard offset
+    assert f.accumulate_device(d, 0, 0, 64) == -errno.EINVAL	# empty shard
+    assert f.accumulate_device(0, 32, 0, 64) == -errno.EINVAL	# no samples
+    assert f.launch_stats() == (0, 0, 0)			# nothing refused was launched
+    assert f.accumulate_device(d, 32, 32, 64) == 0 and f.launch_stats() == (1, 0, 0)
+    assert f.finish() >= 0
     with pytest.raises(RuntimeError):
         amd.Fosphor(n_bins=100)					# not a multiple of 16
     with pytest.raises(RuntimeError):
@@ -1749,4 +1756,13 @@ def test_capacity_and_argument_errors(amd, torch_cuda):
     d = torch.zeros((16 * 8192, 2), dtype=torch.float32, device="cuda")
     assert f.fft_device(d, torch.empty_like(d), 12) == -errno.EINVAL
     assert f.fft_device(d, torch.empty_like(d), 16) == 0
+    # ... and a shard's overlap ratio divides the FFT length there as everywhere
+    assert f.accumulate_device(d, 16, 0, 16, overlap=3) == -errno.EINVAL
+    assert f.accumulate_device(d, 16, 0, 16, overlap=16384) == -errno.EINVAL
+    assert f.accumulate_device(d, 80, 0, 80, overlap=2) == -errno.EINVAL	# over capacity
+    assert f.accumulate_device(d, 16, -16, 32, overlap=2) == -errno.EINVAL
+    assert f.launch_stats() == (0, 0, 0)
+    L = amd.load()
+    assert L.fosphor_amd_launch_stats(f.h, None, None, None) == 0
+    assert L.fosphor_amd_launch_stats(None, None, None, None) == -errno.EINVAL
     f.close()
