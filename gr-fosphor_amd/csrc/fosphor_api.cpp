@@ -47,10 +47,7 @@ static const int kMaxK1Streams = 4;	/* `stream` + up to three more FFT streams *
  * finds empty, no CU mask involved (hardware masks that remove CUs unevenly from the shader engines unbalance a grid of CU-sized
  * work-groups: tools/ubench/cu_mask_big.hip).  Measured at BASELINE C3: 333 -> 367-371 GSamples/s with 28 batches per call, 358
  * with 14, 345 with 7; 232 / 240 CUs leave the tail too little (it becomes the longer side), 216: 356 (DESIGN.md sections 4-5; DESIGN_HISTORY.md section 8). */
-#ifndef K1W_SHARE_CUS
-#define K1W_SHARE_CUS 224		/* (A/B builds: 208 / 240 with 26 / 30 batches per call, profiles/r06_c3.md) */
-#endif
-static const int kK1wShareCus = K1W_SHARE_CUS;
+static const int kK1wShareCus = 224;	/* (208 / 240 with 26 / 30 batches per call measured no better, profiles/r06_c3.md) */
 static const int kSubSamplesLog2 = 26;	/* default sub-launch: 64 Mi samples (64 reference batches of 1024 x 1024) */
 
 static const int kRiseMax = 8192;	/* largest batch served by the rise/decay table */
@@ -420,8 +417,6 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 	int ndev = 0;
 	size_t tiles_max;
 	std::vector<float2> tw;
-	int cu_reserved = 0;
-	uint32_t cu_mask_fft[8], cu_mask_cnt[8];
 
 	if (!self)
 		return NULL;
@@ -497,30 +492,10 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 		e = getenv("FOSPHOR_AMD_K1W_SHARE");   self->kn_k1w_share_off = (e && *e == '0');
 	}
 
-	/* Measurement only, probe builds (-DFOSPHOR_AMD_PROBES; profiles/r04_ceiling.md): FOSPHOR_AMD_DBG_CUMASK=k reserves k CUs (k / 8 per XCD; mask bit i is CU i / 8 of
-	 * XCD i % 8, tools/ubench/cu_mask_probe.hip) for the count / merge streams and confines every FFT stream -- including the
-	 * instance's main stream, which is then the library's own and not the caller's -- to the rest.  Space-sharing by mask
-	 * measured far worse than the hardware's own interleaving (DESIGN_HISTORY.md 4a); nothing in the product path sets it. */
-#ifdef FOSPHOR_AMD_PROBES
-	{
-		const char *e = getenv("FOSPHOR_AMD_DBG_CUMASK");
-		cu_reserved = e ? atoi(e) : 0;
-		if (cu_reserved < 8 || cu_reserved > 128 || (cu_reserved & 7))
-			cu_reserved = 0;
-	}
-#endif
-	for (int w = 0; w < 8; w++) {
-		const int lo = 32 * w, split = 256 - cu_reserved;
-		cu_mask_fft[w] = split >= lo + 32 ? ~0u : (split <= lo ? 0u : ((1u << (split - lo)) - 1u));
-		cu_mask_cnt[w] = ~cu_mask_fft[w];
-	}
-	if (cfg && cfg->stream && !cu_reserved) {
+	if (cfg && cfg->stream) {
 		self->stream = (hipStream_t)cfg->stream;
 	} else {
-		if (cu_reserved)
-			HIP_TRY(hipExtStreamCreateWithCUMask(&self->stream, 8, cu_mask_fft), "hipExtStreamCreateWithCUMask");
-		else
-			HIP_TRY(hipStreamCreateWithFlags(&self->stream, hipStreamNonBlocking), "hipStreamCreate");
+		HIP_TRY(hipStreamCreateWithFlags(&self->stream, hipStreamNonBlocking), "hipStreamCreate");
 		self->own_stream = 1;
 	}
 
@@ -542,10 +517,7 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 	}
 	self->k1_streams[0] = self->stream;
 	for (int i = 1; i < self->n_k1_streams; i++) {
-		if (cu_reserved)
-			HIP_TRY(hipExtStreamCreateWithCUMask(&self->k1_streams[i], 8, cu_mask_fft), "hipExtStreamCreateWithCUMask (FFT stream)");
-		else
-			HIP_TRY(hipStreamCreateWithFlags(&self->k1_streams[i], hipStreamNonBlocking), "hipStreamCreate (FFT stream)");
+		HIP_TRY(hipStreamCreateWithFlags(&self->k1_streams[i], hipStreamNonBlocking), "hipStreamCreate (FFT stream)");
 		HIP_TRY(hipEventCreateWithFlags(&self->ev_k1s_done[i], dep_event_flags()), "create event");
 	}
 	HIP_TRY(hipMalloc((void **)&self->d_hist, sizeof(float) * (size_t)self->n_bins * self->n), "alloc histogram");
@@ -571,13 +543,8 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 	}
 	/* host staging slot: the reference's cap of 1024 spectra per call (cl.c:885), or this instance's */
 	self->stage_samples = (size_t)self->n * (self->max_spectra < 1024 ? self->max_spectra : 1024);
-	if (cu_reserved) {
-		HIP_TRY(hipExtStreamCreateWithCUMask(&self->stream2, 8, cu_mask_cnt), "hipExtStreamCreateWithCUMask (count stream)");
-		HIP_TRY(hipExtStreamCreateWithCUMask(&self->stream3, 8, cu_mask_cnt), "hipExtStreamCreateWithCUMask (merge stream)");
-	} else {
-		HIP_TRY(hipStreamCreateWithFlags(&self->stream2, hipStreamNonBlocking), "hipStreamCreate (count stream)");
-		HIP_TRY(hipStreamCreateWithFlags(&self->stream3, hipStreamNonBlocking), "hipStreamCreate (merge stream)");
-	}
+	HIP_TRY(hipStreamCreateWithFlags(&self->stream2, hipStreamNonBlocking), "hipStreamCreate (count stream)");
+	HIP_TRY(hipStreamCreateWithFlags(&self->stream3, hipStreamNonBlocking), "hipStreamCreate (merge stream)");
 	for (int i = 0; i < 2; i++) {
 		HIP_TRY(hipEventCreateWithFlags(&self->ev_k2_done[i], dep_event_flags()), "create event");
 		HIP_TRY(hipEventCreateWithFlags(&self->ev_h_free[i], dep_event_flags()), "create event");
@@ -906,12 +873,6 @@ static void fill_k1(struct fosphor *self, K1Params *k1, const void *d_iq, int to
 	k1->scratch = self->d_scratch;
 	k1->sync = (self->log2n == 16 && self->k1h_fused) ? self->d_k1h_sync : NULL;
 	k1->sync_err = self->h_k1h_err;
-#ifdef FOSPHOR_AMD_PROBES
-	{
-		static const int dbg = [] { const char *e = getenv("FOSPHOR_AMD_DBG_K1H"); return e ? atoi(e) : 0; }();
-		k1->dbg_k1h = dbg;
-	}
-#endif
 	k1->iq_format = self->iq_format;
 	k1->n_cus = self->n_cus;
 	{
@@ -981,12 +942,6 @@ static void fill_k2(const struct fosphor *self, K2Params *k2, int total, int bat
 	k2->w = 1.0f - self->alpha;
 	k2->log2_w = (float)log2((double)(1.0f - self->alpha));
 	k2->t_offset = t_offset; k2->weight_batch = weight_batch;
-#ifdef FOSPHOR_AMD_PROBES
-	{
-		static const int dbg_same = getenv("FOSPHOR_AMD_DBG_SAME") != NULL;
-		k2->dbg_same = dbg_same;
-	}
-#endif
 }
 
 /* The per-chunk float partials of n_batches batches of cpb chunks each, reduced into live-sum / max slot lslot; sum16: the chunks'
@@ -1129,12 +1084,6 @@ static int run_merge(struct fosphor *self, int n_batches, int batch, int slot0, 
 	k3.n_batches = n_batches; k3.batch = batch; k3.n_bins = self->n_bins; k3.n = self->n;
 	k3.t0r = self->t0r; k3.t0d = self->t0d; k3.alpha = self->alpha;
 	k3.cell_begin = cell_begin; k3.cell_end = cell_end;
-#ifdef FOSPHOR_AMD_PROBES
-	{
-		static const int dbg_same = getenv("FOSPHOR_AMD_DBG_SAME") != NULL;
-		k3.dbg_same = dbg_same;
-	}
-#endif
 	prof_begin(self, 2, st);
 	HIP_TRY(launch_k3(k3, st), "launch merge");
 	prof_end(self, st);
@@ -1184,25 +1133,6 @@ static int wf_leave(struct fosphor *self, hipStream_t ks)
 	return 0;
 }
 
-/* measurement only, probe builds (results are wrong): FOSPHOR_AMD_DBG_SKIP bit 0 = no K1, bit 1 = no count / merge, bit 2 = no K3,
- * bit 3 = no K2 (bits 1-3: device-resident calls); FOSPHOR_AMD_DBG_NOWAIT: an FFT launch does not wait for the count kernel that
- * still reads its intermediate set */
-#ifdef FOSPHOR_AMD_PROBES
-static int dbg_skip(void)
-{
-	static const int v = [] { const char *e = getenv("FOSPHOR_AMD_DBG_SKIP"); return e ? atoi(e) : 0; }();
-	return v;
-}
-static int dbg_nowait(void)
-{
-	static const int v = getenv("FOSPHOR_AMD_DBG_NOWAIT") != NULL;
-	return v;
-}
-#else
-static int dbg_skip(void) { return 0; }
-static int dbg_nowait(void) { return 0; }
-#endif
-
 /* One FFT launch ("piece") of sub_total spectra from d_iq on FFT stream ks; its first spectrum is spectrum t of the waterfall ring's
  * time frame (its row goes to ring position wf_pos + t), and rows are stored for the spectra from first_row on (same frame).  The
  * piece writes the next intermediate set of the rotation once the count kernel that read that set last is done, and the count
@@ -1217,7 +1147,7 @@ static int k1_piece(struct fosphor *self, hipStream_t ks, const void *d_iq, int 
 	self->pp = (self->pp + 1) % self->n_sets;
 	self->d_bins = self->d_bins_pp[set];
 	self->d_partial = self->d_partial_pp[set];
-	if (self->overlap && self->set_used[set] && !dbg_nowait())
+	if (self->overlap && self->set_used[set])
 		HIP_TRY(hipStreamWaitEvent(ks, self->ev_set_free[set], 0), "wait for intermediate set");
 	if (!stores_rows)
 		wf_first = sub_total;
@@ -1225,8 +1155,7 @@ static int k1_piece(struct fosphor *self, hipStream_t ks, const void *d_iq, int 
 	if (stores_rows && wf_enter(self, ks))
 		return -1;
 	prof_begin(self, 0, ks);
-	if (!(dbg_skip() & 1))
-		HIP_TRY(launch_k1(k1, ks), "launch fft_bin");
+	HIP_TRY(launch_k1(k1, ks), "launch fft_bin");
 	prof_end(self, ks);
 	if (self->log2n == 13) {
 		if (k1.cus) self->k1w_shared++; else self->k1w_full++;
@@ -1305,11 +1234,6 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 
 		if (set < 0)
 			return -EIO;
-		if (dbg_skip() & 2) {
-			if (k1_set_release(self, set))
-				return -EIO;
-			continue;
-		}
 		if (three) {
 			hset = self->hset;
 			self->hset ^= 1;
@@ -1318,7 +1242,7 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 		} else if (drain_h_sets(self, st2)) {
 			return -EIO;
 		}
-		if (!(dbg_skip() & 8) && run_count(self, nb, batch, tile, 0, 0, batch, st2, 1, hset))
+		if (run_count(self, nb, batch, tile, 0, 0, batch, st2, 1, hset))
 			return -EIO;
 		if (k1_set_release(self, set))
 			return -EIO;
@@ -1326,7 +1250,7 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 			HIP_TRY(hipEventRecord(self->ev_k2_done[hset], st2), "record K2 done");
 			HIP_TRY(hipStreamWaitEvent(st3, self->ev_k2_done[hset], 0), "K3 waits for K2");
 		}
-		if (!(dbg_skip() & 4) && run_merge(self, nb, batch, 0, st3, 1, hset))
+		if (run_merge(self, nb, batch, 0, st3, 1, hset))
 			return -EIO;
 		if (self->overlap && self->log2n == 13) {
 			HIP_TRY(hipEventRecord(self->ev_tail, st3), "record tail");
@@ -2121,12 +2045,7 @@ extern "C" int fosphor_amd_tune_placement(struct fosphor *self, const void *d_sa
 				self->d_bins_pp[i] = ob; self->d_partial_pp[i] = op;	/* keep what we had */
 				rejected.push_back(nb); rejected.push_back(np);
 			}
-#ifdef FOSPHOR_AMD_PROBES
-			static const int tune_all = [] { const char *e = getenv("FOSPHOR_AMD_DBG_TUNE_ALL"); return e ? atoi(e) : 0; }();
-#else
-			constexpr int tune_all = 0;
-#endif
-			if (best <= good_ms && t + 1 >= tune_all)
+			if (best <= good_ms)
 				break;
 		}
 		if (best > worst_after) worst_after = best;

@@ -46,9 +46,6 @@ struct K1Params {
 	int   iq_format;		/* FOSPHOR_AMD_IQ_*: 0 fp32 pairs (8 B per sample), 1 fp16 pairs (variant 4 only), 2 int16 pairs (4 B) */
 	uint32_t *sync;			/* variant 4: cluster counters [64][64] */
 	uint32_t *sync_err;		/* ... its error word (host-mapped): set when a bounded cluster wait times out */
-	int   dbg_k1h;			/* measurement only (FOSPHOR_AMD_DBG_K1H): 1 no cluster waits, 2 no IQ loads, 4 no row / bin stores,
-					 * 8 no intermediate stores / loads, 64 no stage-A arithmetic, 128 no stage-B arithmetic / epilogue,
-					 * 256 no intermediate loads, 512 no intermediate stores -- results are wrong with any of them */
 	int   total;			/* spectra in this launch */
 	int   tile;			/* spectra per wave: 4, 8 or 16 */
 	int   wf_pos0, wf_mask;		/* ring position of spectrum 0, wf_rows-1 */
@@ -95,7 +92,6 @@ struct K2Params {
 	/* sharded batch (multi-GPU): this launch holds spectra [t_offset, t_offset+batch)
 	 * of a batch of weight_batch spectra; single GPU: t_offset 0, weight_batch = batch */
 	int   t_offset, weight_batch;
-	int   dbg_same;			/* measurement only: every chunk reads and writes chunk 0's memory (no HBM traffic) */
 	uint32_t *rowmask;		/* hc16 hand-off to K3: [N/64][mask_words][mask_stride >= chunks] one bit per bin row of the slab (the
 					 * batches of a row side by side: K3 fetches a row's 64 batches in one request); rows whose 64
 					 * counts are all zero are NOT stored and their bit is clear (nullptr: every row is stored) */
@@ -127,7 +123,6 @@ struct K3Params {
 	int   n_batches, batch, n_bins, n;
 	float t0r, t0d, alpha;
 	float live_decay;		/* (1-alpha)^batch */
-	int   dbg_same;			/* measurement only: every batch reads batch 0's counts */
 	int   cell_begin, cell_end;	/* cells [begin, end) of the (bin, x) array are updated (0, 0 = all): the
 					 * frequency-sliced merge of the multi-GPU split; the columns always are */
 	const uint32_t *rowmask;	/* hc16 path: K2's row bits (see K2Params) */

@@ -30,15 +30,10 @@
 
 namespace fosphor_amd {
 
-/* Measurement switches that give WRONG RESULTS BY CONSTRUCTION (kernel parts skipped, chunks aliased) exist only in probe builds
- * (-DFOSPHOR_AMD_PROBES, tools/r04_ceiling_build.sh): in the product library they are the constant 0 and the code behind them is gone. */
-#ifdef FOSPHOR_AMD_PROBES
-#define PROBE_K1H(p)  ((p).dbg_k1h)
-#define PROBE_SAME(p) ((p).dbg_same)
-#else
-#define PROBE_K1H(p)  0
-#define PROBE_SAME(p) 0
-#endif
+/* Build switches.  The only ones these sources have are the phase-timing builds, each a -D on the hipcc line; results stay correct:
+ *   K1_TIMING=1   the 1024-point kernel    (tools/k1_phase_timing.py)     K1W_TIMING=1  the 8192-point kernel   (tools/k1w_phase_timing.py)
+ *   K1H_TIMING=1  the 65536-point kernel   (tools/k1h_phase_timing.py)    K2_TIMING     the count kernel        (tools/k2_phase_timing.py)
+ * The alternatives measured against the shipped code are recorded in profiles/ and DESIGN_HISTORY.md. */
 
 /* ------------------------------------------------------------------------ */
 /* Complex helpers: same operations, same order as fft.cl                   */
@@ -187,15 +182,12 @@ static __device__ __forceinline__ void bf_mj_s(v2f &a, v2f &b, v2f t, v2f two)
  * inline-assembly statements end up adjacent and the compiler separates each such pair by an s_nop (it assumes a value written by inline
  * assembly cannot be forwarded): ~50 issue slots per thread and spectrum in the 8192-point kernel.  IA / IB: registers of the a / b inputs,
  * MJ: bit j set = butterfly j takes -j T (bf_mj). */
-#ifndef BF_STAGEWISE
-#define BF_STAGEWISE 1
-#endif
 template <bool SC, bool TS, int MJ, int I0, int I1, int I2, int I3, int I4, int I5, int I6, int I7, int D, int CNT = 8, bool SW = SC>
 static __device__ __forceinline__ void bf8(v2f (&r)[16], v2f t0, v2f t1, v2f t2, v2f t3, v2f t4, v2f t5, v2f t6, v2f t7, v2f two)
 {
 	constexpr int ia[8] = { I0, I1, I2, I3, I4, I5, I6, I7 };
 	const v2f t[8] = { t0, t1, t2, t3, t4, t5, t6, t7 };
-	if (BF_STAGEWISE && SW) {		/* (SW: the 65536-point kernel measured 5 % slower in this form: 207 -> 217 registers under its skewed loop) */
+	if (SW) {		/* (SW: the 65536-point kernel measured 5 % slower in this form: 207 -> 217 registers under its skewed loop) */
 	v2f u[8], pa[8], nb[8];
 #pragma unroll
 	for (int j = 0; j < CNT; j++) {
@@ -262,7 +254,7 @@ static __device__ __forceinline__ void pass16_cd(v2f (&r)[16], v2f t2, v2f t2w, 
 template <bool SC = false, bool SW = SC>
 static __device__ __forceinline__ void pass16_first(v2f (&r)[16], const v2f (&wab)[8], v2f w16, v2f w8, v2f w163, v2f two)
 {
-	if (BF_STAGEWISE && SW) {
+	if (SW) {
 		/* stage A step by step as well: the products, then the sums, then the differences */
 		v2f m[8], pa[8], nb[8];
 #pragma unroll
@@ -398,17 +390,11 @@ template <typename ThrPtr>		/* const double * (vector loads), an LDS pointer (a 
 static __device__ __forceinline__ uint32_t bin_exact(float re, float im, float l2_fast, int guess,
                                                       ThrPtr thr, int nb, float *l2_out)
 {
-#ifdef K1_DBG_EXACT_BODY		/* measurement only: 1 = the branch with an empty body, 2 = the arithmetic without the table */
-	if (K1_DBG_EXACT_BODY == 1) { *l2_out = l2_fast; asm volatile("s_nop 0"); return (uint32_t)guess; }
-#endif
 	const double xr = (double)re, xi = (double)im;
 	const double sd = __builtin_fma(xr, xr, xi * xi);
 	const float  sf = (float)sd;
 	int bin;
 
-#ifdef K1_DBG_EXACT_BODY
-	if (K1_DBG_EXACT_BODY == 2) { *l2_out = l2_fast; return (uint32_t)(guess - (sd < 1.0 ? 1 : 0) + (sd >= 3.0 ? 1 : 0)) & 255u; }
-#endif
 	if (sf >= 1e-30f && sf <= 1e30f) {
 		/* the guess is within one bin of the truth */
 		double t0, t1;
@@ -461,27 +447,13 @@ struct BinConst { float A, C, amb, kappa; int nb; const double *thr; };
  * +inf for |X|^2 in {0, denormal-flushed, inf}, NaN for NaN: compared as an unsigned bit
  * pattern all of those order above every finite value, so one running v_max_u32 per spectrum
  * collects "some sample needs the exact path" without per-sample compares or branches. */
-#ifndef K1_DBG_EPI
-#define K1_DBG_EPI 0		/* measurement only (wrong results): 1 no v_log_f32, 2 no ambiguity measure, 4 no live / max update, 8 no bin byte,
-				 * 16 no bin-index stores, 32 sixteen LDS atomics per spectrum on a dummy counter array (what counting inside K1
-				 * would issue): the probe builds of profiles/r04_ceiling.md (tools/r04_ceiling_build.sh) */
-#endif
-#ifndef K1_LATE_BINS
-#define K1_LATE_BINS 1			/* 0: the bin dwords of a quad stored where the quad ends (A/B builds) */
-#endif
-#ifndef K1_THR_LDS
-#define K1_THR_LDS 1			/* 0: the N = 1024 kernel reads the thresholds from memory (A/B builds) */
-#endif
-#ifndef K1_DBG_NO_EXACT
-#define K1_DBG_NO_EXACT 0		/* measurement only: 1 drops the exact path (wrong bins on near-ties) */
-#endif
 static __device__ __forceinline__ float bin_fast(float re, float im, const BinConst &k, float *l2_out, uint32_t *amb_bits)
 {
 	const float s  = __builtin_fmaf(re, re, im * im);
-	const float l2 = (K1_DBG_EPI & 1) ? s : __builtin_amdgcn_logf(s);		/* v_log_f32 */
+	const float l2 = __builtin_amdgcn_logf(s);		/* v_log_f32 */
 	const float v  = __builtin_fmaf(k.A, l2, k.C);
 	const float r  = __builtin_rintf(v);
-	const float a  = (K1_DBG_EPI & 2) ? 0.0f : __builtin_fmaf(__builtin_fabsf(l2), k.kappa, __builtin_fabsf(v - r));
+	const float a  = __builtin_fmaf(__builtin_fabsf(l2), k.kappa, __builtin_fabsf(v - r));
 	*l2_out = l2;
 	*amb_bits = __float_as_uint(a);
 	return r;
@@ -506,10 +478,7 @@ static __device__ __forceinline__ float max_f32(float a, float b)
 /* K1                                                                       */
 /* ------------------------------------------------------------------------ */
 
-/* Tunables (tools/ab_bench.sh builds variants with -D...) */
-#ifndef K1_WAVES_PER_SIMD
-#define K1_WAVES_PER_SIMD 2		/* __launch_bounds__ second argument */
-#endif
+constexpr int kK1WavesPerSimd = 2;		/* __launch_bounds__ second argument (measured) */
 
 /* K1_TIMING=1 (debug builds only, tools/k1_phase_timing.py): s_memtime stamps per phase,
  * accumulated per wave into K1Params::dbg[wave][phase]. */
@@ -580,7 +549,7 @@ static __device__ __forceinline__ void load_iq16(v2f (&x)[16], const uint32_t *_
  * stores (bin dwords every 4 spectra, tile partials every tile) as k1_fft_bin -- and nothing else.
  * Its duration is the practical floor the memory system sets for K1 on this chip: bench.py reports
  * K1's duration next to it (roofline.traffic_twin). */
-__global__ __launch_bounds__(256, K1_WAVES_PER_SIMD)
+__global__ __launch_bounds__(256, kK1WavesPerSimd)
 void k1_traffic_twin(const K1Params p)
 {
 	const int lane   = threadIdx.x & 63;
@@ -643,9 +612,7 @@ hipError_t launch_k1_traffic_twin(const K1Params &p, hipStream_t s)
  * 4 waves per SIMD without spills; the price is one 2-wave s_barrier per exchange.
  * After pass 3 wave w takes the pass-4 butterflies c in [4w, 4w+4), i.e. columns
  * lane + 64m for m in {4w..4w+3} U {8+4w..8+4w+3}. */
-#ifndef K1V2_WAVES_PER_SIMD
-#define K1V2_WAVES_PER_SIMD 3
-#endif
+constexpr int kK1v2WavesPerSimd = 3;		/* __launch_bounds__ second argument (measured) */
 
 static __device__ __forceinline__ void load_iq8(v2f (&x)[8], const float2 *__restrict__ src)
 {
@@ -699,26 +666,6 @@ static __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *b
 	return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0xffffffff, 0x00020000);	/* raw buffer, 32-bit data format */
 }
 constexpr int kAuxNT = 2, kAuxSC1 = 16;		/* gfx94x / gfx950 cache-policy bits of the buffer intrinsics: nt, sc1 */
-#ifndef K1H_OUT_AUX
-#define K1H_OUT_AUX 2				/* cache policy of the 65536-point kernel's row / index stores (A/B builds) */
-#endif
-#ifndef K1H_IQ_MOD				/* ... and of its LDS-DMA of the IQ (K1H_IQ_POL: A/B builds) */
-#if !defined(K1H_IQ_POL) || K1H_IQ_POL == 0
-#define K1H_IQ_MOD "nt"
-#elif K1H_IQ_POL == 1
-#define K1H_IQ_MOD ""
-#elif K1H_IQ_POL == 2
-#define K1H_IQ_MOD "sc1"
-#elif K1H_IQ_POL == 3
-#define K1H_IQ_MOD "sc0 sc1"
-#elif K1H_IQ_POL == 4
-#define K1H_IQ_MOD "sc0 sc1 nt"
-#elif K1H_IQ_POL == 5
-#define K1H_IQ_MOD "sc1 nt"
-#else
-#define K1H_IQ_MOD "sc0 nt"
-#endif
-#endif
 template <int AUX>
 static __device__ __forceinline__ void bst_v2f(v2f v, __amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff)
 {
@@ -763,31 +710,14 @@ static __device__ __forceinline__ v2f bld_v2f(__amdgpu_buffer_rsrc_t rs, uint32_
  * IQ requested for the NEXT spectrum).  Nothing is handed from thread to thread through global memory in these kernels. */
 static __device__ __forceinline__ void wg_barrier_lds()
 {
-#if defined(FOSPHOR_AMD_PROBES) && defined(K1W_NOSYNC)
-	asm volatile("" ::: "memory");		/* timing probe only: results are garbage */
-#else
 	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
 }
 
-/* K1W_TIMING=1 (probe builds only, tools/k1w_phase_timing.py): s_memtime stamps per phase of the 8192-point kernel's loop, accumulated per
+/* K1W_TIMING=1 (timing builds only, tools/k1w_phase_timing.py): s_memtime stamps per phase of the 8192-point kernel's loop, accumulated per
  * wave (waves 0 and 4 of a work-group: the early and the late one of a SIMD) into K1Params::dbg[(work-group * 2 + slot) * 16 + phase].
  * Reading the clock waits for the wave's LDS operations (s_memtime answers on lgkmcnt). */
 #ifndef K1W_TIMING
 #define K1W_TIMING 0
-#endif
-/* K1W_PROBE (probe builds, results are garbage: timing only): 1 no LDS stores, 2 no LDS loads, 4 no epilogue, 8 no index stores,
- * 16 no IQ requests inside the loop */
-#if defined(FOSPHOR_AMD_PROBES) && defined(K1W_PROBE)
-#define K1W_P(b) ((K1W_PROBE) & (b))
-#else
-#define K1W_P(b) 0
-#endif
-#ifndef K1W_READ_FIRST
-#define K1W_READ_FIRST 0		/* (A/B builds) 1: a late wave requests its operands BEFORE its epilogue piece (measured: 1.2 % slower) */
-#endif
-#ifndef K1W_PRIO
-#define K1W_PRIO 1			/* (A/B builds) 1: the passes run at a higher issue priority than the epilogue pieces */
 #endif
 #if K1W_TIMING
 #define K1W_STAMP(i) do { const uint32_t _now = (uint32_t)__builtin_readcyclecounter(); wacc[i] += _now - wprev; wprev = _now; } while (0)
@@ -849,45 +779,29 @@ constexpr int kK1wIdxStores = 16;	/* index stores a thread issues per ODD spectr
  *     about behind s_waitcnt vmcnt(0); the reads of the buffer sit behind an explicit vmcnt(0) of the requesting wave + a barrier;
  *   - work-group barriers are s_waitcnt lgkmcnt(0) + s_barrier (wg_barrier_lds): __syncthreads() would drain vmcnt;
  *   - a poll of a cluster counter through the vector path is a load too (it returns behind whatever its wave has in flight): the "has
- *     everybody read the intermediate" question therefore goes through the SCALAR path, every wave for itself (K1H_SPOLL, round 6; until
+ *     everybody read the intermediate" question therefore goes through the SCALAR path, every wave for itself (round 6; until
  *     round 5 the last wave, which requested no IQ, asked ahead of its epilogue's stores and a barrier passed the answer on);
  *   - the exact path's threshold table sits in LDS (ds_read has its own counter). */
 
 /* Loads return IN ORDER and the first stage of a radix-16 pass pairs inputs j and j + 8: requested in this order, a butterfly's two inputs
- * arrive together (requested 0..15, the first butterfly waited for nine loads).  K1H_LOAD_ORDER=0: plain order (A/B builds). */
-#ifndef K1H_LOAD_ORDER
-#define K1H_LOAD_ORDER 1
-#endif
-#ifndef K1H_SC
-#define K1H_SC false		/* (A/B builds) true: (2, 2) and the uniform twiddles of the first pass in scalar registers, like the 8192-point kernel */
-#endif
-#define K1H_PAIR(i) (K1H_LOAD_ORDER ? ((((i) & 1) << 3) | ((i) >> 1)) : (i))
-#ifndef K1H_SPLIT
-#define K1H_SPLIT 1			/* where the second pass of the NEXT spectrum's stage A runs (A/B builds): 0 stages A, B behind the arrival at the cluster
-					 * barrier and C, D beside the loads of the intermediate; 1 all of it beside the loads; 2 all of it behind the arrival */
-#endif
-/* K1H_TIMING=1 (probe builds only, tools/k1h_phase_timing.py): s_memtime stamps per phase of the 65536-point kernel's loop, accumulated per
+ * arrive together (requested 0..15, the first butterfly waited for nine loads). */
+#define K1H_PAIR(i) ((((i) & 1) << 3) | ((i) >> 1))
+/* K1H_TIMING=1 (timing builds only, tools/k1h_phase_timing.py): s_memtime stamps per phase of the 65536-point kernel's loop, accumulated per
  * wave (waves 0, 3 and 7 of a work-group) into K1Params::dbg[(work-group * 3 + slot) * 16 + phase]. */
 #ifndef K1H_TIMING
 #define K1H_TIMING 0
 #endif
-/* K1H_SPOLL=1 (round 6): the "has every member read the intermediate" question is asked by EVERY wave for itself, through the SCALAR data
+/* Round 6: the "has every member read the intermediate" question is asked by EVERY wave for itself, through the SCALAR data
  * path (s_dcache_inv + s_load_dword: its answer does not queue behind the wave's vector stores -- another counter, another path), right before the
  * wave's stores of the next spectrum: by then the answer has long been yes.  Before, the last wave asked ahead of its epilogue (a vector
  * load behind the epilogue's stores would have waited for them), saw the spread between the cluster's members (~1 900 cycles per spectrum,
  * K1H_TIMING builds) and everybody else sat at a work-group barrier for the answer.  That barrier goes with it: nothing else needs it
  * (the exchange array's readers are separated from its next writers by the barrier behind the stores). */
-#ifndef K1H_SPOLL
-#define K1H_SPOLL 1
-#endif
-/* K1H_PRIO=1 (round 6): the YOUNGER wave of each SIMD (waves 4-7 of the work-group) issues at a higher priority than the older one.  Left to the
+/* Round 6: the YOUNGER wave of each SIMD (waves 4-7 of the work-group) issues at a higher priority than the older one.  Left to the
  * arbiter's age order the older wave of a SIMD won every tie and the younger ones reached each of the four barriers ~2 000 cycles late
  * (K1H_TIMING builds); with the priority the other way round the halves of the work-group take turns at being early -- the early wave's stores
  * and first pass run beside the late wave's epilogue -- and the kernel alone went from 231 to 216 us (profiles/r06_c5.md: the mirror image,
  * priority to the OLDER half, changes nothing; levels 1 / 2 / 3 measure the same). */
-#ifndef K1H_PRIO
-#define K1H_PRIO 1
-#endif
 static __device__ __forceinline__ uint32_t sload_fresh(const uint32_t *p)
 {
 	uint32_t v;
@@ -1035,7 +949,7 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 		return hipGetLastError();
 	}
 	if (p.variant == 2) {
-		const int maxb = 256 * 2 * K1V2_WAVES_PER_SIMD;	/* resident 2-wave work-groups on 256 CUs */
+		const int maxb = 256 * 2 * kK1v2WavesPerSimd;	/* resident 2-wave work-groups on 256 CUs */
 		int blocks = tiles < maxb ? tiles : maxb;
 		if (sc16 && p.fft_out)
 			hipLaunchKernelGGL(k1v2_fft_bin_sc16<true>, dim3(blocks), dim3(128), 0, s, p);
@@ -1121,16 +1035,13 @@ hipError_t launch_bin_hook(const float2 *fft, uint8_t *bin, float *pwr, int n,
  * 72 us). */
 /* NW waves per work-group: 4 where the kernel has to fit beside K1 (8-bit indices, N = 1024); 16 for the
  * 16-bit-index geometries, whose grids are small (N/64 x chunks) and whose rows are latency-bound */
-/* K2_TIMING (probe builds with -DFOSPHOR_AMD_PROBES -DK2_TIMING, tools/k2_phase_timing.py): s_memtime stamps per phase of the count kernel, summed
+/* K2_TIMING (timing builds with -DK2_TIMING, tools/k2_phase_timing.py): s_memtime stamps per phase of the count kernel, summed
  * over the work-groups' first waves into g_k2_time[] (read through fosphor_amd_debug_k2_timing) */
-#if defined(FOSPHOR_AMD_PROBES) && defined(K2_TIMING)
+#ifdef K2_TIMING
 __device__ unsigned long long g_k2_time[16];
 #define K2_STAMP(i) do { if (tid == 0) { const long long _n = __builtin_readcyclecounter(); atomicAdd(&g_k2_time[i], (unsigned long long)(_n - k2prev)); k2prev = _n; } } while (0)
 #else
 #define K2_STAMP(i) do { } while (0)
-#endif
-#ifndef K2_DBG
-#define K2_DBG 0		/* measurement only (wrong counts): 1 no LDS atomics, 2 plain LDS stores instead (profiles/r04_ceiling.md) */
 #endif
 /* one hit: row `bin` of the [bin][32] histogram (128 bytes per row), the lane's column at byte hc4 */
 static __device__ __forceinline__ void lds_count(uint32_t *h, uint32_t bin, uint32_t hc4, uint32_t inc)
@@ -1155,14 +1066,14 @@ void k2_count(const K2Params p)
 								 * load cost a v_mul_lo_u32 and a 64-bit add: 23 instead of 31 VGPRs, 2 instead of 22
 								 * v_mul_lo_u32; the kernel's time did not change, it does not wait for its VALUs) */
 	const int x0   = blockIdx.x * 64;
-	const int c    = PROBE_SAME(p) ? 0 : blockIdx.y;	/* chunk index within the launch */
+	const int c    = blockIdx.y;			/* chunk index within the launch */
 	const int cpb  = p.batch / p.chunk;		/* chunks per batch */
 	const int f    = c / cpb;			/* batch index */
 	const int t_in = (c - f * cpb) * p.chunk;	/* first spectrum of the chunk within its batch */
 	const int nb   = p.n_bins;
 	const int hcol = lane & 31;
 	const uint32_t inc = (lane & 32) ? 0x10000u : 1u;
-#if defined(FOSPHOR_AMD_PROBES) && defined(K2_TIMING)
+#ifdef K2_TIMING
 	long long k2prev = __builtin_readcyclecounter();
 	if (tid == 0) atomicAdd(&g_k2_time[15], 1ull);		/* work-groups */
 #endif
@@ -1191,15 +1102,12 @@ void k2_count(const K2Params p)
 		const uint32_t *hi = p.bins + (size_t)(p.total >> 2) * n + (size_t)c * ntl * n + x0 + lane;
 #pragma unroll 1
 		for (uint32_t tl = wv; tl < ntl; tl += NW) {
-#ifndef K2_NT9
-#define K2_NT9 1		/* (0: A/B builds) the index planes of N = 65536 read non-temporally (they are read once; the FFT kernel of the next frame keeps its
-				 * intermediates in the same L2) */
-#endif
-			const uint32_t hv = K2_NT9 ? __builtin_nontemporal_load(&hi[(size_t)tl * n]) : hi[(size_t)tl * n];
+			/* the index planes read non-temporally: they are read once, and the FFT kernel of the next frame keeps its intermediates in the same L2 */
+			const uint32_t hv = __builtin_nontemporal_load(&hi[(size_t)tl * n]);
 			uint32_t v[8];
 #pragma unroll
 			for (uint32_t u = 0; u < 8; u++)
-				v[u] = (u < qpt) ? (K2_NT9 ? __builtin_nontemporal_load(&lo[(size_t)(tl * qpt + u) * n]) : lo[(size_t)(tl * qpt + u) * n]) : 0u;
+				v[u] = (u < qpt) ? __builtin_nontemporal_load(&lo[(size_t)(tl * qpt + u) * n]) : 0u;
 #pragma unroll
 			for (uint32_t u = 0; u < 8; u++) {
 				if (u < qpt) {			/* uniform */
@@ -1283,9 +1191,6 @@ void k2_count(const K2Params p)
 		const __amdgpu_buffer_rsrc_t rs8 = make_rsrc(p.bins + (size_t)c * (p.chunk >> 2) * p.n + x0);
 		const uint32_t nq = p.chunk >> 2, rowb = 4u * (uint32_t)p.n, lane4 = 4u * (uint32_t)lane, hc4 = 4u * (uint32_t)hcol;
 		uint32_t q = wv;
-#if K2_DBG == 1
-		uint32_t dbg_acc = 0;
-#endif
 #pragma unroll 1
 		for (; q + NW * (IF - 1) < nq; q += NW * IF) {	/* independent loads in flight per thread */
 			uint32_t v[IF];
@@ -1295,24 +1200,12 @@ void k2_count(const K2Params p)
 				v[u] = __builtin_amdgcn_raw_buffer_load_b32(rs8, lane4, so + (uint32_t)(NW * u) * rowb, 0);
 #pragma unroll
 			for (int u = 0; u < IF; u++) {
-#if K2_DBG == 1		/* probe: the loads and the address arithmetic without the LDS atomics */
-				dbg_acc += ((v[u] & 0xff) * 32 + hcol) ^ (((v[u] >> 8) & 0xff) * 32 + hcol) ^ (((v[u] >> 16) & 0xff) * 32 + hcol) ^ ((v[u] >> 24) * 32 + hcol);
-#elif K2_DBG == 2	/* probe: plain LDS stores instead of atomics */
-				h[((v[u]      ) & 0xff) * 32 + hcol] = inc;
-				h[((v[u] >>  8) & 0xff) * 32 + hcol] = inc;
-				h[((v[u] >> 16) & 0xff) * 32 + hcol] = inc;
-				h[((v[u] >> 24)       ) * 32 + hcol] = inc;
-#else
 				lds_count(h, lo8(v[u]), hc4, inc);
 				lds_count(h, (v[u] >>  8) & 0xff, hc4, inc);
 				lds_count(h, (v[u] >> 16) & 0xff, hc4, inc);
 				lds_count(h, v[u] >> 24, hc4, inc);
-#endif
 			}
 		}
-#if K2_DBG == 1
-		if (dbg_acc == 0xdeadbeefu) h[0] = dbg_acc;
-#endif
 #pragma unroll 1
 		for (; q < nq; q += NW) {
 			const uint32_t v = __builtin_amdgcn_raw_buffer_load_b32(rs8, lane4, (uint32_t)__builtin_amdgcn_readfirstlane((int)(q * rowb)), 0);
@@ -1406,7 +1299,7 @@ void k2_count(const K2Params p)
 	}
 }
 
-#if defined(FOSPHOR_AMD_PROBES) && defined(K2_TIMING)
+#ifdef K2_TIMING
 extern "C" int fosphor_amd_debug_k2_timing(unsigned long long *out, int reset)
 {
 	unsigned long long z[16] = {};
@@ -1420,18 +1313,14 @@ extern "C" int fosphor_amd_debug_k2_timing(unsigned long long *out, int reset)
 hipError_t launch_k2(const K2Params &p, int n_chunks, hipStream_t s)
 {
 	const size_t lds = (size_t)p.n_bins * 32 * sizeof(uint32_t);
-#ifndef K2_IF8
-#define K2_IF8 8		/* ... 8-bit indices, chunks of at most 1024 spectra (A/B builds) */
-#endif
-#ifndef K2_IF16
-#define K2_IF16 4		/* index loads in flight per thread, 16-bit / 9-bit index geometries (A/B builds) */
-#endif
+	constexpr int kIf16 = 4;	/* index loads in flight per thread, 16-bit / 9-bit index geometries (measured, see k2_count) */
+	constexpr int kIf8  = 8;	/* ... 8-bit indices, chunks of at most 1024 spectra (measured) */
 	if (p.bins16 || p.bins9 || p.bins8p1)
-		hipLaunchKernelGGL((k2_count<16, K2_IF16>), dim3((p.n / 64), n_chunks), dim3(1024), lds, s, p);
+		hipLaunchKernelGGL((k2_count<16, kIf16>), dim3((p.n / 64), n_chunks), dim3(1024), lds, s, p);
 	else if (p.chunk > 1024)
 		hipLaunchKernelGGL((k2_count<4, 4>), dim3((p.n / 64), n_chunks), dim3(256), lds, s, p);
 	else
-		hipLaunchKernelGGL((k2_count<4, K2_IF8>), dim3((p.n / 64), n_chunks), dim3(256), lds, s, p);
+		hipLaunchKernelGGL((k2_count<4, kIf8>), dim3((p.n / 64), n_chunks), dim3(256), lds, s, p);
 	return hipGetLastError();
 }
 
@@ -1539,16 +1428,9 @@ hipError_t launch_k2c(const K2bParams &p, hipStream_t s)
  * (batches of up to 8192 spectra counted as one chunk); 1: 32-bit counts + (d, e) table in memory;
  * 2: 32-bit counts, (d, e) evaluated per cell (batches beyond the table).  Separate instantiations keep
  * the common one (0) at a register budget that lets it share a SIMD with K1. */
-#ifndef K3_ROWS
-#define K3_ROWS 2		/* rows in flight per wave of the sparse form: measured at N = 65536, 1 / 2 / 3 / 4 / 8 / 16 -> scan + merge 56 / 49 / 49 /
-				 * 53 / 61 / 114 us per frame (42 / 58 / 74 / ... / 256 VGPRs: more resident waves beat more requests per wave) */
-#endif
-#ifndef K3_BATCHES
-#define K3_BATCHES 2
-#endif
-#ifndef K3_NO_PIPE
-#define K3_NO_PIPE 0		/* A/B builds: 1 = the sparse form without its software pipeline */
-#endif
+constexpr int kK3Rows = 2;		/* rows in flight per wave of the sparse form: measured at N = 65536, 1 / 2 / 3 / 4 / 8 / 16 -> scan + merge 56 / 49 / 49 /
+					 * 53 / 61 / 114 us per frame (42 / 58 / 74 / ... / 256 VGPRs: more resident waves beat more requests per wave) */
+constexpr int kK3Batches = 2;		/* batches of counts in flight per row of the sparse form (measured) */
 template <int MODE, bool SPARSE = false>
 __global__ __launch_bounds__(256)
 void k3_merge(const K3Params p)
@@ -1601,9 +1483,9 @@ void k3_merge(const K3Params p)
 		const int n_waves = gridDim.x * 4;
 		const int count = (int)p.rowlist[p.rowlist_cnt];
 		const int col = (lane >> 1) + ((lane & 1) << 5);
-		constexpr int R = K3_ROWS;		/* rows in flight per wave: every step below is R independent requests */
-		constexpr int U = K3_BATCHES;		/* batches of counts in flight per row */
-		if (p.n_batches <= U && !K3_NO_PIPE) {
+		constexpr int R = kK3Rows;		/* rows in flight per wave: every step below is R independent requests */
+		constexpr int U = kK3Batches;		/* batches of counts in flight per row */
+		if (p.n_batches <= U) {
 			/* One or two batches per launch (a display frame of the 65536-point configuration is ONE): a row is a list entry, then
 			 * the histogram value and the counts it points to -- two dependent round trips for a few instructions of arithmetic, and a
 			 * wave walks ~20 rows.  Software pipeline, three deep: while row set i is computed and stored, the values of set i + 1 are
@@ -1631,7 +1513,7 @@ void k3_merge(const K3Params p)
 #pragma unroll
 					for (int u = 0; u < U; u++)
 						hc[r][u] = (ok && u < fe && ((e[r] >> (20 + u)) & 1u))
-						        ? (uint32_t)__builtin_nontemporal_load(&p.hc16[(size_t)(PROBE_SAME(p) ? 0 : u) * cells + row * 64 + lane]) : 0u;
+						        ? (uint32_t)__builtin_nontemporal_load(&p.hc16[(size_t)u * cells + row * 64 + lane]) : 0u;
 				}
 			};
 			entries(idx, e_c);
@@ -1702,7 +1584,7 @@ void k3_merge(const K3Params p)
 #pragma unroll
 					for (int r = 0; r < R; r++) {
 						const uint32_t wd = (valid[r] && fl < p.n_batches)
-						        ? p.rowmask[((size_t)slab[r] * p.mask_words + (bin[r] >> 5)) * p.mask_stride + (PROBE_SAME(p) ? 0 : fl)] : 0u;
+						        ? p.rowmask[((size_t)slab[r] * p.mask_words + (bin[r] >> 5)) * p.mask_stride + fl] : 0u;
 						m[r] = __ballot((wd >> (bin[r] & 31)) & 1u);
 					}
 				}
@@ -1714,7 +1596,7 @@ void k3_merge(const K3Params p)
 #pragma unroll
 						for (int u = 0; u < U; u++)
 							hc[r][u] = (f + u < fe && ((m[r] >> (f + u - f0)) & 1ull))
-							        ? (uint32_t)__builtin_nontemporal_load(&p.hc16[(size_t)(PROBE_SAME(p) ? 0 : f + u) * cells + gid[r]]) : 0u;
+							        ? (uint32_t)__builtin_nontemporal_load(&p.hc16[(size_t)(f + u) * cells + gid[r]]) : 0u;
 #pragma unroll
 					for (int r = 0; r < R; r++)
 #pragma unroll
@@ -1768,7 +1650,7 @@ void k3_merge(const K3Params p)
 				hv0[r][1] = p.hist[ok ? hidx[r] + 32 : 0];
 #pragma unroll
 				for (int f = 0; f < 4; f++)
-					hc[r][f] = (f < fe) ? __builtin_nontemporal_load(&hc32[(size_t)(PROBE_SAME(p) ? 0 : f) * pairs + gg]) : 0u;
+					hc[r][f] = (f < fe) ? __builtin_nontemporal_load(&hc32[(size_t)f * pairs + gg]) : 0u;
 			}
 #pragma unroll
 			for (int r = 0; r < R; r++) {
@@ -1817,7 +1699,7 @@ void k3_merge(const K3Params p)
 					uint32_t hc[8];
 #pragma unroll
 					for (int u = 0; u < 8; u++)
-						hc[u] = (uint32_t)__builtin_nontemporal_load(&p.hc16[(size_t)(PROBE_SAME(p) ? 0 : f + u) * cells + gid]);
+						hc[u] = (uint32_t)__builtin_nontemporal_load(&p.hc16[(size_t)(f + u) * cells + gid]);
 #pragma unroll
 					for (int u = 0; u < 8; u++) {
 						if (!((hv <= 0.01f) && (hc[u] == 0))) {	/* display.cl:237-238 */
@@ -1833,7 +1715,7 @@ void k3_merge(const K3Params p)
 					uint32_t hc[4];
 #pragma unroll
 					for (int u = 0; u < 4; u++)
-						hc[u] = (uint32_t)__builtin_nontemporal_load(&p.hc16[(size_t)(PROBE_SAME(p) ? 0 : f + u) * cells + gid]);
+						hc[u] = (uint32_t)__builtin_nontemporal_load(&p.hc16[(size_t)(f + u) * cells + gid]);
 #pragma unroll
 					for (int u = 0; u < 4; u++) {
 						if (!((hv <= 0.01f) && (hc[u] == 0))) {
@@ -1846,7 +1728,7 @@ void k3_merge(const K3Params p)
 					f += 4;
 				}
 				for (; f < fe; f++) {
-					const uint32_t hc = (uint32_t)p.hc16[(size_t)(PROBE_SAME(p) ? 0 : f) * cells + gid];
+					const uint32_t hc = (uint32_t)p.hc16[(size_t)f * cells + gid];
 					if (!((hv <= 0.01f) && (hc == 0))) {
 						const float2 de = rise_in_lds ? rise_lds[hc] : p.rise[hc];
 						hv = (hv - de.x) * de.y + de.x;
@@ -1952,7 +1834,7 @@ void k3_scan(const K3Params p)
 			const uint32_t *mw = p.rowmask + ((size_t)slab * p.mask_words + (bin >> 5)) * p.mask_stride;
 			uint32_t any = 0;
 			for (int f = 0; f < p.n_batches; f++) {
-				const uint32_t b = (mw[PROBE_SAME(p) ? 0 : f] >> (bin & 31)) & 1u;
+				const uint32_t b = (mw[f] >> (bin & 31)) & 1u;
 				any |= b;
 				if (carry)
 					bits[k] |= b << f;
@@ -1996,7 +1878,7 @@ hipError_t launch_k3(const K3Params &p, hipStream_t s)
 		/* sparse form: list the live rows, then one wave per listed row (strided) */
 		const int rows = p.n_bins * (p.n / 64);
 		hipLaunchKernelGGL(k3_scan, dim3((rows + 4095) / 4096), dim3(1024), 0, s, p);
-		int sb = (rows + 4 * K3_ROWS - 1) / (4 * K3_ROWS);	/* 4 waves x K3_ROWS rows in flight per block; the list is usually far shorter */
+		int sb = (rows + 4 * kK3Rows - 1) / (4 * kK3Rows);	/* 4 waves x kK3Rows rows in flight per block; the list is usually far shorter */
 		if (sb > 2048) sb = 2048;
 		if (p.batch <= 1024)
 			hipLaunchKernelGGL((k3_merge<0, true>), dim3(sb), dim3(256), 0, s, p);

@@ -3,7 +3,7 @@
  * one `k1_fft_bin_sc16` (K1_ENTRY names the function, K1_SC16 is 0 / 1, K1_IQ is p.iq as the format reads it; see "IQ formats" there).
  */
 template <bool WRITE_FFT, bool NB256 = false>	/* NB256: 256 bins -- the saturating conversion of the bin byte IS the clamp at n_bins - 1 */
-__global__ __launch_bounds__(256, K1_WAVES_PER_SIMD)
+__global__ __launch_bounds__(256, kK1WavesPerSimd)
 void K1_ENTRY(k1_fft_bin)(const K1Params p)
 {
 	__shared__ v2f   lds[4][kN];			/* 8 KiB exchange slab per wave */
@@ -12,9 +12,6 @@ void K1_ENTRY(k1_fft_bin)(const K1Params p)
 	/* exact-bin thresholds (n_bins <= 256 in this kernel): the rare path that consults them would otherwise wait for its two table
 	 * loads BEHIND the next spectrum's IQ, already requested from HBM -- loads return in order */
 	__shared__ double thr_tab[264];
-#if K1_DBG_EPI & 32
-	__shared__ uint32_t dbg_cnt[256 * 32];		/* probe: the counter image of a 64-column slab */
-#endif
 
 	const int lane   = threadIdx.x & 63;
 	const int wv     = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);	/* tile, spectrum index, row predicate: SGPRs */
@@ -95,18 +92,9 @@ void K1_ENTRY(k1_fft_bin)(const K1Params p)
 	int pend_row = -1;			/* row of p.bins the bytes in pack belong to, or -1 (uniform) */
 	auto flush_pack = [&]() {
 		uint32_t *dst = p.bins + (size_t)pend_row * kN + lane;
-		if (K1_DBG_EPI & 16) {
-			uint32_t any = 0;			/* keep the values alive without the stores */
 #pragma unroll
-			for (int m = 0; m < 16; m++)
-				any |= pack[m];
-			if (any == 0xdeadbeefu)
-				dst[0] = any;
-		} else {
-#pragma unroll
-			for (int m = 0; m < 16; m++)
-				dst[64 * m] = pack[m];
-		}
+		for (int m = 0; m < 16; m++)
+			dst[64 * m] = pack[m];
 #pragma unroll
 		for (int m = 0; m < 16; m++)
 			pack[m] = 0;
@@ -128,7 +116,7 @@ void K1_ENTRY(k1_fft_bin)(const K1Params p)
 				x[2 * k + 1] = mul_bcast_hi(xn[2 * k + 1], w);
 			}
 
-			if (K1_LATE_BINS && u == 0 && pend_row >= 0)
+			if (u == 0 && pend_row >= 0)
 				flush_pack();		/* the previous quad's bin dwords: behind the wait above, ahead of the prefetch below */
 			/* prefetch the next spectrum this wave will process */
 			{
@@ -254,12 +242,9 @@ void K1_ENTRY(k1_fft_bin)(const K1Params p)
 				uint32_t ab;
 				const float r = bin_fast(x[m].x, x[m].y, bk, &l2[m], &ab);
 				amb = amb > ab ? amb : ab;			/* v_max_u32: NaN / inf propagate */
-				if (!(K1_DBG_EPI & 8))
-					pack[m] = NB256 ? __builtin_amdgcn_cvt_pk_u8_f32(r, (uint32_t)u, pack[m]) : pack_bin(r, top, (uint32_t)u, pack[m]);
-				else
-					pack[m] ^= __float_as_uint(r);
+				pack[m] = NB256 ? __builtin_amdgcn_cvt_pk_u8_f32(r, (uint32_t)u, pack[m]) : pack_bin(r, top, (uint32_t)u, pack[m]);
 			}
-			if (!K1_DBG_NO_EXACT && amb > __float_as_uint(bk.amb)) {
+			if (amb > __float_as_uint(bk.amb)) {
 				/* rare (a few % of spectra have one such sample): find the samples, decide them
 				 * against the exact thresholds, patch their bin byte and log-power */
 #pragma unroll
@@ -270,12 +255,8 @@ void K1_ENTRY(k1_fft_bin)(const K1Params p)
 					if (!(a <= bk.amb)) {
 						const int guess = (int)__builtin_amdgcn_fmed3f(r, 0.0f, top);
 						float nl2;
-#if K1_THR_LDS
 						const uint32_t nbn = bin_exact(x[m].x, x[m].y, l2[m], guess,
 						                               (const __attribute__((address_space(3))) double *)thr_tab, bk.nb, &nl2);
-#else
-						const uint32_t nbn = bin_exact(x[m].x, x[m].y, l2[m], guess, bk.thr, bk.nb, &nl2);
-#endif
 						pack[m] = (pack[m] & ~(0xffu << (8 * u))) | (nbn << (8 * u));
 						l2[m] = nl2;
 					}
@@ -286,15 +267,9 @@ void K1_ENTRY(k1_fft_bin)(const K1Params p)
 			for (int m = 0; m < 16; m++) {
 				/* Horner form of display.cl:149-150, in place (v_fma with the accumulator as destination:
 				 * the compiler's v_fmac into the dying l2 register costs a v_mov per column) */
-				if (K1_DBG_EPI & 4) { live[m] = l2[m]; continue; }
 				asm("v_fma_f32 %0, %0, %1, %2" : "+v"(live[m]) : "s"(p.w), "v"(l2[m]));
 				vmax[m] = max_f32(vmax[m], l2[m]);		/* display.cl:139 */
 			}
-#if K1_DBG_EPI & 32
-#pragma unroll
-			for (int m = 0; m < 16; m++)
-				atomicAdd(&dbg_cnt[((pack[m] >> (8 * u)) & 0xffu) * 32 + (lane & 31)], (lane & 32) ? 0x10000u : 1u);
-#endif
 			if (t >= p.wf_first) {				/* uniform: one scalar branch */
 				float *wf_row = p.wf + (size_t)((p.wf_pos0 + t) & p.wf_mask) * kN + lane;
 #pragma unroll
@@ -307,8 +282,6 @@ void K1_ENTRY(k1_fft_bin)(const K1Params p)
 		K1_STAMP(5);			/* 4th epilogue (the first three land in 7) */
 		/* 4 spectra x 1 column per dword, coalesced 256 B per instruction: stored at the top of the next quad (or below) */
 		pend_row = (t0 + g0) >> 2;
-		if (!K1_LATE_BINS)
-			flush_pack();
 	}
 	if (pend_row >= 0)
 		flush_pack();

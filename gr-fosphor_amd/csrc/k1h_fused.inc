@@ -145,7 +145,7 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 	const int eb_w = kkl * 257 + ib;		/* + 16 jj3: pass-3 outputs [offset][jj3][a3] */
 	const int eb_r = kkl * 257 + ib * 16;		/* + j4    : pass-4 inputs of item jj3 = ib */
 
-	if (K1H_PRIO && wv >= NWV / 2)
+	if (wv >= NWV / 2)
 		__builtin_amdgcn_s_setprio(2);
 	uint32_t done = 0;						/* spectra this cluster has finished */
 	uint32_t round = 0;						/* tiles this cluster has taken */
@@ -166,26 +166,20 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 	const int in_rd  = kRpm == 32 ? ia * 32 + ((wv ^ (ia & 7)) << 2) + sa	/* + kRpm * 16 j: row m = ia + 16 j, residue 4 wave + sa (dwords) */
 	                              : ia * 16 + ((wv ^ ((ia >> 2) & 3)) << 2) + sa;
 	const uint32_t inb_lds = (uint32_t)(size_t)(__attribute__((address_space(3))) void *)inb;
-	if (PROBE_K1H(p) & 2)			/* (measurement only: noise-like input that is never loaded) */
-		for (int e = tid; e < 2 * kInLen; e += NT)
-			inb[e] = ((0x211fu + 977u * e) & 0x3fffu) | 0x20000000u | (((0x2c11u + 131u * e) & 0x3fffu) << 16) | ((e & 1u) << 15) | ((e & 2u) << 30);
-	auto fetch_iq = [&](int t, int buf) {		/* row groups g = wave, wave + NWV - 1, ... (256 dwords each) into buffer `buf`; the last wave
-							 * requests nothing: it polls the cluster counters, and a poll returns behind whatever
-							 * its wave has in flight */
-		constexpr int kFetchWaves = K1H_SPOLL ? NWV : NWV - 1;	/* (K1H_SPOLL: nobody polls through the vector path, every wave fetches) */
-		if (!HALF || (PROBE_K1H(p) & 2) || wv >= kFetchWaves)
+	auto fetch_iq = [&](int t, int buf) {		/* row groups g = wave, wave + NWV, ... (256 dwords each) into buffer `buf`: every wave fetches
+							 * (the cluster counters are polled through the scalar path, not behind these requests) */
+		if (!HALF || wv >= NWV)		/* (wv < NWV always; without the test the compiler allocates the kernel's scalar registers differently) */
 			return;
-		if (PROBE_K1H(p) & 32) t = gc;	/* (measurement only: the same rows again and again) */
 		/* global_load_lds_dwordx4 by hand: the compiler parks every LDS read and every __syncthreads() that follows an LDS-DMA it
 		 * knows about behind s_waitcnt vmcnt(0) -- the request would be waited for at the very next barrier instead of an iteration
 		 * later.  Whoever reads the buffer is behind an explicit `s_waitcnt vmcnt(..)` of the requesting wave and a barrier. */
 		const uint32_t *src = reinterpret_cast<const uint32_t *>(p.iq) + (size_t)t * p.hop + kRpm * member;
 #pragma unroll 1
-		for (int g = wv; g < kRpm; g += kFetchWaves) {
+		for (int g = wv; g < kRpm; g += NWV) {
 			const uint32_t *sk = src + 256 * kRowsPerDma * g;				/* 8 / 16 rows of 1 KiB */
 			const uint32_t la = inb_lds + 4u * (unsigned)(buf * kInLen + 256 * g);
 			uint32_t keep;
-			asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 " K1H_IQ_MOD "\n\ts_mov_b32 m0, %0"
+			asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0"
 			             : "=&s"(keep) : "v"(iq_vo), "s"(sk), "s"(la) : "memory");
 		}
 	};
@@ -193,7 +187,6 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 	v2f ra[16];				/* stage A of the spectrum AFTER the one stage B is working on */
 	/* pass 1 (p = 1: no twiddles) of spectrum t and the 16 x 16 transpose inside the wave */
 	auto stage_a1 = [&](int t, int buf) {
-		if (PROBE_K1H(p) & 64) return;		/* (measurement only: stage B alone) */
 		const __amdgpu_buffer_rsrc_t rs_f = make_rsrc(p.iq + (size_t)t * p.hop);
 #pragma unroll
 		for (int jo = 0; jo < 16; jo++) {
@@ -208,8 +201,6 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 				const uint32_t raw = inb[buf * kInLen + in_rd + 16 * kRpm * j];
 				const h2 h = __builtin_bit_cast(h2, raw);
 				xv = v2f{ (float)h.x, (float)h.y };		/* v_cvt_f32_f16: exact */
-			} else if (PROBE_K1H(p) & 2) {
-				xv = v2f{ 0.01f * (float)(((tid * 37 + j * 11) & 63) - 32), 0.01f * (float)(((tid * 29 + j * 7) & 63) - 31) };
 			} else {
 				xv = bld_v2f<kAuxNT>(rs_f, 8u * (unsigned)(qa + 256 * ia), 32768u * j);
 			}
@@ -217,18 +208,17 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 		}
 		/* first pass (p = 1), the window of fft.cl:415-417 on its stage-A butterflies */
 		if constexpr (HALF) {
-			pass16_first<K1H_SC, false>(ra, wab, w16c, w8c, w163c, two);
+			pass16_first(ra, wab, w16c, w8c, w163c, two);
 		} else {
 			v2f wl[8];
 #pragma unroll
 			for (int j = 0; j < 8; j++)
 				wl[j] = v2f{ p.win[qa + 256 * (ia + 16 * j)], p.win[qa + 256 * (ia + 16 * (j + 8))] };
-			pass16_first<K1H_SC, false>(ra, wl, w16c, w8c, w163c, two);
+			pass16_first(ra, wl, w16c, w8c, w163c, two);
 		}
 	};
 	/* ... and the 16 x 16 transpose inside the wave that follows it */
 	auto stage_a1x = [&]() {
-		if (PROBE_K1H(p) & 64) return;
 #pragma unroll
 		for (int jj = 0; jj < 16; jj++)
 			xa[ea_w + 17 * jj] = ra[R16_PERM(jj)];
@@ -238,27 +228,14 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 			ra[K1H_PAIR(jo)] = xa[ea_r + K1H_PAIR(jo)];
 		wave_lds_sync();
 	};
-	/* pass 2, p = 16, k = ia */
-#ifndef K1H_TW_REGS
-#define K1H_TW_REGS 0		/* 1: the pass-2 / pass-3 twiddles of a thread (fixed for its lifetime) in registers instead of 16 LDS reads per spectrum.
-				 * Measured (round 5): the kernel ALONE 2.6 % faster (15 850 against 16 270 cycles per spectrum, K1H_TIMING builds) -- and the
-				 * path 10 % slower (209 against 231 GSamples/s, three interleaved runs each): 233 instead of 209 VGPRs leave the scan / merge
-				 * kernels of the previous frame no registers on a CU this kernel occupies, and the frame's tail no longer runs beside it */
-#endif
-#if K1H_TW_REGS
-	v2f twa_r[8], tw3_r[8];
-#pragma unroll
-	for (int j = 0; j < 8; j++) {
-		twa_r[j] = twa_t[ia * kTwRow + j];
-		tw3_r[j] = tw3_t[kkl * kTwRow + j];
-	}
-#else
+	/* pass 2, p = 16, k = ia.  The pass-2 / pass-3 twiddles are read from LDS every spectrum: held in registers (round 5) the kernel alone
+	 * ran 2.6 % faster and the path 10 % slower (233 instead of 209 VGPRs leave the previous frame's scan / merge kernels no room beside it) */
 	const v2f *twa_r = twa_t + ia * kTwRow;
 	const v2f *tw3_r = tw3_t + kkl * kTwRow;
-#endif
-	auto stage_a2_ab = [&]() { if (PROBE_K1H(p) & 64) return; pass16_ab<K1H_SC, false>(ra, twa_r[0], twa_r[1], two); };
-	auto stage_a2_cd = [&]() { if (PROBE_K1H(p) & 64) return; pass16_cd<K1H_SC, false>(ra, twa_r[2], twa_r[3], twa_r[4], twa_r[5], twa_r[6], twa_r[7], two); };
-	auto stage_a2 = [&]() { stage_a2_ab(); stage_a2_cd(); };
+	auto stage_a2 = [&]() {
+		pass16_ab(ra, twa_r[0], twa_r[1], two);
+		pass16_cd(ra, twa_r[2], twa_r[3], twa_r[4], twa_r[5], twa_r[6], twa_r[7], two);
+	};
 
 #if K1H_TIMING
 	long long hacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -303,7 +280,7 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 		}
 
 		/* epilogue (display.cl:136-150,161-168), 9-bit bin indices: low byte into the quad's dword, 9th bit into the tile's */
-		const bool store_row = (t >= p.wf_first) && !(PROBE_K1H(p) & 4);
+		const bool store_row = (t >= p.wf_first);
 		const uint32_t wf_so = (uint32_t)((p.wf_pos0 + t) & p.wf_mask) * (uint32_t)(N * 4);
 		const int sh8 = 8 * (u & 3);
 		/* four samples at a time: fast path, ONE branch for the four (rare: some sample is not provably exact -- find it again and
@@ -319,7 +296,7 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 				amb = amb > ab ? amb : ab;		/* v_max_u32: NaN / inf order above every finite measure */
 				bng[k] = (uint32_t)(int)__builtin_amdgcn_fmed3f(rr, 0.0f, top);
 			}
-			if (amb > __float_as_uint(bk.amb) && !(PROBE_K1H(p) & 16)) {
+			if (amb > __float_as_uint(bk.amb)) {
 #pragma unroll
 				for (int k = 0; k < 4; k++) {
 					const v2f x = r[R16_PERM(4 * g + k)];
@@ -344,14 +321,14 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 				/* rows and bin indices are streamed out non-temporally: plain stores allocate in the XCD's L2 and push the cluster's
 				 * intermediate out of it */
 				if (store_row)
-					__builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(l2v * F_HALF_LOG10_2), rs_wf, 4u * ucol0, wf_so + 16384u * c, K1H_OUT_AUX);
+					__builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(l2v * F_HALF_LOG10_2), rs_wf, 4u * ucol0, wf_so + 16384u * c, kAuxNT);
 			}
 		}
-		if ((u & 3) == 3 && !(PROBE_K1H(p) & 4)) {
+		if ((u & 3) == 3) {
 			const __amdgpu_buffer_rsrc_t rs_lo = make_rsrc(bins_lo + (size_t)(t >> 2) * N);
 #pragma unroll
 			for (int c = 0; c < 16; c++) {
-				__builtin_amdgcn_raw_buffer_store_b32(plo[c], rs_lo, 4u * ucol0, 16384u * c, K1H_OUT_AUX);
+				__builtin_amdgcn_raw_buffer_store_b32(plo[c], rs_lo, 4u * ucol0, 16384u * c, kAuxNT);
 				plo[c] = 0;
 			}
 		}
@@ -378,30 +355,22 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 		const bool more = (u + 1 < p.tile);
 
 		K1H_STAMP(0);		/* loop overhead, tile claim (first spectrum of a tile) */
-		/* (every member has read the previous spectrum out of the intermediate: the last wave looked before its epilogue)
-		 * every read of the stage-B exchange array is done -- stage A writes the same memory */
-		if (K1H_SPOLL) {
-			/* every member has read the previous spectrum out of the intermediate? */
-			if (!(PROBE_K1H(p) & 1)) {
-				uint32_t spins = 0;
-				while ((int)(sload_fresh(c_b) - (uint32_t)kMem * done) < 0) {
-					if (++spins > kSpinLimit) { if (lane == 0) *p.sync_err = 0x80000002u; break; }
-					__builtin_amdgcn_s_sleep(1);
-				}
+		/* every member has read the previous spectrum out of the intermediate?  Every wave asks for itself, through the scalar path */
+		{
+			uint32_t spins = 0;
+			while ((int)(sload_fresh(c_b) - (uint32_t)kMem * done) < 0) {
+				if (++spins > kSpinLimit) { if (lane == 0) *p.sync_err = 0x80000002u; break; }
+				__builtin_amdgcn_s_sleep(1);
 			}
-		} else {
-			wg_barrier_lds();
 		}
-		K1H_STAMP(1);		/* top barrier: waiting for the work-group's slowest wave (K1H_SPOLL: this wave's own look at the counter) */
-		if (!(PROBE_K1H(p) & (8 | 512))) {
-			/* w[256 q + kk], kk = ia + 16 jj2, at [kk >> 5][q][(kk & 31) ^ 16 (q & 1)]: 16 lanes x 8 B = 128-byte runs; odd residues
-			 * keep their two halves swapped so that one store instruction (one jj for every lane) is spread over both halves of the
-			 * 256-byte rows -- both values of the address bit that picks an L2 channel -- instead of one */
+		K1H_STAMP(1);		/* this wave's own look at the counter */
+		/* w[256 q + kk], kk = ia + 16 jj2, at [kk >> 5][q][(kk & 31) ^ 16 (q & 1)]: 16 lanes x 8 B = 128-byte runs; odd residues
+		 * keep their two halves swapped so that one store instruction (one jj for every lane) is spread over both halves of the
+		 * 256-byte rows -- both values of the address bit that picks an L2 channel -- instead of one */
 #pragma unroll
-			for (int jj = 0; jj < 16; jj++) {
-				if (kRpm == 32) bst_v2f<0>(ra[R16_PERM(jj)], rs_w, (jj & 1) ? wst1 : wst0, 65536u * (jj >> 1));
-				else            bst_v2f<0>(ra[R16_PERM(jj)], rs_w, wst0, 32768u * jj);	/* (one instruction: four residues = 512 B in a row) */
-			}
+		for (int jj = 0; jj < 16; jj++) {
+			if (kRpm == 32) bst_v2f<0>(ra[R16_PERM(jj)], rs_w, (jj & 1) ? wst1 : wst0, 65536u * (jj >> 1));
+			else            bst_v2f<0>(ra[R16_PERM(jj)], rs_w, wst0, 32768u * jj);	/* (one instruction: four residues = 512 B in a row) */
 		}
 		if (more)
 			stage_a1(t + 1, (u + 1) & 1);			/* (while the stores travel) */
@@ -413,17 +382,11 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 		if (tid == 0)
 			__hip_atomic_fetch_add(c_a, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		K1H_STAMP(4);		/* barrier + arrival */
-		if (more) {
-			if (K1H_SPLIT != 3)
-				stage_a1x();				/* (while the arrivals travel) */
-			if (K1H_SPLIT == 0)
-				stage_a2_ab();				/* second pass, stages A and B (C and D: beside the loads below) */
-			else if (K1H_SPLIT == 2)
-				stage_a2();
-		}
+		if (more)
+			stage_a1x();				/* (while the arrivals travel) */
 
-		K1H_STAMP(5);		/* transpose (+ what of the second pass runs here) */
-		if (tid == 0 && !(PROBE_K1H(p) & 1)) {
+		K1H_STAMP(5);		/* transpose */
+		if (tid == 0) {
 			uint32_t spins = 0;
 			while ((int)(__hip_atomic_load(c_a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (uint32_t)kMem * (done + 1)) < 0) {
 				if (++spins > kSpinLimit) { *p.sync_err = 0x80000003u; break; }
@@ -436,29 +399,14 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 
 		/* ================= stage B: offsets kk = 32 member .. + 31 ================= */
 		v2f r[16];
-		if (!(PROBE_K1H(p) & (8 | 256))) {
-			/* residues q = ib + 16 j3 (q & 1 = ib & 1); sc1: the loads miss the CU's L1 by construction and are served by the L2 */
+		/* residues q = ib + 16 j3 (q & 1 = ib & 1); sc1: the loads miss the CU's L1 by construction and are served by the L2 */
 #pragma unroll
-			for (int jo = 0; jo < 16; jo++)
-				r[K1H_PAIR(jo)] = bld_v2f<kAuxSC1>(rs_w, wld, (uint32_t)(2048 * kRpm) * member + (uint32_t)(128 * kRpm) * K1H_PAIR(jo));
-		} else {
-#pragma unroll
-			for (int j = 0; j < 16; j++)
-				r[j] = ra[j];
-		}
-		if (more) {						/* (while the loads travel) */
-			if (K1H_SPLIT == 0)
-				stage_a2_cd();
-			else if (K1H_SPLIT == 1)
-				stage_a2();
-			else if (K1H_SPLIT == 3) {
-				stage_a1x();
-				stage_a2();
-			}
-		}
+		for (int jo = 0; jo < 16; jo++)
+			r[K1H_PAIR(jo)] = bld_v2f<kAuxSC1>(rs_w, wld, (uint32_t)(2048 * kRpm) * member + (uint32_t)(128 * kRpm) * K1H_PAIR(jo));
+		if (more)						/* (while the loads travel) */
+			stage_a2();
 		K1H_STAMP(7);		/* loads of the intermediate issued + second pass of the next spectrum */
-		if (!(PROBE_K1H(p) & 128))	/* (128, measurement only: stage A alone -- no stage-B arithmetic, exchange or epilogue; the barriers stay) */
-		pass16_ab<K1H_SC, false>(r, tw3_r[0], tw3_r[1], two);				/* pass 3, p = 256, k = kk */
+		pass16_ab(r, tw3_r[0], tw3_r[1], two);						/* pass 3, p = 256, k = kk */
 #if K1H_TIMING
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -468,51 +416,32 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 		 * loads return in order, and these come from HBM */
 		if (u + 3 < p.tile)
 			fetch_iq(t + 3, (u + 1) & 1);
-		if (!(PROBE_K1H(p) & 128)) {
-		pass16_cd<K1H_SC, false>(r, tw3_r[2], tw3_r[3], tw3_r[4], tw3_r[5], tw3_r[6], tw3_r[7], two);
+		pass16_cd(r, tw3_r[2], tw3_r[3], tw3_r[4], tw3_r[5], tw3_r[6], tw3_r[7], two);
 #pragma unroll
 		for (int jj = 0; jj < 16; jj++)
 			xb[eb_w + 16 * jj] = r[R16_PERM(jj)];
-		} else {
-			asm volatile("s_waitcnt vmcnt(0)" :: "v"(r[0]), "v"(r[15]) : "memory");
-		}
 		K1H_STAMP(9);		/* IQ request + third pass, stages C and D + exchange stores */
 		wg_barrier_lds();
 		if (tid == 0)							/* everybody's loads of the intermediate have landed */
 			__hip_atomic_fetch_add(c_b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		done++;
 		K1H_STAMP(10);		/* exchange barrier */
-		if (!(PROBE_K1H(p) & 128)) {
 #pragma unroll
 		for (int jo = 0; jo < 16; jo++)
 			r[K1H_PAIR(jo)] = xb[eb_r + K1H_PAIR(jo)];
-		pass16_ab<K1H_SC, false>(r, tw4[0], tw4[1], two);					/* pass 4, p = 4096, k = kk + 256 ib */
-		pass16_cd<K1H_SC, false>(r, tw4[2], tw4[3], tw4[4], tw4[5], tw4[6], tw4[7], two);
-		}
+		pass16_ab(r, tw4[0], tw4[1], two);							/* pass 4, p = 4096, k = kk + 256 ib */
+		pass16_cd(r, tw4[2], tw4[3], tw4[4], tw4[5], tw4[6], tw4[7], two);
 
 		K1H_STAMP(11);		/* exchange loads + fourth pass */
-		/* every member has read this spectrum out of the intermediate?  (they said so about a pass ago.)  Asked here because this
-		 * wave has nothing in flight now: behind the epilogue's stores the answer would wait for them.  (Round 5, K1H_TIMING build: the
-		 * ~2000 cycles this wave spends here per spectrum are the spread between the cluster's members, not a round trip -- requesting
-		 * the counter one pass EARLIER and looking at the answer here returned "not yet" and cost 50 us per frame on top.) */
-		if (!K1H_SPOLL && tid == NT - 64 && !(PROBE_K1H(p) & 1)) {
-			uint32_t spins = 0;
-			while ((int)(__hip_atomic_load(c_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (uint32_t)kMem * done) < 0) {
-				if (++spins > kSpinLimit) { *p.sync_err = 0x80000002u; break; }
-				__builtin_amdgcn_s_sleep(1);
-			}
-		}
-
-		K1H_STAMP(12);		/* "everyone has read the intermediate" poll (last wave only) */
-		if (!(PROBE_K1H(p) & 128))
+		K1H_STAMP(12);		/* (empty since round 6: the "everyone has read the intermediate" poll moved to the top of the loop) */
 		epilogue(r, t, u);
 		K1H_STAMP(13);		/* epilogue */
 	}
-	if (!(PROBE_K1H(p) & 4)) {
+	{
 		const __amdgpu_buffer_rsrc_t rs_hi = make_rsrc(bins_hi + (size_t)tile * N);
 #pragma unroll
 		for (int c = 0; c < 16; c++)
-			__builtin_amdgcn_raw_buffer_store_b32(phi[c], rs_hi, 4u * ucol0, 16384u * c, K1H_OUT_AUX);
+			__builtin_amdgcn_raw_buffer_store_b32(phi[c], rs_hi, 4u * ucol0, 16384u * c, kAuxNT);
 	}
 #pragma unroll
 	for (int c = 0; c < 16; c++)

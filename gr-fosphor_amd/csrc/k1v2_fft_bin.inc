@@ -3,7 +3,7 @@
  * one `k1v2_fft_bin_sc16` (K1_ENTRY names the function, K1_SC16 is 0 / 1, K1_IQ is p.iq as the format reads it; see "IQ formats" there).
  */
 template <bool WRITE_FFT>
-__global__ __launch_bounds__(128, K1V2_WAVES_PER_SIMD)
+__global__ __launch_bounds__(128, kK1v2WavesPerSimd)
 void K1_ENTRY(k1v2_fft_bin)(const K1Params p)
 {
 	__shared__ v2f   buf[kN];			/* 8 KiB exchange slab of the work-group's spectrum */

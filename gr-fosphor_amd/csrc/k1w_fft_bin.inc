@@ -86,14 +86,10 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 	 * (display.cl:136-150,161-168).  Per column, nothing carried from column to column: it is cut into three pieces that
 	 * run between the LDS stores of the NEXT spectrum's exchanges and the barrier behind them, i.e. while this wave
 	 * would otherwise wait for the slowest one. */
-#ifndef K1W_P1
-#define K1W_P1 6		/* the three epilogue pieces: columns [0, P1), [P1, P2), [P2, 16) of a thread (A/B builds) */
-#define K1W_P2 11
-#endif
+	constexpr int kP1 = 6, kP2 = 11;	/* the three epilogue pieces: columns [0, kP1), [kP1, kP2), [kP2, 16) of a thread (measured) */
 #define K1W_COL(m) (256 * ((m) & 7) + 4096 * ((m) >> 3))
 #define K1W_EPI(M0, M1, tp) do { \
-		if (K1W_P(4)) break; \
-		if (K1W_PRIO) __builtin_amdgcn_s_setprio(0); \
+		__builtin_amdgcn_s_setprio(0);		/* the passes run at a higher issue priority than the epilogue pieces */ \
 		const bool _row = ((tp) >= p.wf_first); \
 		float *_wfr = p.wf + (size_t)((p.wf_pos0 + (tp)) & p.wf_mask) * N; \
 		/* index stores (512 bins: 9 bits), 1.125 B per sample instead of the 2 B of a 16-bit index (round 6): \
@@ -119,7 +115,7 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 		} \
 		/* ONE branch per piece (a compare + exec save + branch per sample cost 9 % of this kernel): rare -- find the samples again \
 		 * and decide them against the exact thresholds */ \
-		if (!K1_DBG_NO_EXACT && _amb > __float_as_uint(bk.amb)) { \
+		if (_amb > __float_as_uint(bk.amb)) { \
 			_Pragma("unroll") \
 			for (int m = (M0); m < (M1); m++) { \
 				const float v = __builtin_fmaf(bk.A, _l2[m - (M0)], bk.C); \
@@ -139,7 +135,7 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 			for (int m = (M0); m < (M1); m++) \
 				held[m >> 2] = __builtin_amdgcn_perm(_bn[m - (M0)], held[m >> 2], \
 				                                     (m & 3) == 0 ? 0x03020104u : (m & 3) == 1 ? 0x03020400u : (m & 3) == 2 ? 0x03040100u : 0x04020100u); \
-		} else if (!K1W_P(8)) {		/* odd spectrum: the short of both */ \
+		} else {		/* odd spectrum: the short of both */ \
 			_Pragma("unroll") \
 			for (int m = (M0); m < (M1); m++) { \
 				const char *_sb = _blo + 8192 * (m >> 3); \
@@ -192,10 +188,10 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 			for (int m = (M0); m < (M1); m++) \
 				_wf[K1W_COL(m)] = _l2[m - (M0)] * F_HALF_LOG10_2; \
 		} \
-		if (K1W_PRIO) __builtin_amdgcn_s_setprio(2); \
+		__builtin_amdgcn_s_setprio(2); \
 	} while (0)
 
-	if (K1W_PRIO) __builtin_amdgcn_s_setprio(2);
+	__builtin_amdgcn_s_setprio(2);
 #if K1W_TIMING
 	uint32_t wacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	uint32_t wprev = (uint32_t)__builtin_readcyclecounter();
@@ -242,7 +238,7 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 		 * format that packs the stores must change both; tools/check_k1w_loads.py counts the stores of the compiled loop against it) */
 		static_assert(kK1wIdxStores == 16, "the counted wait below and K1W_EPI's index stores (one dword per column and pair of spectra) go together");
 		asm volatile("s_cmp_eq_u32 %16, 0\n\ts_cbranch_scc1 1f\n\ts_waitcnt vmcnt(%17)\n\ts_branch 2f\n1:\ts_waitcnt vmcnt(0)\n2:"
-		             : K1W_Q16 : "s"(__builtin_amdgcn_readfirstlane((!K1W_P(8) && (g & 1) && g >= 3) ? 1 : 0)), "n"(kK1wIdxStores) : "scc");
+		             : K1W_Q16 : "s"(__builtin_amdgcn_readfirstlane(((g & 1) && g >= 3) ? 1 : 0)), "n"(kK1wIdxStores) : "scc");
 #undef K1W_Q16
 #pragma unroll
 		for (int j = 0; j < 16; j++)
@@ -276,36 +272,26 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 			 * the requests, profiles/r05_c3.md) */
 #pragma unroll
 			for (int j = 16 - SHIFT; j < 16; j++)
-				if (!K1W_P(16))
 #if K1_SC16
-					asm volatile("buffer_load_dword %0, %1, %2, %3 offen nt" : "=v"(q[j]) : "v"(iq_vo), "s"(src), "s"(2048u * (uint32_t)j));
+				asm volatile("buffer_load_dword %0, %1, %2, %3 offen nt" : "=v"(q[j]) : "v"(iq_vo), "s"(src), "s"(2048u * (uint32_t)j));
 #else
-					asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen nt" : "=v"(q[j]) : "v"(iq_vo), "s"(src), "s"(4096u * (uint32_t)j));
+				asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen nt" : "=v"(q[j]) : "v"(iq_vo), "s"(src), "s"(4096u * (uint32_t)j));
 #endif
 		}
 
 #pragma unroll
 		for (int m = 0; m < 16; m++)
-			if (!K1W_P(1)) slab0[st1 ^ m] = x[R16_PERM(m)];
-		if (have_prev && !late) K1W_EPI(0, K1W_P1, t - 1);
+			slab0[st1 ^ m] = x[R16_PERM(m)];
+		if (have_prev && !late) K1W_EPI(0, kP1, t - 1);
 		K1W_STAMP(2);			/* IQ requests, stores (until done), early piece */
 		wg_barrier_lds();
 		K1W_STAMP(3);			/* barrier */
-#if K1W_READ_FIRST
-		/* the reads are requested BEFORE the late piece: a late wave's piece then runs while its operands travel (and while the early
-		 * wave of its SIMD, whose reads were requested at the same moment, has nothing to compute yet) */
-#pragma unroll
-		for (int j = 0; j < 16; j++)
-			if (!K1W_P(2)) x[j] = slab0[rd + 512 * j];
-		if (have_prev && late) K1W_EPI(0, K1W_P1, t - 1);
-		K1W_STAMP(4);			/* late piece */
-#else
-		if (have_prev && late) K1W_EPI(0, K1W_P1, t - 1);
+		/* a late wave runs its piece BEFORE it requests its operands (requesting them first measured 1.2 % slower) */
+		if (have_prev && late) K1W_EPI(0, kP1, t - 1);
 		K1W_STAMP(4);			/* late piece */
 #pragma unroll
 		for (int j = 0; j < 16; j++)
-			if (!K1W_P(2)) x[j] = slab0[rd + 512 * j];
-#endif
+			x[j] = slab0[rd + 512 * j];
 		K1W_STAMP(5);			/* reads (until all have arrived) */
 
 		/* ---- pass 2: p = 16, k = th & 15, outputs e = 256 (th >> 4) + (th & 15) + 16 m -> slab1 ---- */
@@ -314,24 +300,16 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 		K1W_STAMP(6);			/* pass 2 */
 #pragma unroll
 		for (int m = 0; m < 16; m++)
-			if (!K1W_P(1)) slab1[st2 ^ ((m ^ (16 * (m & 1))) | (32 * (m >> 1)))] = x[R16_PERM(m)];
-		if (have_prev && !late) K1W_EPI(K1W_P1, K1W_P2, t - 1);
+			slab1[st2 ^ ((m ^ (16 * (m & 1))) | (32 * (m >> 1)))] = x[R16_PERM(m)];
+		if (have_prev && !late) K1W_EPI(kP1, kP2, t - 1);
 		K1W_STAMP(7);
 		wg_barrier_lds();
 		K1W_STAMP(8);
-#if K1W_READ_FIRST
-#pragma unroll
-		for (int j = 0; j < 16; j++)
-			if (!K1W_P(2)) x[j] = slab1[rd + 512 * j];
-		if (have_prev && late) K1W_EPI(K1W_P1, K1W_P2, t - 1);
-		K1W_STAMP(9);
-#else
-		if (have_prev && late) K1W_EPI(K1W_P1, K1W_P2, t - 1);
+		if (have_prev && late) K1W_EPI(kP1, kP2, t - 1);
 		K1W_STAMP(9);
 #pragma unroll
 		for (int j = 0; j < 16; j++)
-			if (!K1W_P(2)) x[j] = slab1[rd + 512 * j];
-#endif
+			x[j] = slab1[rd + 512 * j];
 		K1W_STAMP(10);
 
 		/* ---- pass 3: p = 256, k = kk: X3[4096 hh + kk + 256 m] = x[R16_PERM(m)]; the half this thread's butterflies do not need goes to
@@ -342,13 +320,13 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 		if (hu == 0) {			/* uniform per wave (waves 0-3 / 4-7): a scalar branch */
 #pragma unroll
 			for (int c = 0; c < 8; c++)
-				if (!K1W_P(1)) slab0[512 * c + th] = x[R16_PERM(8 + c)];
+				slab0[512 * c + th] = x[R16_PERM(8 + c)];
 		} else {
 #pragma unroll
 			for (int c = 0; c < 8; c++)
-				if (!K1W_P(1)) slab0[512 * c + th] = x[R16_PERM(c)];
+				slab0[512 * c + th] = x[R16_PERM(c)];
 		}
-		if (have_prev && !late) K1W_EPI(K1W_P2, 16, t - 1);
+		if (have_prev && !late) K1W_EPI(kP2, 16, t - 1);
 		K1W_STAMP(12);
 		wg_barrier_lds();
 		K1W_STAMP(13);
@@ -356,19 +334,11 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 		 * xo[c] = X[jb], xo[c + 8] = X[jb + 4096] ---- */
 		{
 			v2f o[8];
-#if K1W_READ_FIRST
-#pragma unroll
-			for (int c = 0; c < 8; c++)
-				o[c] = K1W_P(2) ? x[c] : slab0[512 * c + (th ^ 256)];
-			if (have_prev && late) K1W_EPI(K1W_P2, 16, t - 1);
-			K1W_STAMP(14);
-#else
-			if (have_prev && late) K1W_EPI(K1W_P2, 16, t - 1);
+			if (have_prev && late) K1W_EPI(kP2, 16, t - 1);
 			K1W_STAMP(14);
 #pragma unroll
 			for (int c = 0; c < 8; c++)
-				o[c] = K1W_P(2) ? x[c] : slab0[512 * c + (th ^ 256)];
-#endif
+				o[c] = slab0[512 * c + (th ^ 256)];
 			K1W_STAMP(15);
 			/* (step by step, like bf8; the two forms differ in where a and b come from) */
 #define K1W_R2(A, B) do { \

@@ -46,12 +46,17 @@ def test_library_exports_every_declared_symbol(amd):
 
 
 def test_product_library_has_no_wrong_result_switches(amd):
-    """The measurement switches that produce wrong spectra by construction (FOSPHOR_AMD_DBG_*: skip a kernel, alias chunks, drop
-    a wait, CU masks) exist only in probe builds (-DFOSPHOR_AMD_PROBES, tools/r04_ceiling_build.sh).  The shipped library must not
-    contain the name of any of them: a stray environment variable cannot change its results."""
+    """Measurement switches that produce wrong spectra by construction (skip a kernel, alias chunks, drop a wait, CU masks) have
+    no place in the product.  The shipped library must not contain the name of any such environment switch, so a stray
+    environment variable cannot change its results; and the sources have no probe build that could bring them back."""
     blob = open(amd.LIB_PATH, "rb").read()
     assert b"FOSPHOR_AMD_DBG" not in blob
     assert b"FOSPHOR_AMD_TILE" in blob			# (the check can see environment names: a tuning knob that IS read, once, at init)
+    csrc = os.path.join(ROOT, "gr-fosphor_amd", "csrc")
+    for name in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, name), "rb").read()
+        for word in (b"FOSPHOR_AMD_PROBES", b"FOSPHOR_AMD_DBG"):
+            assert word not in text, "%s names %s" % (name, word.decode())
 
 
 def test_piece_planner_host_logic(amd):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build A/B variants of the product library into build/ab/ (cross-compiled here; build/ travels to the GPU box):
-#   tools/ab_build.sh "name1:-DK1H_SPLIT=1" "name2:-DK1H_LOAD_ORDER=0 -DK1H_SPLIT=2"      then   gpurun -- 'bash tools/ab_libs.sh C5 3 name1 name2 cur'
+#   tools/ab_build.sh "k1htime:-DK1H_TIMING=1"      then, on the GPU:   FOSPHOR_AMD_LIB=$PWD/build/ab/lib_k1htime.so FOSPHOR_AMD_K1_TIMING=1 python3 tools/k1h_phase_timing.py
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$ROOT/build/ab"

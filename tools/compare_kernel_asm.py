@@ -8,7 +8,14 @@
 Every function of OLD is looked up in NEW by its mangled name; its instructions are compared after the basic-block labels are
 renumbered in order of appearance and comments / assembler directives are dropped.  The register counts, LDS and scratch sizes the
 compiler reports in the comment block behind each function are compared as well.  One line per function; exit status 1 if any function
-of OLD is missing from NEW or differs.  Functions that exist only in NEW (new entry points) are listed, not compared."""
+of OLD is missing from NEW or differs.  Functions that exist only in NEW (new entry points) are listed, not compared.
+
+    python3 tools/compare_kernel_asm.py --vector old.s new.s
+
+compares less, for a change that only moves kernel arguments: per function the resources, and the multiset of vector instructions
+(v_, ds_, global_, buffer_, flat_ lines) with scalar register numbers masked.  Argument offsets, scalar registers and the order of
+the instructions may differ."""
+import collections
 import re
 import sys
 
@@ -59,7 +66,12 @@ def resources(tail):
     return res
 
 
-def main(old_path, new_path):
+def vector_multiset(code):
+    return collections.Counter(re.sub(r"\bs(\d+|\[\d+:\d+\])", "s#", l) for l in code
+                               if re.match(r"(v_|ds_|global_|buffer_|flat_)", l))
+
+
+def main(old_path, new_path, vector=False):
     old, new = functions(old_path), functions(new_path)
     bad = 0
     for name in old:
@@ -69,8 +81,11 @@ def main(old_path, new_path):
             continue
         a, b = normalise(old[name][0]), normalise(new[name][0])
         ra, rb = resources(old[name][1]), resources(new[name][1])
+        if vector:
+            a, b = vector_multiset(a), vector_multiset(b)
         if a == b and ra == rb:
-            print("same     %s (%d instructions)" % (name, sum(1 for l in a if not l.endswith(":"))))
+            print("same     %s (%d %sinstructions)" % (name, sum(1 for l in a if not l.endswith(":")) if not vector else sum(a.values()),
+                                                     "vector " if vector else ""))
         else:
             bad += 1
             print("DIFFERS  %s (%d vs %d lines; resources %s vs %s)" % (name, len(a), len(b), ra, rb))
@@ -82,6 +97,7 @@ def main(old_path, new_path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    args = [a for a in sys.argv[1:] if a != "--vector"]
+    if len(args) != 2:
         raise SystemExit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(args[0], args[1], vector="--vector" in sys.argv))

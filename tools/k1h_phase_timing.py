@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Per-phase cycle breakdown of the 65536-point kernel's loop from a K1H_TIMING=1 build (probe build, timing only; with
--DFOSPHOR_AMD_PROBES as well, FOSPHOR_AMD_DBG_K1H=15 times the loop without memory accesses and cluster waits).
+"""Per-phase cycle breakdown of the 65536-point kernel's loop from a K1H_TIMING=1 build (timing only).
 
     tools/ab_build.sh "k1htime:-DK1H_TIMING=1"
     gpurun -- 'FOSPHOR_AMD_LIB=$PWD/build/ab/lib_k1htime.so FOSPHOR_AMD_K1_TIMING=1 FOSPHOR_AMD_OVERLAP=0 python3 tools/k1h_phase_timing.py'

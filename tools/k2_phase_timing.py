@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Per-phase breakdown of the count kernel (first wave of every work-group) from a probe build.
+"""Per-phase breakdown of the count kernel (first wave of every work-group) from a K2_TIMING build.
 
-    tools/ab_build.sh "k2time:-DFOSPHOR_AMD_PROBES -DK2_TIMING"
+    tools/ab_build.sh "k2time:-DK2_TIMING"
     gpurun -- 'FOSPHOR_AMD_LIB=$PWD/build/ab/lib_k2time.so python3 tools/k2_phase_timing.py C3'      (C2 | C3 | C5)
 """
 import ctypes as C

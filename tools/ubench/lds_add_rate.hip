@@ -8,7 +8,7 @@
 //   layout 4  [bin][64] with 16-bit halves of two SPECTRA packed: one ds_add_u32 counts bin b for spectrum t (low) ... not possible (different bins) -- skipped
 //   layout 5  plain ds_write_b32 in the place of the atomic, layout 1 addresses (the LDS pipe's store rate)
 // (addresses are fixed per lane and computed outside the loop: an earlier form hashed them inside it and timed the hash)
-// hipcc --offload-arch=gfx950 -O3 lds_atomic_rate.hip -o lds_atomic_rate && ./lds_atomic_rate
+// hipcc --offload-arch=gfx950 -O3 lds_add_rate.hip -o lds_add_rate && ./lds_add_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
