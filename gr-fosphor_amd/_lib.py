@@ -116,6 +116,7 @@ SIGNATURES = {
     "fosphor_amd_plan_piece_batches": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong]),
     "fosphor_amd_share_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "fosphor_amd_launch_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "fosphor_amd_merge_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 11)]),
     "fosphor_amd_version": (C.c_char_p, []),
     # include/fosphor_amd_axis.h
     "fosphor_amd_freq_axis_build": (None, [C.c_void_p, C.c_double, C.c_double, C.c_int]),

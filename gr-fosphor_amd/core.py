@@ -275,6 +275,18 @@ class Fosphor:
             raise RuntimeError("fosphor_amd_launch_stats -> %d" % rv)
         return a.value, b.value, c.value
 
+    MERGE_FORMS = ("dense16", "dense16_long4", "dense16_long", "table32", "eval32", "sparse16", "sparse16_long", "table_in_memory",
+                   "sparse_max_batches", "sparse_long_max_batches", "sparse_listed_rows")
+
+    def merge_stats(self):
+        """fosphor_amd_merge_stats as a dict: merge launches since the instance was made by form (MERGE_FORMS[:7]), how many of the
+        long-batch ones read the rise/decay table from memory, the most batches one sparse launch of either kind merged, the rows the last sparse launch listed (-1: none yet; waits for it)"""
+        st = (C.c_longlong * 11)()
+        rv = self.L.fosphor_amd_merge_stats(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("fosphor_amd_merge_stats -> %d" % rv)
+        return dict(zip(self.MERGE_FORMS, list(st)))
+
     def kernel_busy(self):
         """ms during which >= 1 kernel of each kind ran (call before kernel_times)"""
         ms = (C.c_float * 3)()

@@ -127,6 +127,10 @@ struct fosphor
 	int       n_cus;			/* hipDeviceProp_t::multiProcessorCount */
 	int       share_cus;			/* N = 8192: work-groups of an FFT launch that leaves CUs to the count / merge kernels (0: never) */
 	long long k1w_shared, k1w_full;		/* N = 8192: FFT launches made in the shared / the full-chip form (fosphor_amd_share_stats) */
+	long long k3_forms[K3_FORMS], k3_rise_mem;	/* merge launches by form; long-batch launches that read the (d, e) table from memory (fosphor_amd_merge_stats) */
+	const uint32_t *k3_listed;		/* device word holding the row count of the last sparse launch's list, and the stream it ran on */
+	hipStream_t k3_listed_stream;
+	int       k3_sparse_max[2];		/* most batches in one sparse launch: batches up to 1024 spectra / longer ones */
 	long long acc_pieces, n_k2c, n_k2b;	/* FFT pieces launched by accumulate(); chunk sums (k2c) / chunk reduces (k2b) launched (fosphor_amd_launch_stats) */
 	uint32_t *d_hc;
 	uint32_t *d_hc_export;			/* [n_bins][N] last batch, written by K3 on the 16-bit path */
@@ -1068,6 +1072,8 @@ static int run_merge(struct fosphor *self, int n_batches, int batch, int slot0, 
 			k3.hot = self->d_hot;
 			k3.rowlist = self->d_rowlist;
 			k3.rowlist_cnt = self->rowlist_flip ? 1 + self->n_bins * (self->n / 64) : 0;
+			self->k3_listed = k3.rowlist + k3.rowlist_cnt;
+			self->k3_listed_stream = st;
 			self->rowlist_flip ^= 1;
 			k3.hot_all = !self->hot_valid;
 			self->hot_valid = 1;
@@ -1086,6 +1092,14 @@ static int run_merge(struct fosphor *self, int n_batches, int batch, int slot0, 
 	k3.cell_begin = cell_begin; k3.cell_end = cell_end;
 	prof_begin(self, 2, st);
 	HIP_TRY(launch_k3(k3, st), "launch merge");
+	{
+		const K3Form form = k3_form(k3);
+		self->k3_forms[form]++;
+		if (form == K3_SPARSE16_LONG || ((form == K3_DENSE16_LONG4 || form == K3_DENSE16_LONG) && batch >= kK3RiseLdsLong))
+			self->k3_rise_mem++;
+		if ((form == K3_SPARSE16 || form == K3_SPARSE16_LONG) && n_batches > self->k3_sparse_max[form == K3_SPARSE16_LONG])
+			self->k3_sparse_max[form == K3_SPARSE16_LONG] = n_batches;
+	}
 	prof_end(self, st);
 	return 0;
 error:
@@ -2083,6 +2097,33 @@ extern "C" int fosphor_amd_launch_stats(struct fosphor *self, long long *pieces,
 	if (pieces) *pieces = self->acc_pieces;
 	if (k2c) *k2c = self->n_k2c;
 	if (k2b) *k2b = self->n_k2b;
+	return 0;
+}
+
+/* Merge launches since the instance was made, by the form launch_k3 chose (k3_form): stats[0..6] in the order of K3Form, stats[7] =
+ * how many of the long-batch launches (forms 1, 2, 6) read the (d, e) table from memory, stats[8] / stats[9] = the most batches one
+ * launch of form 5 / form 6 merged, stats[10] = the rows the last sparse launch listed (read back from the device behind that launch;
+ * -1: none yet).  The others are host counters that only grow; nothing on the submit path reads them. */
+extern "C" int fosphor_amd_merge_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_MERGE_STATS])
+{
+	if (!self)
+		return -EINVAL;
+	if (!stats)
+		return 0;
+	for (int i = 0; i < K3_FORMS; i++)
+		stats[i] = self->k3_forms[i];
+	stats[FOSPHOR_AMD_MERGE_TABLE_IN_MEMORY] = self->k3_rise_mem;
+	stats[FOSPHOR_AMD_MERGE_SPARSE_MAX_BATCHES] = self->k3_sparse_max[0];
+	stats[FOSPHOR_AMD_MERGE_SPARSE_LONG_MAX_BATCHES] = self->k3_sparse_max[1];
+	stats[FOSPHOR_AMD_MERGE_SPARSE_LISTED_ROWS] = -1;
+	if (self->k3_listed) {
+		/* (the word stays as the launch left it until the scan after the next one zeroes it: k3_scan) */
+		uint32_t listed = 0;
+		if (hipMemcpyAsync(&listed, self->k3_listed, sizeof(listed), hipMemcpyDeviceToHost, self->k3_listed_stream) != hipSuccess ||
+		    hipStreamSynchronize(self->k3_listed_stream) != hipSuccess)
+			return -EIO;
+		stats[FOSPHOR_AMD_MERGE_SPARSE_LISTED_ROWS] = listed;
+	}
 	return 0;
 }
 

@@ -140,6 +140,11 @@ hipError_t launch_k1_traffic_twin(const K1Params &p, hipStream_t s);
 hipError_t launch_k2(const K2Params &p, int n_chunks, hipStream_t s);
 hipError_t launch_k2b(const K2bParams &p, hipStream_t s);
 hipError_t launch_k2c(const K2bParams &p, hipStream_t s);
+/* The forms of the merge, in the order fosphor_amd_merge_stats reports them (include/fosphor_amd.h) */
+enum K3Form { K3_DENSE16, K3_DENSE16_LONG4, K3_DENSE16_LONG, K3_TABLE32, K3_EVAL32, K3_SPARSE16, K3_SPARSE16_LONG, K3_FORMS };
+constexpr int kK3LongFew = 4;		/* dense long-batch form: launches of up to this many batches keep four cells in flight per thread */
+constexpr int kK3RiseLdsLong = 4097;	/* dense long-batch form: (d, e) table entries that fit in LDS (batches up to 4096 spectra) */
+K3Form k3_form(const K3Params &p);		/* the form launch_k3 launches for p */
 hipError_t launch_k3(const K3Params &p, hipStream_t s);
 hipError_t launch_fill(float *dst, float value, size_t n, hipStream_t s);
 hipError_t launch_export_hc16(const uint16_t *hc16, const uint32_t *rowmask, int mask_words, int mask_stride, uint32_t *out, int n_bins, int n, hipStream_t s);

@@ -1442,7 +1442,7 @@ void k3_merge(const K3Params p)
 	 * over the cells (the grid is capped, so a 128 MiB state does not reload it 131 072 times) */
 	/* (long batches, MODE 3: in LDS as well up to 4096 spectra -- a look-up in memory is one more dependent round trip per batch
 	 * and cell; longer batches read it from memory) */
-	constexpr int kRiseLds = (MODE == 0) ? 1025 : (MODE == 3 && !SPARSE) ? 4097 : 1;
+	constexpr int kRiseLds = (MODE == 0) ? 1025 : (MODE == 3 && !SPARSE) ? kK3RiseLdsLong : 1;
 	__shared__ float2 rise_lds[kRiseLds];
 	const bool rise_in_lds = (MODE == 0) || (MODE == 3 && !SPARSE && p.batch < kRiseLds);
 	if (rise_in_lds) {
@@ -1627,7 +1627,7 @@ void k3_merge(const K3Params p)
 		return;
 	}
 
-	if (MODE == 3 && !SPARSE && p.n_batches <= 4) {
+	if (MODE == 3 && !SPARSE && p.n_batches <= kK3LongFew) {
 		/* Long batches come a few per launch (4 at N = 8192): too few for the batches-in-flight scheme below to hide anything, and a
 		 * thread that walks its cells one after the other pays a memory round trip per cell.  FOUR CELLS IN FLIGHT per thread instead:
 		 * their histogram values and all their counts are requested together. */
@@ -1637,7 +1637,7 @@ void k3_merge(const K3Params p)
 		const int pairs = cells >> 1;		/* a dword of the slabs = columns c and c + 32 of one (slab, bin) */
 		const uint32_t *hc32 = reinterpret_cast<const uint32_t *>(p.hc16);
 		for (int base = blockIdx.x * 256 + threadIdx.x; base < pairs; base += R * stride) {
-			int hidx[R]; float hv0[R][2]; uint32_t hc[R][4];
+			int hidx[R]; float hv0[R][2]; uint32_t hc[R][kK3LongFew];
 #pragma unroll
 			for (int r = 0; r < R; r++) {
 				const int g = base + r * stride;
@@ -1649,7 +1649,7 @@ void k3_merge(const K3Params p)
 				hv0[r][0] = p.hist[ok ? hidx[r] : 0];
 				hv0[r][1] = p.hist[ok ? hidx[r] + 32 : 0];
 #pragma unroll
-				for (int f = 0; f < 4; f++)
+				for (int f = 0; f < kK3LongFew; f++)
 					hc[r][f] = (f < fe) ? __builtin_nontemporal_load(&hc32[(size_t)f * pairs + gg]) : 0u;
 			}
 #pragma unroll
@@ -1658,7 +1658,7 @@ void k3_merge(const K3Params p)
 				for (int h = 0; h < 2; h++) {
 					float hv = hv0[r][h];
 #pragma unroll
-					for (int f = 0; f < 4; f++) {
+					for (int f = 0; f < kK3LongFew; f++) {
 						const uint32_t c16 = h ? (hc[r][f] >> 16) : (hc[r][f] & 0xffffu);
 						if (f < fe && !((hv <= 0.01f) && (c16 == 0))) {	/* display.cl:237-238 */
 							const float2 de = rise_in_lds ? rise_lds[c16] : p.rise[c16];
@@ -1869,12 +1869,26 @@ void k3_scan(const K3Params p)
 			p.rowlist[1 + pos++] = (uint32_t)(row0 + 1024 * k) | (bits[k] << 20) | (hot[k] ? 0x80000000u : 0u);
 }
 
+/* Which form a launch takes: the shape of the launch and the buffers the host filled in decide, never the data */
+K3Form k3_form(const K3Params &p)
+{
+	if (p.hc16 && p.rowmask && p.n_bins * (p.n / 64) <= (1 << 20))	/* (list entries hold 20 bits of row index: every geometry the library accepts) */
+		return p.batch <= 1024 ? K3_SPARSE16 : K3_SPARSE16_LONG;
+	if (p.hc16 && p.batch <= 1024)
+		return K3_DENSE16;
+	if (p.hc16)
+		return p.n_batches <= kK3LongFew ? K3_DENSE16_LONG4 : K3_DENSE16_LONG;	/* (the branch k3_merge<3> takes inside) */
+	return p.rise ? K3_TABLE32 : K3_EVAL32;
+}
+
 hipError_t launch_k3(const K3Params &p, hipStream_t s)
 {
 	const int threads = p.n_bins * p.n + p.n;
 	int blocks = (threads + 255) / 256;
 	if (blocks > 8192) blocks = 8192;
-	if (p.hc16 && p.rowmask && p.n_bins * (p.n / 64) <= (1 << 20)) {	/* (list entries hold 20 bits of row index: every geometry the library accepts) */
+	switch (k3_form(p)) {
+	case K3_SPARSE16:
+	case K3_SPARSE16_LONG: {
 		/* sparse form: list the live rows, then one wave per listed row (strided) */
 		const int rows = p.n_bins * (p.n / 64);
 		hipLaunchKernelGGL(k3_scan, dim3((rows + 4095) / 4096), dim3(1024), 0, s, p);
@@ -1884,16 +1898,22 @@ hipError_t launch_k3(const K3Params &p, hipStream_t s)
 			hipLaunchKernelGGL((k3_merge<0, true>), dim3(sb), dim3(256), 0, s, p);
 		else
 			hipLaunchKernelGGL((k3_merge<3, true>), dim3(sb), dim3(256), 0, s, p);
-		return hipGetLastError();
+		break;
 	}
-	if (p.hc16 && p.batch <= 1024)
+	case K3_DENSE16:
 		hipLaunchKernelGGL(k3_merge<0>, dim3(blocks), dim3(256), 0, s, p);
-	else if (p.hc16)	/* (each work-group loads the 32 KiB table: four per CU stride over the cells) */
+		break;
+	case K3_DENSE16_LONG4:
+	case K3_DENSE16_LONG:	/* (each work-group loads the 32 KiB table: four per CU stride over the cells) */
 		hipLaunchKernelGGL(k3_merge<3>, dim3(p.batch <= 4096 && blocks > 1024 ? 1024 : blocks), dim3(256), 0, s, p);
-	else if (p.rise)
+		break;
+	case K3_TABLE32:
 		hipLaunchKernelGGL(k3_merge<1>, dim3(blocks), dim3(256), 0, s, p);
-	else
+		break;
+	default:
 		hipLaunchKernelGGL(k3_merge<2>, dim3(blocks), dim3(256), 0, s, p);
+		break;
+	}
 	return hipGetLastError();
 }
 

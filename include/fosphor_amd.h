@@ -296,6 +296,33 @@ int fosphor_amd_share_stats(struct fosphor *self, long long *shared, long long *
  * pointer may be NULL. */
 int fosphor_amd_launch_stats(struct fosphor *self, long long *pieces, long long *k2c, long long *k2b);
 
+/* Merge launches since the instance was made, by the form the launch took -- for tests that must prove which form of the merge kernel
+ * a call ran (the form follows from the shape of the launch and the instance's geometry, never from the data):
+ *   stats[FOSPHOR_AMD_MERGE_DENSE16]        16-bit counts, batches up to 1024 spectra, every cell visited
+ *   stats[FOSPHOR_AMD_MERGE_DENSE16_LONG4]  16-bit counts, batches of 1025..8192 spectra counted as one chunk, up to 4 batches per launch
+ *   stats[FOSPHOR_AMD_MERGE_DENSE16_LONG]   ... more than 4 batches per launch
+ *   stats[FOSPHOR_AMD_MERGE_TABLE32]        32-bit counts, rise/decay table (sharded frames, batches of several chunks)
+ *   stats[FOSPHOR_AMD_MERGE_EVAL32]         32-bit counts, rise/decay evaluated per cell (batches beyond the table's 8192 spectra)
+ *   stats[FOSPHOR_AMD_MERGE_SPARSE16]       fft_len_log = 16: listed rows only, batches up to 1024 spectra
+ *   stats[FOSPHOR_AMD_MERGE_SPARSE16_LONG]  ... batches of 1025..8192 spectra
+ *   stats[FOSPHOR_AMD_MERGE_TABLE_IN_MEMORY]  how many of the LONG launches read the rise/decay table from memory instead of LDS
+ *                                             (every SPARSE16_LONG launch; the dense ones with batches above 4096 spectra)
+ *   stats[FOSPHOR_AMD_MERGE_SPARSE_MAX_BATCHES], stats[FOSPHOR_AMD_MERGE_SPARSE_LONG_MAX_BATCHES]  the most batches one SPARSE16 /
+ *                                             SPARSE16_LONG launch merged (above 11 the row list stops carrying the per-batch bits,
+ *                                             above 64 the merge fetches the row masks in several rounds)
+ *   stats[FOSPHOR_AMD_MERGE_SPARSE_LISTED_ROWS]  rows (one bin x 64 aligned columns) the last SPARSE launch listed and visited: the rows
+ *                                             flagged hot plus the rows with a count in some batch of the launch; every row when the
+ *                                             flags had to be rebuilt (first launch, or another form wrote the histogram); -1 before
+ *                                             the first.  Read back from the device: the call waits for that launch (-EIO if it cannot)
+ * The other counters only grow and nothing reads them but this call.  stats may be NULL. */
+enum {
+	FOSPHOR_AMD_MERGE_DENSE16, FOSPHOR_AMD_MERGE_DENSE16_LONG4, FOSPHOR_AMD_MERGE_DENSE16_LONG, FOSPHOR_AMD_MERGE_TABLE32,
+	FOSPHOR_AMD_MERGE_EVAL32, FOSPHOR_AMD_MERGE_SPARSE16, FOSPHOR_AMD_MERGE_SPARSE16_LONG, FOSPHOR_AMD_MERGE_TABLE_IN_MEMORY,
+	FOSPHOR_AMD_MERGE_SPARSE_MAX_BATCHES, FOSPHOR_AMD_MERGE_SPARSE_LONG_MAX_BATCHES, FOSPHOR_AMD_MERGE_SPARSE_LISTED_ROWS,
+	FOSPHOR_AMD_MERGE_STATS
+};
+int fosphor_amd_merge_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_MERGE_STATS]);
+
 /* Library identification: "fosphor_amd <version> gfx950". */
 const char *fosphor_amd_version(void);
 
