@@ -1,5 +1,5 @@
-"""ctypes binding of gr-fosphor_amd/libfosphor_amd.so (the C ABI of include/fosphor.h and
-include/fosphor_amd.h).  No CPU fallback: a missing library is a hard error."""
+"""ctypes binding of gr-fosphor_amd/libfosphor_amd.so (the C ABI of include/fosphor.h,
+include/fosphor_amd.h and the headers beside them).  No CPU fallback: a missing library is a hard error."""
 import ctypes as C
 import os
 import subprocess
@@ -53,6 +53,25 @@ class FreqAxis(C.Structure):
     _fields_ = [("center", C.c_double), ("span", C.c_double), ("step", C.c_double), ("mode", C.c_int),
                 ("abs_fmt", C.c_char * 16), ("abs_scale", C.c_double), ("rel_fmt", C.c_char * 16),
                 ("rel_step", C.c_double)]
+
+
+class View(C.Structure):
+    """struct fosphor_amd_view (include/fosphor_amd_view.h)"""
+    _fields_ = [("first_bin", C.c_int), ("n_cols", C.c_int), ("width", C.c_int),
+                ("wf_src_rows", C.c_int), ("wf_out_rows", C.c_int), ("detector", C.c_int)]
+
+
+class ViewColor(C.Structure):
+    """struct fosphor_amd_view_color"""
+    _fields_ = [("palette", C.c_void_p), ("n", C.c_int), ("use_defaults", C.c_int),
+                ("scale", C.c_float), ("offset", C.c_float)]
+
+
+class ViewOut(C.Structure):
+    """struct fosphor_amd_view_out"""
+    _fields_ = [("d_waterfall", C.c_void_p), ("d_histogram", C.c_void_p), ("d_live", C.c_void_p), ("d_max", C.c_void_p),
+                ("d_waterfall_rgba", C.c_void_p), ("d_histogram_rgba", C.c_void_p),
+                ("wf_color", ViewColor), ("histo_color", ViewColor)]
 
 
 SIGNATURES = {
@@ -127,6 +146,11 @@ SIGNATURES = {
     "fosphor_amd_cmap_generate": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
     "fosphor_amd_colorize": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
                                        C.c_int, C.c_void_p]),
+    # include/fosphor_amd_view.h
+    "fosphor_amd_view": (C.c_int, [C.c_void_p, C.POINTER(View), C.POINTER(ViewOut)]),
+    "fosphor_amd_view_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 4)]),
+    "fosphor_amd_view_span": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fosphor_amd_view_from_render": (C.c_int, [C.c_int, C.c_int, C.POINTER(Render), C.c_int, C.c_int, C.POINTER(View)]),
     # include/fosphor_amd_sink.h
     "fosphor_amd_process_pinned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "fosphor_amd_upload_pinned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

@@ -205,6 +205,84 @@ class Fosphor:
             raise RuntimeError("fosphor_amd_colorize -> %d" % rv)
         return out.view(torch.uint8).reshape(rows, self.n, 4)
 
+    DETECTORS = {"peak": 0, "average": 1}	# FOSPHOR_AMD_DET_* (include/fosphor_amd_view.h)
+    VIEW_OUTPUTS = ("waterfall", "histogram", "live", "max", "waterfall_rgba", "histogram_rgba")
+    VIEW_FORMS = ("tiled", "tiled_lanes", "wide", "lines")
+
+    def view(self, first_bin=0, n_cols=None, width=None, wf_src_rows=None, wf_out_rows=None, detector="peak",
+             rgba=True, floats=True, wf_palette=None, histo_palette=None, wf_scale=None, wf_offset=None,
+             histo_scale=None, histo_offset=None, outputs=None):
+        """A zoomed, display-width view (include/fosphor_amd_view.h): the shifted columns [first_bin, first_bin + n_cols) and the
+        newest wf_src_rows waterfall rows, reduced to width pixels across and wf_out_rows waterfall rows by the detector ("peak" or
+        "average").  Defaults: every column from first_bin on, one pixel per column, every row, one picture row per source row.
+        Returns a dict of torch device tensors: floats "waterfall" [wf_out_rows][width], "histogram" [n_bins][width], "live" and
+        "max" [width] (floats=True); uint8 "waterfall_rgba" [wf_out_rows][width][4], "histogram_rgba" [n_bins][width][4] (rgba=True).
+        outputs: an iterable of those names instead, to produce exactly them.  Palettes, scales and offsets as in colorize();
+        None = the reference's."""
+        import torch
+        if n_cols is None:
+            n_cols = self.n - first_bin
+        if width is None:
+            width = n_cols
+        if wf_src_rows is None:
+            wf_src_rows = self.wf_rows
+        if wf_out_rows is None:
+            wf_out_rows = wf_src_rows
+        if isinstance(detector, str):
+            if detector not in self.DETECTORS:
+                raise ValueError("detector must be one of %s" % ", ".join(self.DETECTORS))
+            detector = self.DETECTORS[detector]
+        if outputs is None:
+            outputs = [k for k in self.VIEW_OUTPUTS if (rgba if k.endswith("_rgba") else floats)]
+        else:
+            outputs = list(outputs)
+            for k in outputs:
+                if k not in self.VIEW_OUTPUTS:
+                    raise ValueError("no such view output: %r" % (k,))
+        v = _lib.View(int(first_bin), int(n_cols), int(width), int(wf_src_rows), int(wf_out_rows), int(detector))
+        # shapes for the allocations only: the library checks the view itself
+        w, wr = max(int(width), 1), max(int(wf_out_rows), 1)
+        shapes = {"waterfall": (wr, w), "histogram": (self.n_bins, w), "live": (w,), "max": (w,),
+                  "waterfall_rgba": (wr, w), "histogram_rgba": (self.n_bins, w)}
+        o = _lib.ViewOut()
+        res, keep = {}, []
+        for k in outputs:
+            t = torch.empty(shapes[k], dtype=torch.int32 if k.endswith("_rgba") else torch.float32, device="cuda")
+            setattr(o, "d_" + k, t.data_ptr())
+            res[k] = t
+        for col, pal, scale, offset in ((o.wf_color, wf_palette, wf_scale, wf_offset),
+                                        (o.histo_color, histo_palette, histo_scale, histo_offset)):
+            if pal is not None:
+                pal = np.ascontiguousarray(pal, dtype=np.uint32)
+                keep.append(pal)
+                col.palette, col.n = pal.ctypes.data, pal.size
+            col.use_defaults = 1 if scale is None and offset is None else 0
+            col.scale, col.offset = float(scale or 0.0), float(offset or 0.0)
+        rv = self.L.fosphor_amd_view(self.h, C.byref(v), C.byref(o))
+        if rv:
+            raise RuntimeError("fosphor_amd_view -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        for k in res:
+            if k.endswith("_rgba"):
+                res[k] = res[k].view(torch.uint8).reshape(res[k].shape + (4,))
+        return res
+
+    def view_from_render(self, render, width, wf_out_rows, **kw):
+        """view() of the window that the zoom fields of a struct fosphor_render (freq_center, freq_span, wf_span) select, as the
+        reference's GL side places it (fosphor_amd_view_from_render); peak detector.  Further arguments go to view()."""
+        v = _lib.View()
+        rv = self.L.fosphor_amd_view_from_render(self.n, self.wf_rows, C.byref(render), int(width), int(wf_out_rows), C.byref(v))
+        if rv:
+            raise RuntimeError("fosphor_amd_view_from_render -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return self.view(v.first_bin, v.n_cols, v.width, v.wf_src_rows, v.wf_out_rows, detector=v.detector, **kw)
+
+    def view_stats(self):
+        """fosphor_amd_view_stats as a dict: view launches since the instance was made, by form (VIEW_FORMS)"""
+        st = (C.c_longlong * 4)()
+        rv = self.L.fosphor_amd_view_stats(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("fosphor_amd_view_stats -> %d" % rv)
+        return dict(zip(self.VIEW_FORMS, list(st)))
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

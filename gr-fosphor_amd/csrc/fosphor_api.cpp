@@ -150,6 +150,7 @@ struct fosphor
 	float    *d_chunk_sum, *d_chunk_max;	/* [max_spectra/16][N] */
 	long long *d_dbg;			/* K1_TIMING builds only (FOSPHOR_AMD_K1_TIMING=1) */
 	uint32_t *d_palette;			/* colour-map scratch (fosphor_cmap.hip), allocated on first use */
+	long long view_forms[4];		/* view launches by form (fosphor_view.hip, fosphor_amd_view_stats) */
 	float2   *d_rise;			/* [kRiseMax+1] (d, e) per hit count */
 	float2   *h_rise;			/* pinned */
 	int       rise_batch;			/* batch the table was built for (0 = none) */
@@ -2160,6 +2161,12 @@ extern "C" void fosphor_amd_priv_power(struct fosphor *self, float *scale, float
 {
 	*scale = self->power.scale;
 	*offset = self->power.offset;
+}
+
+/* private accessor for fosphor_view.hip: its launch counters (host counters that only grow; nothing on the submit path reads them) */
+extern "C" long long *fosphor_amd_priv_view_forms(struct fosphor *self)
+{
+	return self->view_forms;
 }
 
 /* ------------------------------------------------------------------------ */

@@ -17,6 +17,7 @@
 
 #include "../../include/fosphor_amd.h"
 #include "../../include/fosphor_amd_cmap.h"
+#include "fosphor_cmap_dev.h"
 
 /* accessors implemented next to struct fosphor (fosphor_api.cpp) */
 extern "C" int  fosphor_amd_priv_palette(struct fosphor *self, int n, uint32_t **d_palette);
@@ -113,44 +114,16 @@ void palette_prog(uint32_t *rgba, int n)
 struct CmapParams {
 	const float *src;		/* [src_rows][n] */
 	uint32_t    *dst;		/* [rows][n] */
-	const uint32_t *pal;		/* [pal_n] device */
+	CmapLut      lut;		/* palette, scale, offset (fosphor_cmap_dev.h) */
 	int   n, rows;
 	int   row_base, row_mask;	/* source row of output row r: (row_base - r) & row_mask */
-	int   pal_n;
-	float scale, offset;
 };
-
-constexpr int kPalMax = 4096;
-
-__device__ __forceinline__ uint32_t lookup(float t, const CmapParams &p, const uint32_t *pal)
-{
-	const float m = (t + p.offset) * p.scale;		/* cmap_simple.glsl:44 */
-	float u = m * (float)p.pal_n - 0.5f;
-	u = (u != u) ? -1.0f : u;				/* NaN -> entry 0 */
-	u = fminf(fmaxf(u, -1.0f), (float)p.pal_n);
-	const float fl = floorf(u);
-	const float f  = u - fl;
-	int i0 = (int)fl, i1 = i0 + 1;
-	i0 = i0 < 0 ? 0 : (i0 > p.pal_n - 1 ? p.pal_n - 1 : i0);
-	i1 = i1 < 0 ? 0 : (i1 > p.pal_n - 1 ? p.pal_n - 1 : i1);
-	const uint32_t a = pal[i0], b = pal[i1];
-	uint32_t out = 0;
-#pragma unroll
-	for (int ch = 0; ch < 4; ch++) {
-		const float c0 = (float)((a >> (8 * ch)) & 0xffu);
-		const float c1 = (float)((b >> (8 * ch)) & 0xffu);
-		const float c  = c0 + f * (c1 - c0);		/* -ffp-contract=off: mul, add */
-		out |= ((uint32_t)(c + 0.5f) & 0xffu) << (8 * ch);
-	}
-	return out;
-}
 
 __global__ __launch_bounds__(256)
 void k_colorize(const CmapParams p)
 {
 	extern __shared__ uint32_t pal[];
-	for (int i = threadIdx.x; i < p.pal_n; i += 256)
-		pal[i] = p.pal[i];
+	cmap_stage_lds(p.lut, pal);
 	__syncthreads();
 
 	const int quads = p.n >> 2;				/* 4 pixels per thread */
@@ -161,8 +134,8 @@ void k_colorize(const CmapParams p)
 		const int sc = (c + (p.n >> 1)) & (p.n - 1);	/* fft-shift; stays 4-aligned and contiguous */
 		const float4 t = *reinterpret_cast<const float4 *>(p.src + (size_t)sr * p.n + sc);
 		uint4 o;
-		o.x = lookup(t.x, p, pal); o.y = lookup(t.y, p, pal);
-		o.z = lookup(t.z, p, pal); o.w = lookup(t.w, p, pal);
+		o.x = lookup(t.x, p.lut, pal); o.y = lookup(t.y, p.lut, pal);
+		o.z = lookup(t.z, p.lut, pal); o.w = lookup(t.w, p.lut, pal);
 		*reinterpret_cast<uint4 *>(p.dst + (size_t)r * p.n + c) = o;
 	}
 }
@@ -181,17 +154,12 @@ extern "C" int fosphor_amd_cmap_generate(int which, uint32_t *rgba, int n)
 	return -EINVAL;
 }
 
-extern "C" int fosphor_amd_colorize(struct fosphor *self, int image, const uint32_t *palette, int n,
-                                    int use_defaults, float scale, float offset, int rows, uint32_t *d_rgba)
+int fosphor_cmap_stage(struct fosphor *self, int image, const uint32_t *palette, int n, int use_defaults,
+                       float scale, float offset, int slot, CmapLut *lut)
 {
-	struct fosphor_amd_buffers b;
 	uint32_t own[256];
 	uint32_t *d_pal = NULL;
-	CmapParams p;
-	hipStream_t st;
 
-	if (!self || !d_rgba || (image != FOSPHOR_AMD_IMG_WATERFALL && image != FOSPHOR_AMD_IMG_HISTOGRAM))
-		return -EINVAL;
 	if (!palette) {
 		n = 256;					/* gl.c:265-268 */
 		fosphor_amd_cmap_generate(image == FOSPHOR_AMD_IMG_WATERFALL ? FOSPHOR_AMD_CMAP_WATERFALL
@@ -200,26 +168,46 @@ extern "C" int fosphor_amd_colorize(struct fosphor *self, int image, const uint3
 	}
 	if (n < 2 || n > kPalMax)
 		return -EINVAL;
+	if (use_defaults) {
+		if (image == FOSPHOR_AMD_IMG_WATERFALL)
+			fosphor_amd_priv_power(self, &scale, &offset);	/* gl.c:406-409 */
+		else { scale = 1.1f; offset = 0.0f; }			/* gl.c:430-432 */
+	}
+	if (fosphor_amd_priv_palette(self, kPalMax * kPalSlots, &d_pal) || !d_pal)
+		return -EIO;
+	d_pal += (size_t)kPalMax * slot;
+	if (hipMemcpyAsync(d_pal, palette, sizeof(uint32_t) * n, hipMemcpyHostToDevice,
+	                   (hipStream_t)fosphor_amd_stream(self)) != hipSuccess)
+		return -EIO;
+	lut->pal = d_pal; lut->pal_n = n;
+	lut->scale = scale; lut->offset = offset;
+	return 0;
+}
+
+extern "C" int fosphor_amd_colorize(struct fosphor *self, int image, const uint32_t *palette, int n,
+                                    int use_defaults, float scale, float offset, int rows, uint32_t *d_rgba)
+{
+	struct fosphor_amd_buffers b;
+	CmapParams p;
+	hipStream_t st;
+	int rv;
+
+	if (!self || !d_rgba || (image != FOSPHOR_AMD_IMG_WATERFALL && image != FOSPHOR_AMD_IMG_HISTOGRAM))
+		return -EINVAL;
+	if (palette && (n < 2 || n > kPalMax))
+		return -EINVAL;
 	if (fosphor_amd_finish(self) < 0)			/* like fosphor_draw: wait for the compute side */
 		return -EIO;
 	if (fosphor_amd_get_buffers(self, &b))
 		return -EIO;
 	if (image == FOSPHOR_AMD_IMG_WATERFALL ? (rows < 1 || rows > b.wf_rows) : (rows != b.n_bins))
 		return -EINVAL;
-	if (use_defaults) {
-		if (image == FOSPHOR_AMD_IMG_WATERFALL)
-			fosphor_amd_priv_power(self, &scale, &offset);	/* gl.c:406-409 */
-		else { scale = 1.1f; offset = 0.0f; }			/* gl.c:430-432 */
-	}
-	if (fosphor_amd_priv_palette(self, kPalMax, &d_pal) || !d_pal)
-		return -EIO;
+	if ((rv = fosphor_cmap_stage(self, image, palette, n, use_defaults, scale, offset, 0, &p.lut)))
+		return rv;
 	st = (hipStream_t)fosphor_amd_stream(self);
-	if (hipMemcpyAsync(d_pal, palette, sizeof(uint32_t) * n, hipMemcpyHostToDevice, st) != hipSuccess)
-		return -EIO;
 
-	p.dst = d_rgba; p.pal = d_pal; p.pal_n = n;
+	p.dst = d_rgba;
 	p.n = b.fft_len; p.rows = rows;
-	p.scale = scale; p.offset = offset;
 	if (image == FOSPHOR_AMD_IMG_WATERFALL) {
 		p.src = b.d_waterfall;
 		p.row_base = b.waterfall_pos - 1 + b.wf_rows;	/* kept non-negative before the mask */
@@ -233,7 +221,7 @@ extern "C" int fosphor_amd_colorize(struct fosphor *self, int image, const uint3
 		const int total = rows * (p.n >> 2);
 		int blocks = (total + 255) / 256;
 		if (blocks > 4096) blocks = 4096;
-		hipLaunchKernelGGL(k_colorize, dim3(blocks), dim3(256), sizeof(uint32_t) * n, st, p);
+		hipLaunchKernelGGL(k_colorize, dim3(blocks), dim3(256), sizeof(uint32_t) * p.lut.pal_n, st, p);
 		if (hipGetLastError() != hipSuccess)
 			return -EIO;
 	}

@@ -12,8 +12,9 @@
  *     the newest waterfall row / the highest power bin on top (gl.c:403-404, 427-428).
  *
  * What a GL implementation leaves open -- the precision of the palette texture's GL_LINEAR
- * filter -- is defined here (float32, formula below); zooming / resampling to a window size is
- * the front end's business.
+ * filter -- is defined here (float32, formula below).  This pass writes one pixel per texel;
+ * zooming and resampling to a window size, coloured by the same lookup, is fosphor_amd_view
+ * (fosphor_amd_view.h).
  */
 #ifndef FOSPHOR_AMD_CMAP_H
 #define FOSPHOR_AMD_CMAP_H
