@@ -495,52 +495,122 @@ constexpr int kK1WavesPerSimd = 2;		/* __launch_bounds__ second argument (measur
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 
-/* IQ formats (K1Params::iq_format, FOSPHOR_AMD_IQ_*).  The FFT kernels' text sits in k1*.inc and is compiled twice: as the fp32 / fp16
- * entry points (k1_fft_bin, ..., k1h_fused: K1_SC16 = 0, the code of those kernels is exactly what it was before sc16 existed) and as the
- * sc16 ones (k1_fft_bin_sc16, ...: K1_SC16 = 1, K1_IQ the IQ as uint32_t, one dword per sample).  An sc16 sample (re in the low, im in
- * the high half) is widened where it is loaded: (float)(short) v * 2^-15 is exact (int16 -> float is exact, and a power-of-two scale of
- * a value >= 2^-15 in magnitude stays normal), so everything behind the load computes on the very floats an fp32 instance fed those
- * values would -- no conversion pass, no fp32 copy in memory. */
+/* Buffer addressing for the 8192- and 65536-point kernels: every global access of their loops is `scalar base (descriptor) + ONE 32-bit per-lane
+ * offset + a scalar offset` -- buffer_load / buffer_store ... offen -- where the per-lane offset is fixed for the kernel's lifetime and
+ * everything that changes (spectrum, row, column block c) is scalar arithmetic.  With plain pointers the compiler folded the
+ * column-block constants into 64-bit per-lane adds (240 of them per spectrum) and spilled.  Arrays addressed this way are < 4 GiB. */
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+static __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base)
+{
+	return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0xffffffff, 0x00020000);	/* raw buffer, 32-bit data format */
+}
+constexpr int kAuxNT = 2, kAuxSC1 = 16;		/* gfx94x / gfx950 cache-policy bits of the buffer intrinsics: nt, sc1 */
+template <int AUX>
+static __device__ __forceinline__ void bst_v2f(v2f v, __amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff)
+{
+	__builtin_amdgcn_raw_buffer_store_b64(u2v{ __float_as_uint(v.x), __float_as_uint(v.y) }, rs, voff, soff, AUX);
+}
+template <int AUX>
+static __device__ __forceinline__ v2f bld_v2f(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff)
+{
+	const u2v u = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, AUX);
+	return v2f{ __uint_as_float(u.x), __uint_as_float(u.y) };
+}
+
+/* IQ formats (K1Params::iq_format, FOSPHOR_AMD_IQ_*).  The format is a compile-time property of an FFT kernel: each kernel of k1*.inc is a
+ * template whose first parameter IQ is one of the tags below, and reads K1Params::iq as `const IQ::elem *`.  A tag holds what differs
+ * between the formats and nothing else -- the type of a sample in memory and the loads that turn samples into v2f; behind the loads the
+ * kernels are one text.  The tag is part of an entry point's name: k1_fft_bin<iq_fp32, ...>, k1_fft_bin<iq_sc16, ...>.
+ * An sc16 sample (re in the low, im in the high half of a dword) is widened where it is loaded: (float)(short) v * 2^-15 is exact
+ * (int16 -> float is exact, and a power-of-two scale of a value >= 2^-15 in magnitude stays normal), so everything behind the load
+ * computes on the very floats an fp32 instance fed those values would -- no conversion pass, no fp32 copy in memory. */
 constexpr int kIqFp32 = 0, kIqFp16 = 1, kIqSc16 = 2;
 static __device__ __forceinline__ v2f widen_sc16(uint32_t v)
 {
 	return v2f{ (float)(short)(v & 0xffffu) * 0x1p-15f, (float)(short)(v >> 16) * 0x1p-15f };
 }
-/* one sample, non-temporal (read-once) */
-static __device__ __forceinline__ v2f ld_sample(const float2 *src) { return __builtin_nontemporal_load(reinterpret_cast<const v2f *>(src)); }
-static __device__ __forceinline__ v2f ld_sample(const uint32_t *src) { return widen_sc16(__builtin_nontemporal_load(src)); }
-
-/* 8 x (64 lanes x 16 B) = 1 KiB per instruction, read-once: non-temporal.  `src` points at this
- * lane's pair: elements (2L, 2L+1) + 128k land in x[2k], x[2k+1].  (Ablation on MI355X: with
- * 8-byte-per-lane loads the load path alone caps K1 near 4.7 TB/s; 16-byte ones do not.) */
-static __device__ __forceinline__ void load_iq16(v2f (&x)[16], const float2 *__restrict__ src)
-{
+/* Members of a tag:
+ *   elem         a sample in memory
+ *   ld_sample    one sample, non-temporal (read-once)
+ *   load_iq16    the 1024-point kernel's 16 samples of a lane: `src` points at this lane's pair, elements (2L, 2L+1) + 128k land in
+ *                x[2k], x[2k+1]
+ *   load_iq8     the two-wave kernel's 8 samples of a thread: elements i + 128 j
+ *   raw, ld_iq, request, mov, widen
+ *                the 8192-point kernel: what it holds of a sample between the request and the first pass (one register per dword of
+ *                elem), the request of row j of a window (element th + 512 j: `voff` = sizeof(elem) * th), the same request written by
+ *                hand and the hand-written move of the overlap reuse (why by hand: k1w_fft_bin.inc), and raw -> v2f
+ * The 65536-point kernel stages one-dword formats in LDS and takes them out with widen(); iq_fp16 exists for it alone. */
+struct iq_fp32 {
+	typedef float2 elem;
+	static __device__ __forceinline__ v2f ld_sample(const elem *src) { return __builtin_nontemporal_load(reinterpret_cast<const v2f *>(src)); }
+	/* 8 x (64 lanes x 16 B) = 1 KiB per instruction.  (Ablation on MI355X: with 8-byte-per-lane loads the load path alone caps K1
+	 * near 4.7 TB/s; 16-byte ones do not.) */
+	static __device__ __forceinline__ void load_iq16(v2f (&x)[16], const elem *__restrict__ src)
+	{
 #pragma unroll
-	for (int k = 0; k < 8; k++) {
-		const v4f q = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(src + 128 * k));
-		x[2 * k]     = v2f{ q.x, q.y };
-		x[2 * k + 1] = v2f{ q.z, q.w };
+		for (int k = 0; k < 8; k++) {
+			const v4f q = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(src + 128 * k));
+			x[2 * k]     = v2f{ q.x, q.y };
+			x[2 * k + 1] = v2f{ q.z, q.w };
+		}
 	}
-}
-/* sc16: the same lane-to-sample map at half the bytes, 8 x (64 lanes x 8 B): `src` 8-byte aligned (even hop, 8-byte aligned base) */
-static __device__ __forceinline__ void load_iq16(v2f (&x)[16], const uint32_t *__restrict__ src)
-{
+	static __device__ __forceinline__ void load_iq8(v2f (&x)[8], const elem *__restrict__ src)
+	{
 #pragma unroll
-	for (int k = 0; k < 8; k++) {
-		const u2v q = __builtin_nontemporal_load(reinterpret_cast<const u2v *>(src + 128 * k));
-		x[2 * k]     = widen_sc16(q.x);
-		x[2 * k + 1] = widen_sc16(q.y);
+		for (int j = 0; j < 8; j++)
+			x[j] = __builtin_nontemporal_load(reinterpret_cast<const v2f *>(src + 128 * j));
 	}
-}
+	typedef v2f raw;
+	static __device__ __forceinline__ raw ld_iq(__amdgpu_buffer_rsrc_t rs, uint32_t voff, int j) { return bld_v2f<kAuxNT>(rs, voff, 4096u * (uint32_t)j); }
+	static __device__ __forceinline__ void request(raw &d, uint32_t voff, __amdgpu_buffer_rsrc_t rs, int j)
+	{
+		asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen nt" : "=v"(d) : "v"(voff), "s"(rs), "s"(4096u * (uint32_t)j));
+	}
+	static __device__ __forceinline__ void mov(raw &d, const raw &s) { asm volatile("v_mov_b64 %0, %1" : "=v"(d) : "v"(s)); }
+	static __device__ __forceinline__ v2f widen(raw q) { return q; }
+};
+struct iq_sc16 {
+	typedef uint32_t elem;
+	static __device__ __forceinline__ v2f ld_sample(const elem *src) { return widen_sc16(__builtin_nontemporal_load(src)); }
+	/* the same lane-to-sample map at half the bytes, 8 x (64 lanes x 8 B): `src` 8-byte aligned (even hop, 8-byte aligned base) */
+	static __device__ __forceinline__ void load_iq16(v2f (&x)[16], const elem *__restrict__ src)
+	{
+#pragma unroll
+		for (int k = 0; k < 8; k++) {
+			const u2v q = __builtin_nontemporal_load(reinterpret_cast<const u2v *>(src + 128 * k));
+			x[2 * k]     = widen_sc16(q.x);
+			x[2 * k + 1] = widen_sc16(q.y);
+		}
+	}
+	static __device__ __forceinline__ void load_iq8(v2f (&x)[8], const elem *__restrict__ src)
+	{
+#pragma unroll
+		for (int j = 0; j < 8; j++)
+			x[j] = ld_sample(src + 128 * j);
+	}
+	/* one dword per sample and request -- the same number of requests as fp32's dwordx2 (the 8192-point kernel's counted wait is the
+	 * same); the raw dwords are what is held and moved down for the overlap reuse (16 registers fewer), widened where x is formed */
+	typedef uint32_t raw;
+	static __device__ __forceinline__ raw ld_iq(__amdgpu_buffer_rsrc_t rs, uint32_t voff, int j) { return __builtin_amdgcn_raw_buffer_load_b32(rs, voff, 2048u * (uint32_t)j, kAuxNT); }
+	static __device__ __forceinline__ void request(raw &d, uint32_t voff, __amdgpu_buffer_rsrc_t rs, int j)
+	{
+		asm volatile("buffer_load_dword %0, %1, %2, %3 offen nt" : "=v"(d) : "v"(voff), "s"(rs), "s"(2048u * (uint32_t)j));
+	}
+	static __device__ __forceinline__ void mov(raw &d, const raw &s) { asm volatile("v_mov_b32 %0, %1" : "=v"(d) : "v"(s)); }
+	static __device__ __forceinline__ v2f widen(raw q) { return widen_sc16(q); }
+};
+struct iq_fp16 {
+	typedef uint32_t elem;
+	static __device__ __forceinline__ v2f widen(uint32_t q)
+	{
+		typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+		const h2 h = __builtin_bit_cast(h2, q);
+		return v2f{ (float)h.x, (float)h.y };		/* v_cvt_f32_f16: exact */
+	}
+};
 #define K1_LANE_SRC(lane) (2 * (lane))
 
-#define K1_ENTRY(name) name
-#define K1_SC16 0
-#define K1_IQ p.iq
 #include "k1_fft_bin.inc"
-#undef K1_ENTRY
-#undef K1_SC16
-#undef K1_IQ
 
 /* ------------------------------------------------------------------------ */
 /* K1's memory traffic without K1's arithmetic (measurement hook)             */
@@ -560,7 +630,7 @@ void k1_traffic_twin(const K1Params p)
 	if (tile >= ntiles)
 		return;
 	v2f xn[16];
-	load_iq16(xn, p.iq + (size_t)tile * p.tile * p.hop + K1_LANE_SRC(lane));
+	iq_fp32::load_iq16(xn, p.iq + (size_t)tile * p.tile * p.hop + K1_LANE_SRC(lane));
 	for (; tile < ntiles; tile += stride) {
 		const int t0 = tile * p.tile;
 		v2f acc = { 0.0f, 0.0f };
@@ -575,7 +645,7 @@ void k1_traffic_twin(const K1Params p)
 				const bool last = (g0 + u + 1 == p.tile);
 				const int t_next = last ? (tile + stride) * p.tile : t + 1;
 				if (!last || tile + stride < ntiles)
-					load_iq16(xn, p.iq + (size_t)t_next * p.hop + K1_LANE_SRC(lane));
+					iq_fp32::load_iq16(xn, p.iq + (size_t)t_next * p.hop + K1_LANE_SRC(lane));
 #pragma unroll
 				for (int m = 0; m < 16; m++)
 					acc += x[m];			/* consume the data: 16 adds per spectrum */
@@ -614,26 +684,7 @@ hipError_t launch_k1_traffic_twin(const K1Params &p, hipStream_t s)
  * lane + 64m for m in {4w..4w+3} U {8+4w..8+4w+3}. */
 constexpr int kK1v2WavesPerSimd = 3;		/* __launch_bounds__ second argument (measured) */
 
-static __device__ __forceinline__ void load_iq8(v2f (&x)[8], const float2 *__restrict__ src)
-{
-#pragma unroll
-	for (int j = 0; j < 8; j++)		/* elements i + 128 j */
-		x[j] = __builtin_nontemporal_load(reinterpret_cast<const v2f *>(src + 128 * j));
-}
-static __device__ __forceinline__ void load_iq8(v2f (&x)[8], const uint32_t *__restrict__ src)
-{
-#pragma unroll
-	for (int j = 0; j < 8; j++)
-		x[j] = ld_sample(src + 128 * j);
-}
-
-#define K1_ENTRY(name) name
-#define K1_SC16 0
-#define K1_IQ p.iq
 #include "k1v2_fft_bin.inc"
-#undef K1_ENTRY
-#undef K1_SC16
-#undef K1_IQ
 
 /* ------------------------------------------------------------------------ */
 /* K1 general N: N/8 threads per spectrum                                    */
@@ -648,35 +699,7 @@ static __device__ __forceinline__ void load_iq8(v2f (&x)[8], const uint32_t *__r
  * involves address bits 0..6).  Bin indices are 16-bit, 2 spectra per dword. */
 static __device__ __forceinline__ int swz(int e) { return e ^ ((e >> 3) & 15); }
 
-#define K1_ENTRY(name) name
-#define K1_SC16 0
-#define K1_IQ p.iq
 #include "k1big_fft_bin.inc"
-#undef K1_ENTRY
-#undef K1_SC16
-#undef K1_IQ
-
-/* Buffer addressing for the 8192- and 65536-point kernels: every global access of their loops is `scalar base (descriptor) + ONE 32-bit per-lane
- * offset + a scalar offset` -- buffer_load / buffer_store ... offen -- where the per-lane offset is fixed for the kernel's lifetime and
- * everything that changes (spectrum, row, column block c) is scalar arithmetic.  With plain pointers the compiler folded the
- * column-block constants into 64-bit per-lane adds (240 of them per spectrum) and spilled.  Arrays addressed this way are < 4 GiB. */
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base)
-{
-	return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0xffffffff, 0x00020000);	/* raw buffer, 32-bit data format */
-}
-constexpr int kAuxNT = 2, kAuxSC1 = 16;		/* gfx94x / gfx950 cache-policy bits of the buffer intrinsics: nt, sc1 */
-template <int AUX>
-static __device__ __forceinline__ void bst_v2f(v2f v, __amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff)
-{
-	__builtin_amdgcn_raw_buffer_store_b64(u2v{ __float_as_uint(v.x), __float_as_uint(v.y) }, rs, voff, soff, AUX);
-}
-template <int AUX>
-static __device__ __forceinline__ v2f bld_v2f(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff)
-{
-	const u2v u = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, AUX);
-	return v2f{ __uint_as_float(u.x), __uint_as_float(u.y) };
-}
 
 /* X[jj] of a radix-16 pass sits in r[bitrev4(jj)] */
 #define R16_PERM(jj) ((((jj) & 1) << 3) | (((jj) & 2) << 1) | (((jj) & 4) >> 1) | (((jj) & 8) >> 3))
@@ -727,13 +750,7 @@ static __device__ __forceinline__ void wg_barrier_lds()
 
 constexpr int kK1wIdxStores = 16;	/* index stores a thread issues per ODD spectrum (one dword per column and pair of spectra): the immediate of the
 					 * hand-written wait for the IQ requested before them */
-#define K1_ENTRY(name) name
-#define K1_SC16 0
-#define K1_IQ p.iq
 #include "k1w_fft_bin.inc"
-#undef K1_ENTRY
-#undef K1_SC16
-#undef K1_IQ
 
 /* ------------------------------------------------------------------------ */
 /* K1 for N = 65536: radix-16 plan, two stages, the intermediate in the XCD's L2 */
@@ -835,27 +852,7 @@ template <int NWV> struct K1hGeom {
 						/* (exchange, two twiddle tables, staged input, thresholds) */
 };
 
-#define K1_ENTRY(name) name
-#define K1_SC16 0
-#define K1_IQ p.iq
 #include "k1h_fused.inc"
-#undef K1_ENTRY
-#undef K1_SC16
-#undef K1_IQ
-
-/* The sc16 entry points: the same kernel text, K1_SC16 = 1 (compiled behind every fp32 / fp16 kernel, which therefore keep their
- * place and code in the listing) */
-#define K1_ENTRY(name) name##_sc16
-#define K1_SC16 1
-#define K1_IQ reinterpret_cast<const uint32_t *>(p.iq)
-#include "k1_fft_bin.inc"
-#include "k1v2_fft_bin.inc"
-#include "k1big_fft_bin.inc"
-#include "k1w_fft_bin.inc"
-#include "k1h_fused.inc"
-#undef K1_ENTRY
-#undef K1_SC16
-#undef K1_IQ
 
 typedef void (*k1_fn)(const K1Params);
 
@@ -878,20 +875,18 @@ static hipError_t set_lds_once(const k1_fn *fns, int n, int lds, std::atomic<uns
 	return hipSuccess;
 }
 
-template <int NWV>
+template <typename IQ, int NWV>
 static hipError_t launch_k1h_form(const K1Params &p0, hipStream_t s)
 {
-	static const k1_fn fn[6] = { k1h_fused<false, false, NWV>, k1h_fused<true, false, NWV>, k1h_fused<false, true, NWV>, k1h_fused<true, true, NWV>,
-	                             k1h_fused_sc16<true, false, NWV>, k1h_fused_sc16<true, true, NWV> };
+	static const k1_fn fn[2] = { k1h_fused<IQ, false, NWV>, k1h_fused<IQ, true, NWV> };
 	constexpr size_t lds = K1hGeom<NWV>::kLds;
 	static std::atomic<unsigned long long> attr_dev{0};
-	const hipError_t ae = set_lds_once(fn, 6, (int)lds, attr_dev);
+	const hipError_t ae = set_lds_once(fn, 2, (int)lds, attr_dev);
 	if (ae != hipSuccess)
 		return ae;
 	/* (the counters in p0.sync are zero: cleared at allocation, and by the last work-group of every launch) */
 	/* 32 clusters: 8 work-groups of 8 waves, one per CU -- or 16 work-groups of 4 waves, two per CU */
-	const int which = p0.iq_format == kIqSc16 ? 4 + (p0.fft_out ? 1 : 0) : (p0.iq_format == kIqFp16 ? 1 : 0) | (p0.fft_out ? 2 : 0);
-	hipLaunchKernelGGL(fn[which], dim3(256 * 8 / NWV), dim3(64 * NWV), lds, s, p0);
+	hipLaunchKernelGGL(fn[p0.fft_out ? 1 : 0], dim3(256 * 8 / NWV), dim3(64 * NWV), lds, s, p0);
 	return hipGetLastError();
 }
 
@@ -900,17 +895,14 @@ static hipError_t launch_k1h(const K1Params &p0, hipStream_t s)
 	/* tiles of 4 .. 32 spectra (whole quads of low bytes, the 9th bits of a tile in one dword); tile index: 20 bits of the claim word */
 	if (!p0.sync || !p0.scratch || p0.tile < 4 || p0.tile > 32 || (p0.tile & 3) || p0.total % p0.tile || p0.total / p0.tile >= (1 << 20))
 		return hipErrorInvalidValue;
-	return launch_k1h_form<8>(p0, s);
+	return p0.iq_format == kIqSc16 ? launch_k1h_form<iq_sc16, 8>(p0, s)
+	     : p0.iq_format == kIqFp16 ? launch_k1h_form<iq_fp16, 8>(p0, s) : launch_k1h_form<iq_fp32, 8>(p0, s);
 }
 
-
-hipError_t launch_k1(const K1Params &p, hipStream_t s)
+/* The 1024- and 8192-point kernels of one format; each kernel's options are chosen here, once */
+template <typename IQ>
+static hipError_t launch_k1_as(const K1Params &p, hipStream_t s)
 {
-	if (p.variant == 4)
-		return launch_k1h(p, s);
-	if (p.iq_format != kIqFp32 && p.iq_format != kIqSc16)
-		return hipErrorInvalidValue;		/* (fp16: the 65536-point kernel only) */
-	const bool sc16 = p.iq_format == kIqSc16;
 	const int tiles = p.total / p.tile;
 	if (p.variant == 3) {
 		if (p.log2n == 10) {
@@ -918,24 +910,16 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 			constexpr int N = 1024;
 			constexpr int lds = (N + ((N / 2 - 8) / 7) * 7 + N / 2) * 8 + N * 4;		/* exchange slab + the reference's twiddles + window */
 			const int blocks = tiles < 4096 ? tiles : 4096;
-			if (sc16 && p.fft_out)
-				hipLaunchKernelGGL((k1big_fft_bin_sc16<10, true>), dim3(blocks), dim3(N / 8), lds, s, p);
-			else if (sc16)
-				hipLaunchKernelGGL((k1big_fft_bin_sc16<10, false>), dim3(blocks), dim3(N / 8), lds, s, p);
-			else if (p.fft_out)
-				hipLaunchKernelGGL((k1big_fft_bin<10, true>), dim3(blocks), dim3(N / 8), lds, s, p);
-			else
-				hipLaunchKernelGGL((k1big_fft_bin<10, false>), dim3(blocks), dim3(N / 8), lds, s, p);
+			hipLaunchKernelGGL((p.fft_out ? k1big_fft_bin<IQ, 10, true> : k1big_fft_bin<IQ, 10, false>), dim3(blocks), dim3(N / 8), lds, s, p);
 			return hipGetLastError();
 		}
 		if (p.log2n != 13 || (p.tile & 7) || (p.total & 7))	/* (the kernel packs the 9th bits of spectra 8 u .. 8 u + 7 of a tile into one byte per column) */
 			return hipErrorInvalidValue;
 		/* N = 8192: 16 points per thread, tables in registers, overlap reuse in registers (k1w_fft_bin); any hop */
 		constexpr int ldsw = 2 * 8192 * 8 + 520 * 8;	/* two slabs + the exact-bin thresholds */
-		static const k1_fn fns[10] = { k1w_fft_bin<8>, k1w_fft_bin<4>, k1w_fft_bin<2>, k1w_fft_bin<1>, k1w_fft_bin<16>,
-		                               k1w_fft_bin_sc16<8>, k1w_fft_bin_sc16<4>, k1w_fft_bin_sc16<2>, k1w_fft_bin_sc16<1>, k1w_fft_bin_sc16<16> };
+		static const k1_fn fns[5] = { k1w_fft_bin<IQ, 8>, k1w_fft_bin<IQ, 4>, k1w_fft_bin<IQ, 2>, k1w_fft_bin<IQ, 1>, k1w_fft_bin<IQ, 16> };
 		static std::atomic<unsigned long long> attr_dev{0};
-		const hipError_t ae = set_lds_once(fns, 10, ldsw, attr_dev);
+		const hipError_t ae = set_lds_once(fns, 5, ldsw, attr_dev);
 		if (ae != hipSuccess)
 			return ae;
 		/* rows of 512 samples the next window of a tile shares with this one: hop = 8192 / R, R = 2, 4, 8, 16; any other hop: none */
@@ -945,20 +929,13 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 		const int all_cus = p.n_cus > 0 ? p.n_cus : 256;
 		const int cus = (p.cus > 0 && p.cus < all_cus && tiles % p.cus == 0) ? p.cus : all_cus;
 		const int bw = tiles < cus ? tiles : cus;
-		hipLaunchKernelGGL(fns[which + (sc16 ? 5 : 0)], dim3(bw), dim3(512), ldsw, s, p);
+		hipLaunchKernelGGL(fns[which], dim3(bw), dim3(512), ldsw, s, p);
 		return hipGetLastError();
 	}
 	if (p.variant == 2) {
 		const int maxb = 256 * 2 * kK1v2WavesPerSimd;	/* resident 2-wave work-groups on 256 CUs */
 		int blocks = tiles < maxb ? tiles : maxb;
-		if (sc16 && p.fft_out)
-			hipLaunchKernelGGL(k1v2_fft_bin_sc16<true>, dim3(blocks), dim3(128), 0, s, p);
-		else if (sc16)
-			hipLaunchKernelGGL(k1v2_fft_bin_sc16<false>, dim3(blocks), dim3(128), 0, s, p);
-		else if (p.fft_out)
-			hipLaunchKernelGGL(k1v2_fft_bin<true>, dim3(blocks), dim3(128), 0, s, p);
-		else
-			hipLaunchKernelGGL(k1v2_fft_bin<false>, dim3(blocks), dim3(128), 0, s, p);
+		hipLaunchKernelGGL((p.fft_out ? k1v2_fft_bin<IQ, true> : k1v2_fft_bin<IQ, false>), dim3(blocks), dim3(128), 0, s, p);
 		return hipGetLastError();
 	}
 	int blocks = (tiles + 3) / 4;
@@ -967,21 +944,20 @@ hipError_t launch_k1(const K1Params &p, hipStream_t s)
 	                                   return (v > 0 && v < kK1MaxBlocks) ? v : kK1MaxBlocks; }();
 	if (blocks > max_blocks)
 		blocks = max_blocks;		/* persistent: 2 work-groups per CU */
-	if (sc16) {
-		if (p.fft_out)
-			hipLaunchKernelGGL((k1_fft_bin_sc16<true, false>), dim3(blocks), dim3(256), 0, s, p);
-		else if (p.n_bins == 256)
-			hipLaunchKernelGGL((k1_fft_bin_sc16<false, true>), dim3(blocks), dim3(256), 0, s, p);
-		else
-			hipLaunchKernelGGL((k1_fft_bin_sc16<false, false>), dim3(blocks), dim3(256), 0, s, p);
-	} else if (p.fft_out)
-		hipLaunchKernelGGL((k1_fft_bin<true, false>), dim3(blocks), dim3(256), 0, s, p);
-	else
-		if (p.n_bins == 256)
-			hipLaunchKernelGGL((k1_fft_bin<false, true>), dim3(blocks), dim3(256), 0, s, p);
-		else
-			hipLaunchKernelGGL((k1_fft_bin<false, false>), dim3(blocks), dim3(256), 0, s, p);
+	hipLaunchKernelGGL((p.fft_out ? k1_fft_bin<IQ, true, false> : p.n_bins == 256 ? k1_fft_bin<IQ, false, true> : k1_fft_bin<IQ, false, false>),
+	                   dim3(blocks), dim3(256), 0, s, p);
 	return hipGetLastError();
+}
+
+hipError_t launch_k1(const K1Params &p, hipStream_t s)
+{
+	if (p.variant == 4)
+		return launch_k1h(p, s);
+	if (p.iq_format == kIqFp32)
+		return launch_k1_as<iq_fp32>(p, s);
+	if (p.iq_format == kIqSc16)
+		return launch_k1_as<iq_sc16>(p, s);
+	return hipErrorInvalidValue;		/* (fp16: the 65536-point kernel only) */
 }
 
 /* Test hook: the K1 epilogue alone on FFT values read from memory */

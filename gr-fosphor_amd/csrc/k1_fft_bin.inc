@@ -1,10 +1,11 @@
 /*
- * k1_fft_bin.inc -- kernel text included twice by fosphor_kernels.hip: once as the fp32 / fp16 entry point `k1_fft_bin`, once as the sc16
- * one `k1_fft_bin_sc16` (K1_ENTRY names the function, K1_SC16 is 0 / 1, K1_IQ is p.iq as the format reads it; see "IQ formats" there).
+ * k1_fft_bin.inc -- the 1024-point kernel, one wave per spectrum (8-bit bin indices).  A template over the IQ format: IQ is one of the tags
+ * of "IQ formats" in fosphor_kernels.hip, which includes this file once; `iq` below is K1Params::iq as that format's samples and
+ * IQ::load_iq16 the only place where the formats differ.
  */
-template <bool WRITE_FFT, bool NB256 = false>	/* NB256: 256 bins -- the saturating conversion of the bin byte IS the clamp at n_bins - 1 */
+template <typename IQ, bool WRITE_FFT, bool NB256 = false>	/* NB256: 256 bins -- the saturating conversion of the bin byte IS the clamp at n_bins - 1 */
 __global__ __launch_bounds__(256, kK1WavesPerSimd)
-void K1_ENTRY(k1_fft_bin)(const K1Params p)
+void k1_fft_bin(const K1Params p)
 {
 	__shared__ v2f   lds[4][kN];			/* 8 KiB exchange slab per wave */
 	__shared__ v2f   tw4_tab[512];			/* pass-4 twiddles, shared by the block */
@@ -22,6 +23,7 @@ void K1_ENTRY(k1_fft_bin)(const K1Params p)
 #endif
 	int tile = blockIdx.x * 4 + wv;
 	const v2f *twg = reinterpret_cast<const v2f *>(p.tw);
+	const typename IQ::elem *iq = reinterpret_cast<const typename IQ::elem *>(p.iq);
 
 	for (int i = threadIdx.x; i < kN; i += 256)
 		win_tab[i] = p.win[i];
@@ -63,7 +65,7 @@ void K1_ENTRY(k1_fft_bin)(const K1Params p)
 	const float vmax_init = -1000.0f / F_HALF_LOG10_2;	/* display.cl:91, in log2 units */
 
 	v2f xn[16];
-	load_iq16(xn, K1_IQ + (size_t)tile * p.tile * p.hop + K1_LANE_SRC(lane));
+	IQ::load_iq16(xn, iq + (size_t)tile * p.tile * p.hop + K1_LANE_SRC(lane));
 #if K1_TIMING
 	long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	long long tprev = __builtin_readcyclecounter();
@@ -123,7 +125,7 @@ void K1_ENTRY(k1_fft_bin)(const K1Params p)
 				const bool last = (g0 + u + 1 == p.tile);
 				const int t_next = last ? (tile + stride) * p.tile : t + 1;
 				if (!last || tile + stride < ntiles)
-					load_iq16(xn, K1_IQ + (size_t)t_next * p.hop + K1_LANE_SRC(lane));
+					IQ::load_iq16(xn, iq + (size_t)t_next * p.hop + K1_LANE_SRC(lane));
 			}
 
 			K1_STAMP(0);		/* window (includes waiting for the prefetched IQ) + prefetch issue */

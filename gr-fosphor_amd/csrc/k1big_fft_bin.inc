@@ -1,10 +1,10 @@
 /*
- * k1big_fft_bin.inc -- kernel text included twice by fosphor_kernels.hip: once as the fp32 / fp16 entry point `k1big_fft_bin`, once as the sc16
- * one `k1big_fft_bin_sc16` (K1_ENTRY names the function, K1_SC16 is 0 / 1, K1_IQ is p.iq as the format reads it; see "IQ formats" there).
+ * k1big_fft_bin.inc -- the general-N kernel, N / 8 threads per spectrum (16-bit bin indices).  A template over the IQ format: IQ is one of the
+ * tags of "IQ formats" in fosphor_kernels.hip, which includes this file once; IQ::ld_sample is the only place where the formats differ.
  */
-template <int LOG2N, bool WRITE_FFT>
+template <typename IQ, int LOG2N, bool WRITE_FFT>
 __global__ __launch_bounds__((1 << LOG2N) / 8)
-void K1_ENTRY(k1big_fft_bin)(const K1Params p)
+void k1big_fft_bin(const K1Params p)
 {
 	constexpr int N = 1 << LOG2N, T = N / 8, NP8 = LOG2N / 3;
 	static_assert(LOG2N % 3 == 1, "plan: radix-8 passes then one radix-2 pass");
@@ -43,17 +43,13 @@ void K1_ENTRY(k1big_fft_bin)(const K1Params p)
 #pragma unroll 1
 		for (int u = 0; u < 2; u++) {
 			const int t = t0 + g0 + u;
-			const auto *src = K1_IQ + (size_t)t * p.hop;
+			const typename IQ::elem *src = reinterpret_cast<const typename IQ::elem *>(p.iq) + (size_t)t * p.hop;
 			v2f r[8];
 
 			/* window (fft.cl:415-417) */
 #pragma unroll
 			for (int j = 0; j < 8; j++) {
-#if K1_SC16
-				const v2f xv = ld_sample(src + i + T * j);
-#else
-				const v2f xv = __builtin_nontemporal_load(reinterpret_cast<const v2f *>(src + i + T * j));
-#endif
+				const v2f xv = IQ::ld_sample(src + i + T * j);
 				const float wv = wins[i + T * j];
 				r[j] = v2f{ xv.x * wv, xv.y * wv };
 			}

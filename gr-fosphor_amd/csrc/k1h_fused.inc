@@ -1,12 +1,14 @@
 /*
- * k1h_fused.inc -- kernel text included twice by fosphor_kernels.hip: once as the fp32 / fp16 entry point `k1h_fused`, once as the sc16
- * one `k1h_fused_sc16` (K1_ENTRY names the function, K1_SC16 is 0 / 1, K1_IQ is p.iq as the format reads it; see "IQ formats" there).
+ * k1h_fused.inc -- the 65536-point kernel.  A template over the IQ format: IQ is one of the tags of "IQ formats" in fosphor_kernels.hip, which
+ * includes this file once.  The formats of one dword per sample (HALF below: fp16, sc16) are staged in LDS by LDS-DMA and taken out
+ * with IQ::widen; fp32 is gathered per lane where it is used.
  */
-template <bool HALF, bool WRITE_FFT, int NWV>
+template <typename IQ, bool WRITE_FFT, int NWV>
 __global__ __launch_bounds__(64 * NWV, 2)
-void K1_ENTRY(k1h_fused)(const K1Params p)
+void k1h_fused(const K1Params p)
 {
 	constexpr int N = 65536;
+	constexpr bool HALF = sizeof(typename IQ::elem) == 4;
 	typedef K1hGeom<NWV> G;
 	constexpr int NT = 64 * NWV, kMem = G::kMem, kRpm = G::kRpm, kXLen = G::kXLen, kInLen = G::kInLen;
 	/* Every wait on another work-group is bounded (a poll is ~1 us: seconds, far beyond any legitimate wait): a protocol failure
@@ -150,7 +152,6 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 	uint32_t done = 0;						/* spectra this cluster has finished */
 	uint32_t round = 0;						/* tiles this cluster has taken */
 
-	typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 	/* fp16 IQ: the work-group fetches its 32 residues of a spectrum as whole 128-byte runs STRAIGHT INTO LDS (buffer_load_dwordx4 ... lds:
 	 * no staging registers, no ds_write pass) -- one wave-instruction lands 64 x 16 B = 8 rows x 128 B back to back, so rows cannot be
 	 * padded; the 16-byte piece pc of row m sits at slot 8 m + (pc ^ (m & 7)) instead (the permutation is applied to the per-lane SOURCE
@@ -192,15 +193,8 @@ void K1_ENTRY(k1h_fused)(const K1Params p)
 		for (int jo = 0; jo < 16; jo++) {
 			const int j = K1H_PAIR(jo);
 			v2f xv;
-#if K1_SC16
-			if (HALF) {
-				xv = widen_sc16(inb[buf * kInLen + in_rd + 16 * kRpm * j]);
-			} else
-#endif
-			if (HALF) {
-				const uint32_t raw = inb[buf * kInLen + in_rd + 16 * kRpm * j];
-				const h2 h = __builtin_bit_cast(h2, raw);
-				xv = v2f{ (float)h.x, (float)h.y };		/* v_cvt_f32_f16: exact */
+			if constexpr (HALF) {
+				xv = IQ::widen(inb[buf * kInLen + in_rd + 16 * kRpm * j]);
 			} else {
 				xv = bld_v2f<kAuxNT>(rs_f, 8u * (unsigned)(qa + 256 * ia), 32768u * j);
 			}

@@ -1,10 +1,11 @@
 /*
- * k1v2_fft_bin.inc -- kernel text included twice by fosphor_kernels.hip: once as the fp32 / fp16 entry point `k1v2_fft_bin`, once as the sc16
- * one `k1v2_fft_bin_sc16` (K1_ENTRY names the function, K1_SC16 is 0 / 1, K1_IQ is p.iq as the format reads it; see "IQ formats" there).
+ * k1v2_fft_bin.inc -- the 1024-point kernel, two waves per spectrum.  A template over the IQ format: IQ is one of the tags of "IQ formats" in
+ * fosphor_kernels.hip, which includes this file once; `iq` below is K1Params::iq as that format's samples and IQ::load_iq8 the only
+ * place where the formats differ.
  */
-template <bool WRITE_FFT>
+template <typename IQ, bool WRITE_FFT>
 __global__ __launch_bounds__(128, kK1v2WavesPerSimd)
-void K1_ENTRY(k1v2_fft_bin)(const K1Params p)
+void k1v2_fft_bin(const K1Params p)
 {
 	__shared__ v2f   buf[kN];			/* 8 KiB exchange slab of the work-group's spectrum */
 	__shared__ v2f   tw4_tab[512];
@@ -17,6 +18,7 @@ void K1_ENTRY(k1v2_fft_bin)(const K1Params p)
 	const int stride = gridDim.x;
 	int tile = blockIdx.x;
 	const v2f *twg = reinterpret_cast<const v2f *>(p.tw);
+	const typename IQ::elem *iq = reinterpret_cast<const typename IQ::elem *>(p.iq);
 
 	for (int i = threadIdx.x; i < kN; i += 128)
 		win_tab[i] = p.win[i];
@@ -48,7 +50,7 @@ void K1_ENTRY(k1v2_fft_bin)(const K1Params p)
 
 	v2f xn[8];
 	if (tile < ntiles)
-		load_iq8(xn, K1_IQ + (size_t)tile * p.tile * p.hop + i0);
+		IQ::load_iq8(xn, iq + (size_t)tile * p.tile * p.hop + i0);
 
 	for (; tile < ntiles; tile += stride) {		/* uniform over the work-group */
 	const int t0 = tile * p.tile;
@@ -84,7 +86,7 @@ void K1_ENTRY(k1v2_fft_bin)(const K1Params p)
 				const bool last = (g0 + u + 1 == p.tile);
 				const int t_next = last ? (tile + stride) * p.tile : t + 1;
 				if (!last || tile + stride < ntiles)
-					load_iq8(xn, K1_IQ + (size_t)t_next * p.hop + i0);
+					IQ::load_iq8(xn, iq + (size_t)t_next * p.hop + i0);
 			}
 
 			/* pass 1 (fft.cl:419-420) */

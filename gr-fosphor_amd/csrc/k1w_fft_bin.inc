@@ -1,10 +1,11 @@
 /*
- * k1w_fft_bin.inc -- kernel text included twice by fosphor_kernels.hip: once as the fp32 / fp16 entry point `k1w_fft_bin`, once as the sc16
- * one `k1w_fft_bin_sc16` (K1_ENTRY names the function, K1_SC16 is 0 / 1, K1_IQ is p.iq as the format reads it; see "IQ formats" there).
+ * k1w_fft_bin.inc -- the 8192-point kernel.  A template over the IQ format: IQ is one of the tags of "IQ formats" in fosphor_kernels.hip, which
+ * includes this file once.  The formats differ in what a thread holds of its sixteen rows between their request and the first pass
+ * (IQ::raw q[16]) and in the four operations on it: IQ::ld_iq, IQ::request, IQ::mov, IQ::widen.
  */
-template <int SHIFT>
+template <typename IQ, int SHIFT>
 __global__ __launch_bounds__(512, 2)
-void K1_ENTRY(k1w_fft_bin)(const K1Params p)
+void k1w_fft_bin(const K1Params p)
 {
 	constexpr int N = 8192, TH = 512;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -59,23 +60,9 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 
 	/* SHIFT = 16 / R for hop = N / R, R = 2, 4, 8, 16: the next window's row j is this window's row j + SHIFT of the same thread;
 	 * SHIFT = 16: any other hop, every row is requested again */
-#if K1_SC16
-	/* sc16: one dword per sample and request -- the same number of requests as fp32's dwordx2 (the counted wait below is unchanged);
-	 * the raw dwords are what is held and moved down for the overlap reuse (16 registers fewer), widened where x is formed */
-	const uint32_t iq_vo = 4u * (uint32_t)th;		/* element th + 512 j of a window at 4 th + 2048 j */
-	auto ld_iq = [&](__amdgpu_buffer_rsrc_t rs, int j) __attribute__((always_inline)) -> uint32_t {
-		return __builtin_amdgcn_raw_buffer_load_b32(rs, iq_vo, 2048u * (uint32_t)j, kAuxNT);
-	};
-
-	uint32_t q[16];			/* raw IQ of the spectrum to be processed next: rows th + 512 j */
-#else
-	const uint32_t iq_vo = 8u * (uint32_t)th;		/* element th + 512 j of a window at 8 th + 4096 j (scalar descriptor + one lane offset) */
-	auto ld_iq = [&](__amdgpu_buffer_rsrc_t rs, int j) __attribute__((always_inline)) -> v2f {
-		return bld_v2f<kAuxNT>(rs, iq_vo, 4096u * (uint32_t)j);
-	};
-
-	v2f q[16];			/* raw IQ of the spectrum to be processed next: rows th + 512 j */
-#endif
+	const typename IQ::elem *iq = reinterpret_cast<const typename IQ::elem *>(p.iq);
+	const uint32_t iq_vo = (uint32_t)sizeof(typename IQ::elem) * (uint32_t)th;	/* element th + 512 j of a window at this byte offset + that of row j (scalar descriptor + one lane offset) */
+	typename IQ::raw q[16];		/* raw IQ of the spectrum to be processed next: rows th + 512 j */
 	/* column of xo[m]: cb + 256 (m & 7) + 4096 (m >> 3), cb = kk + 2048 hh.  ONE register carries it through the spectrum loop, as the
 	 * byte offset 2 cb of the column's short in an index row (the kernel has no register to spare: tools/check_k1w_loads.py); the rare
 	 * users of cb itself (waterfall rows, the bytes of 9th bits, the tile's partials) take it back out of it where they run */
@@ -205,10 +192,10 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 	for (int m = 0; m < 16; m++) { live[m] = 0.0f; vmax[m] = vmax_init; }
 
 	{
-		const __amdgpu_buffer_rsrc_t src = make_rsrc(K1_IQ + (size_t)t0 * p.hop);
+		const __amdgpu_buffer_rsrc_t src = make_rsrc(iq + (size_t)t0 * p.hop);
 #pragma unroll
 		for (int j = 0; j < 16; j++)
-			q[j] = ld_iq(src, j);
+			q[j] = IQ::ld_iq(src, iq_vo, j);
 	}
 
 	v2f xo[16];			/* FFT of the previous spectrum of the tile, its epilogue still to do */
@@ -242,11 +229,7 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 #undef K1W_Q16
 #pragma unroll
 		for (int j = 0; j < 16; j++)
-#if K1_SC16
-			x[j] = widen_sc16(q[j]);
-#else
-			x[j] = q[j];
-#endif
+			x[j] = IQ::widen(q[j]);
 		K1W_STAMP(0);			/* radix 2 of the previous spectrum, loop overhead, wait for the IQ */
 		pass16_first<true>(x, wab, w16c, w8c, w163c, two);
 		K1W_STAMP(1);
@@ -256,27 +239,19 @@ void K1_ENTRY(k1w_fft_bin)(const K1Params p)
 		 * join makes the compiler wait for it right there */
 		{
 			const int tn = (g + 1 < p.tile) ? t + 1 : t;
-			const __amdgpu_buffer_rsrc_t src = make_rsrc(K1_IQ + (size_t)tn * p.hop);
+			const __amdgpu_buffer_rsrc_t src = make_rsrc(iq + (size_t)tn * p.hop);
 			/* (moves the compiler cannot sink: left to it, they went behind the requests -- whose results then needed registers of their
 			 * own, a copy at the end of the loop and, for that copy, a wait for every store issued in between) */
 #pragma unroll
 			for (int j = 0; j < 16 - SHIFT; j++)
-#if K1_SC16
-				asm volatile("v_mov_b32 %0, %1" : "=v"(q[j]) : "v"(q[j + SHIFT]));
-#else
-				asm volatile("v_mov_b64 %0, %1" : "=v"(q[j]) : "v"(q[j + SHIFT]));
-#endif
+				IQ::mov(q[j], q[j + SHIFT]);
 			/* The requests are made by hand, and so is the wait for them at the top of the next iteration: loads and stores leave the
 			 * vmcnt queue IN ORDER, and the wait the compiler places for loads it knows about -- vmcnt(0) -- also sat through the
 			 * acknowledgement of every index store issued since (a third of this kernel's time: probe builds without the stores / without
 			 * the requests, profiles/r05_c3.md) */
 #pragma unroll
 			for (int j = 16 - SHIFT; j < 16; j++)
-#if K1_SC16
-				asm volatile("buffer_load_dword %0, %1, %2, %3 offen nt" : "=v"(q[j]) : "v"(iq_vo), "s"(src), "s"(2048u * (uint32_t)j));
-#else
-				asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen nt" : "=v"(q[j]) : "v"(iq_vo), "s"(src), "s"(4096u * (uint32_t)j));
-#endif
+				IQ::request(q[j], iq_vo, src, j);
 		}
 
 #pragma unroll

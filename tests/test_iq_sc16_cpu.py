@@ -37,11 +37,11 @@ def test_check_k1w_loads_sc16(kernels_asm):
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     lines = r.stdout.strip().splitlines()
-    assert len(lines) == 5 and all("k1w_fft_bin_sc16" in l and l.endswith("ScratchSize 0") for l in lines), r.stdout
+    assert len(lines) == 5 and all("k1w_fft_bin" in l and "iq_sc16" in l and l.endswith("ScratchSize 0") for l in lines), r.stdout
 
 
 def test_sc16_kernels_do_not_spill():
-    """-Rpass-analysis=kernel-resource-usage: every sc16 entry point has 0 bytes of scratch and at most 256 VGPRs."""
+    """-Rpass-analysis=kernel-resource-usage: every sc16 entry point (the format tag iq_sc16 in its name) has 0 bytes of scratch and at most 256 VGPRs."""
     r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-x", "hip", "--cuda-device-only",
                         "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage", SRC], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -56,7 +56,7 @@ def test_sc16_kernels_do_not_spill():
             m = re.search(r"remark:\s+%s( \[bytes/lane\])?: (\d+)" % key, line)
             if m and cur:
                 found.setdefault(cur, {})[key] = int(m.group(2))
-    sc16 = {k: v for k, v in found.items() if "_sc16" in k}
+    sc16 = {k: v for k, v in found.items() if "iq_sc16" in k}
     assert len(sc16) == 14, sorted(sc16)
     for name, res in sc16.items():
         assert res.get("ScratchSize") == 0, (name, res)

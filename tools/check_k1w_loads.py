@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build-time check of the 8192-point kernel's hand-issued IQ requests (gr-fosphor_amd/csrc/fosphor_kernels.hip, k1w_fft_bin).
+"""Build-time check of the 8192-point kernel's hand-issued IQ requests (gr-fosphor_amd/csrc/k1w_fft_bin.inc, k1w_fft_bin<iq_fp32, SHIFT>).
 
 The kernel requests the next spectrum's IQ with `buffer_load_dwordx2` written as inline assembly and waits for it with a hand-written
 `s_waitcnt vmcnt(16)` at the top of the next iteration, so the compiler does not know that the destination registers are in flight (8-byte requests per row, or 16-byte requests per pair of rows).  That is
@@ -8,7 +8,7 @@ stale data.  This script compiles the kernels to assembly and checks exactly tha
 
     python3 tools/check_k1w_loads.py [--sc16] [kernels.s]        (without a file: runs hipcc -S itself)
 
---sc16 checks the sc16 entry points (k1w_fft_bin_sc16: one `buffer_load_dword` per row) instead, and requires ScratchSize 0.
+--sc16 checks the sc16 entry points (k1w_fft_bin<iq_sc16, SHIFT>: one `buffer_load_dword` per row) instead, and requires ScratchSize 0.
 
 Exit status 0 and one line per kernel if the property holds."""
 import os
@@ -38,7 +38,7 @@ def regs(line):
 
 def check(path, sc16=False):
     src = open(path).read().splitlines()
-    sym = r"^_ZN11fosphor_amd16k1w_fft_bin_sc16ILi\d+EEEvNS_8K1ParamsE:" if sc16 else r"^_ZN11fosphor_amd11k1w_fft_binILi\d+EEEvNS_8K1ParamsE:"
+    sym = r"^_ZN11fosphor_amd11k1w_fft_binINS_7iq_%sELi\d+EEEvNS_8K1ParamsE:" % ("sc16" if sc16 else "fp32")		# k1w_fft_bin<iq_sc16 / iq_fp32, SHIFT>
     req = r"buffer_load_dword " if sc16 else r"buffer_load_dwordx[24] "
     req_dst = r"buffer_load_dword v(\d+)()," if sc16 else r"buffer_load_dwordx[24] v\[(\d+):(\d+)\]"
     starts = [i for i, l in enumerate(src) if re.match(sym, l)]

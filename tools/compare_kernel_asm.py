@@ -14,9 +14,18 @@ of OLD is missing from NEW or differs.  Functions that exist only in NEW (new en
 
 compares less, for a change that only moves kernel arguments: per function the resources, and the multiset of vector instructions
 (v_, ds_, global_, buffer_, flat_ lines) with scalar register numbers masked.  Argument offsets, scalar registers and the order of
-the instructions may differ."""
+the instructions may differ.
+
+    python3 tools/compare_kernel_asm.py --rename 'PATTERN=REPLACEMENT' [--rename ...] old.s new.s
+
+follows functions that were renamed on purpose: each PATTERN (a Python regular expression, the renames applied in the order given) is
+replaced in the DEMANGLED name of every function of OLD (llvm-cxxfilt of the ROCm toolchain, or c++filt), and the result is looked up
+among the demangled names of NEW."""
 import collections
+import os
 import re
+import shutil
+import subprocess
 import sys
 
 
@@ -71,16 +80,36 @@ def vector_multiset(code):
                                if re.match(r"(v_|ds_|global_|buffer_|flat_)", l))
 
 
-def main(old_path, new_path, vector=False):
+def demangle(names):
+    tool = next((t for t in (shutil.which("llvm-cxxfilt"), os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-cxxfilt"),
+                             shutil.which("c++filt")) if t and os.path.exists(t)), None)
+    if tool is None:
+        raise SystemExit("--rename needs llvm-cxxfilt or c++filt")
+    out = subprocess.run([tool], input="\n".join(names) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
+    return dict(zip(names, out))
+
+
+def main(old_path, new_path, vector=False, renames=()):
     old, new = functions(old_path), functions(new_path)
+    # OLD's name -> the name it has in NEW
+    target = {name: name for name in old}
+    if renames:
+        dem_old, by_dem = demangle(list(old)), {d: n for n, d in demangle(list(new)).items()}
+        for name in old:
+            d = dem_old[name]
+            for pat, repl in renames:
+                d = re.sub(pat, repl, d)
+            target[name] = by_dem.get(d, name if d == dem_old[name] else d)
     bad = 0
     for name in old:
-        if name not in new:
-            print("MISSING  %s" % name)
+        if target[name] not in new:
+            print("MISSING  %s" % (name if target[name] == name else "%s (as %s)" % (name, target[name])))
             bad += 1
             continue
-        a, b = normalise(old[name][0]), normalise(new[name][0])
-        ra, rb = resources(old[name][1]), resources(new[name][1])
+        a, b = normalise(old[name][0]), normalise(new[target[name]][0])
+        ra, rb = resources(old[name][1]), resources(new[target[name]][1])
+        if target[name] != name:
+            name = "%s -> %s" % (name, target[name])
         if vector:
             a, b = vector_multiset(a), vector_multiset(b)
         if a == b and ra == rb:
@@ -90,14 +119,20 @@ def main(old_path, new_path, vector=False):
             bad += 1
             print("DIFFERS  %s (%d vs %d lines; resources %s vs %s)" % (name, len(a), len(b), ra, rb))
     for name in new:
-        if name not in old:
+        if name not in target.values():
             print("new      %s %s" % (name, resources(new[name][1])))
     print("%d of %d functions of %s identical in %s" % (len(old) - bad, len(old), old_path, new_path))
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if a != "--vector"]
+    args, renames = [a for a in sys.argv[1:] if a != "--vector"], []
+    while "--rename" in args:
+        i = args.index("--rename")
+        if i + 1 >= len(args) or "=" not in args[i + 1]:
+            raise SystemExit(__doc__)
+        renames.append(tuple(args[i + 1].split("=", 1)))
+        del args[i:i + 2]
     if len(args) != 2:
         raise SystemExit(__doc__)
-    sys.exit(main(args[0], args[1], vector="--vector" in sys.argv))
+    sys.exit(main(args[0], args[1], vector="--vector" in sys.argv, renames=renames))
