@@ -32,6 +32,12 @@ class Partials(C.Structure):
                 ("n_hc", C.c_int), ("n_cols", C.c_int)]
 
 
+class CountPlan(C.Structure):
+    """struct fosphor_amd_count_plan"""
+    _fields_ = [("chunk", C.c_int), ("cpb", C.c_int), ("handoff", C.c_int), ("two_sets", C.c_int), ("rowmask", C.c_int),
+                ("table", C.c_int), ("merge_form", C.c_int), ("table_in_memory", C.c_int)]
+
+
 class Channel(C.Structure):
     _fields_ = [("enabled", C.c_int), ("center", C.c_float), ("width", C.c_float)]
 
@@ -133,6 +139,7 @@ SIGNATURES = {
     "fosphor_amd_upload_stream": (C.c_void_p, [C.c_void_p]),
     "fosphor_amd_tune_placement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "fosphor_amd_plan_piece_batches": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong]),
+    "fosphor_amd_plan_count": (C.c_int, [C.c_int] * 8 + [C.POINTER(CountPlan)]),
     "fosphor_amd_share_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "fosphor_amd_launch_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "fosphor_amd_merge_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 11)]),

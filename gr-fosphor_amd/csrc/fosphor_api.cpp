@@ -12,6 +12,7 @@
 #include <assert.h>
 #include <errno.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -52,6 +53,53 @@ static const int kSubSamplesLog2 = 26;	/* default sub-launch: 64 Mi samples (64 
 
 static const int kRiseMax = 8192;	/* largest batch served by the rise/decay table */
 
+/* An event that may not have been recorded yet: the work queued on one stream that work on another must follow.  Nothing waits
+ * for a fence that was never recorded (or that was forgotten: `recorded = 0`). */
+struct Fence
+{
+	hipEvent_t  ev;
+	int         recorded;
+	hipStream_t stream;			/* the stream it was last recorded on */
+
+	hipError_t create(unsigned flags) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }	/* (no-op when it exists) */
+	/* behind everything queued on st so far */
+	hipError_t record(hipStream_t st)
+	{
+		const hipError_t e = hipEventRecord(ev, st);
+		if (e == hipSuccess) { recorded = 1; stream = st; }
+		return e;
+	}
+	/* what is queued on st next follows the record; unless_same: not when st is the stream of the record (stream order does it) */
+	hipError_t wait(hipStream_t st, bool unless_same = false) const
+	{
+		if (!recorded || (unless_same && stream == st))
+			return hipSuccess;
+		return hipStreamWaitEvent(st, ev, 0);
+	}
+};
+
+/* Every fence of an instance (nothing but Fence members: fosphor_amd_init and fosphor_release walk them as an array) */
+struct Fences
+{
+	/* made by fosphor_amd_init, with dep_event_flags() */
+	Fence wf[2];				/* last K1 that stored rows into ring b */
+	Fence in;				/* what the caller queued on `stream` before a call, for the other FFT streams */
+	Fence k1_done[kSets];			/* K1 wrote set pp */
+	Fence set_free[kSets];			/* K2 finished reading set pp */
+	Fence k2_done[2];			/* K2 wrote hit-count set h */
+	Fence h_free[2];			/* K3 finished reading hit-count set h */
+	Fence k3_done;				/* orders K3s that are issued on different streams */
+	Fence tail;				/* N = 8192: behind the merge kernel of the last launch (is there a tail to share the chip with?) */
+	/* made with the stream or the staging slot they belong to */
+	Fence k1s_done[kMaxK1Streams];
+	Fence stage_free[2];
+	Fence upload_slot[2];			/* upload into d_stage[k] done: the instance's stream waits for it before the FFT kernel */
+	Fence upload_done;			/* H2D of the last fosphor_amd_process_pinned */
+};
+static const int kInitFences = offsetof(Fences, k1s_done) / sizeof(Fence);
+static const int kFences = sizeof(Fences) / sizeof(Fence);
+static_assert(sizeof(Fences) == kFences * sizeof(Fence) && offsetof(Fences, upload_done) == (kFences - 1) * sizeof(Fence), "Fences is an array of Fence");
+
 struct fosphor
 {
 	/* geometry / constants */
@@ -82,9 +130,7 @@ struct fosphor
 	float    *d_wf_pp[2], *d_hist;		/* two waterfall rings: a call that rewrites every row targets the other one,
 						 * so its K1s need not wait for the previous call's (see run()) */
 	int       wf_cur;			/* ring the results are in */
-	hipEvent_t ev_wf[2];			/* last K1 that stored rows into ring b */
-	int       wf_used[2];
-	hipStream_t wf_stream[2];
+	Fences    f;
 	float2   *d_spectrum;
 	uint32_t *d_bins_pp[kSets];		/* rotating sets: K1 of launch i+1 overlaps K2/K3 of launch i */
 	float2   *d_partial_pp[kSets];
@@ -95,27 +141,16 @@ struct fosphor
 						 * n_k1_streams of them: the next K1s are already queued when work-groups of the current one exit */
 	int       n_sets;			/* intermediate sets in use (3, <= kSets) */
 	int       n_k1_streams;			/* FOSPHOR_AMD_K1_STREAMS (default 2) */
-	hipEvent_t ev_k1s_done[kMaxK1Streams];
 	int       alt;				/* FOSPHOR_AMD_ALT=0 keeps every K1 on `stream` */
 	int       k1_seq;
 	int       relaxed;			/* fosphor_amd_set_input_ordering(self, 0) */
-	hipEvent_t ev_in;
 	long long sub_samples;			/* samples per sub-launch of a device-resident call */
 	hipStream_t stream2;			/* K2 (and K3 unless pipe3) of the multi-batch path */
 	hipStream_t stream3;			/* K3 of the multi-batch path: K3 of launch i beside K2 of launch i+1 */
 	int       pipe3;			/* FOSPHOR_AMD_PIPE3=0 keeps K3 on stream2 */
 	int       hset;				/* hit-count / live-sum set of the next launch (two, like the bin sets) */
-	int       hset_used[2];
-	hipEvent_t ev_k2_done[2];		/* K2 wrote hit-count set h */
-	hipEvent_t ev_h_free[2];		/* K3 finished reading hit-count set h */
-	hipEvent_t ev_k3_done;			/* orders K3s that are issued on different streams */
-	hipEvent_t ev_tail;			/* N = 8192: behind the merge kernel of the last launch (is there a tail to share the chip with?) */
-	int       tail_set;
 	hipStream_t last_k3_stream;
 	hipStream_t k2_stream_last;		/* stream of the most recent count kernel */
-	hipEvent_t ev_k1_done[kSets];		/* K1 wrote set pp */
-	hipEvent_t ev_set_free[kSets];		/* K2 finished reading set pp */
-	int       set_used[kSets];
 	int       overlap;			/* 1: two-stream pipeline for process paths */
 	int       k1_variant;			/* FOSPHOR_AMD_K1: 1 (default) = wave per spectrum, 2 = two waves per spectrum (what odd hops use) */
 	/* tuning / test knobs, read from the environment ONCE, at init (nothing on the submit path calls getenv) */
@@ -145,7 +180,7 @@ struct fosphor
 	int       hot_valid;			/* 0 after anything but the 16-bit K3 wrote the histogram */
 	uint16_t *d_slab16;			/* per-chunk packed 16-bit count slabs of batches longer than 1024 spectra / of a shard */
 	int       slab_chunks;			/* capacity of d_slab16 in 1024-spectrum chunks */
-	int       last_hc16;
+	const uint32_t *hc_view;		/* the hit counts of the last batch merged, as fosphor_amd_get_buffers shows them */
 	float    *d_live_sum, *d_vmax;
 	float    *d_chunk_sum, *d_chunk_max;	/* [max_spectra/16][N] */
 	long long *d_dbg;			/* K1_TIMING builds only (FOSPHOR_AMD_K1_TIMING=1) */
@@ -157,19 +192,14 @@ struct fosphor
 	float     rise_t0r, rise_t0d;
 	int       slot;				/* partial-array slot used by accumulate/merge */
 	float2   *d_scratch;			/* N = 65536: [max_spectra][N] spectrum between the two FFT stages */
-	int       k1h_fused;			/* N = 65536: both levels of the plan in one kernel, the intermediate in the XCDs' L2 (always 1 since round 4) */
-	uint32_t *d_k1h_sync;			/* its cluster counters */
+	uint32_t *d_k1h_sync;			/* N = 65536 (both levels of the plan in one kernel, the intermediate in the XCDs' L2): its cluster counters */
 	uint32_t *h_k1h_err;			/* ... and its error word (host memory the kernel writes: work-groups of a cluster on different XCDs) */
 
 	/* host->device staging for fosphor_process (pinned ring of 2) */
 	float2   *h_stage[2];
 	float2   *d_stage[2];
-	hipEvent_t stage_free[2];
-	hipEvent_t upload_done;			/* H2D of the last fosphor_amd_process_pinned */
-	hipStream_t copy_stream;		/* ... queued here, so that the upload of one batch runs beside the kernels of the batch before
-						 * (created by the first fosphor_amd_process_pinned) */
-	hipEvent_t upload_slot[2];		/* upload into d_stage[k] done: the instance's stream waits for it before the FFT kernel */
-	int       stage_used[2];
+	hipStream_t copy_stream;		/* the H2D of fosphor_amd_process_pinned is queued here, so that the upload of one batch runs beside
+						 * the kernels of the batch before (created by the first fosphor_amd_process_pinned) */
 	size_t    d_stage_cap[2];		/* samples d_stage[k] holds */
 	int       pend_slot[2], pend_len[2], pend_head, pend_n;	/* uploads queued by fosphor_amd_upload_pinned, kernels not yet */
 	int       stage_idx;
@@ -179,11 +209,15 @@ struct fosphor
 	/* state */
 	int state;
 	int wf_pos;
-	int last_batches;			/* batches in the most recent launch (hitcount view) */
-	int last_slot0;
 
-	/* the rise/decay table serves batches up to kRiseMax (K3's 16-bit path needs it) */
-	bool rise_ok(int batch) const { return batch <= 8192; }
+	/* where a launch's count hand-off lives */
+	size_t cells() const { return (size_t)n_bins * n; }
+	uint32_t *hc_slot(int slot) const { return d_hc + (size_t)slot * cells(); }				/* 32-bit counts of one batch */
+	uint16_t *hc16_set(int hset) const { return (uint16_t *)d_hc + (size_t)hset * max_batches * cells(); }	/* 16-bit counts of a launch */
+	int       live_slot(int slot, int hset) const { return slot + hset * max_batches; }			/* live-sum / max slot ... */
+	float    *live_sum_at(int lslot) const { return d_live_sum + (size_t)lslot * n; }			/* ... and its arrays */
+	float    *vmax_at(int lslot) const { return d_vmax + (size_t)lslot * n; }
+	uint32_t *rowmask_set(int hset) const { return d_rowmask + (size_t)hset * max_batches * (n / 64) * mask_words; }
 
 	/* profiling */
 	int prof;				/* 0 off, 1 every kernel, 2 K1 only (fewer events beside K2/K3) */
@@ -367,27 +401,16 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_win); (void)hipFree(self->d_tw); (void)hipFree(self->d_thr);
 	(void)hipFree(self->d_wf_pp[0]); (void)hipFree(self->d_wf_pp[1]);
 	(void)hipFree(self->d_hist); (void)hipFree(self->d_spectrum);
-	for (int i = 0; i < 2; i++)
-		if (self->ev_wf[i]) (void)hipEventDestroy(self->ev_wf[i]);
-	if (self->ev_in) (void)hipEventDestroy(self->ev_in);
-	for (int i = 1; i < kMaxK1Streams; i++) {
+	for (int i = 1; i < kMaxK1Streams; i++)
 		if (self->k1_streams[i]) { (void)hipStreamSynchronize(self->k1_streams[i]); (void)hipStreamDestroy(self->k1_streams[i]); }
-		if (self->ev_k1s_done[i]) (void)hipEventDestroy(self->ev_k1s_done[i]);
-	}
 	for (int i = 0; i < kSets; i++) {
 		(void)hipFree(self->d_bins_pp[i]); (void)hipFree(self->d_partial_pp[i]);
-		if (self->ev_k1_done[i]) (void)hipEventDestroy(self->ev_k1_done[i]);
-		if (self->ev_set_free[i]) (void)hipEventDestroy(self->ev_set_free[i]);
 	}
 	if (self->copy_stream) { (void)hipStreamSynchronize(self->copy_stream); (void)hipStreamDestroy(self->copy_stream); }
 	if (self->stream2) { (void)hipStreamSynchronize(self->stream2); (void)hipStreamDestroy(self->stream2); }
 	if (self->stream3) { (void)hipStreamSynchronize(self->stream3); (void)hipStreamDestroy(self->stream3); }
-	for (int i = 0; i < 2; i++) {
-		if (self->ev_k2_done[i]) (void)hipEventDestroy(self->ev_k2_done[i]);
-		if (self->ev_h_free[i]) (void)hipEventDestroy(self->ev_h_free[i]);
-	}
-	if (self->ev_k3_done) (void)hipEventDestroy(self->ev_k3_done);
-	if (self->ev_tail) (void)hipEventDestroy(self->ev_tail);
+	for (Fence *f = (Fence *)&self->f; f < (Fence *)&self->f + kFences; f++)
+		if (f->ev) (void)hipEventDestroy(f->ev);
 	(void)hipFree(self->d_hc); (void)hipFree(self->d_hc_export); (void)hipFree(self->d_slab16);
 	(void)hipFree(self->d_rowmask); (void)hipFree(self->d_hot); (void)hipFree(self->d_rowlist);
 	(void)hipFree(self->d_live_sum); (void)hipFree(self->d_vmax);
@@ -402,11 +425,7 @@ extern "C" void fosphor_release(struct fosphor *self)
 	for (int i = 0; i < 2; i++) {
 		if (self->h_stage[i]) (void)hipHostFree(self->h_stage[i]);
 		if (self->d_stage[i]) (void)hipFree(self->d_stage[i]);
-		if (self->stage_free[i]) (void)hipEventDestroy(self->stage_free[i]);
 	}
-	if (self->upload_done) (void)hipEventDestroy(self->upload_done);
-	for (int i = 0; i < 2; i++)
-		if (self->upload_slot[i]) (void)hipEventDestroy(self->upload_slot[i]);
 	if (self->h_thr) (void)hipHostFree(self->h_thr);
 	if (self->h_win) (void)hipHostFree(self->h_win);
 	for (hipEvent_t e : self->ev_pool) (void)hipEventDestroy(e);
@@ -511,9 +530,9 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 	HIP_TRY(hipMalloc((void **)&self->d_thr, sizeof(double) * (self->n_bins + 1)), "alloc thresholds");
 	for (int i = 0; i < 2; i++) {
 		HIP_TRY(alloc_output((void **)&self->d_wf_pp[i], sizeof(float) * (size_t)self->wf_rows * self->n, self->log2n == 16), "alloc waterfall");
-		HIP_TRY(hipEventCreateWithFlags(&self->ev_wf[i], dep_event_flags()), "create event");
 	}
-	HIP_TRY(hipEventCreateWithFlags(&self->ev_in, dep_event_flags()), "create event");
+	for (Fence *f = (Fence *)&self->f; f < (Fence *)&self->f + kInitFences; f++)
+		HIP_TRY(f->create(dep_event_flags()), "create event");
 	/* Only the streams in use are created: the runtime spreads streams over a few hardware queues (4 unless
 	 * GPU_MAX_HW_QUEUES says otherwise) and two streams that share one do not overlap. */
 	{
@@ -523,22 +542,19 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 	self->k1_streams[0] = self->stream;
 	for (int i = 1; i < self->n_k1_streams; i++) {
 		HIP_TRY(hipStreamCreateWithFlags(&self->k1_streams[i], hipStreamNonBlocking), "hipStreamCreate (FFT stream)");
-		HIP_TRY(hipEventCreateWithFlags(&self->ev_k1s_done[i], dep_event_flags()), "create event");
+		HIP_TRY(self->f.k1s_done[i].create(dep_event_flags()), "create event");
 	}
 	HIP_TRY(hipMalloc((void **)&self->d_hist, sizeof(float) * (size_t)self->n_bins * self->n), "alloc histogram");
 	HIP_TRY(hipMalloc((void **)&self->d_spectrum, sizeof(float2) * 2 * self->n), "alloc spectrum");
 	for (int i = 0; i < kSets; i++) {
 		HIP_TRY(alloc_output((void **)&self->d_bins_pp[i], (size_t)self->max_spectra * self->n * (self->bins16 ? 2 : 1), self->log2n == 16), "alloc bin indices");
 		HIP_TRY(hipMalloc((void **)&self->d_partial_pp[i], sizeof(float2) * tiles_max * self->n), "alloc partials");
-		HIP_TRY(hipEventCreateWithFlags(&self->ev_k1_done[i], dep_event_flags()), "create event");
-		HIP_TRY(hipEventCreateWithFlags(&self->ev_set_free[i], dep_event_flags()), "create event");
 	}
 	self->d_bins = self->d_bins_pp[0];
 	self->d_partial = self->d_partial_pp[0];
 	if (self->log2n == 16) {
 		/* One FFT kernel takes a spectrum through both 256-point levels of the radix-16 plan, the intermediate staying in the
 		 * XCD's L2 (DESIGN.md sections 4-5; DESIGN_HISTORY.md section 8; the two-kernel form of rounds 1-3 went with the radix-8 plan in round 4). */
-		self->k1h_fused = 1;
 		/* 512 KiB of intermediate per cluster, at most 8 clusters on each of the 8 XCDs */
 		HIP_TRY(hipMalloc((void **)&self->d_scratch, sizeof(float2) * (size_t)64 * self->n), "alloc cluster intermediates");
 		HIP_TRY(hipMalloc((void **)&self->d_k1h_sync, sizeof(uint32_t) * 64 * 64), "alloc cluster counters");
@@ -550,12 +566,6 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 	self->stage_samples = (size_t)self->n * (self->max_spectra < 1024 ? self->max_spectra : 1024);
 	HIP_TRY(hipStreamCreateWithFlags(&self->stream2, hipStreamNonBlocking), "hipStreamCreate (count stream)");
 	HIP_TRY(hipStreamCreateWithFlags(&self->stream3, hipStreamNonBlocking), "hipStreamCreate (merge stream)");
-	for (int i = 0; i < 2; i++) {
-		HIP_TRY(hipEventCreateWithFlags(&self->ev_k2_done[i], dep_event_flags()), "create event");
-		HIP_TRY(hipEventCreateWithFlags(&self->ev_h_free[i], dep_event_flags()), "create event");
-	}
-	HIP_TRY(hipEventCreateWithFlags(&self->ev_k3_done, dep_event_flags()), "create event");
-	HIP_TRY(hipEventCreateWithFlags(&self->ev_tail, dep_event_flags()), "create event");
 	if (getenv("FOSPHOR_AMD_K1_TIMING")) {
 		HIP_TRY(hipMalloc((void **)&self->d_dbg, sizeof(long long) * 16 * 4 * kK1MaxBlocks), "alloc timing buffer");
 		HIP_TRY(hipMemset(self->d_dbg, 0, sizeof(long long) * 16 * 4 * kK1MaxBlocks), "clear timing buffer");
@@ -604,6 +614,7 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 	HIP_TRY(hipMemset(self->d_rowlist, 0, sizeof(uint32_t) * (2 + (size_t)(self->n / 64) * self->n_bins)), "clear row list");
 	self->rowlist_flip = 0;
 	self->hot_valid = 0;
+	self->hc_view = self->d_hc;
 	if (self->max_spectra > 1024) {
 		/* one slab per 1024-spectrum chunk of the largest launch: a whole shard (accumulate) or a sub-launch */
 		self->slab_chunks = self->max_spectra / 1024;
@@ -619,7 +630,6 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 	HIP_TRY(hipHostMalloc((void **)&self->h_thr, sizeof(double) * (self->n_bins + 1), hipHostMallocDefault), "alloc pinned thr");
 	HIP_TRY(hipHostMalloc((void **)&self->h_win, sizeof(float) * self->n, hipHostMallocDefault), "alloc pinned win");
 
-	self->tw_len = build_twiddles(NULL, self->log2n, NULL);
 	tw.resize(self->tw_len);
 	build_twiddles(tw.data(), self->log2n, self->tw_off);
 	HIP_TRY(hipMemcpy(self->d_tw, tw.data(), sizeof(float2) * self->tw_len, hipMemcpyHostToDevice), "upload twiddles");
@@ -742,8 +752,7 @@ static int sync_all(struct fosphor *self)
 static int k3_stream_enter(struct fosphor *self, hipStream_t st)
 {
 	if (self->last_k3_stream && self->last_k3_stream != st) {
-		if (hipEventRecord(self->ev_k3_done, self->last_k3_stream) != hipSuccess ||
-		    hipStreamWaitEvent(st, self->ev_k3_done, 0) != hipSuccess)
+		if (self->f.k3_done.record(self->last_k3_stream) != hipSuccess || self->f.k3_done.wait(st) != hipSuccess)
 			return -EIO;
 	}
 	self->last_k3_stream = st;
@@ -755,11 +764,9 @@ static int k3_stream_enter(struct fosphor *self, hipStream_t st)
 static int drain_h_sets(struct fosphor *self, hipStream_t st)
 {
 	for (int h = 0; h < 2; h++) {
-		if (self->hset_used[h]) {
-			if (hipStreamWaitEvent(st, self->ev_h_free[h], 0) != hipSuccess)
-				return -EIO;
-			self->hset_used[h] = 0;
-		}
+		if (self->f.h_free[h].wait(st) != hipSuccess)
+			return -EIO;
+		self->f.h_free[h].recorded = 0;
 	}
 	return 0;
 }
@@ -804,7 +811,7 @@ static int pick_tile(const struct fosphor *self, int total, int batch)
 	const int v = self->kn_tile;
 	if (v >= (self->log2n == 13 ? 8 : 4) && v <= (self->log2n == 16 ? 32 : 128) && !(v & (v - 1)) && batch % v == 0 && total % v == 0)
 		return v;
-	if (self->log2n == 16 && self->k1h_fused) {
+	if (self->log2n == 16) {
 		/* a cluster owns whole tiles: the largest tile that still gives each of the 32 clusters one (at most 32 spectra: the
 		 * 9th bits of a tile's bin indices share one dword per column) */
 		for (int t = 32; t >= 8; t >>= 1)
@@ -876,7 +883,7 @@ static void fill_k1(struct fosphor *self, K1Params *k1, const void *d_iq, int to
 	k1->w = 1.0f - self->alpha;		/* display.cl:99 */
 	k1->variant = (self->log2n == 10 && !self->bins16) ? self->k1_variant : (self->log2n == 16 ? 4 : 3);
 	k1->scratch = self->d_scratch;
-	k1->sync = (self->log2n == 16 && self->k1h_fused) ? self->d_k1h_sync : NULL;
+	k1->sync = (self->log2n == 16) ? self->d_k1h_sync : NULL;
 	k1->sync_err = self->h_k1h_err;
 	k1->iq_format = self->iq_format;
 	k1->n_cus = self->n_cus;
@@ -886,30 +893,13 @@ static void fill_k1(struct fosphor *self, K1Params *k1, const void *d_iq, int to
 		/* ... when there is a tail to share with: the count / merge kernels of the launch before this one are still queued or running
 		 * (calls issued back to back).  A launch that finds the chip idle takes all of it.  (The choice depends on timing; the results
 		 * do not: the tile loop is grid-stride.  fosphor_amd_share_stats reports how many launches took which form.) */
-		if (k1->cus && !(self->tail_set && hipEventQuery(self->ev_tail) == hipErrorNotReady))
+		if (k1->cus && !(self->f.tail.recorded && hipEventQuery(self->f.tail.ev) == hipErrorNotReady))
 			k1->cus = 0;
 	}
 	if (k1->variant == 1 && (k1->hop & 1))
 		k1->variant = 2;		/* 16-byte IQ loads of variant 1 need an even hop */
 	if (k1->variant == 1 && self->iq_format == FOSPHOR_AMD_IQ_SC16 && ((uintptr_t)d_iq & 7))
 		k1->variant = 2;		/* ... and its 8-byte sc16 loads an 8-byte aligned start (variant 2 loads one 4-byte sample per lane) */
-}
-
-/* A batch longer than 1024 spectra is counted as ONE chunk where that still gives the chip enough work-groups
- * (N/64 slabs per batch) and the (d, e) table covers it: the 16-bit packed counters hold up to 65535 spectra, and K3
- * then reads slab-major 16-bit counts (0.5 B per cell) instead of 32-bit sums of per-chunk slabs. */
-static int count_one_chunk(const struct fosphor *self, int batch, int n_batches)
-{
-	return batch > 1024 && batch <= kRiseMax && (self->n / 64) * n_batches >= 128;
-}
-
-/* Sparse K2 -> K3 hand-off (row masks + hot flags) for the large state of N = 65536 (128 MiB, one batch = one frame: +10 % for
- * the path).  At N = 1024 / 8192 it measured slower (K3 there is bound by its dependent chain over the batches of a launch,
- * not by the rows it touches: -1 % / -2.5 %) and is not offered.  FOSPHOR_AMD_ROWMASK=0 selects the dense form at N = 65536
- * (the tests run both). */
-static int use_rowmask(const struct fosphor *self)
-{
-	return self->log2n == 16 && !self->kn_rowmask_off;
 }
 
 static int gcd_int(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
@@ -935,6 +925,59 @@ extern "C" int fosphor_amd_plan_piece_batches(int log2n, int overlap, int n_batc
 	return sub_b;
 }
 
+/* The count hand-off of one launch: which buffer the count kernel fills and the merge kernel reads, for n_batches batches of
+ * `batch` spectra on an instance of 2^log2n columns, n_bins bins and room for slab_chunks 1024-spectrum count slabs.  pipelined: the
+ * process paths (run()), whose launches hand 16-bit counts from kernel to kernel where they can; else the partial arrays of
+ * accumulate / merge, 32-bit because they are exchanged.  Every launch site takes its decisions from here and nowhere else.  Pure
+ * host arithmetic, exported for the CPU test suite as fosphor_amd_plan_count (include/fosphor_amd.h). */
+static struct fosphor_amd_count_plan plan_count(int log2n, int n_bins, int slab_chunks, int rowmask_off, int no_sum16,
+                                                int n_batches, int batch, int pipelined)
+{
+	struct fosphor_amd_count_plan p;
+	const int n = 1 << log2n;
+	/* the rise/decay table serves batches up to kRiseMax (K3's 16-bit path needs it) */
+	p.table = batch <= kRiseMax;
+	/* A batch longer than 1024 spectra is counted as ONE chunk where that still gives the chip enough work-groups
+	 * (N/64 slabs per batch) and the (d, e) table covers it: the 16-bit packed counters hold up to 65535 spectra, and K3
+	 * then reads slab-major 16-bit counts (0.5 B per cell) instead of 32-bit sums of per-chunk slabs. */
+	const int count_one_chunk = pipelined && batch > 1024 && p.table && (n / 64) * n_batches >= 128;
+	const int direct16 = pipelined && (batch <= 1024 || count_one_chunk);
+	p.chunk = (batch <= 1024 || count_one_chunk) ? batch : gcd_int(batch, 1024);
+	p.cpb = batch / p.chunk;
+	/* Batches of several 1024-spectrum chunks (a batch longer than the reference's cap, or the time shard of
+	 * a display frame): K2 leaves per-chunk packed 16-bit slabs in d_slab16 (no zeroing, no global atomics)
+	 * and k2c_sum adds each batch's slabs into its 32-bit array.  Needs whole chunks and room for the slabs. */
+	const int sum16 = p.chunk == 1024 && p.cpb > 1 && n_batches * p.cpb <= slab_chunks && !no_sum16;
+	p.handoff = direct16 ? FOSPHOR_AMD_COUNT_DIRECT16 : sum16 ? FOSPHOR_AMD_COUNT_SUM16 : FOSPHOR_AMD_COUNT_32;
+	/* only batches up to the reference's cap alternate between two sets of 16-bit counts (the merge of one launch beside the count of the next) */
+	p.two_sets = direct16 && !count_one_chunk;
+	/* Sparse K2 -> K3 hand-off (row masks + hot flags) for the large state of N = 65536 (128 MiB, one batch = one frame: +10 % for
+	 * the path).  At N = 1024 / 8192 it measured slower (K3 there is bound by its dependent chain over the batches of a launch,
+	 * not by the rows it touches: -1 % / -2.5 %) and is not offered.  FOSPHOR_AMD_ROWMASK=0 selects the dense form at N = 65536
+	 * (the tests run both). */
+	p.rowmask = direct16 && log2n == 16 && !rowmask_off;
+	const K3Shape shape = { direct16 != 0, p.rowmask != 0, p.table != 0, n_batches, batch, n_bins, n };
+	p.merge_form = k3_form(shape);
+	p.table_in_memory = p.merge_form == K3_SPARSE16_LONG ||
+	                    ((p.merge_form == K3_DENSE16_LONG4 || p.merge_form == K3_DENSE16_LONG) && batch >= kK3RiseLdsLong);
+	return p;
+}
+
+extern "C" int fosphor_amd_plan_count(int log2n, int n_bins, int slab_chunks, int rowmask_off, int no_sum16,
+                                      int n_batches, int batch, int pipelined, struct fosphor_amd_count_plan *out)
+{
+	if (!out || n_batches < 1 || batch < 1 || log2n < 1 || log2n > 30 || n_bins < 1 || slab_chunks < 0)
+		return -EINVAL;
+	*out = plan_count(log2n, n_bins, slab_chunks, rowmask_off != 0, no_sum16 != 0, n_batches, batch, pipelined != 0);
+	return 0;
+}
+
+/* ... of a launch of this instance */
+static struct fosphor_amd_count_plan plan_count(const struct fosphor *self, int n_batches, int batch, int pipelined)
+{
+	return plan_count(self->log2n, self->n_bins, self->slab_chunks, self->kn_rowmask_off, self->kn_no_sum16, n_batches, batch, pipelined);
+}
+
 /* The count-kernel fields every K2 launch sets alike: `total` spectra of the current set's bin indices / tile partials in batches of
  * `batch`, counted `chunk` spectra per work-group; the first of them is spectrum t_offset of a batch of weight_batch (live-sum weights) */
 static void fill_k2(const struct fosphor *self, K2Params *k2, int total, int batch, int chunk, int tile, int t_offset, int weight_batch)
@@ -956,55 +999,48 @@ static hipError_t launch_chunk_sum(struct fosphor *self, int n_batches, int cpb,
 	K2bParams k2b;
 	memset(&k2b, 0, sizeof(k2b));
 	k2b.chunk_sum = self->d_chunk_sum; k2b.chunk_max = self->d_chunk_max;
-	k2b.live_sum = self->d_live_sum + (size_t)lslot * self->n;
-	k2b.vmax = self->d_vmax + (size_t)lslot * self->n;
+	k2b.live_sum = self->live_sum_at(lslot);
+	k2b.vmax = self->vmax_at(lslot);
 	k2b.n_batches = n_batches; k2b.cpb = cpb; k2b.n = self->n;
 	if (!sum16) {
 		self->n_k2b++;
 		return launch_k2b(k2b, st);
 	}
-	k2b.hc16 = self->d_slab16; k2b.hc = self->d_hc + (size_t)slot0 * self->n_bins * self->n; k2b.n_bins = self->n_bins;
+	k2b.hc16 = self->d_slab16; k2b.hc = self->hc_slot(slot0); k2b.n_bins = self->n_bins;
 	self->n_k2c++;
 	return launch_k2c(k2b, st);
 }
 
 /* K2 (+K2b) for n_batches batches of `batch` spectra whose bin indices / tile partials are in
- * d_bins / d_partial; results land in slot `slot0`.. of hc / live_sum / vmax. */
-static int run_count(struct fosphor *self, int n_batches, int batch, int tile, int slot0,
-                     int t_offset, int weight_batch, hipStream_t st, int use16 = 0, int hset = 0)
+ * d_bins / d_partial, handed off as `plan` says; results land in slot `slot0`.. of hc / live_sum / vmax (pipelined launches: of
+ * hit-count set hset). */
+static int run_count(struct fosphor *self, const struct fosphor_amd_count_plan &plan, int n_batches, int batch, int tile, int slot0,
+                     int hset, int t_offset, int weight_batch, hipStream_t st)
 {
 	K2Params k2;
-	const int one_chunk = use16 && count_one_chunk(self, batch, n_batches);
-	const int chunk = (batch <= 1024 || one_chunk) ? batch : gcd_int(batch, 1024);
-	const int cpb = batch / chunk;
-	const size_t cells = (size_t)self->n_bins * self->n;
+	const int cpb = plan.cpb;
+	const int sum16 = plan.handoff == FOSPHOR_AMD_COUNT_SUM16;
+	const int lslot = self->live_slot(slot0, hset);
 
-	/* Batches of several 1024-spectrum chunks (a batch longer than the reference's cap, or the time shard of
-	 * a display frame): K2 leaves per-chunk packed 16-bit slabs in d_slab16 (no zeroing, no global atomics)
-	 * and k2c_sum adds each batch's slabs into its 32-bit array.  Needs whole chunks and room for the slabs. */
-	const int sum16 = (!use16 || batch > 1024) && chunk == 1024 && cpb > 1 && self->d_slab16 &&
-	                  n_batches * cpb <= self->slab_chunks && !self->kn_no_sum16;
-
-	fill_k2(self, &k2, n_batches * batch, batch, chunk, tile, t_offset, weight_batch);
-	k2.hc = self->d_hc + (size_t)slot0 * cells;
-	k2.hc16 = (use16 && (batch <= 1024 || one_chunk) && self->rise_ok(batch))
-	          ? (uint16_t *)self->d_hc + (size_t)hset * self->max_batches * cells : NULL;
-	if (k2.hc16 && use_rowmask(self)) {
-		k2.rowmask = self->d_rowmask + (size_t)hset * self->max_batches * (self->n / 64) * self->mask_words;
+	fill_k2(self, &k2, n_batches * batch, batch, plan.chunk, tile, t_offset, weight_batch);
+	k2.hc = self->hc_slot(slot0);
+	if (plan.handoff == FOSPHOR_AMD_COUNT_DIRECT16)
+		k2.hc16 = self->hc16_set(hset);
+	if (plan.rowmask) {
+		k2.rowmask = self->rowmask_set(hset);
 		k2.mask_words = self->mask_words;
 		k2.mask_stride = self->max_batches;
 	}
 	if (sum16)
-		k2.hc16 = self->d_slab16, k2.rowmask = NULL;
-	const int lslot = slot0 + hset * self->max_batches;	/* live-sum / max slot */
+		k2.hc16 = self->d_slab16;
 	if (cpb == 1) {
-		k2.chunk_sum = self->d_live_sum + (size_t)lslot * self->n;
-		k2.chunk_max = self->d_vmax + (size_t)lslot * self->n;
+		k2.chunk_sum = self->live_sum_at(lslot);
+		k2.chunk_max = self->vmax_at(lslot);
 	} else {
 		k2.chunk_sum = self->d_chunk_sum;
 		k2.chunk_max = self->d_chunk_max;
 		if (!sum16)
-			HIP_TRY(hipMemsetAsync(k2.hc, 0, sizeof(uint32_t) * cells * n_batches, st), "zero hit counts");
+			HIP_TRY(hipMemsetAsync(k2.hc, 0, sizeof(uint32_t) * self->cells() * n_batches, st), "zero hit counts");
 	}
 	prof_begin(self, 1, st);
 	HIP_TRY(launch_k2(k2, n_batches * cpb, st), "launch count");
@@ -1021,8 +1057,6 @@ error:
  * expressions as the kernel source, powf from the host libm (the oracle's binding). */
 static int ensure_rise_table(struct fosphor *self, int batch, hipStream_t st)
 {
-	if (batch > kRiseMax)
-		return 0;
 	if (self->rise_batch == batch && self->rise_t0r == self->t0r && self->rise_t0d == self->t0d)
 		return 1;
 	if (sync_all(self))				/* h_rise may be in flight */
@@ -1041,32 +1075,28 @@ static int ensure_rise_table(struct fosphor *self, int batch, hipStream_t st)
 	return 1;
 }
 
-static int run_merge(struct fosphor *self, int n_batches, int batch, int slot0, hipStream_t st, int use16 = 0, int hset = 0,
-                     int cell_begin = 0, int cell_end = 0)
+static int run_merge(struct fosphor *self, const struct fosphor_amd_count_plan &plan, int n_batches, int batch, int slot0, int hset,
+                     hipStream_t st, int cell_begin = 0, int cell_end = 0)
 {
 	K3Params k3;
-	const size_t cells = (size_t)self->n_bins * self->n;
-	const int lslot = slot0 + hset * self->max_batches;
-	const int have_table = ensure_rise_table(self, batch, st);
-	if (have_table < 0 || k3_stream_enter(self, st))
+	const int lslot = self->live_slot(slot0, hset);
+	if ((plan.table && ensure_rise_table(self, batch, st) < 0) || k3_stream_enter(self, st))
 		return -EIO;
 	memset(&k3, 0, sizeof(k3));
-	k3.rise = have_table ? self->d_rise : NULL;
+	k3.rise = plan.table ? self->d_rise : NULL;
 	k3.live_decay = powf(1.0f - self->alpha, (float)batch);	/* display.cl:210 */
-	k3.hc = self->d_hc + (size_t)slot0 * cells;
-	const int one_chunk = use16 && count_one_chunk(self, batch, n_batches);
-	k3.hc16 = (use16 && (batch <= 1024 || one_chunk) && have_table)
-	          ? (const uint16_t *)self->d_hc + (size_t)hset * self->max_batches * cells : NULL;
+	k3.hc = self->hc_slot(slot0);
 	k3.hc_export = self->d_hc_export;
-	if (k3.hc16) {
+	if (plan.handoff == FOSPHOR_AMD_COUNT_DIRECT16) {
 		/* the uint32 view of the last batch is made when somebody asks for it (fosphor_amd_get_buffers) */
-		const size_t per_batch = (size_t)(self->n / 64) * self->mask_words;
+		k3.hc16 = self->hc16_set(hset);
 		k3.hc_export = NULL;
-		self->export_src = k3.hc16 + (size_t)(n_batches - 1) * cells;
+		self->export_src = k3.hc16 + (size_t)(n_batches - 1) * self->cells();
 		self->export_mask = NULL;
 		self->export_stream = self->k2_stream_last ? self->k2_stream_last : st;
-		if (use_rowmask(self)) {
-			k3.rowmask = self->d_rowmask + (size_t)hset * self->max_batches * per_batch;
+		self->hc_view = self->d_hc_export;
+		if (plan.rowmask) {
+			k3.rowmask = self->rowmask_set(hset);
 			k3.mask_words = self->mask_words;
 			k3.mask_stride = self->max_batches;
 			self->export_mask = k3.rowmask + (n_batches - 1);
@@ -1084,9 +1114,10 @@ static int run_merge(struct fosphor *self, int n_batches, int batch, int slot0, 
 	} else {
 		self->export_src = NULL;
 		self->hot_valid = 0;
+		self->hc_view = self->hc_slot(slot0 + n_batches - 1);
 	}
-	k3.live_sum = self->d_live_sum + (size_t)lslot * self->n;
-	k3.vmax = self->d_vmax + (size_t)lslot * self->n;
+	k3.live_sum = self->live_sum_at(lslot);
+	k3.vmax = self->vmax_at(lslot);
 	k3.hist = self->d_hist; k3.spectrum = self->d_spectrum;
 	k3.n_batches = n_batches; k3.batch = batch; k3.n_bins = self->n_bins; k3.n = self->n;
 	k3.t0r = self->t0r; k3.t0d = self->t0d; k3.alpha = self->alpha;
@@ -1094,9 +1125,10 @@ static int run_merge(struct fosphor *self, int n_batches, int batch, int slot0, 
 	prof_begin(self, 2, st);
 	HIP_TRY(launch_k3(k3, st), "launch merge");
 	{
-		const K3Form form = k3_form(k3);
+		const int form = plan.merge_form;	/* (what launch_k3 launched: k3_form of the buffers filled in above) */
+		assert(form == k3_form(k3_shape(k3)));
 		self->k3_forms[form]++;
-		if (form == K3_SPARSE16_LONG || ((form == K3_DENSE16_LONG4 || form == K3_DENSE16_LONG) && batch >= kK3RiseLdsLong))
+		if (plan.table_in_memory)
 			self->k3_rise_mem++;
 		if ((form == K3_SPARSE16 || form == K3_SPARSE16_LONG) && n_batches > self->k3_sparse_max[form == K3_SPARSE16_LONG])
 			self->k3_sparse_max[form == K3_SPARSE16_LONG] = n_batches;
@@ -1110,10 +1142,10 @@ error:
 /* the other FFT streams see what the caller (and prepare()) queued on `stream` ... */
 static int k1_streams_fork(struct fosphor *self)
 {
-	if (hipEventRecord(self->ev_in, self->stream) != hipSuccess)
+	if (self->f.in.record(self->stream) != hipSuccess)
 		return -EIO;
 	for (int i = 1; i < self->n_k1_streams; i++)
-		if (hipStreamWaitEvent(self->k1_streams[i], self->ev_in, 0) != hipSuccess)
+		if (self->f.in.wait(self->k1_streams[i]) != hipSuccess)
 			return -EIO;
 	return 0;
 }
@@ -1122,29 +1154,8 @@ static int k1_streams_fork(struct fosphor *self)
 static int k1_streams_join(struct fosphor *self)
 {
 	for (int i = 1; i < self->n_k1_streams; i++)
-		if (hipEventRecord(self->ev_k1s_done[i], self->k1_streams[i]) != hipSuccess ||
-		    hipStreamWaitEvent(self->stream, self->ev_k1s_done[i], 0) != hipSuccess)
+		if (self->f.k1s_done[i].record(self->k1_streams[i]) != hipSuccess || self->f.k1s_done[i].wait(self->stream) != hipSuccess)
 			return -EIO;
-	return 0;
-}
-
-/* Waterfall ring ownership between K1s that may run on different streams: a K1 that stores rows into ring b
- * follows the previous K1 that did. */
-static int wf_enter(struct fosphor *self, hipStream_t ks)
-{
-	const int b = self->wf_cur;
-	if (self->wf_used[b] && self->wf_stream[b] != ks && hipStreamWaitEvent(ks, self->ev_wf[b], 0) != hipSuccess)
-		return -EIO;
-	return 0;
-}
-
-static int wf_leave(struct fosphor *self, hipStream_t ks)
-{
-	const int b = self->wf_cur;
-	if (hipEventRecord(self->ev_wf[b], ks) != hipSuccess)
-		return -EIO;
-	self->wf_used[b] = 1;
-	self->wf_stream[b] = ks;
 	return 0;
 }
 
@@ -1162,24 +1173,26 @@ static int k1_piece(struct fosphor *self, hipStream_t ks, const void *d_iq, int 
 	self->pp = (self->pp + 1) % self->n_sets;
 	self->d_bins = self->d_bins_pp[set];
 	self->d_partial = self->d_partial_pp[set];
-	if (self->overlap && self->set_used[set])
-		HIP_TRY(hipStreamWaitEvent(ks, self->ev_set_free[set], 0), "wait for intermediate set");
+	if (self->overlap)
+		HIP_TRY(self->f.set_free[set].wait(ks), "wait for intermediate set");
 	if (!stores_rows)
 		wf_first = sub_total;
 	fill_k1(self, &k1, d_iq, sub_total, tile, (self->wf_pos + t) & (self->wf_rows - 1), wf_first, hop);
-	if (stores_rows && wf_enter(self, ks))
-		return -1;
+	/* waterfall ring ownership between K1s that may run on different streams: a K1 that stores rows into ring b follows the
+	 * previous K1 that did (on its own stream it does anyway) */
+	if (stores_rows)
+		HIP_TRY(self->f.wf[self->wf_cur].wait(ks, true), "wait for the waterfall ring");
 	prof_begin(self, 0, ks);
 	HIP_TRY(launch_k1(k1, ks), "launch fft_bin");
 	prof_end(self, ks);
 	if (self->log2n == 13) {
 		if (k1.cus) self->k1w_shared++; else self->k1w_full++;
 	}
-	if (stores_rows && wf_leave(self, ks))
-		return -1;
+	if (stores_rows)
+		HIP_TRY(self->f.wf[self->wf_cur].record(ks), "record waterfall rows");
 	if (self->overlap) {
-		HIP_TRY(hipEventRecord(self->ev_k1_done[set], ks), "record K1 done");
-		HIP_TRY(hipStreamWaitEvent(count_stream(self), self->ev_k1_done[set], 0), "K2 waits for K1");
+		HIP_TRY(self->f.k1_done[set].record(ks), "record K1 done");
+		HIP_TRY(self->f.k1_done[set].wait(count_stream(self)), "K2 waits for K1");
 	}
 	return set;
 error:
@@ -1189,10 +1202,8 @@ error:
 /* ... behind the count kernel (queued on the count stream) that read intermediate set `set`: the set is free again */
 static int k1_set_release(struct fosphor *self, int set)
 {
-	if (self->overlap) {
-		HIP_TRY(hipEventRecord(self->ev_set_free[set], count_stream(self)), "record set free");
-		self->set_used[set] = 1;
-	}
+	if (self->overlap)
+		HIP_TRY(self->f.set_free[set].record(count_stream(self)), "record set free");
 	return 0;
 error:
 	return -EIO;
@@ -1206,9 +1217,6 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 	const size_t sample_bytes = self->sample_bytes;
 	const int hop_samples = hop ? hop : self->n;
 	hipStream_t st2 = count_stream(self);
-	/* third stream: only the 16-bit count path has a second hit-count set */
-	const int three = self->overlap && self->pipe3 && batch <= 1024 && self->rise_ok(batch);
-	hipStream_t st3 = three ? self->stream3 : st2;
 	const int did_prep = self->win_dirty || self->thr_dirty || self->state == ST_BOOTING;
 	int sub_b, n_sub, use_alt;
 
@@ -1226,7 +1234,7 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 	sub_b = fosphor_amd_plan_piece_batches(self->log2n, self->overlap, n_batches, batch, self->sub_samples);
 	n_sub = (n_batches + sub_b - 1) / sub_b;
 	use_alt = self->overlap && self->alt && device_call && (n_sub > 1 || self->relaxed);
-	if (self->log2n == 16 && self->k1h_fused)
+	if (self->log2n == 16)
 		use_alt = 0;		/* one fused FFT kernel at a time: its clusters own the counters and the intermediate */
 
 	/* A call that stores every row of the ring does so in the other ring: its K1s then owe nothing to the
@@ -1242,6 +1250,10 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 		const int nb = (n_batches - b0 < sub_b) ? n_batches - b0 : sub_b;
 		const int t0 = b0 * batch, sub_total = nb * batch;
 		const int tile = pick_tile(self, sub_total, batch);
+		const struct fosphor_amd_count_plan plan = plan_count(self, nb, batch, 1);
+		/* third stream: only a hand-off with a second hit-count set lets the merge run beside the next count */
+		const int three = self->overlap && self->pipe3 && plan.two_sets;
+		hipStream_t st3 = three ? self->stream3 : st2;
 		hipStream_t ks = use_alt ? self->k1_streams[self->k1_seq++ % self->n_k1_streams] : self->stream;
 		const int set = k1_piece(self, ks, (const char *)d_iq + (size_t)t0 * hop_samples * sample_bytes, t0, sub_total, tile,
 		                         total - self->wf_rows, hop);
@@ -1252,40 +1264,32 @@ static int run(struct fosphor *self, const void *d_iq, int n_batches, int batch,
 		if (three) {
 			hset = self->hset;
 			self->hset ^= 1;
-			if (self->hset_used[hset])
-				HIP_TRY(hipStreamWaitEvent(st2, self->ev_h_free[hset], 0), "wait for hit-count set");
+			HIP_TRY(self->f.h_free[hset].wait(st2), "wait for hit-count set");
 		} else if (drain_h_sets(self, st2)) {
 			return -EIO;
 		}
-		if (run_count(self, nb, batch, tile, 0, 0, batch, st2, 1, hset))
+		if (run_count(self, plan, nb, batch, tile, 0, hset, 0, batch, st2))
 			return -EIO;
 		if (k1_set_release(self, set))
 			return -EIO;
 		if (three) {
-			HIP_TRY(hipEventRecord(self->ev_k2_done[hset], st2), "record K2 done");
-			HIP_TRY(hipStreamWaitEvent(st3, self->ev_k2_done[hset], 0), "K3 waits for K2");
+			HIP_TRY(self->f.k2_done[hset].record(st2), "record K2 done");
+			HIP_TRY(self->f.k2_done[hset].wait(st3), "K3 waits for K2");
 		}
-		if (run_merge(self, nb, batch, 0, st3, 1, hset))
+		if (run_merge(self, plan, nb, batch, 0, hset, st3))
 			return -EIO;
-		if (self->overlap && self->log2n == 13) {
-			HIP_TRY(hipEventRecord(self->ev_tail, st3), "record tail");
-			self->tail_set = 1;
-		}
-		if (three) {
-			HIP_TRY(hipEventRecord(self->ev_h_free[hset], st3), "record hit-count set free");
-			self->hset_used[hset] = 1;
-		}
-		self->last_batches = nb;
+		if (self->overlap && self->log2n == 13)
+			HIP_TRY(self->f.tail.record(st3), "record tail");
+		if (three)
+			HIP_TRY(self->f.h_free[hset].record(st3), "record hit-count set free");
 	}
 	if (use_alt && !self->relaxed) {
 		/* what the caller queues on `stream` next (e.g. refilling the sample buffer) follows every K1 */
 		if (k1_streams_join(self))
 			return -EIO;
 	}
-	self->last_hc16 = (batch <= 1024 || count_one_chunk(self, batch, self->last_batches));
 
 	self->wf_pos = (self->wf_pos + total) & (self->wf_rows - 1);	/* cl.c:954 */
-	self->last_slot0 = 0;
 	self->state = ST_PENDING;
 	return 0;
 error:
@@ -1324,9 +1328,8 @@ extern "C" int fosphor_amd_process_device_overlap(struct fosphor *self, const vo
 static int run_staged(struct fosphor *self, int k, int n_batches, int batch)
 {
 	int rv = run(self, self->d_stage[k], n_batches, batch);
-	if (hipEventRecord(self->stage_free[k], self->stream) != hipSuccess && !rv)
+	if (self->f.stage_free[k].record(self->stream) != hipSuccess && !rv)
 		rv = -EIO;
-	self->stage_used[k] = 1;
 	return rv;
 }
 
@@ -1362,10 +1365,10 @@ extern "C" int fosphor_process(struct fosphor *self, void *samples, int len)
 		HIP_TRY(hipMalloc((void **)&self->d_stage[k], sample_bytes * self->stage_samples), "alloc device staging");
 		self->d_stage_cap[k] = self->stage_samples;
 	}
-	if (!self->stage_free[k])
-		HIP_TRY(hipEventCreateWithFlags(&self->stage_free[k], hipEventDisableTiming), "create staging event");
+	if (!self->f.stage_free[k].ev)
+		HIP_TRY(self->f.stage_free[k].create(hipEventDisableTiming), "create staging event");
 	else
-		HIP_TRY(hipEventSynchronize(self->stage_free[k]), "wait staging slot");
+		HIP_TRY(hipEventSynchronize(self->f.stage_free[k].ev), "wait staging slot");	/* (the HOST waits: it refills h_stage[k] next) */
 	memcpy(self->h_stage[k], samples, sample_bytes * (size_t)len);
 	HIP_TRY(hipMemcpyAsync(self->d_stage[k], self->h_stage[k], sample_bytes * (size_t)len, hipMemcpyHostToDevice, self->stream), "H2D samples");
 	{
@@ -1408,22 +1411,19 @@ extern "C" int fosphor_amd_upload_pinned(struct fosphor *self, const void *sampl
 		HIP_TRY(hipMalloc((void **)&self->d_stage[k], sample_bytes * cap), "alloc device staging");
 		self->d_stage_cap[k] = cap;
 	}
-	if (!self->stage_free[k])
-		HIP_TRY(hipEventCreateWithFlags(&self->stage_free[k], hipEventDisableTiming), "create staging event");
-	if (!self->upload_done)
-		HIP_TRY(hipEventCreateWithFlags(&self->upload_done, hipEventDisableTiming), "create upload event");
+	/* (events the host waits on, or behind a copy from host memory: no hipEventDisableSystemFence) */
+	HIP_TRY(self->f.stage_free[k].create(hipEventDisableTiming), "create staging event");
+	HIP_TRY(self->f.upload_done.create(hipEventDisableTiming), "create upload event");
 	if (!self->copy_stream)
 		HIP_TRY(hipStreamCreateWithFlags(&self->copy_stream, hipStreamNonBlocking), "create upload stream");
-	if (!self->upload_slot[k])
-		HIP_TRY(hipEventCreateWithFlags(&self->upload_slot[k], hipEventDisableTiming), "create upload event");
+	HIP_TRY(self->f.upload_slot[k].create(hipEventDisableTiming), "create upload event");
 	/* The upload runs on its own stream, beside the kernels of the batch before it (on one stream a batch cost its 150 us of DMA PLUS
 	 * its kernels: 3.9 GSamples/s where the link does 7).  d_stage[k] was last read by the FFT kernel of the call before the last:
 	 * the copy waits for the event recorded behind that call; the instance's stream waits for the copy. */
-	if (self->stage_used[k])
-		HIP_TRY(hipStreamWaitEvent(self->copy_stream, self->stage_free[k], 0), "upload waits for the staging slot");
+	HIP_TRY(self->f.stage_free[k].wait(self->copy_stream), "upload waits for the staging slot");
 	HIP_TRY(hipMemcpyAsync(self->d_stage[k], samples, sample_bytes * (size_t)len, hipMemcpyHostToDevice, self->copy_stream), "H2D samples (pinned)");
-	HIP_TRY(hipEventRecord(self->upload_slot[k], self->copy_stream), "record upload");
-	HIP_TRY(hipEventRecord(self->upload_done, self->copy_stream), "record upload");
+	HIP_TRY(self->f.upload_slot[k].record(self->copy_stream), "record upload");
+	HIP_TRY(self->f.upload_done.record(self->copy_stream), "record upload");
 	self->pend_slot[(self->pend_head + self->pend_n) & 1] = k;
 	self->pend_len[(self->pend_head + self->pend_n) & 1] = len;
 	self->pend_n++;
@@ -1450,7 +1450,7 @@ extern "C" int fosphor_amd_process_uploaded(struct fosphor *self, int *len_out)
 	self->pend_n--;
 	if (len_out)
 		*len_out = len;
-	HIP_TRY(hipStreamWaitEvent(self->stream, self->upload_slot[k], 0), "kernels wait for the upload");
+	HIP_TRY(self->f.upload_slot[k].wait(self->stream), "kernels wait for the upload");
 	return run_staged(self, k, n_batches, len / self->n / n_batches);
 error:
 	return -EIO;
@@ -1470,9 +1470,9 @@ extern "C" int fosphor_amd_process_pinned(struct fosphor *self, const void *samp
 
 extern "C" int fosphor_amd_wait_upload(struct fosphor *self)
 {
-	if (!self || !self->upload_done)
+	if (!self || !self->f.upload_done.ev)
 		return 0;
-	return hipEventSynchronize(self->upload_done) == hipSuccess ? 0 : -EIO;
+	return hipEventSynchronize(self->f.upload_done.ev) == hipSuccess ? 0 : -EIO;
 }
 
 extern "C" int fosphor_amd_finish(struct fosphor *self)
@@ -1510,7 +1510,7 @@ static int get_buffers(struct fosphor *self, struct fosphor_amd_buffers *out, in
 {
 	if (!self || !out)
 		return -EINVAL;
-	if (want_hitcount && self->last_hc16 && self->export_src) {
+	if (want_hitcount && self->export_src) {
 		/* queued on the stream of the K2 that wrote the slabs (stream order = behind it); the view is complete when
 		 * this call returns */
 		hipStream_t st = self->export_stream ? self->export_stream : self->stream;
@@ -1522,8 +1522,7 @@ static int get_buffers(struct fosphor *self, struct fosphor_amd_buffers *out, in
 	out->d_waterfall = self->d_wf_pp[self->wf_cur];
 	out->d_histogram = self->d_hist;
 	out->d_spectrum  = (float *)self->d_spectrum;
-	out->d_hitcount  = !want_hitcount ? NULL : self->last_hc16 ? self->d_hc_export
-	                   : self->d_hc + (size_t)(self->last_slot0 + (self->last_batches > 0 ? self->last_batches - 1 : 0)) * self->n_bins * self->n;
+	out->d_hitcount  = want_hitcount ? (uint32_t *)self->hc_view : NULL;	/* (run_merge: the export view, or the last batch's 32-bit slot) */
 	out->waterfall_pos = self->wf_pos;
 	out->fft_len = self->n; out->n_bins = self->n_bins; out->wf_rows = self->wf_rows;
 	out->histo_scale = self->histo_scale; out->histo_offset = self->histo_offset;
@@ -1633,8 +1632,9 @@ static int accumulate(struct fosphor *self, const void *d_samples, int n_local, 
 	const int hop = self->n / overlap;
 	const int first_row = total_batch - self->wf_rows;	/* spectrum t_offset + t stores its row iff t_offset + t >= first_row */
 	hipStream_t st2 = count_stream(self);
-	const int cpb = n_local / 1024;
-	const int chunked = (n_local % 1024) == 0 && cpb > 1 && self->d_slab16 && cpb <= self->slab_chunks && !self->kn_no_sum16;
+	const struct fosphor_amd_count_plan plan = plan_count(self, 1, n_local, 0);
+	const int cpb = plan.cpb;
+	const int chunked = plan.handoff == FOSPHOR_AMD_COUNT_SUM16;	/* whole 1024-spectrum chunks, and room for their slabs */
 	const int sub_c = self->sub_samples / (1024LL * self->n) > 1 ? (int)(self->sub_samples / (1024LL * self->n)) : 1;
 
 	if (prepare(self))
@@ -1644,8 +1644,8 @@ static int accumulate(struct fosphor *self, const void *d_samples, int n_local, 
 		 * sub_samples samples, K1s alternating between two streams, K2 of piece j beside K1 of piece j + 1.
 		 * Each K2 leaves its chunks' packed 16-bit count slabs and float partials at the chunks' places;
 		 * one k2c_sum at the end adds all of them into the 32-bit slot that is exchanged. */
-		const size_t cells = (size_t)self->n_bins * self->n;
-		const int use_alt = self->overlap && self->alt && !(self->log2n == 16 && self->k1h_fused);
+		const size_t cells = self->cells();
+		const int use_alt = self->overlap && self->alt && self->log2n != 16;
 		/* K2 counts G consecutive 1024-spectrum chunks per work-group (16-bit counters hold 65535 spectra): 1 / G of the
 		 * slab traffic, as long as enough work-groups are left to keep the bin-index reads in flight */
 		int G = 1;
@@ -1671,7 +1671,7 @@ static int accumulate(struct fosphor *self, const void *d_samples, int n_local, 
 				return -EIO;
 			self->acc_pieces++;
 			fill_k2(self, &k2, sub_total, sub_total, 1024 * G, tile, t_offset + t0, total_batch);
-			k2.hc = self->d_hc + (size_t)self->slot * cells;
+			k2.hc = self->hc_slot(self->slot);
 			k2.hc16 = self->d_slab16 + (size_t)(c0 / G) * cells;
 			k2.chunk_sum = self->d_chunk_sum + (size_t)(c0 / G) * self->n;
 			k2.chunk_max = self->d_chunk_max + (size_t)(c0 / G) * self->n;
@@ -1692,7 +1692,7 @@ static int accumulate(struct fosphor *self, const void *d_samples, int n_local, 
 		if (set < 0)
 			return -EIO;
 		self->acc_pieces++;
-		if (drain_h_sets(self, st2) || run_count(self, 1, n_local, tile, self->slot, t_offset, total_batch, st2) ||
+		if (drain_h_sets(self, st2) || run_count(self, plan, 1, n_local, tile, self->slot, 0, t_offset, total_batch, st2) ||
 		    k1_set_release(self, set))
 			return -EIO;
 	}
@@ -1731,9 +1731,9 @@ extern "C" int fosphor_amd_get_partials(struct fosphor *self, struct fosphor_amd
 {
 	if (!self || !out)
 		return -EINVAL;
-	out->d_hc = self->d_hc + (size_t)self->slot * self->n_bins * self->n;
-	out->d_live_sum = self->d_live_sum + (size_t)self->slot * self->n;
-	out->d_max = self->d_vmax + (size_t)self->slot * self->n;
+	out->d_hc = self->hc_slot(self->slot);
+	out->d_live_sum = self->live_sum_at(self->slot);
+	out->d_max = self->vmax_at(self->slot);
 	out->n_hc = self->n_bins * self->n;
 	out->n_cols = self->n;
 	return 0;
@@ -1743,11 +1743,8 @@ extern "C" int fosphor_amd_get_partials(struct fosphor *self, struct fosphor_amd
  * histogram (0, 0: all of them) */
 static int merge_slot(struct fosphor *self, int total_batch, int cell_begin, int cell_end)
 {
-	if (prepare(self) || run_merge(self, 1, total_batch, self->slot, count_stream(self), 0, 0, cell_begin, cell_end))
+	if (prepare(self) || run_merge(self, plan_count(self, 1, total_batch, 0), 1, total_batch, self->slot, 0, count_stream(self), cell_begin, cell_end))
 		return -EIO;
-	self->last_batches = 1;
-	self->last_slot0 = self->slot;
-	self->last_hc16 = 0;
 	self->state = ST_PENDING;
 	return 0;
 }
@@ -1838,13 +1835,10 @@ extern "C" int fosphor_amd_exchange(struct fosphor *self, void *comm)
 {
 	if (!self || !comm)
 		return -EINVAL;
-	const size_t cells = (size_t)self->n_bins * self->n;
 	hipStream_t st = count_stream(self);
 	xprof_begin(self, st);
-	const int rv = xchg_allreduce3(comm, st,
-	                               self->d_hc + (size_t)self->slot * cells, cells,
-	                               self->d_live_sum + (size_t)self->slot * self->n, self->d_vmax + (size_t)self->slot * self->n,
-	                               (size_t)self->n);
+	const int rv = xchg_allreduce3(comm, st, self->hc_slot(self->slot), self->cells(),
+	                               self->live_sum_at(self->slot), self->vmax_at(self->slot), (size_t)self->n);
 	xprof_end(self, st);
 	return rv;
 }
@@ -1862,13 +1856,10 @@ extern "C" int fosphor_amd_exchange_sliced(struct fosphor *self, void *comm, int
 {
 	if (!comm || !slice_ok(self, world, rank))
 		return -EINVAL;
-	const size_t cells = (size_t)self->n_bins * self->n;
 	hipStream_t st = count_stream(self);
 	xprof_begin(self, st);
-	const int rv = xchg_reduce_scatter(comm, st,
-	                                   self->d_hc + (size_t)self->slot * cells, cells, world, rank,
-	                                   self->d_live_sum + (size_t)self->slot * self->n, self->d_vmax + (size_t)self->slot * self->n,
-	                                   (size_t)self->n);
+	const int rv = xchg_reduce_scatter(comm, st, self->hc_slot(self->slot), self->cells(), world, rank,
+	                                   self->live_sum_at(self->slot), self->vmax_at(self->slot), (size_t)self->n);
 	xprof_end(self, st);
 	return rv;
 }
@@ -2211,9 +2202,10 @@ extern "C" int fosphor_amd_set_overlap(struct fosphor *self, int enable)
 	if (fosphor_amd_finish(self) < 0)
 		return -EIO;
 	self->overlap = enable ? 1 : 0;
+	/* (everything queued has finished: nothing is left to wait for) */
 	for (int i = 0; i < kSets; i++)
-		self->set_used[i] = 0;
-	self->hset_used[0] = self->hset_used[1] = 0;
+		self->f.set_free[i].recorded = 0;
+	self->f.h_free[0].recorded = self->f.h_free[1].recorded = 0;
 	return 0;
 }
 

@@ -144,7 +144,13 @@ hipError_t launch_k2c(const K2bParams &p, hipStream_t s);
 enum K3Form { K3_DENSE16, K3_DENSE16_LONG4, K3_DENSE16_LONG, K3_TABLE32, K3_EVAL32, K3_SPARSE16, K3_SPARSE16_LONG, K3_FORMS };
 constexpr int kK3LongFew = 4;		/* dense long-batch form: launches of up to this many batches keep four cells in flight per thread */
 constexpr int kK3RiseLdsLong = 4097;	/* dense long-batch form: (d, e) table entries that fit in LDS (batches up to 4096 spectra) */
-K3Form k3_form(const K3Params &p);		/* the form launch_k3 launches for p */
+/* What decides the form: the hand-off of the launch (16-bit counts? row masks? a (d, e) table?) and its shape, never the data */
+struct K3Shape { bool hc16, rowmask, table; int n_batches, batch, n_bins, n; };
+inline K3Shape k3_shape(const K3Params &p)
+{
+	return K3Shape{ p.hc16 != nullptr, p.rowmask != nullptr, p.rise != nullptr, p.n_batches, p.batch, p.n_bins, p.n };
+}
+K3Form k3_form(const K3Shape &s);		/* the form launch_k3 launches for a launch of that shape */
 hipError_t launch_k3(const K3Params &p, hipStream_t s);
 hipError_t launch_fill(float *dst, float value, size_t n, hipStream_t s);
 hipError_t launch_export_hc16(const uint16_t *hc16, const uint32_t *rowmask, int mask_words, int mask_stride, uint32_t *out, int n_bins, int n, hipStream_t s);

@@ -1846,7 +1846,7 @@ void k3_scan(const K3Params p)
 }
 
 /* Which form a launch takes: the shape of the launch and the buffers the host filled in decide, never the data */
-K3Form k3_form(const K3Params &p)
+K3Form k3_form(const K3Shape &p)
 {
 	if (p.hc16 && p.rowmask && p.n_bins * (p.n / 64) <= (1 << 20))	/* (list entries hold 20 bits of row index: every geometry the library accepts) */
 		return p.batch <= 1024 ? K3_SPARSE16 : K3_SPARSE16_LONG;
@@ -1854,7 +1854,7 @@ K3Form k3_form(const K3Params &p)
 		return K3_DENSE16;
 	if (p.hc16)
 		return p.n_batches <= kK3LongFew ? K3_DENSE16_LONG4 : K3_DENSE16_LONG;	/* (the branch k3_merge<3> takes inside) */
-	return p.rise ? K3_TABLE32 : K3_EVAL32;
+	return p.table ? K3_TABLE32 : K3_EVAL32;
 }
 
 hipError_t launch_k3(const K3Params &p, hipStream_t s)
@@ -1862,7 +1862,7 @@ hipError_t launch_k3(const K3Params &p, hipStream_t s)
 	const int threads = p.n_bins * p.n + p.n;
 	int blocks = (threads + 255) / 256;
 	if (blocks > 8192) blocks = 8192;
-	switch (k3_form(p)) {
+	switch (k3_form(k3_shape(p))) {
 	case K3_SPARSE16:
 	case K3_SPARSE16_LONG: {
 		/* sparse form: list the live rows, then one wave per listed row (strided) */

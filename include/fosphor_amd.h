@@ -282,6 +282,33 @@ int fosphor_amd_tune_placement(struct fosphor *self, const void *d_samples, int 
  * pieces).  -EINVAL for nonsense. */
 int fosphor_amd_plan_piece_batches(int fft_len_log, int overlap, int n_batches, int batch, long long sub_samples);
 
+/* Host-logic test hook (no device needed): the count hand-off of ONE launch -- which buffer the count kernel fills and the merge kernel
+ * reads -- for n_batches batches of `batch` spectra on an instance of FFT length 2^fft_len_log with n_bins bins and room for slab_chunks
+ * 1024-spectrum count slabs (max_spectra / 1024 of an instance made with max_spectra > 1024, else 0).  rowmask_off / no_sum16: the
+ * FOSPHOR_AMD_ROWMASK=0 / FOSPHOR_AMD_NO_SUM16 knobs.  pipelined: 1 for a launch of fosphor_process / fosphor_amd_process_device* (one
+ * piece of the call, fosphor_amd_plan_piece_batches), 0 for the partial arrays of fosphor_amd_accumulate_device* (n_batches 1, batch =
+ * the shard) and of fosphor_amd_merge* (n_batches 1, batch = the frame).  This is the function every launch site of the library takes
+ * its decisions from.  0, or -EINVAL for nonsense. */
+enum {
+	FOSPHOR_AMD_COUNT_DIRECT16,	/* packed 16-bit counts straight into a hit-count set: batches up to 1024 spectra, and batches up to 8192
+					 * counted as one chunk where the launch has at least 128 slabs of 64 columns */
+	FOSPHOR_AMD_COUNT_SUM16,	/* 16-bit slabs per 1024-spectrum chunk, summed into 32-bit counts (k2c): whole chunks with room for their slabs */
+	FOSPHOR_AMD_COUNT_32		/* 32-bit counts: stored (one chunk per batch) or added, the float partials reduced beside them (k2b) */
+};
+struct fosphor_amd_count_plan
+{
+	int chunk;		/* spectra one count work-group takes; divides batch */
+	int cpb;		/* chunks per batch */
+	int handoff;		/* FOSPHOR_AMD_COUNT_* */
+	int two_sets;		/* the hand-off alternates between two sets of counts: the merge may run beside the next launch's count */
+	int rowmask;		/* the count kernel leaves row masks, the merge visits listed rows only (fft_len_log = 16) */
+	int table;		/* the rise/decay table serves the batch (up to 8192 spectra) */
+	int merge_form;		/* FOSPHOR_AMD_MERGE_DENSE16 .. FOSPHOR_AMD_MERGE_SPARSE16_LONG: the form fosphor_amd_merge_stats will count */
+	int table_in_memory;	/* ... and whether it counts under FOSPHOR_AMD_MERGE_TABLE_IN_MEMORY */
+};
+int fosphor_amd_plan_count(int fft_len_log, int n_bins, int slab_chunks, int rowmask_off, int no_sum16,
+                           int n_batches, int batch, int pipelined, struct fosphor_amd_count_plan *out);
+
 /* FFT launches made in the space-sharing form (*cus work-groups, the count / merge kernels of the launch before on the CUs they
  * leave) and in the full-chip form since the instance was made: counted at fft_len_log = 13 only (the one length that shares; both
  * counters stay 0 otherwise).  *cus is the device's share whatever the length: 224 on a 256-CU device, 0 on any other (this device
