@@ -80,6 +80,12 @@ class ViewOut(C.Structure):
                 ("wf_color", ViewColor), ("histo_color", ViewColor)]
 
 
+class Wire(C.Structure):
+    """struct fosphor_amd_wire (include/fosphor_amd_wire.h)"""
+    _fields_ = [("d_masks", C.c_void_p), ("mask_words", C.c_int), ("world", C.c_int), ("d_words", C.c_void_p),
+                ("n_words", C.c_int), ("form", C.c_int), ("live_rows", C.c_int), ("rows", C.c_int)]
+
+
 SIGNATURES = {
     # include/fosphor.h
     "fosphor_init": (C.c_void_p, []),
@@ -158,6 +164,14 @@ SIGNATURES = {
     "fosphor_amd_view_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 4)]),
     "fosphor_amd_view_span": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fosphor_amd_view_from_render": (C.c_int, [C.c_int, C.c_int, C.POINTER(Render), C.c_int, C.c_int, C.POINTER(View)]),
+    # include/fosphor_amd_wire.h
+    "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),
+    "fosphor_amd_wire_unpack": (C.c_int, [C.c_void_p]),
+    "fosphor_amd_wire_get": (C.c_int, [C.c_void_p, C.POINTER(Wire)]),
+    "fosphor_amd_exchange_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "fosphor_amd_wire_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 5)]),
+    "fosphor_amd_wire_kernel_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float * 3)]),
     # include/fosphor_amd_sink.h
     "fosphor_amd_process_pinned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "fosphor_amd_upload_pinned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

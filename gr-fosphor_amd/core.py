@@ -19,6 +19,8 @@ MAX_BATCH = 1024		# private.h:25
 
 
 IQ_FORMATS = {"fp32": 0, "fp16": 1, "sc16": 2}	# FOSPHOR_AMD_IQ_* (include/fosphor_amd.h)
+WIRE_FORMS = {"packed16": 1, "sparse16": 2}	# FOSPHOR_AMD_WIRE_* (include/fosphor_amd_wire.h)
+WIRE_MAX_BATCH = 65535
 
 
 def _ptr(x):
@@ -148,6 +150,59 @@ class Fosphor:
 
     def gather_state(self, comm, world, rank):
         return self.L.fosphor_amd_gather_state(self.h, comm, world, rank)
+
+    # ---- compact wire formats of the exchange (include/fosphor_amd_wire.h) ----
+    @staticmethod
+    def _wire_form(form):
+        """"packed16" / "sparse16" or the FOSPHOR_AMD_WIRE_* number (which the library checks)"""
+        if isinstance(form, str):
+            if form not in WIRE_FORMS:
+                raise ValueError("wire form must be one of %s" % ", ".join(WIRE_FORMS))
+            return WIRE_FORMS[form]
+        return int(form)
+
+    def wire_mask(self, total_batch, world, rank):
+        """stage (a) of the sparse form: this rank's presence bits into its part of the mask buffer; 0 / -EINVAL / -EIO"""
+        return self.L.fosphor_amd_wire_mask(self.h, int(total_batch), int(world), int(rank))
+
+    def wire_pack(self, total_batch, form, world):
+        """fosphor_amd_wire_pack: (return value, struct fosphor_amd_wire)"""
+        w = _lib.Wire()
+        rv = self.L.fosphor_amd_wire_pack(self.h, int(total_batch), self._wire_form(form), int(world), C.byref(w))
+        return rv, w
+
+    def wire_unpack(self):
+        return self.L.fosphor_amd_wire_unpack(self.h)
+
+    def wire_info(self):
+        """struct fosphor_amd_wire as it stands: the buffers and what the last pack decided"""
+        w = _lib.Wire()
+        rv = self.L.fosphor_amd_wire_get(self.h, C.byref(w))
+        if rv:
+            raise RuntimeError("fosphor_amd_wire_get -> %d" % rv)
+        return w
+
+    def exchange_compact(self, comm, total_batch, form, world, rank):
+        return self.L.fosphor_amd_exchange_compact(self.h, comm, int(total_batch), self._wire_form(form), int(world), int(rank))
+
+    WIRE_STATS = ("packed16", "sparse16", "fell_back", "live_rows", "wire_bytes")
+
+    def wire_stats(self):
+        """fosphor_amd_wire_stats as a dict: packs since the instance was made by the form they took (WIRE_STATS[:3]), live rows
+        and wire bytes (masks included) of the last one"""
+        st = (C.c_longlong * 5)()
+        rv = self.L.fosphor_amd_wire_stats(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("fosphor_amd_wire_stats -> %d" % rv)
+        return dict(zip(self.WIRE_STATS, list(st)))
+
+    def wire_kernel_times(self):
+        """ms of the last k_wire_mask / k_wire_pack / k_wire_unpack launch made while profiling was on (-1: none)"""
+        ms = (C.c_float * 3)()
+        rv = self.L.fosphor_amd_wire_kernel_times(self.h, C.byref(ms))
+        if rv:
+            raise RuntimeError("fosphor_amd_wire_kernel_times -> %d" % rv)
+        return dict(zip(("mask", "pack", "unpack"), list(ms)))
 
     def buffers(self, hitcount=True):
         """struct fosphor_amd_buffers; hitcount=False: no export kernel, no wait, d_hitcount is NULL."""

@@ -24,6 +24,7 @@
 #include "fosphor_internal.h"
 #include "../../include/fosphor_amd.h"
 #include "../../include/fosphor_amd_sink.h"
+#include "../../include/fosphor_amd_wire.h"
 #include "../../include/fosphor_portable_math.h"
 
 using namespace fosphor_amd;
@@ -186,6 +187,23 @@ struct fosphor
 	long long *d_dbg;			/* K1_TIMING builds only (FOSPHOR_AMD_K1_TIMING=1) */
 	uint32_t *d_palette;			/* colour-map scratch (fosphor_cmap.hip), allocated on first use */
 	long long view_forms[4];		/* view launches by form (fosphor_view.hip, fosphor_amd_view_stats) */
+	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
+	struct {
+		uint32_t *d_masks;		/* [mask_cap][rows / 32] presence bits, one part per rank */
+		int       mask_cap;		/* parts d_masks holds */
+		int       world;		/* parts it is laid out for (the last mask stage's world) */
+		int       masked;		/* world of a mask stage no sparse pack has consumed yet, else 0 */
+		int       masked_slot, packed_slot;	/* the slot that mask stage read; the slot the last pack read */
+		uint32_t *d_union, *d_prefix;	/* [rows / 32] union mask, live rows in the words before each */
+		uint32_t *d_live;		/* the union's live-row count, for the row copies ... */
+		uint32_t *h_live;		/* ... and in pinned host memory, for the host (the one wait of the sparse form) */
+		uint32_t *d_words;		/* [cells / 2] wire words */
+		int       form;			/* form the last pack took, 0 once it is unpacked */
+		int       n_words, live_rows;	/* of the last pack */
+		long long stats[FOSPHOR_AMD_WIRE_STATS];
+		hipEvent_t ev[6];		/* (start, stop) of the last mask / pack / unpack launch made while profiling was on */
+		int       ev_rec[3];
+	} wire;
 	float2   *d_rise;			/* [kRiseMax+1] (d, e) per hit count */
 	float2   *h_rise;			/* pinned */
 	int       rise_batch;			/* batch the table was built for (0 = none) */
@@ -417,6 +435,11 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_chunk_sum); (void)hipFree(self->d_chunk_max);
 	(void)hipFree(self->d_rise);
 	(void)hipFree(self->d_palette);
+	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
+	(void)hipFree(self->wire.d_live); (void)hipFree(self->wire.d_words);
+	if (self->wire.h_live) (void)hipHostFree(self->wire.h_live);
+	for (hipEvent_t e : self->wire.ev)
+		if (e) (void)hipEventDestroy(e);
 	(void)hipFree(self->d_scratch);
 	(void)hipFree(self->d_k1h_sync);
 	if (self->h_k1h_err) (void)hipHostFree(self->h_k1h_err);
@@ -455,6 +478,9 @@ extern "C" struct fosphor *fosphor_amd_init(const struct fosphor_amd_config *cfg
 	self->max_spectra = (cfg && cfg->max_spectra > 0) ? cfg->max_spectra : 1024;
 	self->max_batches = (cfg && cfg->max_batches > 0) ? cfg->max_batches
 	                    : (self->max_spectra / 1024 > 8 ? self->max_spectra / 1024 : 8);
+
+	self->wire.live_rows = -1;
+	self->wire.stats[FOSPHOR_AMD_WIRE_LAST_LIVE_ROWS] = -1;
 
 	if (self->log2n != 10 && self->log2n != 13 && self->log2n != 16) {
 		fprintf(stderr, "[!] fosphor_amd: fft_len_log=%d not supported (10, 13 or 16)\n", self->log2n);
@@ -1882,6 +1908,219 @@ extern "C" int fosphor_amd_gather_state(struct fosphor *self, void *comm, int wo
 		return -EIO;
 	self->hot_valid = 0;		/* other ranks' cells arrive: the hot-row flags of the sparse merge no longer describe d_hist */
 	return xchg_allgather_f32(comm, st, self->d_hist, cells, world, rank);
+}
+
+/* ---- compact wire formats (include/fosphor_amd_wire.h, kernels in fosphor_wire.hip) ---- */
+
+static unsigned wire_rows(const struct fosphor *self)
+{
+	return (unsigned)(self->cells() / FOSPHOR_AMD_WIRE_ROW_CELLS);
+}
+
+/* what every entry point refuses before it does anything */
+static int wire_args_ok(const struct fosphor *self, int total_batch, int form, int world, int rank)
+{
+	return self && total_batch >= 16 && total_batch <= FOSPHOR_AMD_WIRE_MAX_BATCH &&
+	       (form == FOSPHOR_AMD_WIRE_PACKED16 || form == FOSPHOR_AMD_WIRE_SPARSE16) &&
+	       world >= 1 && rank >= 0 && rank < world && self->cells() % (FOSPHOR_AMD_WIRE_ROW_CELLS * 32) == 0;
+}
+
+/* hipEvents around the last launch of wire kernel `kind` (0 mask, 1 pack, 2 unpack), while profiling is on */
+static void wire_prof(struct fosphor *self, int kind, int end, hipStream_t st)
+{
+	hipEvent_t *e = &self->wire.ev[2 * kind + end];
+	if (!self->prof)
+		return;
+	if (!end)
+		self->wire.ev_rec[kind] = 0;
+	if (!*e && hipEventCreateWithFlags(e, dep_event_flags() & ~hipEventDisableTiming) != hipSuccess)
+		return;
+	if (hipEventRecord(*e, st) == hipSuccess && end && self->wire.ev[2 * kind])
+		self->wire.ev_rec[kind] = 1;
+}
+
+/* work is queued on the count stream: fosphor_amd_finish has something to wait for again (an instance that is still booting
+ * stays so: its boot fills are yet to be queued) */
+static void wire_queued(struct fosphor *self)
+{
+	if (self->state == ST_READY)
+		self->state = ST_PENDING;
+}
+
+static void wire_fill(const struct fosphor *self, struct fosphor_amd_wire *out)
+{
+	out->d_masks = self->wire.d_masks;
+	out->mask_words = (int)(wire_rows(self) / 32);
+	out->world = self->wire.world;
+	out->d_words = self->wire.d_words;
+	out->n_words = self->wire.form ? self->wire.n_words : 0;
+	out->form = self->wire.form;
+	out->live_rows = self->wire.live_rows;
+	out->rows = (int)wire_rows(self);
+}
+
+static int wire_mask_stage(struct fosphor *self, int world, int rank, hipStream_t st)
+{
+	const unsigned rows = wire_rows(self);
+	const size_t part = rows / 32;
+	if (world > self->wire.mask_cap) {
+		/* (kernels of an earlier frame may still read the old buffer) */
+		HIP_TRY(hipStreamSynchronize(st), "drain the count stream before the mask buffer grows");
+		(void)hipFree(self->wire.d_masks);
+		self->wire.d_masks = nullptr;
+		self->wire.mask_cap = 0;
+		HIP_TRY(hipMalloc((void **)&self->wire.d_masks, sizeof(uint32_t) * part * world), "alloc wire masks");
+		self->wire.mask_cap = world;
+	}
+	self->wire.world = world;
+	wire_prof(self, 0, 0, st);
+	HIP_TRY(launch_wire_mask(self->hc_slot(self->slot), self->wire.d_masks + part * rank, rows, st), "launch wire mask");
+	wire_prof(self, 0, 1, st);
+	wire_queued(self);
+	self->wire.masked = world;
+	self->wire.masked_slot = self->slot;
+	return 0;
+error:
+	return -EIO;
+}
+
+static int wire_pack_stage(struct fosphor *self, int form, int world, hipStream_t st)
+{
+	const unsigned rows = wire_rows(self);
+	const size_t cells = self->cells();
+	int taken = form;
+	if (!self->wire.d_words)
+		HIP_TRY(hipMalloc((void **)&self->wire.d_words, sizeof(uint32_t) * (cells / 2)), "alloc wire words");
+	self->wire.form = 0;
+	if (form == FOSPHOR_AMD_WIRE_SPARSE16) {
+		if (!self->wire.d_union)
+			HIP_TRY(hipMalloc((void **)&self->wire.d_union, sizeof(uint32_t) * (rows / 32)), "alloc wire union mask");
+		if (!self->wire.d_prefix)
+			HIP_TRY(hipMalloc((void **)&self->wire.d_prefix, sizeof(uint32_t) * (rows / 32)), "alloc wire prefix counts");
+		if (!self->wire.d_live)
+			HIP_TRY(hipMalloc((void **)&self->wire.d_live, sizeof(uint32_t)), "alloc wire live-row count");
+		if (!self->wire.h_live)
+			HIP_TRY(hipHostMalloc((void **)&self->wire.h_live, 64, hipHostMallocMapped), "alloc wire live-row word");
+		self->wire.masked = 0;
+		wire_prof(self, 1, 0, st);
+		HIP_TRY(launch_wire_pack_sparse(self->hc_slot(self->slot), self->wire.d_masks, world, self->wire.d_union, self->wire.d_prefix,
+		                                self->wire.d_live, self->wire.h_live, self->wire.d_words, rows, st), "launch wire pack (sparse)");
+		wire_prof(self, 1, 1, st);
+		/* THE host wait of the sparse form: the all-reduce is sized by the union's live rows */
+		HIP_TRY(hipStreamSynchronize(st), "wait for the live-row count");
+		self->wire.live_rows = (int)self->wire.h_live[0];
+		if ((unsigned)self->wire.live_rows > rows / 2)
+			taken = FOSPHOR_AMD_WIRE_PACKED16;
+	} else {
+		self->wire.live_rows = -1;
+	}
+	if (taken == FOSPHOR_AMD_WIRE_PACKED16) {
+		wire_prof(self, 1, 0, st);		/* (of a frame that fell back, the dense pack is the one timed) */
+		HIP_TRY(launch_wire_pack_dense(self->hc_slot(self->slot), self->wire.d_words, cells, st), "launch wire pack (dense)");
+		wire_prof(self, 1, 1, st);
+	}
+	wire_queued(self);
+	self->wire.form = taken;
+	self->wire.packed_slot = self->slot;
+	self->wire.n_words = taken == FOSPHOR_AMD_WIRE_PACKED16 ? (int)(cells / 2) : self->wire.live_rows * FOSPHOR_AMD_WIRE_ROW_WORDS;
+	self->wire.stats[form == FOSPHOR_AMD_WIRE_PACKED16 ? FOSPHOR_AMD_WIRE_FRAMES_PACKED16 :
+	                 taken == form ? FOSPHOR_AMD_WIRE_FRAMES_SPARSE16 : FOSPHOR_AMD_WIRE_FRAMES_FELL_BACK]++;
+	self->wire.stats[FOSPHOR_AMD_WIRE_LAST_LIVE_ROWS] = self->wire.live_rows;
+	self->wire.stats[FOSPHOR_AMD_WIRE_LAST_WIRE_BYTES] = 4LL * self->wire.n_words +
+		(form == FOSPHOR_AMD_WIRE_SPARSE16 ? 4LL * world * (rows / 32) : 0);
+	return 0;
+error:
+	return -EIO;
+}
+
+static int wire_unpack_stage(struct fosphor *self, hipStream_t st)
+{
+	wire_prof(self, 2, 0, st);
+	if (self->wire.form == FOSPHOR_AMD_WIRE_PACKED16)
+		HIP_TRY(launch_wire_unpack_dense(self->wire.d_words, self->hc_slot(self->slot), self->cells(), st), "launch wire unpack (dense)");
+	else
+		HIP_TRY(launch_wire_unpack_sparse(self->wire.d_words, self->wire.d_union, self->wire.d_prefix, self->wire.d_live,
+		                                  self->hc_slot(self->slot), wire_rows(self), st), "launch wire unpack (sparse)");
+	wire_prof(self, 2, 1, st);
+	wire_queued(self);
+	self->wire.form = 0;
+	return 0;
+error:
+	return -EIO;
+}
+
+extern "C" int fosphor_amd_wire_mask(struct fosphor *self, int total_batch, int world, int rank)
+{
+	if (!wire_args_ok(self, total_batch, FOSPHOR_AMD_WIRE_SPARSE16, world, rank))
+		return -EINVAL;
+	return wire_mask_stage(self, world, rank, count_stream(self));
+}
+
+extern "C" int fosphor_amd_wire_pack(struct fosphor *self, int total_batch, int form, int world, struct fosphor_amd_wire *out)
+{
+	if (!out || !wire_args_ok(self, total_batch, form, world, 0) ||
+	    (form == FOSPHOR_AMD_WIRE_SPARSE16 && (self->wire.masked != world || self->wire.masked_slot != self->slot)))
+		return -EINVAL;
+	const int rv = wire_pack_stage(self, form, world, count_stream(self));
+	wire_fill(self, out);
+	return rv;
+}
+
+extern "C" int fosphor_amd_wire_unpack(struct fosphor *self)
+{
+	if (!self || !self->wire.form || self->wire.packed_slot != self->slot)
+		return -EINVAL;
+	return wire_unpack_stage(self, count_stream(self));
+}
+
+extern "C" int fosphor_amd_wire_get(struct fosphor *self, struct fosphor_amd_wire *out)
+{
+	if (!self || !out)
+		return -EINVAL;
+	wire_fill(self, out);
+	return 0;
+}
+
+extern "C" int fosphor_amd_exchange_compact(struct fosphor *self, void *comm, int total_batch, int form, int world, int rank)
+{
+	if (!comm || !wire_args_ok(self, total_batch, form, world, rank))
+		return -EINVAL;
+	hipStream_t st = count_stream(self);
+	int rv = 0;
+	xprof_begin(self, st);
+	if (form == FOSPHOR_AMD_WIRE_SPARSE16) {
+		rv = wire_mask_stage(self, world, rank, st);
+		rv = rv ? rv : xchg_allgather_u32(comm, st, self->wire.d_masks, wire_rows(self) / 32, rank);
+	}
+	rv = rv ? rv : wire_pack_stage(self, form, world, st);
+	rv = rv ? rv : xchg_allreduce3(comm, st, self->wire.d_words, (size_t)self->wire.n_words,
+	                               self->live_sum_at(self->slot), self->vmax_at(self->slot), (size_t)self->n);
+	rv = rv ? rv : wire_unpack_stage(self, st);
+	xprof_end(self, st);
+	return rv;
+}
+
+extern "C" int fosphor_amd_wire_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_WIRE_STATS])
+{
+	if (!self || !stats)
+		return -EINVAL;
+	for (int i = 0; i < FOSPHOR_AMD_WIRE_STATS; i++)
+		stats[i] = self->wire.stats[i];
+	return 0;
+}
+
+extern "C" int fosphor_amd_wire_kernel_times(struct fosphor *self, float ms[3])
+{
+	if (!self || !ms)
+		return -EINVAL;
+	if (hipStreamSynchronize(count_stream(self)) != hipSuccess)
+		return -EIO;
+	for (int k = 0; k < 3; k++) {
+		ms[k] = -1.0f;
+		if (self->wire.ev_rec[k] && hipEventElapsedTime(&ms[k], self->wire.ev[2 * k], self->wire.ev[2 * k + 1]) != hipSuccess)
+			ms[k] = -1.0f;
+	}
+	return 0;
 }
 
 /* ------------------------------------------------------------------------ */

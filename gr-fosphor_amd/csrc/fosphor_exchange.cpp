@@ -186,4 +186,13 @@ int xchg_allgather_f32(void *comm, hipStream_t st, float *a, size_t n, int world
 	return check(r, r->AllGather(a + per * rank, a, per, ncclFloat32, (ncclComm_t)comm, st), "ncclAllGather(histogram)");
 }
 
+/* every rank's part of `per` words (the presence masks of the compact wire, fosphor_amd_wire.h) to every rank, in place */
+int xchg_allgather_u32(void *comm, hipStream_t st, uint32_t *a, size_t per, int rank)
+{
+	Rccl *r = rccl();
+	if (!r)
+		return -ENOSYS;
+	return check(r, r->AllGather(a + per * rank, a, per, ncclUint32, (ncclComm_t)comm, st), "ncclAllGather(row masks)");
+}
+
 } // namespace fosphor_amd

@@ -157,6 +157,18 @@ hipError_t launch_export_hc16(const uint16_t *hc16, const uint32_t *rowmask, int
 hipError_t launch_bin_hook(const float2 *fft, uint8_t *bin, float *pwr, int n,
                            const K1Params &p, int force_exact, hipStream_t s);
 
+/* fosphor_wire.hip: the compact wire formats of include/fosphor_amd_wire.h.  hc: the slot's uint32 counts, rows = cells / 64,
+ * mask words = rows / 32; `live` is a device word and `h_live` a pinned host word that both receive the union's live-row count. */
+hipError_t launch_wire_mask(const uint32_t *hc, uint32_t *mask, unsigned rows, hipStream_t s);
+hipError_t launch_wire_pack_dense(const uint32_t *hc, uint32_t *words, size_t cells, hipStream_t s);
+hipError_t launch_wire_unpack_dense(const uint32_t *words, uint32_t *hc, size_t cells, hipStream_t s);
+/* sparse form: OR of the `world` parts, prefix counts, live-row count; then the row copy (which does nothing when more than half of
+ * the rows are live: the frame falls back to the dense form) */
+hipError_t launch_wire_pack_sparse(const uint32_t *hc, const uint32_t *masks, int world, uint32_t *uni, uint32_t *prefix,
+                                   uint32_t *live, uint32_t *h_live, uint32_t *words, unsigned rows, hipStream_t s);
+hipError_t launch_wire_unpack_sparse(const uint32_t *words, const uint32_t *uni, const uint32_t *prefix, const uint32_t *live,
+                                     uint32_t *hc, unsigned rows, hipStream_t s);
+
 /* fosphor_exchange.cpp: RCCL bound at run time */
 int xchg_available(void);
 int xchg_comm_count(void *comm);
@@ -167,6 +179,7 @@ int xchg_allreduce3(void *comm, hipStream_t st, uint32_t *hc, size_t n_hc, float
 int xchg_reduce_scatter(void *comm, hipStream_t st, uint32_t *hc, size_t n_hc, int world, int rank,
                         float *sum, float *mx, size_t n_cols);
 int xchg_allgather_f32(void *comm, hipStream_t st, float *a, size_t n, int world, int rank);
+int xchg_allgather_u32(void *comm, hipStream_t st, uint32_t *a, size_t per, int rank);
 
 } // namespace fosphor_amd
 

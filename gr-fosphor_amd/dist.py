@@ -16,6 +16,11 @@ The communicator is the library's own (`NativeComm`); torch.distributed is only 
 128-byte RCCL id from rank 0 to the others.  For large states (65536 x 512: 128 MiB of counts) the
 frequency-sliced form reduce-scatters the counts and lets every rank merge only its slice.
 
+The counts can travel in a compact wire format instead (include/fosphor_amd_wire.h; `ShardedFosphor(..., wire=...)`): 16-bit
+halves of uint32 words, all of them ("packed16") or only the 64-cell rows that hold a hit on some rank ("sparse16").  Both are
+exact.  `wire_pack_numpy` / `wire_unpack_numpy` / `wire_union_rows` state the formats on numpy arrays; the kernels are tested
+against them.
+
 `allreduce_partials` / `combine_partials_numpy` are the same combination rule on torch / numpy
 arrays: the CPU tests (gloo, world size 2) and two-ranks-on-one-GPU tests use them as transport.
 """
@@ -79,6 +84,71 @@ def slice_range(cells, rank, world):
     return per * rank, per * (rank + 1)
 
 
+# ---- the compact wire formats, stated on numpy arrays (include/fosphor_amd_wire.h) --------------------------------------------
+
+WIRE_ROW_CELLS = 64		# a row: 64 consecutive cells of the flattened [bin][x] counts = 32 packed words
+WIRE_ROW_WORDS = 32
+WIRE_MAX_BATCH = 65535		# both halves of a word stay below 2^16 on every rank and in the sum
+WIRE_AUTO_SPARSE_BYTES = 16 << 20	# wire="auto": states of this many bytes of uint32 counts and more go out sparse
+
+
+def wire_mask_numpy(hc):
+    """Presence bits of one rank's counts: uint32[rows / 32], bit r & 31 of word r >> 5 = some cell of row r is not zero."""
+    hc = np.asarray(hc, dtype=np.uint32).reshape(-1)
+    if hc.size % (WIRE_ROW_CELLS * 32):
+        raise ValueError("%d cells do not fill whole mask words" % hc.size)
+    live = hc.reshape(-1, WIRE_ROW_CELLS).any(axis=1)
+    return np.packbits(live.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
+
+
+def wire_union_rows(masks):
+    """masks: uint32[world][rows / 32], every rank's presence bits.  Returns (the rows live on ANY rank, ascending -- the order
+    they are packed in --, fall_back): fall_back when more than half of the rows are live, in which case the frame goes out dense."""
+    masks = np.asarray(masks, dtype=np.uint32)
+    masks = masks.reshape(1, -1) if masks.ndim == 1 else masks
+    union = np.bitwise_or.reduce(masks, axis=0)
+    bits = np.unpackbits(union.astype("<u4").view(np.uint8), bitorder="little")
+    rows = np.flatnonzero(bits)
+    return rows, bool(2 * rows.size > bits.size)
+
+
+def wire_pack_numpy(hc, rows=None):
+    """One rank's counts as wire words (uint32).  rows=None, the dense form: word w = hc[2 w] | hc[2 w + 1] << 16 for every pair of
+    cells.  rows (from wire_union_rows), the sparse form: the same words of those rows only, in that order, 32 per row; a row
+    without hits on this rank contributes zeros."""
+    hc = np.asarray(hc, dtype=np.uint32).reshape(-1)
+    if rows is not None:
+        hc = hc.reshape(-1, WIRE_ROW_CELLS)[np.asarray(rows, dtype=np.int64)].reshape(-1)
+    return hc[0::2] | (hc[1::2] << np.uint32(16))
+
+
+def wire_unpack_numpy(words, n_hc, rows=None):
+    """The inverse, on the words summed over the ranks: uint32[n_hc] counts; in the sparse form every row outside `rows` is zero."""
+    words = np.asarray(words, dtype=np.uint32).reshape(-1)
+    cells = np.empty(2 * words.size, dtype=np.uint32)
+    cells[0::2] = words & np.uint32(0xFFFF)
+    cells[1::2] = words >> np.uint32(16)
+    if rows is None:
+        if cells.size != n_hc:
+            raise ValueError("%d words do not hold %d cells" % (words.size, n_hc))
+        return cells
+    out = np.zeros(n_hc, dtype=np.uint32)
+    out.reshape(-1, WIRE_ROW_CELLS)[np.asarray(rows, dtype=np.int64)] = cells.reshape(-1, WIRE_ROW_CELLS)
+    return out
+
+
+def resolve_wire(wire, total_batch, state_bytes):
+    """The wire format of a frame: "u32", "packed16" or "sparse16".  "auto": "u32" when total_batch > 65535 (16 bits do not hold
+    the counts), else "sparse16" for states of 16 MiB and more, else "packed16"."""
+    if wire not in ("u32", "packed16", "sparse16", "auto"):
+        raise ValueError("wire must be u32, packed16, sparse16 or auto, not %r" % (wire,))
+    if wire != "auto":
+        return wire
+    if total_batch > WIRE_MAX_BATCH:
+        return "u32"
+    return "sparse16" if state_bytes >= WIRE_AUTO_SPARSE_BYTES else "packed16"
+
+
 class NativeComm:
     """The library's own RCCL communicator (fosphor_amd_comm_*).  `broadcast_id(id_bytes_or_None) -> bytes`
     hands rank 0's 128-byte id to every rank; by default torch.distributed does it (any backend)."""
@@ -138,6 +208,11 @@ class ShardedFosphor:
                         (any backend; what the two-ranks-on-one-GPU gloo test uses).  With overlap=True the
                         exchange of frame k is left in flight while frame k+1 is submitted (two slots).
     sliced: reduce-scatter + frequency-sliced merge (rccl only); default for states of 16 MiB and more.
+    wire: how the hit counts travel.  "u32" (the default, also when FOSPHOR_AMD_WIRE is unset): as they lie in memory.  "packed16" /
+                "sparse16": the compact formats of include/fosphor_amd_wire.h (exact; total_batch <= 65535; the sparse one waits
+                on the host once per frame for its live-row count).  "auto": see resolve_wire.  With sliced on, the counts are
+                all-reduced in the compact form and every rank still merges only its slice.  With the torch transport the
+                collectives run on views of the wire buffers and a frame is retired at once (overlap is ignored).
     force_exchange: run the collectives on a single rank too (smoke test of the RCCL path).
     connect=False: do everything that can fail on this rank ALONE (bind RCCL, construct the instance) and leave the
                 collective part -- rank 0's id to every rank, ncclCommInitRank -- to connect(): agree_on_transport puts
@@ -145,10 +220,12 @@ class ShardedFosphor:
     """
 
     def __init__(self, fosphor_cls, rank, world, group=None, exchange=None, sliced=None, force_exchange=False,
-                 comm=None, connect=True, **kw):
+                 comm=None, connect=True, wire=None, **kw):
         import os
         import torch
         self.torch = torch
+        self.wire = wire if wire is not None else os.environ.get("FOSPHOR_AMD_WIRE", "u32")
+        resolve_wire(self.wire, 16, 0)		# (refuses an unknown name)
         self.rank, self.world, self.group = rank, world, group
         # K1 runs on a torch-owned, NON-default stream (torch's default stream has handle 0, which the C ABI
         # reads as "create a private stream"), so that the caller's producer of the samples can be ordered
@@ -201,17 +278,52 @@ class ShardedFosphor:
         import torch.distributed as dist
         return dist.get_world_size(self.group) if dist.is_initialized() else 1
 
+    def wire_form(self, total_batch):
+        """the wire format a frame of total_batch spectra goes out in ("u32", "packed16" or "sparse16")"""
+        return resolve_wire(self.wire, total_batch, 4 * self.f.n_bins * self.f.n)
+
     # ---- torch transport --------------------------------------------------------
+    def _torch_compact(self, slot, total_batch, form):
+        """The stages of fosphor_amd_exchange_compact with torch.distributed as the collective, on views of the wire buffers.  To be
+        called with the count / merge stream current; returns when the slot holds the summed counts."""
+        import torch.distributed as dist
+        torch, f = self.torch, self.f
+        _, s, m = self.views[slot]
+        f.set_partial_slot(slot)		# (retiring the frame before may have left the other slot current)
+        if form == "sparse16":
+            rv = f.wire_mask(total_batch, self.world, self.rank)
+            if rv:
+                raise RuntimeError("wire_mask -> %d" % rv)
+            w = f.wire_info()
+            masks = wrap_device_array(w.d_masks, (self.world, w.mask_words), torch.int32)
+            dist.all_gather(list(masks.unbind(0)), masks[self.rank].clone(), group=self.group)
+        rv, w = f.wire_pack(total_batch, form, self.world)
+        if rv:
+            raise RuntimeError("wire_pack -> %d" % rv)
+        works = [dist.all_reduce(s, op=dist.ReduceOp.SUM, group=self.group, async_op=True),
+                 dist.all_reduce(m, op=dist.ReduceOp.MAX, group=self.group, async_op=True)]
+        if w.n_words:
+            words = wrap_device_array(w.d_words, (w.n_words,), torch.int32)	# (halves below 2^16: the int32 sum is the uint32 sum)
+            works.append(dist.all_reduce(words, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+        for k in works:
+            k.wait()
+        rv = f.wire_unpack()
+        if rv:
+            raise RuntimeError("wire_unpack -> %d" % rv)
+
+    def _merge(self, slot, total):
+        self.f.set_partial_slot(slot)
+        rv = self.f.merge(total)
+        if rv:
+            raise RuntimeError("merge -> %d" % rv)
+
     def _retire(self):
         if self.pending is None:
             return
         works, slot, total = self.pending
         for w in works:
             w.wait()
-        self.f.set_partial_slot(slot)
-        rv = self.f.merge(total)
-        if rv:
-            raise RuntimeError("merge -> %d" % rv)
+        self._merge(slot, total)
         self.pending = None
 
     def frame(self, d_samples_local, total_batch, overlap=False, wait_producer=True, overlap_ratio=1):
@@ -230,6 +342,13 @@ class ShardedFosphor:
                 rv = self.f.accumulate_device(d_samples_local, n, off, total_batch, overlap_ratio)	# K1 here, K2 on stream_b
                 if rv:
                     raise RuntimeError("accumulate_device -> %d" % rv)
+            form = self.wire_form(total_batch)
+            if form != "u32":
+                with torch.cuda.stream(self.stream_b):
+                    self._retire()
+                    self._torch_compact(slot, total_batch, form)
+                    self._merge(slot, total_batch)
+                return
             with torch.cuda.stream(self.stream_b):
                 import torch.distributed as dist
                 h, s, m = self.views[slot]
@@ -247,7 +366,15 @@ class ShardedFosphor:
         rv = self.f.accumulate_device(d_samples_local, n, off, total_batch, overlap_ratio)
         if rv:
             raise RuntimeError("accumulate_device -> %d" % rv)
-        if self.comm is not None:
+        form = self.wire_form(total_batch) if self.comm is not None else "u32"
+        if form != "u32":
+            # compact wire: the counts are all-reduced in every case; a sliced instance still merges only its slice
+            rv = self.f.exchange_compact(self.comm.h, total_batch, form, self.world, self.rank)
+            if self.sliced:
+                rv = rv or self.f.merge_sliced(total_batch, self.world, self.rank)
+            else:
+                rv = rv or self.f.merge(total_batch)
+        elif self.comm is not None:
             if self.sliced:
                 rv = self.f.exchange_sliced(self.comm.h, self.world, self.rank)
                 rv = rv or self.f.merge_sliced(total_batch, self.world, self.rank)
