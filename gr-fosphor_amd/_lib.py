@@ -80,6 +80,25 @@ class ViewOut(C.Structure):
                 ("wf_color", ViewColor), ("histo_color", ViewColor)]
 
 
+class DetectCfg(C.Structure):
+    """struct fosphor_amd_detect_cfg (include/fosphor_amd_detect.h)"""
+    _fields_ = [("trace", C.c_int), ("first_bin", C.c_int), ("n_cols", C.c_int), ("floor_mode", C.c_int),
+                ("floor_q", C.c_float), ("margin_y", C.c_float), ("threshold_y", C.c_float),
+                ("max_gap", C.c_int), ("min_cols", C.c_int)]
+
+
+class DetectResult(C.Structure):
+    """struct fosphor_amd_detect_result"""
+    _fields_ = [("n_found", C.c_int32), ("n_written", C.c_int32), ("floor_bin", C.c_int32),
+                ("floor_y", C.c_float), ("threshold_y", C.c_float)]
+
+
+class Band(C.Structure):
+    """struct fosphor_amd_band"""
+    _fields_ = [("first", C.c_int32), ("last", C.c_int32), ("peak_col", C.c_int32),
+                ("peak_y", C.c_float), ("power_y", C.c_float)]
+
+
 class Wire(C.Structure):
     """struct fosphor_amd_wire (include/fosphor_amd_wire.h)"""
     _fields_ = [("d_masks", C.c_void_p), ("mask_words", C.c_int), ("world", C.c_int), ("d_words", C.c_void_p),
@@ -164,6 +183,13 @@ SIGNATURES = {
     "fosphor_amd_view_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 4)]),
     "fosphor_amd_view_span": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fosphor_amd_view_from_render": (C.c_int, [C.c_int, C.c_int, C.POINTER(Render), C.c_int, C.c_int, C.POINTER(View)]),
+    # include/fosphor_amd_detect.h
+    "fosphor_amd_percentiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fosphor_amd_detect": (C.c_int, [C.c_void_p, C.POINTER(DetectCfg), C.c_void_p, C.c_void_p, C.c_int]),
+    "fosphor_amd_detect_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 3)]),
+    "fosphor_amd_detect_bin_y": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "fosphor_amd_detect_bands_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                C.POINTER(C.c_int)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

@@ -338,6 +338,64 @@ class Fosphor:
             raise RuntimeError("fosphor_amd_view_stats -> %d" % rv)
         return dict(zip(self.VIEW_FORMS, list(st)))
 
+    TRACES = {"live": 0, "maxhold": 1}		# FOSPHOR_AMD_TRACE_* (include/fosphor_amd_detect.h)
+    FLOOR_MODES = {"absolute": 0, "percentile": 1}	# FOSPHOR_AMD_FLOOR_*
+    DETECT_STATS = ("percentiles", "floor", "bands")
+    DETECT_MAX_Q = 4
+    DETECT_LANES = 1024				# FOSPHOR_AMD_DETECT_LANES
+    BAND_DTYPE = np.dtype([("first", "<i4"), ("last", "<i4"), ("peak_col", "<i4"), ("peak_y", "<f4"), ("power_y", "<f4")])
+
+    def percentiles(self, q, bins=False):
+        """Per-column percentiles of the persistence histogram (fosphor_amd_percentiles): q is one value or up to 4 in ]0, 1].
+        Returns the y of each percentile's bin as a float32 numpy array [n_q][N] in fft-shifted column order (NaN where a column
+        is empty); bins=True: (y, bin), bin an int32 array of the same shape (-1 where a column is empty)."""
+        import torch
+        qa = np.ascontiguousarray(np.atleast_1d(q), dtype=np.float32).reshape(-1)
+        shape = (max(qa.size, 1), self.n)
+        d_y = torch.empty(shape, dtype=torch.float32, device="cuda")
+        d_bin = torch.empty(shape, dtype=torch.int32, device="cuda") if bins else None
+        rv = self.L.fosphor_amd_percentiles(self.h, qa.ctypes.data, qa.size, d_y.data_ptr(), d_bin.data_ptr() if bins else None)
+        if rv:
+            raise RuntimeError("fosphor_amd_percentiles -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        y = d_y.cpu().numpy()
+        return (y, d_bin.cpu().numpy()) if bins else y
+
+    def detect(self, trace="live", floor="percentile", floor_q=0.5, margin_db=6.0, threshold_y=0.0, max_gap=0, min_cols=1,
+               first_bin=0, n_cols=None, max_bands=1024):
+        """Occupied bands of the live or max-hold trace (fosphor_amd_detect) in the shifted columns [first_bin, first_bin + n_cols).
+        floor="percentile": the threshold is the window's noise floor (the lower median over its columns of the histogram's
+        floor_q percentile) plus margin_db (margin_db / 20 in y); floor="absolute": threshold_y.  Runs of up to max_gap columns
+        below the threshold inside a band are closed; bands shorter than min_cols are dropped.
+        Returns (result, bands): a dict with n_found, n_written, floor_bin, floor_y, threshold_y and a numpy structured array
+        (BAND_DTYPE: first, last, peak_col, peak_y, power_y) of the n_written = min(n_found, max_bands) bands."""
+        import torch
+        if trace not in self.TRACES:
+            raise ValueError("trace must be one of %s" % ", ".join(self.TRACES))
+        if floor not in self.FLOOR_MODES:
+            raise ValueError("floor must be one of %s" % ", ".join(self.FLOOR_MODES))
+        if n_cols is None:
+            n_cols = self.n - first_bin
+        cfg = _lib.DetectCfg(self.TRACES[trace], int(first_bin), int(n_cols), self.FLOOR_MODES[floor], float(floor_q),
+                             float(margin_db) / 20.0, float(threshold_y), int(max_gap), int(min_cols))
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_res = torch.empty(C.sizeof(_lib.DetectResult), dtype=torch.uint8, device="cuda")
+        d_bands = torch.empty(max(int(max_bands), 1) * self.BAND_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        rv = self.L.fosphor_amd_detect(self.h, C.byref(cfg), d_res.data_ptr(), d_bands.data_ptr(), int(max_bands))
+        if rv:
+            raise RuntimeError("fosphor_amd_detect -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        r = _lib.DetectResult.from_buffer_copy(d_res.cpu().numpy().tobytes())
+        res = {k: getattr(r, k) for k, _ in _lib.DetectResult._fields_}
+        bands = d_bands.cpu().numpy().view(self.BAND_DTYPE)[:res["n_written"]].copy()
+        return res, bands
+
+    def detect_stats(self):
+        """fosphor_amd_detect_stats as a dict: launches since the instance was made, by kernel (DETECT_STATS)"""
+        st = (C.c_longlong * 3)()
+        rv = self.L.fosphor_amd_detect_stats(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("fosphor_amd_detect_stats -> %d" % rv)
+        return dict(zip(self.DETECT_STATS, list(st)))
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

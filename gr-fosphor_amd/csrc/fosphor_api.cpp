@@ -187,6 +187,8 @@ struct fosphor
 	long long *d_dbg;			/* K1_TIMING builds only (FOSPHOR_AMD_K1_TIMING=1) */
 	uint32_t *d_palette;			/* colour-map scratch (fosphor_cmap.hip), allocated on first use */
 	long long view_forms[4];		/* view launches by form (fosphor_view.hip, fosphor_amd_view_stats) */
+	long long detect_stats[3];		/* detect launches by kernel (fosphor_detect.hip, fosphor_amd_detect_stats) */
+	void     *d_detect;			/* scratch of fosphor_detect.hip, allocated on first use; the instance never reads it */
 	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
 	struct {
 		uint32_t *d_masks;		/* [mask_cap][rows / 32] presence bits, one part per rank */
@@ -435,6 +437,7 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_chunk_sum); (void)hipFree(self->d_chunk_max);
 	(void)hipFree(self->d_rise);
 	(void)hipFree(self->d_palette);
+	(void)hipFree(self->d_detect);
 	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
 	(void)hipFree(self->wire.d_live); (void)hipFree(self->wire.d_words);
 	if (self->wire.h_live) (void)hipHostFree(self->wire.h_live);
@@ -2397,6 +2400,20 @@ extern "C" void fosphor_amd_priv_power(struct fosphor *self, float *scale, float
 extern "C" long long *fosphor_amd_priv_view_forms(struct fosphor *self)
 {
 	return self->view_forms;
+}
+
+/* private accessors for fosphor_detect.hip: its launch counters, and its scratch of a size that file fixes */
+extern "C" long long *fosphor_amd_priv_detect_stats(struct fosphor *self)
+{
+	return self->detect_stats;
+}
+
+extern "C" int fosphor_amd_priv_detect_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
+{
+	if (!self->d_detect && hipMalloc(&self->d_detect, bytes) != hipSuccess)
+		return -EIO;
+	*d_scratch = self->d_detect;
+	return 0;
 }
 
 /* ------------------------------------------------------------------------ */
