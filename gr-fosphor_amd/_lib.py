@@ -99,6 +99,28 @@ class Band(C.Structure):
                 ("peak_y", C.c_float), ("power_y", C.c_float)]
 
 
+class MaskChannel(C.Structure):
+    """struct fosphor_amd_mask_channel (include/fosphor_amd_mask.h)"""
+    _fields_ = [("first", C.c_int32), ("last", C.c_int32)]
+
+
+class MaskCfg(C.Structure):
+    """struct fosphor_amd_mask_cfg"""
+    _fields_ = [("first_bin", C.c_int), ("n_cols", C.c_int), ("rows", C.c_int), ("min_cols", C.c_int),
+                ("n_channels", C.c_int), ("channels", MaskChannel * 8)]
+
+
+class MaskRow(C.Structure):
+    """struct fosphor_amd_mask_row"""
+    _fields_ = [("n_over", C.c_int32), ("n_under", C.c_int32), ("first_col", C.c_int32), ("last_col", C.c_int32),
+                ("peak_col", C.c_int32), ("peak_over", C.c_float)]
+
+
+class MaskResult(C.Structure):
+    """struct fosphor_amd_mask_result"""
+    _fields_ = [("n_triggered", C.c_int32), ("n_written", C.c_int32), ("newest", C.c_int32), ("oldest", C.c_int32)]
+
+
 class Wire(C.Structure):
     """struct fosphor_amd_wire (include/fosphor_amd_wire.h)"""
     _fields_ = [("d_masks", C.c_void_p), ("mask_words", C.c_int), ("world", C.c_int), ("d_words", C.c_void_p),
@@ -190,6 +212,13 @@ SIGNATURES = {
     "fosphor_amd_detect_bin_y": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "fosphor_amd_detect_bands_host": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                 C.POINTER(C.c_int)]),
+    # include/fosphor_amd_mask.h
+    "fosphor_amd_mask_scan": (C.c_int, [C.c_void_p, C.POINTER(MaskCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_void_p]),
+    "fosphor_amd_mask_from_trace": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "fosphor_amd_mask_from_points": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "fosphor_amd_mask_row_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(MaskRow)]),
+    "fosphor_amd_mask_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 4)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

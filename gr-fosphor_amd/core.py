@@ -396,6 +396,90 @@ class Fosphor:
             raise RuntimeError("fosphor_amd_detect_stats -> %d" % rv)
         return dict(zip(self.DETECT_STATS, list(st)))
 
+    MASK_STATS = ("scans", "from_trace", "form_rows", "form_shared")
+    MASK_MAX_EVENTS = 65536				# FOSPHOR_AMD_MASK_MAX_EVENTS (include/fosphor_amd_mask.h)
+    MASK_MAX_CHANNELS = 8				# FOSPHOR_MAX_CHANNELS
+    MASK_STRIP = 1024					# FOSPHOR_AMD_MASK_STRIP
+    MASK_ROW_DTYPE = np.dtype([("n_over", "<i4"), ("n_under", "<i4"), ("first_col", "<i4"), ("last_col", "<i4"),
+                               ("peak_col", "<i4"), ("peak_over", "<f4")])
+
+    def mask_scan(self, upper=None, lower=None, first_bin=0, n_cols=None, rows=None, min_cols=1, channels=(), max_events=1024,
+                  want_rows=True):
+        """Frequency-mask trigger and channel power over the newest `rows` waterfall rows (fosphor_amd_mask_scan).  upper, lower:
+        float32 device tensors [N] indexed by fft-shifted column, or None (never violated); the window is the shifted columns
+        [first_bin, first_bin + n_cols).  A row triggers when at least min_cols of its columns lie over upper or under lower.
+        channels: up to 8 (first, last) pairs of shifted columns, inclusive.  max_events=0: no event list.
+        Returns (result, rows, events, power), numpy copies: a dict with n_triggered, n_written, newest, oldest; a structured
+        array (MASK_ROW_DTYPE), one record per scanned row, j = 0 the newest (None with want_rows=False); the int32 array of the
+        n_written triggered j in ascending order; the float32 array [n_channels][rows] of channel power in y."""
+        import torch
+        if n_cols is None:
+            n_cols = self.n - first_bin
+        if rows is None:
+            rows = self.wf_rows
+        channels = [(int(a), int(b)) for a, b in channels]
+        if len(channels) > self.MASK_MAX_CHANNELS:
+            raise ValueError("at most %d channels" % self.MASK_MAX_CHANNELS)
+        for name, t in (("upper", upper), ("lower", lower)):
+            if t is not None and (str(t.dtype) != "torch.float32" or t.numel() != self.n or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32 device tensor of %d elements" % (name, self.n))
+        cfg = _lib.MaskCfg(int(first_bin), int(n_cols), int(rows), int(min_cols), len(channels))
+        for k, (a, b) in enumerate(channels):
+            cfg.channels[k].first, cfg.channels[k].last = a, b
+        nr = max(int(rows), 1)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_res = torch.empty(C.sizeof(_lib.MaskResult), dtype=torch.uint8, device="cuda")
+        d_rows = torch.empty(nr * self.MASK_ROW_DTYPE.itemsize, dtype=torch.uint8, device="cuda") if want_rows else None
+        d_ev = torch.empty(int(max_events), dtype=torch.int32, device="cuda") if max_events > 0 else None
+        d_pow = torch.empty((len(channels), nr), dtype=torch.float32, device="cuda") if channels else None
+        torch.cuda.synchronize()			# the limits were written on torch's stream
+        rv = self.L.fosphor_amd_mask_scan(self.h, C.byref(cfg), _ptr(upper) if upper is not None else None,
+                                          _ptr(lower) if lower is not None else None, d_res.data_ptr(),
+                                          d_rows.data_ptr() if want_rows else None, d_ev.data_ptr() if d_ev is not None else None,
+                                          int(max_events), d_pow.data_ptr() if channels else None)
+        if rv:
+            raise RuntimeError("fosphor_amd_mask_scan -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        r = _lib.MaskResult.from_buffer_copy(d_res.cpu().numpy().tobytes())
+        res = {k: getattr(r, k) for k, _ in _lib.MaskResult._fields_}
+        recs = d_rows.cpu().numpy().view(self.MASK_ROW_DTYPE).copy() if want_rows else None
+        events = d_ev.cpu().numpy()[:res["n_written"]].copy() if d_ev is not None else np.zeros(0, np.int32)
+        power = d_pow.cpu().numpy() if channels else np.zeros((0, nr), np.float32)
+        return res, recs, events, power
+
+    def mask_from_trace(self, trace="maxhold", margin_db=6.0, spread_cols=0):
+        """A limit line learnt from the live or max-hold trace (fosphor_amd_mask_from_trace): per shifted column the greatest y of
+        the trace within spread_cols columns, plus margin_db (margin_db / 20 in y).  Returns a float32 device tensor [N], an
+        `upper` for mask_scan."""
+        import torch
+        if trace not in self.TRACES:
+            raise ValueError("trace must be one of %s" % ", ".join(self.TRACES))
+        d_out = torch.empty(self.n, dtype=torch.float32, device="cuda")
+        rv = self.L.fosphor_amd_mask_from_trace(self.h, self.TRACES[trace], float(margin_db) / 20.0, int(spread_cols), d_out.data_ptr())
+        if rv:
+            raise RuntimeError("fosphor_amd_mask_from_trace -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return d_out
+
+    def mask_from_points(self, cols, ys):
+        """A piecewise-linear limit line through the points (cols[k], ys[k]), cols strictly ascending in shifted-column units
+        (fosphor_amd_mask_from_points; computed on the host).  Returns a float32 numpy array [N]."""
+        c = np.ascontiguousarray(cols, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(ys, dtype=np.float32).reshape(-1)
+        if c.size != y.size:
+            raise ValueError("cols and ys differ in length")
+        out = np.empty(self.n, np.float32)
+        rv = self.L.fosphor_amd_mask_from_points(self.n, c.ctypes.data, y.ctypes.data, c.size, out.ctypes.data)
+        if rv:
+            raise RuntimeError("fosphor_amd_mask_from_points -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return out
+
+    def mask_stats(self):
+        """fosphor_amd_mask_stats as a dict: calls and launches since the instance was made, by kind and form (MASK_STATS)"""
+        st = (C.c_longlong * 4)()
+        rv = self.L.fosphor_amd_mask_stats(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("fosphor_amd_mask_stats -> %d" % rv)
+        return dict(zip(self.MASK_STATS, list(st)))
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

@@ -189,6 +189,8 @@ struct fosphor
 	long long view_forms[4];		/* view launches by form (fosphor_view.hip, fosphor_amd_view_stats) */
 	long long detect_stats[3];		/* detect launches by kernel (fosphor_detect.hip, fosphor_amd_detect_stats) */
 	void     *d_detect;			/* scratch of fosphor_detect.hip, allocated on first use; the instance never reads it */
+	long long mask_stats[4];		/* mask launches by kind and form (fosphor_mask.hip, fosphor_amd_mask_stats) */
+	void     *d_mask;			/* scratch of fosphor_mask.hip, allocated on first use; the instance never reads it */
 	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
 	struct {
 		uint32_t *d_masks;		/* [mask_cap][rows / 32] presence bits, one part per rank */
@@ -438,6 +440,7 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_rise);
 	(void)hipFree(self->d_palette);
 	(void)hipFree(self->d_detect);
+	(void)hipFree(self->d_mask);
 	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
 	(void)hipFree(self->wire.d_live); (void)hipFree(self->wire.d_words);
 	if (self->wire.h_live) (void)hipHostFree(self->wire.h_live);
@@ -2413,6 +2416,20 @@ extern "C" int fosphor_amd_priv_detect_scratch(struct fosphor *self, size_t byte
 	if (!self->d_detect && hipMalloc(&self->d_detect, bytes) != hipSuccess)
 		return -EIO;
 	*d_scratch = self->d_detect;
+	return 0;
+}
+
+/* private accessors for fosphor_mask.hip: its launch counters, and its scratch of a size that the instance's geometry fixes */
+extern "C" long long *fosphor_amd_priv_mask_stats(struct fosphor *self)
+{
+	return self->mask_stats;
+}
+
+extern "C" int fosphor_amd_priv_mask_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
+{
+	if (!self->d_mask && hipMalloc(&self->d_mask, bytes) != hipSuccess)
+		return -EIO;
+	*d_scratch = self->d_mask;
 	return 0;
 }
 
