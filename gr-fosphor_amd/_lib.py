@@ -121,6 +121,26 @@ class MaskResult(C.Structure):
     _fields_ = [("n_triggered", C.c_int32), ("n_written", C.c_int32), ("newest", C.c_int32), ("oldest", C.c_int32)]
 
 
+class BurstCfg(C.Structure):
+    """struct fosphor_amd_burst_cfg (include/fosphor_amd_burst.h)"""
+    _fields_ = [("first_bin", C.c_int), ("n_cols", C.c_int), ("rows", C.c_int), ("threshold_y", C.c_float),
+                ("max_gap_cols", C.c_int), ("max_gap_rows", C.c_int), ("min_rows", C.c_int), ("min_cols", C.c_int),
+                ("max_runs", C.c_int)]
+
+
+class Burst(C.Structure):
+    """struct fosphor_amd_burst"""
+    _fields_ = [("newest", C.c_int32), ("oldest", C.c_int32), ("first_col", C.c_int32), ("last_col", C.c_int32),
+                ("n_cells", C.c_int32), ("peak_row", C.c_int32), ("peak_col", C.c_int32), ("peak_y", C.c_float),
+                ("energy_y", C.c_float), ("flags", C.c_uint32)]
+
+
+class BurstResult(C.Structure):
+    """struct fosphor_amd_burst_result"""
+    _fields_ = [("n_runs", C.c_int32), ("n_components", C.c_int32), ("n_found", C.c_int32), ("n_written", C.c_int32),
+                ("overflow", C.c_int32)]
+
+
 class Wire(C.Structure):
     """struct fosphor_amd_wire (include/fosphor_amd_wire.h)"""
     _fields_ = [("d_masks", C.c_void_p), ("mask_words", C.c_int), ("world", C.c_int), ("d_words", C.c_void_p),
@@ -219,6 +239,11 @@ SIGNATURES = {
     "fosphor_amd_mask_from_points": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "fosphor_amd_mask_row_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(MaskRow)]),
     "fosphor_amd_mask_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 4)]),
+    # include/fosphor_amd_burst.h
+    "fosphor_amd_bursts": (C.c_int, [C.c_void_p, C.POINTER(BurstCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "fosphor_amd_bursts_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(BurstCfg), C.POINTER(BurstResult),
+                                          C.c_void_p, C.c_int]),
+    "fosphor_amd_burst_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 10)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

@@ -480,6 +480,63 @@ class Fosphor:
             raise RuntimeError("fosphor_amd_mask_stats -> %d" % rv)
         return dict(zip(self.MASK_STATS, list(st)))
 
+    BURST_STATS = ("calls", "overflows", "k_count", "k_rows", "k_scan", "k_init", "k_write", "k_link", "k_reduce", "k_emit")
+    BURST_MAX_RUNS = 1 << 20				# FOSPHOR_AMD_BURST_MAX_RUNS (include/fosphor_amd_burst.h)
+    BURST_MAX_BURSTS = 65536				# FOSPHOR_AMD_BURST_MAX_BURSTS
+    BURST_STRIP = 1024					# FOSPHOR_AMD_BURST_STRIP
+    BURST_FLAGS = {"on": 1, "cut": 2, "first_col": 4, "last_col": 8}	# FOSPHOR_AMD_BURST_ON / CUT / FIRST_COL / LAST_COL
+    BURST_DTYPE = np.dtype([("newest", "<i4"), ("oldest", "<i4"), ("first_col", "<i4"), ("last_col", "<i4"), ("n_cells", "<i4"),
+                            ("peak_row", "<i4"), ("peak_col", "<i4"), ("peak_y", "<f4"), ("energy_y", "<f4"), ("flags", "<u4")])
+
+    def bursts(self, threshold, first_bin=0, n_cols=None, rows=None, max_gap_cols=0, max_gap_rows=0, min_rows=1, min_cols=1,
+               max_bursts=1024, max_runs=1 << 16):
+        """Bursts in time and frequency over the newest `rows` waterfall rows (fosphor_amd_bursts): the connected regions of the
+        cells with y > threshold, after gaps of up to max_gap_cols columns along a row are closed and runs up to max_gap_rows + 1
+        rows apart that overlap in column are joined.  threshold: a float (in y, for every column), a length-N array indexed by
+        fft-shifted column (uploaded), or a float32 device tensor [N] as mask_scan takes its limits.  The window is the shifted
+        columns [first_bin, first_bin + n_cols).
+        Returns (result, bursts): a dict with n_runs, n_components, n_found, n_written, overflow, and a numpy structured array
+        (BURST_DTYPE) of the n_written records in ascending root order (newest first).  overflow = 1 (more than max_runs runs: the
+        threshold sits in the noise) gives no records."""
+        import torch
+        if n_cols is None:
+            n_cols = self.n - first_bin
+        if rows is None:
+            rows = min(self.wf_rows, 65536)
+        thr_y, d_thr = 0.0, None
+        if hasattr(threshold, "data_ptr"):
+            d_thr = threshold
+        elif np.ndim(threshold) == 0:
+            thr_y = float(threshold)
+        else:
+            d_thr = torch.from_numpy(np.ascontiguousarray(threshold, dtype=np.float32).reshape(-1)).cuda()
+        if d_thr is not None and (str(d_thr.dtype) != "torch.float32" or d_thr.numel() != self.n or not d_thr.is_cuda
+                                  or not d_thr.is_contiguous()):
+            raise ValueError("threshold must be a float, %d values, or a contiguous float32 device tensor of as many" % self.n)
+        cfg = _lib.BurstCfg(int(first_bin), int(n_cols), int(rows), thr_y, int(max_gap_cols), int(max_gap_rows), int(min_rows),
+                            int(min_cols), int(max_runs))
+        nb = max(int(max_bursts), 1)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_res = torch.empty(C.sizeof(_lib.BurstResult), dtype=torch.uint8, device="cuda")
+        d_out = torch.empty(nb * self.BURST_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()			# the threshold was written on torch's stream
+        rv = self.L.fosphor_amd_bursts(self.h, C.byref(cfg), d_thr.data_ptr() if d_thr is not None else None, d_res.data_ptr(),
+                                       d_out.data_ptr(), int(max_bursts))
+        if rv:
+            raise RuntimeError("fosphor_amd_bursts -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        r = _lib.BurstResult.from_buffer_copy(d_res.cpu().numpy().tobytes())
+        res = {k: getattr(r, k) for k, _ in _lib.BurstResult._fields_}
+        recs = d_out.cpu().numpy().view(self.BURST_DTYPE)[:res["n_written"]].copy()
+        return res, recs
+
+    def burst_stats(self):
+        """fosphor_amd_burst_stats as a dict: calls, overflows and launches by kernel since the instance was made (BURST_STATS)"""
+        st = (C.c_longlong * 10)()
+        rv = self.L.fosphor_amd_burst_stats(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("fosphor_amd_burst_stats -> %d" % rv)
+        return dict(zip(self.BURST_STATS, list(st)))
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

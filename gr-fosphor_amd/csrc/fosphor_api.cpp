@@ -191,6 +191,9 @@ struct fosphor
 	void     *d_detect;			/* scratch of fosphor_detect.hip, allocated on first use; the instance never reads it */
 	long long mask_stats[4];		/* mask launches by kind and form (fosphor_mask.hip, fosphor_amd_mask_stats) */
 	void     *d_mask;			/* scratch of fosphor_mask.hip, allocated on first use; the instance never reads it */
+	long long burst_stats[10];		/* burst calls and launches by kernel (fosphor_burst.hip, fosphor_amd_burst_stats) */
+	void     *d_burst[2];			/* scratch of fosphor_burst.hip: [0] by rows and strips, [1] by runs; grown on demand, never read here */
+	size_t    burst_cap[2];
 	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
 	struct {
 		uint32_t *d_masks;		/* [mask_cap][rows / 32] presence bits, one part per rank */
@@ -441,6 +444,7 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_palette);
 	(void)hipFree(self->d_detect);
 	(void)hipFree(self->d_mask);
+	(void)hipFree(self->d_burst[0]); (void)hipFree(self->d_burst[1]);
 	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
 	(void)hipFree(self->wire.d_live); (void)hipFree(self->wire.d_words);
 	if (self->wire.h_live) (void)hipHostFree(self->wire.h_live);
@@ -2430,6 +2434,29 @@ extern "C" int fosphor_amd_priv_mask_scratch(struct fosphor *self, size_t bytes,
 	if (!self->d_mask && hipMalloc(&self->d_mask, bytes) != hipSuccess)
 		return -EIO;
 	*d_scratch = self->d_mask;
+	return 0;
+}
+
+/* private accessors for fosphor_burst.hip: its counters, and its two scratch buffers, which only grow (the caller has drained the
+ * stream of every launch that used the old one before it asks for more) */
+extern "C" long long *fosphor_amd_priv_burst_stats(struct fosphor *self)
+{
+	return self->burst_stats;
+}
+
+extern "C" int fosphor_amd_priv_burst_scratch(struct fosphor *self, int which, size_t bytes, void **d_scratch)
+{
+	if (which < 0 || which > 1)
+		return -EINVAL;
+	if (bytes > self->burst_cap[which]) {
+		(void)hipFree(self->d_burst[which]);
+		self->d_burst[which] = nullptr;
+		self->burst_cap[which] = 0;
+		if (hipMalloc(&self->d_burst[which], bytes) != hipSuccess)
+			return -EIO;
+		self->burst_cap[which] = bytes;
+	}
+	*d_scratch = self->d_burst[which];
 	return 0;
 }
 
