@@ -141,6 +141,12 @@ class BurstResult(C.Structure):
                 ("overflow", C.c_int32)]
 
 
+class ExtractJob(C.Structure):
+    """struct fosphor_amd_extract_job (include/fosphor_amd_extract.h)"""
+    _fields_ = [("first", C.c_int64), ("out_offset", C.c_int64), ("n_out", C.c_int32), ("decim", C.c_int32),
+                ("phase_inc", C.c_uint32), ("phase0", C.c_uint32), ("taps_offset", C.c_int32), ("n_taps", C.c_int32)]
+
+
 class Wire(C.Structure):
     """struct fosphor_amd_wire (include/fosphor_amd_wire.h)"""
     _fields_ = [("d_masks", C.c_void_p), ("mask_words", C.c_int), ("world", C.c_int), ("d_words", C.c_void_p),
@@ -244,6 +250,15 @@ SIGNATURES = {
     "fosphor_amd_bursts_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(BurstCfg), C.POINTER(BurstResult),
                                           C.c_void_p, C.c_int]),
     "fosphor_amd_burst_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 10)]),
+    # include/fosphor_amd_extract.h
+    "fosphor_amd_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_int64]),
+    "fosphor_amd_extract_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_int64]),
+    "fosphor_amd_extract_design": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "fosphor_amd_extract_from_burst": (C.c_int, [C.POINTER(Burst), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double,
+                                                 C.POINTER(ExtractJob), C.POINTER(C.c_int)]),
+    "fosphor_amd_extract_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 6)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

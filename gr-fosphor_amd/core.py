@@ -537,6 +537,84 @@ class Fosphor:
             raise RuntimeError("fosphor_amd_burst_stats -> %d" % rv)
         return dict(zip(self.BURST_STATS, list(st)))
 
+    EXTRACT_STATS = ("calls", "k_tile", "k_wave", "jobs_tile", "jobs_wave", "samples")
+    EXTRACT_MAX_JOBS = 4096				# FOSPHOR_AMD_EXTRACT_MAX_JOBS (include/fosphor_amd_extract.h)
+    EXTRACT_MAX_DECIM = 1024				# FOSPHOR_AMD_EXTRACT_MAX_DECIM
+    EXTRACT_MAX_TAPS = 8192				# FOSPHOR_AMD_EXTRACT_MAX_TAPS
+    EXTRACT_TILE_OUT = 256				# FOSPHOR_AMD_EXTRACT_TILE_OUT
+    EXTRACT_TILE_LDS = 6656				# FOSPHOR_AMD_EXTRACT_TILE_LDS
+    EXTRACT_WAVE_OUT = 4				# FOSPHOR_AMD_EXTRACT_WAVE_OUT
+    EXTRACT_DTYPE = np.dtype([("first", "<i8"), ("out_offset", "<i8"), ("n_out", "<i4"), ("decim", "<i4"), ("phase_inc", "<u4"),
+                              ("phase0", "<u4"), ("taps_offset", "<i4"), ("n_taps", "<i4")])
+
+    @staticmethod
+    def extract_form(decim, n_taps):
+        """the kernel form of a job, "tile" or "wave": a function of (D, T) alone (include/fosphor_amd_extract.h)"""
+        row = (Fosphor.EXTRACT_TILE_OUT + (int(n_taps) - 1) // int(decim) + 1) | 1
+        return "tile" if int(decim) * row <= Fosphor.EXTRACT_TILE_LDS else "wave"
+
+    @staticmethod
+    def extract_design(decim, n_taps, guard=0.8):
+        """fosphor_amd_extract_design: the Hamming-windowed sinc low-pass of n_taps float32 taps for decimation decim, cutoff
+        guard / (2 * decim) cycles per sample; the taps sum to 1 and are symmetric"""
+        out = np.empty(max(int(n_taps), 1), np.float32)
+        rv = _lib.load().fosphor_amd_extract_design(int(decim), int(n_taps), float(guard), out.ctypes.data)
+        if rv:
+            raise ValueError("fosphor_amd_extract_design -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return out
+
+    def extract_from_burst(self, burst, newest_first_sample, row_hop, max_decim=64, guard=0.8):
+        """fosphor_amd_extract_from_burst: (job, n_taps) for one record of bursts().  newest_first_sample: the index in the
+        caller's stream of the first sample of the spectrum in ring row 0; row_hop: samples between consecutive rows' spectra.
+        job is a one-element EXTRACT_DTYPE array with out_offset = taps_offset = 0: the caller places it."""
+        b = _lib.Burst.from_buffer_copy(np.asarray(burst, self.BURST_DTYPE).reshape(1).tobytes())
+        job, taps = _lib.ExtractJob(), C.c_int(0)
+        rv = self.L.fosphor_amd_extract_from_burst(C.byref(b), self.n, int(newest_first_sample), int(row_hop), int(max_decim),
+                                                   float(guard), C.byref(job), C.byref(taps))
+        if rv:
+            raise ValueError("fosphor_amd_extract_from_burst -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return np.frombuffer(bytes(job), self.EXTRACT_DTYPE).copy(), taps.value
+
+    def extract(self, d_iq, jobs, taps, iq_format=None, n_samples=None):
+        """Baseband IQ of up to 4096 jobs in one call (fosphor_amd_extract): mix, real FIR, decimate, over samples that are
+        already in device memory.  d_iq: a contiguous device tensor of the stream (complex64 / float32 pairs for fp32, int16 or
+        float16 pairs for sc16 / fp16) or a raw device pointer with n_samples; jobs: an EXTRACT_DTYPE array (out_offset is
+        honoured; ranges must not overlap); taps: float32 values (uploaded) or a float32 device tensor, addressed by the jobs'
+        taps_offset / n_taps; iq_format: "fp32" / "fp16" / "sc16", a FOSPHOR_AMD_IQ_* number, or None for the instance's.
+        Returns a list with one torch complex64 view per job, into one device buffer."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.EXTRACT_DTYPE)
+        fmt = -1 if iq_format is None else IQ_FORMATS[iq_format] if isinstance(iq_format, str) else int(iq_format)
+        if n_samples is None:
+            if not hasattr(d_iq, "numel"):
+                raise ValueError("a raw device pointer needs n_samples")
+            if not d_iq.is_contiguous():
+                raise ValueError("d_iq must be contiguous")
+            n_samples = d_iq.numel() if d_iq.is_complex() else d_iq.numel() // 2
+        if hasattr(taps, "data_ptr"):
+            d_taps = taps
+            if d_taps.dtype != torch.float32 or not d_taps.is_cuda or not d_taps.is_contiguous():
+                raise ValueError("taps must be float32 values or a contiguous float32 device tensor")
+        else:
+            d_taps = torch.from_numpy(np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)).cuda()
+        cap = int((jobs["out_offset"] + jobs["n_out"]).max()) if jobs.size else 0
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 1), dtype=torch.complex64, device="cuda")
+        torch.cuda.synchronize()			# the taps (and the caller's samples) were written on torch's stream
+        rv = self.L.fosphor_amd_extract(self.h, _ptr(d_iq), int(n_samples), fmt, jobs.ctypes.data, int(jobs.size),
+                                        d_taps.data_ptr(), int(d_taps.numel()), d_out.data_ptr(), cap)
+        if rv:
+            raise RuntimeError("fosphor_amd_extract -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return [d_out[int(j["out_offset"]):int(j["out_offset"]) + int(j["n_out"])] for j in jobs]
+
+    def extract_stats(self):
+        """fosphor_amd_extract_stats as a dict: calls, launches and jobs by kernel form, input samples spanned (EXTRACT_STATS)"""
+        st = (C.c_longlong * 6)()
+        rv = self.L.fosphor_amd_extract_stats(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("fosphor_amd_extract_stats -> %d" % rv)
+        return dict(zip(self.EXTRACT_STATS, list(st)))
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

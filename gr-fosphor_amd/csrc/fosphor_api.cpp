@@ -194,6 +194,9 @@ struct fosphor
 	long long burst_stats[10];		/* burst calls and launches by kernel (fosphor_burst.hip, fosphor_amd_burst_stats) */
 	void     *d_burst[2];			/* scratch of fosphor_burst.hip: [0] by rows and strips, [1] by runs; grown on demand, never read here */
 	size_t    burst_cap[2];
+	long long extract_stats[6];		/* extract calls, launches and jobs by form, samples (fosphor_extract.hip, fosphor_amd_extract_stats) */
+	void     *d_extract;			/* job table of fosphor_extract.hip, grown on demand; the instance never reads it */
+	size_t    extract_cap;
 	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
 	struct {
 		uint32_t *d_masks;		/* [mask_cap][rows / 32] presence bits, one part per rank */
@@ -445,6 +448,7 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_detect);
 	(void)hipFree(self->d_mask);
 	(void)hipFree(self->d_burst[0]); (void)hipFree(self->d_burst[1]);
+	(void)hipFree(self->d_extract);
 	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
 	(void)hipFree(self->wire.d_live); (void)hipFree(self->wire.d_words);
 	if (self->wire.h_live) (void)hipHostFree(self->wire.h_live);
@@ -2458,6 +2462,32 @@ extern "C" int fosphor_amd_priv_burst_scratch(struct fosphor *self, int which, s
 	}
 	*d_scratch = self->d_burst[which];
 	return 0;
+}
+
+/* private accessors for fosphor_extract.hip: its counters, its job table, which only grows (every call drains the stream before it
+ * returns, so no launch reads the old one), and the format -1 stands for */
+extern "C" long long *fosphor_amd_priv_extract_stats(struct fosphor *self)
+{
+	return self->extract_stats;
+}
+
+extern "C" int fosphor_amd_priv_extract_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
+{
+	if (bytes > self->extract_cap) {
+		(void)hipFree(self->d_extract);
+		self->d_extract = nullptr;
+		self->extract_cap = 0;
+		if (hipMalloc(&self->d_extract, bytes) != hipSuccess)
+			return -EIO;
+		self->extract_cap = bytes;
+	}
+	*d_scratch = self->d_extract;
+	return 0;
+}
+
+extern "C" int fosphor_amd_priv_iq_format(struct fosphor *self)
+{
+	return self->iq_format;
 }
 
 /* ------------------------------------------------------------------------ */
