@@ -147,6 +147,17 @@ class ExtractJob(C.Structure):
                 ("phase_inc", C.c_uint32), ("phase0", C.c_uint32), ("taps_offset", C.c_int32), ("n_taps", C.c_int32)]
 
 
+class MeasureJob(C.Structure):
+    """struct fosphor_amd_measure_job (include/fosphor_amd_measure.h)"""
+    _fields_ = [("offset", C.c_int64), ("n", C.c_int32), ("threshold", C.c_float)]
+
+
+class MeasureValues(C.Structure):
+    """struct fosphor_amd_measure_values"""
+    _fields_ = [(k, C.c_double) for k in ("mean_power", "mean_db", "peak_db", "papr_db", "freq_offset", "coherence", "kurtosis",
+                                          "circularity", "dc_fraction", "duty", "rise", "fall", "pulses")]
+
+
 class Wire(C.Structure):
     """struct fosphor_amd_wire (include/fosphor_amd_wire.h)"""
     _fields_ = [("d_masks", C.c_void_p), ("mask_words", C.c_int), ("world", C.c_int), ("d_words", C.c_void_p),
@@ -259,6 +270,12 @@ SIGNATURES = {
     "fosphor_amd_extract_from_burst": (C.c_int, [C.POINTER(Burst), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double,
                                                  C.POINTER(ExtractJob), C.POINTER(C.c_int)]),
     "fosphor_amd_extract_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 6)]),
+    # include/fosphor_amd_measure.h
+    "fosphor_amd_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
+    "fosphor_amd_measure_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
+    "fosphor_amd_measure_from_extract": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(MeasureJob)]),
+    "fosphor_amd_measure_derive": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(MeasureValues)]),
+    "fosphor_amd_measure_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 7)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

@@ -615,6 +615,103 @@ class Fosphor:
             raise RuntimeError("fosphor_amd_extract_stats -> %d" % rv)
         return dict(zip(self.EXTRACT_STATS, list(st)))
 
+    MEASURE_STATS = ("calls", "k_wave", "k_split", "k_combine", "jobs_wave", "jobs_split", "samples")
+    MEASURE_MAX_JOBS = 4096				# FOSPHOR_AMD_MEASURE_MAX_JOBS (include/fosphor_amd_measure.h)
+    MEASURE_WAVE_MAX = 4096				# FOSPHOR_AMD_MEASURE_WAVE_MAX
+    MEASURE_CHUNK = 8192				# FOSPHOR_AMD_MEASURE_CHUNK
+    MEASURE_FORMS = ("wave", "split")			# FOSPHOR_AMD_MEASURE_FORM_*
+    MEASURE_JOB_DTYPE = np.dtype([("offset", "<i8"), ("n", "<i4"), ("threshold", "<f4")])
+    MEASURE_RECORD_DTYPE = np.dtype([("n_above", "<i4"), ("first_above", "<i4"), ("last_above", "<i4"), ("n_edges", "<i4"),
+                                     ("peak_index", "<i4"), ("peak_power", "<f4"), ("s_re", "<f8"), ("s_im", "<f8"),
+                                     ("s_p", "<f8"), ("s_p2", "<f8"), ("s_zz_re", "<f8"), ("s_zz_im", "<f8"), ("r1_re", "<f8"),
+                                     ("r1_im", "<f8"), ("n", "<i4"), ("form", "<i4")])
+    MEASURE_VALUES = tuple(k for k, _ in _lib.MeasureValues._fields_)
+
+    @staticmethod
+    def measure_form(n):
+        """the kernel form of a job, "wave" or "split": a function of n alone (include/fosphor_amd_measure.h)"""
+        return "wave" if int(n) <= Fosphor.MEASURE_WAVE_MAX else "split"
+
+    @staticmethod
+    def measure_jobs(jobs, threshold=None):
+        """a MEASURE_JOB_DTYPE array from one, or from an EXTRACT_DTYPE array and threshold= (fosphor_amd_measure_from_extract:
+        each job measures what the extract job wrote, offset = out_offset, n = n_out)"""
+        jobs = np.atleast_1d(np.asarray(jobs))
+        if jobs.dtype != Fosphor.EXTRACT_DTYPE:
+            if threshold is not None:
+                raise ValueError("threshold= goes with extract jobs; measure jobs carry their own")
+            return np.ascontiguousarray(jobs, dtype=Fosphor.MEASURE_JOB_DTYPE)
+        if threshold is None:
+            raise ValueError("extract jobs need threshold=")
+        L = _lib.load()
+        out = np.zeros(jobs.size, Fosphor.MEASURE_JOB_DTYPE)
+        for i, e in enumerate(np.ascontiguousarray(jobs)):
+            job = _lib.MeasureJob()
+            rv = L.fosphor_amd_measure_from_extract(e.tobytes(), float(threshold), C.byref(job))
+            if rv:
+                raise ValueError("fosphor_amd_measure_from_extract -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            out[i] = (job.offset, job.n, job.threshold)
+        return out
+
+    def measure(self, d_iq, jobs, n_samples=None, threshold=None):
+        """One record per job, up to 4096 jobs in one call (fosphor_amd_measure): samples above a threshold, edges, peak, and the
+        double-precision sums of y, p, p^2, y^2 and y[m + 1] conj(y[m]) over float32 IQ that is already in device memory.  d_iq: a
+        contiguous device tensor (complex64 or float32 pairs; what extract() wrote) or a raw device pointer with n_samples;
+        jobs: a MEASURE_JOB_DTYPE array, or an EXTRACT_DTYPE array with threshold= (measure_jobs).  Returns a
+        MEASURE_RECORD_DTYPE array copied from the device, in job order."""
+        import torch
+        jobs = self.measure_jobs(jobs, threshold)
+        if n_samples is None:
+            if not hasattr(d_iq, "numel"):
+                raise ValueError("a raw device pointer needs n_samples")
+            if not d_iq.is_contiguous() or d_iq.dtype not in (torch.complex64, torch.float32):
+                raise ValueError("d_iq must be a contiguous complex64 or float32 tensor")
+            n_samples = d_iq.numel() if d_iq.is_complex() else d_iq.numel() // 2
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_rec = torch.empty(max(jobs.size, 1) * self.MEASURE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()			# the caller's samples were written on torch's stream
+        rv = self.L.fosphor_amd_measure(self.h, _ptr(d_iq), int(n_samples), jobs.ctypes.data, int(jobs.size), d_rec.data_ptr())
+        if rv:
+            raise RuntimeError("fosphor_amd_measure -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return d_rec.cpu().numpy().view(self.MEASURE_RECORD_DTYPE)[:jobs.size].copy()
+
+    @staticmethod
+    def measure_host(iq, jobs):
+        """fosphor_amd_measure_host: the same records on the host, no GPU.  iq: complex64 or float32 pairs"""
+        iq = np.ascontiguousarray(iq)
+        iq = iq.view(np.float32) if iq.dtype == np.complex64 else np.ascontiguousarray(iq, dtype=np.float32)
+        iq = iq.reshape(-1)
+        jobs = Fosphor.measure_jobs(jobs)
+        out = np.zeros(max(jobs.size, 1), Fosphor.MEASURE_RECORD_DTYPE)
+        keep = iq if iq.size else np.zeros(2, np.float32)		# a pointer to pass when there are no samples
+        rv = _lib.load().fosphor_amd_measure_host(keep.ctypes.data, iq.size // 2, jobs.ctypes.data, int(jobs.size), out.ctypes.data)
+        if rv:
+            raise ValueError("fosphor_amd_measure_host -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return out[:jobs.size]
+
+    @staticmethod
+    def measure_derive(records, sample_rate):
+        """fosphor_amd_measure_derive per record: a list of dicts of MEASURE_VALUES (dB, Hz, ratios, seconds; pulses an int)"""
+        L = _lib.load()
+        out = []
+        for r in np.ascontiguousarray(np.atleast_1d(records), dtype=Fosphor.MEASURE_RECORD_DTYPE):
+            v = _lib.MeasureValues()
+            rv = L.fosphor_amd_measure_derive(r.tobytes(), float(sample_rate), C.byref(v))
+            if rv:
+                raise ValueError("fosphor_amd_measure_derive -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            d = {k: getattr(v, k) for k in Fosphor.MEASURE_VALUES}
+            d["pulses"] = int(d["pulses"])
+            out.append(d)
+        return out
+
+    def measure_stats(self):
+        """fosphor_amd_measure_stats as a dict: calls, launches by kernel, jobs by form, samples (MEASURE_STATS)"""
+        st = (C.c_longlong * 7)()
+        rv = self.L.fosphor_amd_measure_stats(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("fosphor_amd_measure_stats -> %d" % rv)
+        return dict(zip(self.MEASURE_STATS, list(st)))
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

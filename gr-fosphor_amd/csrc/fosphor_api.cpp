@@ -197,6 +197,9 @@ struct fosphor
 	long long extract_stats[6];		/* extract calls, launches and jobs by form, samples (fosphor_extract.hip, fosphor_amd_extract_stats) */
 	void     *d_extract;			/* job table of fosphor_extract.hip, grown on demand; the instance never reads it */
 	size_t    extract_cap;
+	long long measure_stats[7];		/* measure calls, launches by kernel, jobs by form, samples (fosphor_measure.hip, fosphor_amd_measure_stats) */
+	void     *d_measure;			/* job table and SPLIT partials of fosphor_measure.hip, grown on demand; the instance never reads it */
+	size_t    measure_cap;
 	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
 	struct {
 		uint32_t *d_masks;		/* [mask_cap][rows / 32] presence bits, one part per rank */
@@ -449,6 +452,7 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_mask);
 	(void)hipFree(self->d_burst[0]); (void)hipFree(self->d_burst[1]);
 	(void)hipFree(self->d_extract);
+	(void)hipFree(self->d_measure);
 	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
 	(void)hipFree(self->wire.d_live); (void)hipFree(self->wire.d_words);
 	if (self->wire.h_live) (void)hipHostFree(self->wire.h_live);
@@ -2482,6 +2486,27 @@ extern "C" int fosphor_amd_priv_extract_scratch(struct fosphor *self, size_t byt
 		self->extract_cap = bytes;
 	}
 	*d_scratch = self->d_extract;
+	return 0;
+}
+
+/* private accessors for fosphor_measure.hip: its counters and its scratch, which only grows (every call drains the stream before
+ * it returns, so no launch reads the old one) */
+extern "C" long long *fosphor_amd_priv_measure_stats(struct fosphor *self)
+{
+	return self->measure_stats;
+}
+
+extern "C" int fosphor_amd_priv_measure_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
+{
+	if (bytes > self->measure_cap) {
+		(void)hipFree(self->d_measure);
+		self->d_measure = nullptr;
+		self->measure_cap = 0;
+		if (hipMalloc(&self->d_measure, bytes) != hipSuccess)
+			return -EIO;
+		self->measure_cap = bytes;
+	}
+	*d_scratch = self->d_measure;
 	return 0;
 }
 

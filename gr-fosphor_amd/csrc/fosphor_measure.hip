@@ -1,0 +1,510 @@
+/*
+ * fosphor_measure.hip -- burst IQ reduced where it lies: power, edges, lag-1 product and moments per job (include/fosphor_amd_measure.h)
+ *
+ * A read-only pass over the CALLER's float32 IQ (what fosphor_amd_extract wrote), in a file of its own: nothing here is on the
+ * process / merge path and no buffer of the instance is read or written but the scratch this file owns (the job table, the
+ * prefix of work-group counts and the SPLIT partials).
+ *
+ *   k_measure_wave     n <= kWaveMax: a wave owns a job, four jobs per work-group, no LDS.
+ *   k_measure_split    longer jobs: a work-group of 256 lanes owns a chunk of kChunk samples of one job, which it finds by a bounded
+ *                      binary search of the prefix (13 steps cover 4096 jobs), and writes the chunk's partial record.
+ *   k_measure_combine  a wave per SPLIT job folds the job's partials in ascending chunk order.
+ * All three scan with one routine: a team of lanes (a wave, or the four waves of a work-group) strides a span of a job with
+ * 16-byte loads, two samples per lane per load, from the first 16-byte boundary on; the single samples before it and behind the
+ * last whole pair go one by one, so no byte outside the job's range is read.  A sample needs two things of its neighbours:
+ * above(m - 1) for the edge count and y[m + 1] for the lag-1 product.  Inside a pair both are at hand; between pairs they come from
+ * the neighbouring lanes by a shuffle, and at the ends of a wave -- lane 0, and lane 63 or the team's last pair -- from one
+ * 8-byte load of a sample the neighbouring wave reads anyway.  A lane sums its samples in ascending order; 64 partials meet by
+ * xor-shuffles 32, 16, .. 1, which leave the same bits in every lane (a + b is b + a).  No atomics of any kind, no work-group
+ * waits for another, every loop carries its bound in its header.
+ */
+#include <errno.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/fosphor_amd.h"
+#include "../../include/fosphor_amd_measure.h"
+
+/* accessors implemented next to struct fosphor (fosphor_api.cpp) */
+extern "C" long long *fosphor_amd_priv_measure_stats(struct fosphor *self);
+extern "C" int fosphor_amd_priv_measure_scratch(struct fosphor *self, size_t bytes, void **d_scratch);
+
+namespace {
+
+typedef struct fosphor_amd_measure_job Job;
+typedef struct fosphor_amd_measure_record Record;
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;				/* jobs of a WAVE work-group */
+constexpr int kWaveMax = FOSPHOR_AMD_MEASURE_WAVE_MAX;
+constexpr int kChunk = FOSPHOR_AMD_MEASURE_CHUNK;
+constexpr int kSearchSteps = 13;				/* 2^12 = MAX_JOBS */
+constexpr long long kMaxGroups = 0x7fffffffLL;
+constexpr int kNone = 0x7fffffff;				/* first_above of a partial without one, until the record is written */
+
+static_assert(FOSPHOR_AMD_MEASURE_MAX_JOBS <= (1 << (kSearchSteps - 1)), "the job search is bounded");
+static_assert(sizeof(Job) == 16, "the job table is built from it");
+static_assert(sizeof(Record) == 96, "the record is 96 bytes");
+static_assert(kChunk % 2 == 0 && kChunk > kWaveMax, "a chunk is whole pairs, and a SPLIT job has two samples at least");
+
+inline __host__ __device__ int form_of(int n) { return n <= kWaveMax ? FOSPHOR_AMD_MEASURE_FORM_WAVE : FOSPHOR_AMD_MEASURE_FORM_SPLIT; }
+
+/* a job on the device: where its record goes and, in the SPLIT form, where its partials begin */
+struct DevJob {
+	int64_t offset;
+	int32_t n;
+	float   threshold;
+	int32_t record;			/* index into d_records */
+	int32_t part0;			/* SPLIT: index of its first partial */
+};
+
+struct Params {
+	const float2   *iq;
+	const DevJob   *jobs;		/* the jobs of this form */
+	const uint32_t *prefix;		/* SPLIT: [n_jobs + 1] work-groups before job j */
+	Record         *parts;		/* SPLIT: one per work-group */
+	Record         *records;
+	int n_jobs;
+};
+
+/* What a lane, a wave, a chunk or a job has seen: Record's fields with first = kNone while nothing is above. */
+struct Acc {
+	int n_above, first, last, n_edges, peak_index;
+	float peak;
+	double s[8];			/* s_re, s_im, s_p, s_p2, s_zz_re, s_zz_im, r1_re, r1_im */
+};
+
+inline __host__ __device__ void acc_clear(Acc &a)
+{
+	a.n_above = 0; a.first = kNone; a.last = -1; a.n_edges = 0; a.peak_index = -1; a.peak = 0.0f;
+	for (int i = 0; i < 8; i++)
+		a.s[i] = 0.0;
+}
+
+/* rule 1: three rounded float32 operations (-ffp-contract=off: no fused multiply-add is formed) */
+inline __host__ __device__ float power(float2 y) { return (y.x * y.x) + (y.y * y.y); }
+
+/* sample m of the job.  prev_above: above(m - 1), false for m == 0; next: y[m + 1] where has_next.  Every product below is of two
+ * float32 values in double, hence exact; the terms of s_zz_re and r1_* round once, in their one addition or subtraction. */
+inline __host__ __device__ void acc_take(Acc &a, int m, float2 y, float thr, bool prev_above, float2 next, bool has_next)
+{
+	const float p = power(y);
+	if (p >= thr) {
+		a.n_above++;
+		a.first = m < a.first ? m : a.first;
+		a.last = m > a.last ? m : a.last;
+		a.n_edges += prev_above ? 0 : 1;
+	}
+	if (p > a.peak || (a.peak_index < 0 && p == p)) {	/* m ascends: the smallest index of the largest p */
+		a.peak = p;
+		a.peak_index = m;
+	}
+	const double re = y.x, im = y.y, pd = p;
+	a.s[0] += re;
+	a.s[1] += im;
+	a.s[2] += pd;
+	a.s[3] += pd * pd;
+	a.s[4] += re * re - im * im;
+	a.s[5] += (2.0 * re) * im;
+	if (has_next) {
+		const double nr = next.x, ni = next.y;
+		a.s[6] += nr * re + ni * im;
+		a.s[7] += ni * re - nr * im;
+	}
+}
+
+/* a <- a then b: b's sums are added to a's.  The integers and the peak do not care about the order. */
+inline __host__ __device__ void acc_fold(Acc &a, const Acc &b)
+{
+	a.n_above += b.n_above;
+	a.first = b.first < a.first ? b.first : a.first;
+	a.last = b.last > a.last ? b.last : a.last;
+	a.n_edges += b.n_edges;
+	if (b.peak_index >= 0 && (a.peak_index < 0 || b.peak > a.peak || (b.peak == a.peak && b.peak_index < a.peak_index))) {
+		a.peak = b.peak;
+		a.peak_index = b.peak_index;
+	}
+	for (int i = 0; i < 8; i++)
+		a.s[i] += b.s[i];
+}
+
+inline __host__ __device__ void acc_store(const Acc &a, int n, Record *r)
+{
+	r->n_above = a.n_above;
+	r->first_above = a.first == kNone ? -1 : a.first;
+	r->last_above = a.last;
+	r->n_edges = a.n_edges;
+	r->peak_index = a.peak_index;
+	r->peak_power = a.peak;
+	r->s_re = a.s[0]; r->s_im = a.s[1]; r->s_p = a.s[2]; r->s_p2 = a.s[3];
+	r->s_zz_re = a.s[4]; r->s_zz_im = a.s[5]; r->r1_re = a.s[6]; r->r1_im = a.s[7];
+	r->n = n;
+	r->form = form_of(n);
+}
+
+__device__ __forceinline__ void acc_load(Acc &a, const Record *r)
+{
+	a.n_above = r->n_above;
+	a.first = r->first_above < 0 ? kNone : r->first_above;
+	a.last = r->last_above;
+	a.n_edges = r->n_edges;
+	a.peak_index = r->peak_index;
+	a.peak = r->peak_power;
+	a.s[0] = r->s_re; a.s[1] = r->s_im; a.s[2] = r->s_p; a.s[3] = r->s_p2;
+	a.s[4] = r->s_zz_re; a.s[5] = r->s_zz_im; a.s[6] = r->r1_re; a.s[7] = r->r1_im;
+}
+
+/* lane `from`'s Acc in every lane (from is the same in every lane) */
+__device__ __forceinline__ Acc acc_of_lane(const Acc &a, int from)
+{
+	Acc b;
+	b.n_above = __shfl(a.n_above, from);
+	b.first = __shfl(a.first, from);
+	b.last = __shfl(a.last, from);
+	b.n_edges = __shfl(a.n_edges, from);
+	b.peak_index = __shfl(a.peak_index, from);
+	b.peak = __shfl(a.peak, from);
+#pragma unroll
+	for (int i = 0; i < 8; i++)
+		b.s[i] = __shfl(a.s[i], from);			/* a double is two 32-bit shuffles */
+	return b;
+}
+
+/* the 64 lanes' Accs into one, the same bits in every lane */
+__device__ __forceinline__ void acc_wave_reduce(Acc &a)
+{
+#pragma unroll
+	for (int d = 32; d; d >>= 1) {
+		Acc b;
+		b.n_above = __shfl_xor(a.n_above, d);
+		b.first = __shfl_xor(a.first, d);
+		b.last = __shfl_xor(a.last, d);
+		b.n_edges = __shfl_xor(a.n_edges, d);
+		b.peak_index = __shfl_xor(a.peak_index, d);
+		b.peak = __shfl_xor(a.peak, d);
+#pragma unroll
+		for (int i = 0; i < 8; i++)
+			b.s[i] = __shfl_xor(a.s[i], d);
+		acc_fold(a, b);
+	}
+}
+
+/* Samples [m0, m1) of the job at y (its sample 0; n samples), by a team of `team` lanes of which this is lane t; team is a multiple
+ * of 64 and every lane of the team calls this with the same arguments.  Reads y[max(m0 - 1, 0) .. min(m1 + 1, n)) and nothing else. */
+__device__ __forceinline__ void scan(Acc &a, const float2 *y, int n, int m0, int m1, float thr, int t, int team)
+{
+	const int lane = t & 63;
+	const int head = min(m1 - m0, (int)(((uintptr_t)(y + m0) >> 3) & 1));	/* 0 or 1 sample before the 16-byte boundary */
+	const int mb = m0 + head;
+	const int pairs = (m1 - mb) >> 1;
+	const int mt = mb + 2 * pairs;						/* the single sample behind the last pair, if mt < m1 */
+
+	if (t == 0 && head) {
+		const bool prev = m0 > 0 && power(y[m0 - 1]) >= thr;
+		const bool has_next = m0 + 1 < n;
+		acc_take(a, m0, y[m0], thr, prev, has_next ? y[m0 + 1] : make_float2(0.0f, 0.0f), has_next);
+	}
+	for (int g0 = 0; g0 < pairs; g0 += team) {
+		const int g = g0 + t;
+		const bool act = g < pairs;
+		const int m = mb + 2 * g;
+		float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		if (act)
+			q = *reinterpret_cast<const float4 *>(y + m);
+		const float2 ya = make_float2(q.x, q.y), yb = make_float2(q.z, q.w);
+		const bool above_a = power(ya) >= thr, above_b = power(yb) >= thr;
+		/* the neighbours, from the lanes beside this one (every lane of the wave is here: the loop's bound is the team's) */
+		bool prev = __shfl_up((int)above_b, 1) != 0;
+		float2 next = make_float2(__shfl_down(ya.x, 1), __shfl_down(ya.y, 1));
+		bool has_next = true;
+		if (act) {
+			if (lane == 0)
+				prev = m > 0 && power(y[m - 1]) >= thr;
+			if (lane == 63 || g == pairs - 1) {
+				has_next = m + 2 < n;
+				if (has_next)
+					next = y[m + 2];
+			}
+			acc_take(a, m, ya, thr, prev, yb, true);
+			acc_take(a, m + 1, yb, thr, above_a, next, has_next);
+		}
+	}
+	if (t == 0 && mt < m1) {
+		const bool prev = mt > 0 && power(y[mt - 1]) >= thr;
+		const bool has_next = mt + 1 < n;
+		acc_take(a, mt, y[mt], thr, prev, has_next ? y[mt + 1] : make_float2(0.0f, 0.0f), has_next);
+	}
+}
+
+/* the job of work-group g: the largest j with prefix[j] <= g (every job of the table has a work-group) */
+__device__ __forceinline__ int find_job(const uint32_t *prefix, int n_jobs, uint32_t g)
+{
+	int lo = 0, hi = n_jobs;
+	for (int step = 0; step < kSearchSteps && hi - lo > 1; step++) {
+		const int mid = (lo + hi) >> 1;
+		if (prefix[mid] <= g)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+
+__global__ __launch_bounds__(kThreads)
+void k_measure_wave(const Params p)
+{
+	const int lane = threadIdx.x & 63;
+	const int j = (int)blockIdx.x * kWaves + (int)(threadIdx.x >> 6);
+	if (j >= p.n_jobs)						/* the whole wave; there is no barrier below */
+		return;
+	const DevJob job = p.jobs[j];
+	Acc a;
+	acc_clear(a);
+	scan(a, p.iq + job.offset, job.n, 0, job.n, job.threshold, lane, 64);
+	acc_wave_reduce(a);
+	if (lane == 0)
+		acc_store(a, job.n, p.records + job.record);
+}
+
+__global__ __launch_bounds__(kThreads)
+void k_measure_split(const Params p)
+{
+	__shared__ Record s_part[kWaves];
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int j = find_job(p.prefix, p.n_jobs, blockIdx.x);
+	const DevJob job = p.jobs[j];
+	const int c = (int)(blockIdx.x - p.prefix[j]);			/* the chunk: c * kChunk < n by the prefix */
+	const int m0 = c * kChunk;
+	const int m1 = min(job.n - m0, kChunk) + m0;			/* no overflow: n - m0 >= 1 */
+	Acc a;
+	acc_clear(a);
+	scan(a, p.iq + job.offset, job.n, m0, m1, job.threshold, tid, kThreads);
+	acc_wave_reduce(a);
+	if (lane == 0)
+		acc_store(a, job.n, &s_part[wave]);
+	__syncthreads();
+	if (tid == 0) {
+		for (int w = 1; w < kWaves; w++) {
+			Acc b;
+			acc_load(b, &s_part[w]);
+			acc_fold(a, b);
+		}
+		acc_store(a, job.n, p.parts + job.part0 + c);
+	}
+}
+
+__global__ __launch_bounds__(kThreads)
+void k_measure_combine(const Params p)
+{
+	const int lane = threadIdx.x & 63;
+	const int j = (int)blockIdx.x * kWaves + (int)(threadIdx.x >> 6);
+	if (j >= p.n_jobs)						/* the whole wave; there is no barrier below */
+		return;
+	const DevJob job = p.jobs[j];
+	const int chunks = (int)(p.prefix[j + 1] - p.prefix[j]);
+	const Record *parts = p.parts + job.part0;
+	Acc total;
+	acc_clear(total);
+	/* 64 partials at a time, one per lane, then folded in lane order: every lane holds the same running total */
+	for (int c0 = 0; c0 < chunks; c0 += 64) {
+		Acc mine;
+		acc_clear(mine);
+		if (c0 + lane < chunks)
+			acc_load(mine, parts + c0 + lane);
+		const int k1 = min(64, chunks - c0);
+		for (int k = 0; k < k1; k++) {
+			const Acc b = acc_of_lane(mine, k);
+			acc_fold(total, b);
+		}
+	}
+	if (lane == 0)
+		acc_store(total, job.n, p.records + job.record);
+}
+
+/* What both entry points refuse, but for the pointers. */
+int check_call(int64_t n_samples, const Job *jobs, int n_jobs)
+{
+	if (!jobs || n_jobs < 1 || n_jobs > FOSPHOR_AMD_MEASURE_MAX_JOBS || n_samples < 0)
+		return -EINVAL;
+	long long groups[2] = { 0, 0 };
+	for (int i = 0; i < n_jobs; i++) {
+		const Job &b = jobs[i];
+		if (b.offset < 0 || b.n < 0 || b.offset > n_samples || b.n > n_samples - b.offset || b.threshold != b.threshold)
+			return -EINVAL;
+		if (form_of(b.n) == FOSPHOR_AMD_MEASURE_FORM_WAVE)
+			groups[0]++;
+		else
+			groups[1] += ((long long)b.n + kChunk - 1) / kChunk;
+	}
+	if ((groups[0] + kWaves - 1) / kWaves > kMaxGroups || groups[1] > kMaxGroups)
+		return -EINVAL;
+	return 0;
+}
+
+int launch_ok(void) { return hipGetLastError() == hipSuccess ? 0 : -EIO; }
+
+} // namespace
+
+extern "C" int fosphor_amd_measure_host(const float *iq, int64_t n_samples, const struct fosphor_amd_measure_job *jobs,
+                                        int n_jobs, struct fosphor_amd_measure_record *records)
+{
+	if (!iq || !records || ((uintptr_t)iq & 7) || ((uintptr_t)records & 7))
+		return -EINVAL;
+	if (check_call(n_samples, jobs, n_jobs))
+		return -EINVAL;
+	for (int i = 0; i < n_jobs; i++) {
+		const float *y = iq + 2 * jobs[i].offset;
+		const int n = jobs[i].n;
+		const float thr = jobs[i].threshold;
+		Acc a;
+		acc_clear(a);
+		bool prev = false;
+		for (int m = 0; m < n; m++) {
+			const float2 v = make_float2(y[2 * m], y[2 * m + 1]);
+			const bool has_next = m + 1 < n;
+			acc_take(a, m, v, thr, prev, has_next ? make_float2(y[2 * m + 2], y[2 * m + 3]) : make_float2(0.0f, 0.0f), has_next);
+			prev = power(v) >= thr;
+		}
+		acc_store(a, n, &records[i]);
+	}
+	return 0;
+}
+
+extern "C" int fosphor_amd_measure_from_extract(const struct fosphor_amd_extract_job *e, float threshold,
+                                                struct fosphor_amd_measure_job *job)
+{
+	if (!e || !job || threshold != threshold || e->out_offset < 0 || e->n_out < 0)
+		return -EINVAL;
+	job->offset = e->out_offset;
+	job->n = e->n_out;
+	job->threshold = threshold;
+	return 0;
+}
+
+extern "C" int fosphor_amd_measure_derive(const struct fosphor_amd_measure_record *r, double sample_rate,
+                                          struct fosphor_amd_measure_values *v)
+{
+	if (!r || !v || !(sample_rate > 0.0) || !(sample_rate < INFINITY))
+		return -EINVAL;
+	memset(v, 0, sizeof(*v));
+	if (r->n <= 0)
+		return 0;
+	const double n = r->n, sp = r->s_p, pi = 3.14159265358979323846;
+	v->mean_power = sp / n;
+	v->peak_db = r->peak_power != 0.0f ? 10.0 * log10((double)r->peak_power) : 0.0;
+	v->freq_offset = atan2(r->r1_im, r->r1_re) / (2.0 * pi) * sample_rate;
+	if (sp != 0.0) {
+		v->mean_db = 10.0 * log10(v->mean_power);
+		v->papr_db = v->peak_db - v->mean_db;
+		v->coherence = hypot(r->r1_re, r->r1_im) / sp;
+		v->kurtosis = (r->s_p2 / n) / (v->mean_power * v->mean_power);
+		v->circularity = hypot(r->s_zz_re, r->s_zz_im) / sp;
+		v->dc_fraction = (r->s_re * r->s_re + r->s_im * r->s_im) / (n * sp);
+	}
+	if (r->n_above > 0) {
+		v->duty = r->n_above / n;
+		v->rise = r->first_above / sample_rate;
+		v->fall = (r->last_above + 1.0) / sample_rate;
+		v->pulses = r->n_edges;
+	}
+	return 0;
+}
+
+extern "C" int fosphor_amd_measure_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_MEASURE_STATS])
+{
+	if (!self)
+		return -EINVAL;
+	if (stats)
+		for (int i = 0; i < FOSPHOR_AMD_MEASURE_STATS; i++)
+			stats[i] = fosphor_amd_priv_measure_stats(self)[i];
+	return 0;
+}
+
+extern "C" int fosphor_amd_measure(struct fosphor *self, const void *d_iq, int64_t n_samples,
+                                   const struct fosphor_amd_measure_job *jobs, int n_jobs,
+                                   struct fosphor_amd_measure_record *d_records)
+{
+	if (!self || !d_iq || !jobs || !d_records)
+		return -EINVAL;
+	if (((uintptr_t)d_iq & 7) || ((uintptr_t)d_records & 7))
+		return -EINVAL;
+	if (check_call(n_samples, jobs, n_jobs))
+		return -EINVAL;
+
+	/* the table: WAVE jobs, SPLIT jobs, the SPLIT prefix; behind it, 8-byte aligned, the SPLIT partials */
+	std::vector<DevJob> form[2];
+	std::vector<uint32_t> prefix(1, 0u);
+	long long samples = 0;
+	for (int i = 0; i < n_jobs; i++) {
+		const int f = form_of(jobs[i].n);
+		DevJob d;
+		d.offset = jobs[i].offset;
+		d.n = jobs[i].n;
+		d.threshold = jobs[i].threshold;
+		d.record = i;
+		d.part0 = 0;
+		if (f == FOSPHOR_AMD_MEASURE_FORM_SPLIT) {
+			d.part0 = (int32_t)prefix.back();
+			prefix.push_back(prefix.back() + (uint32_t)(((long long)jobs[i].n + kChunk - 1) / kChunk));
+		}
+		form[f].push_back(d);
+		samples += jobs[i].n;
+	}
+	const size_t n_form[2] = { form[0].size(), form[1].size() };
+	const size_t job_bytes = sizeof(DevJob) * (n_form[0] + n_form[1]);
+	const size_t table_bytes = (job_bytes + sizeof(uint32_t) * prefix.size() + 7) & ~(size_t)7;
+	const size_t bytes = table_bytes + sizeof(Record) * (size_t)prefix.back();
+	std::vector<uint8_t> table(table_bytes);
+	for (int f = 0; f < 2; f++)
+		if (n_form[f])
+			memcpy(table.data() + (f ? sizeof(DevJob) * n_form[0] : 0), form[f].data(), sizeof(DevJob) * n_form[f]);
+	memcpy(table.data() + job_bytes, prefix.data(), sizeof(uint32_t) * prefix.size());
+
+	if (fosphor_amd_finish(self) < 0)
+		return -EIO;
+	long long *stats = fosphor_amd_priv_measure_stats(self);
+	stats[FOSPHOR_AMD_MEASURE_CALLS]++;
+	stats[FOSPHOR_AMD_MEASURE_JOBS_WAVE] += (long long)n_form[0];
+	stats[FOSPHOR_AMD_MEASURE_JOBS_SPLIT] += (long long)n_form[1];
+	stats[FOSPHOR_AMD_MEASURE_SAMPLES] += samples;
+
+	void *d;
+	if (fosphor_amd_priv_measure_scratch(self, bytes, &d))
+		return -EIO;
+	const hipStream_t st = (hipStream_t)fosphor_amd_stream(self);
+	if (hipMemcpyAsync(d, table.data(), table_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+		return -EIO;
+	Params p;
+	p.iq = static_cast<const float2 *>(d_iq);
+	p.prefix = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(d) + job_bytes);
+	p.parts = reinterpret_cast<Record *>(static_cast<uint8_t *>(d) + table_bytes);
+	p.records = d_records;
+	int rv = 0;
+	if (n_form[0]) {
+		p.jobs = static_cast<const DevJob *>(d);
+		p.n_jobs = (int)n_form[0];
+		hipLaunchKernelGGL(k_measure_wave, dim3((unsigned)((n_form[0] + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, p);
+		if (!(rv = launch_ok()))
+			stats[FOSPHOR_AMD_MEASURE_K_WAVE]++;
+	}
+	if (n_form[1] && !rv) {
+		p.jobs = static_cast<const DevJob *>(d) + n_form[0];
+		p.n_jobs = (int)n_form[1];
+		hipLaunchKernelGGL(k_measure_split, dim3(prefix.back()), dim3(kThreads), 0, st, p);
+		if (!(rv = launch_ok()))
+			stats[FOSPHOR_AMD_MEASURE_K_SPLIT]++;
+		if (!rv) {
+			hipLaunchKernelGGL(k_measure_combine, dim3((unsigned)((n_form[1] + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, p);
+			if (!(rv = launch_ok()))
+				stats[FOSPHOR_AMD_MEASURE_K_COMBINE]++;
+		}
+	}
+	if (hipStreamSynchronize(st) != hipSuccess)			/* the table on the host lives until here */
+		return -EIO;
+	return rv;
+}
