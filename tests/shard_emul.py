@@ -73,7 +73,30 @@ CASES = {
     "i": dict(log2n=10, fmt="fp32", n_bins=256, wf_rows=1024, total=8192, overlap=1, frames=1,
               shards=[(0, 4096), (4096, 4096)], env={"FOSPHOR_AMD_SUB_LOG2": "21", "FOSPHOR_AMD_OVERLAP": "0"},
               power=(0, 10), seed=7009, twin=False, launches=[(2, 1, 0), (2, 1, 0)]),
+    # Bin counts other than 128, 256 and 512 (BIN_COUNT_CASES below), two ranks each, small frames.
+    # 16 bins, the minimum: the count kernel's row bitmask is half a word, its LDS histogram less than one pass of the work-group
+    "j": dict(log2n=10, fmt="fp32", n_bins=16, wf_rows=64, total=64, overlap=1, frames=2,
+              shards=[(0, 16), (16, 48)], env={}, power=(0, 20), seed=7010, twin=False, launches=[(1, 0, 0), (1, 0, 0)]),
+    # N = 8192 at 48 bins (no multiple of 32; the plane of 9th bits is all zero, and still read and stored) ...
+    "k": dict(log2n=13, fmt="fp32", n_bins=48, wf_rows=64, total=64, overlap=2, frames=1,
+              shards=[(0, 16), (16, 48)], env={}, power=(0, 20), seed=7011, twin=False, launches=[(1, 0, 0), (1, 0, 0)]),
+    # ... and at 272 (the 9th bit set in the last 16 rows only)
+    "l": dict(log2n=13, fmt="fp32", n_bins=272, wf_rows=64, total=64, overlap=1, frames=1,
+              shards=[(0, 48), (48, 16)], env={}, power=(-53, 10), seed=7012, twin=False, launches=[(1, 0, 0), (1, 0, 0)]),
+    # N = 65536 at 496 bins, the largest count below 512: 9-bit packing
+    "m": dict(log2n=16, fmt="fp16", n_bins=496, wf_rows=64, total=32, overlap=1, frames=1,
+              shards=[(0, 16), (16, 16)], env={}, power=(-21, 10), seed=7013, twin=False, launches=[(1, 0, 0), (1, 0, 0)]),
 }
+
+# The cases above that are there for their bin count.  Their ranges were chosen on the CPU from the oracle's counts so that
+# (tests/test_bin_counts_cpu.py asserts both) above 256 bins either side of row 256 holds at least 1 % of the hits, and the rows
+# of 64 cells that hold a hit are strictly between 1 % and 50 % of all rows: tests/test_gpu_bin_counts.py sends these frames
+# through the compact exchange in both forms, and the sparse form falls back to the packed one above one half.
+#   "j" (0 dB, 20 dB/div):   0.33 / 0.32 of the rows live (frame 0 / 1)
+#   "k" (0 dB, 20 dB/div):   0.26
+#   "l" (-53 dB, 10 dB/div): 0.36, 0.23 of the hits in rows >= 256
+#   "m" (-21 dB, 10 dB/div): 0.31, 0.34 of the hits in rows >= 256
+BIN_COUNT_CASES = ("j", "k", "l", "m")
 
 SAMPLE_BYTES = {"fp32": 8, "fp16": 4, "sc16": 4}
 MAX_BATCHES = 2			# partial slots per instance (the default of 8 costs 1 GiB of counts at N = 65536, 512 bins)

@@ -37,7 +37,7 @@ def test_sharded_frame_matrix(amd, torch_cuda, oracle_built, monkeypatch, cid):
     for frame in range(c["frames"]):
         x, x32 = se.make_stream(c, frame)
         se.oracle_frame(o, c, x32)
-        if c["n_bins"] == 512:
+        if c["n_bins"] > 256:
             # on the oracle's result, before the GPU's is looked at: both planes of the 9th bin-index bit are under test
             lo, hi = se.plane_fractions(o)
             assert lo >= 0.01 and hi >= 0.01, "case %s: bins < 256 hold %.4f, bins >= 256 hold %.4f of the hits" % (cid, lo, hi)

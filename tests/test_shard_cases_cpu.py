@@ -33,8 +33,17 @@ def test_case_table_is_consistent(cid):
     assert off * hop + (cnt - 1) * hop + n == se.stream_samples(c)
     # the environment a case sets is one the library reads, with values it does not ignore (FOSPHOR_AMD_SUB_LOG2 < 14 is)
     assert set(c["env"]) <= set(se.KNOBS)
+    if cid in se.BIN_COUNT_CASES:
+        assert len(c["shards"]) == 2 and c["n_bins"] not in (128, 256, 512) and 16 <= c["n_bins"] <= 512
     if "FOSPHOR_AMD_SUB_LOG2" in c["env"]:
         assert 14 <= int(c["env"]["FOSPHOR_AMD_SUB_LOG2"]) <= 34
+
+
+def test_bin_count_cases_are_the_listed_ones():
+    assert set(se.BIN_COUNT_CASES) <= set(se.CASES)
+    got = sorted((se.CASES[k]["log2n"], se.CASES[k]["n_bins"]) for k in se.BIN_COUNT_CASES)
+    assert got == [(10, 16), (13, 48), (13, 272), (16, 496)]
+    assert se.CASES["m"]["total"] in (32, 64)
 
 
 def test_case_table_launch_counts_follow_the_documented_rules():
@@ -57,18 +66,22 @@ def test_case_table_launch_counts_follow_the_documented_rules():
 
 
 def _smallest_per_length():
+    """of the shard-shape cases (the bin-count cases are all run, below)"""
     best = {}
     for cid, c in sorted(se.CASES.items()):
+        if cid in se.BIN_COUNT_CASES:
+            continue
         size = c["total"] << c["log2n"]
         if c["log2n"] not in best or size < best[c["log2n"]][0]:
             best[c["log2n"]] = (size, cid)
     return sorted(cid for _, cid in best.values())
 
 
-@pytest.mark.parametrize("cid", sorted(set(_smallest_per_length()) | {k for k, c in se.CASES.items() if c["n_bins"] == 512}))
+@pytest.mark.parametrize("cid", sorted(set(_smallest_per_length()) | {k for k, c in se.CASES.items() if c["n_bins"] > 256}
+                                        | set(se.BIN_COUNT_CASES)))
 def test_case_inputs_through_the_oracle(oracle_built, cid):
-    """The input builder and the oracle on the expanded frame: every sample of the frame is counted once, and at 512 bins
-    both halves of the bin range -- the planes of the 9th index bit -- hold at least 1 % of the hits."""
+    """The input builder and the oracle on the expanded frame: every sample of the frame is counted once, and above 256 bins
+    both sides of row 256 -- the planes of the 9th index bit -- hold at least 1 % of the hits."""
     c = se.CASES[cid]
     n = 1 << c["log2n"]
     x, x32 = se.make_stream(c)
@@ -77,7 +90,7 @@ def test_case_inputs_through_the_oracle(oracle_built, cid):
     o = se.make_oracle(c)
     se.oracle_frame(o, c, x32)
     assert int(o.hitcount.sum(dtype=np.uint64)) == c["total"] * n
-    if c["n_bins"] == 512:
+    if c["n_bins"] > 256:
         lo, hi = se.plane_fractions(o)
         print("case %s: %.3f of the hits in bins < 256, %.3f in bins >= 256" % (cid, lo, hi))
         assert lo >= 0.01 and hi >= 0.01, "case %s: bins < 256 hold %.4f, bins >= 256 hold %.4f of the hits" % (cid, lo, hi)
