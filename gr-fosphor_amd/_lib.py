@@ -152,6 +152,12 @@ class MeasureJob(C.Structure):
     _fields_ = [("offset", C.c_int64), ("n", C.c_int32), ("threshold", C.c_float)]
 
 
+class DemodJob(C.Structure):
+    """struct fosphor_amd_demod_job (include/fosphor_amd_demod.h)"""
+    _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("n", C.c_int32), ("mode", C.c_int32), ("avg", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class MeasureValues(C.Structure):
     """struct fosphor_amd_measure_values"""
     _fields_ = [(k, C.c_double) for k in ("mean_power", "mean_db", "peak_db", "papr_db", "freq_offset", "coherence", "kurtosis",
@@ -276,6 +282,14 @@ SIGNATURES = {
     "fosphor_amd_measure_from_extract": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(MeasureJob)]),
     "fosphor_amd_measure_derive": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(MeasureValues)]),
     "fosphor_amd_measure_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 7)]),
+    # include/fosphor_amd_demod.h
+    "fosphor_amd_demod": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    "fosphor_amd_demod_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    "fosphor_amd_demod_n_out": (C.c_int, [C.c_int, C.c_int32, C.c_int]),
+    "fosphor_amd_demod_from_extract": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(DemodJob)]),
+    "fosphor_amd_demod_atan2_turns": (C.c_float, [C.c_double, C.c_double]),
+    "fosphor_amd_demod_atan2_turns_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "fosphor_amd_demod_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 7)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

@@ -712,6 +712,112 @@ class Fosphor:
             raise RuntimeError("fosphor_amd_measure_stats -> %d" % rv)
         return dict(zip(self.MEASURE_STATS, list(st)))
 
+    DEMOD_STATS = ("calls", "k_direct", "k_avg", "jobs_direct", "jobs_avg", "samples", "outputs")
+    DEMOD_MAX_JOBS = 4096				# FOSPHOR_AMD_DEMOD_MAX_JOBS (include/fosphor_amd_demod.h)
+    DEMOD_MAX_AVG = 256					# FOSPHOR_AMD_DEMOD_MAX_AVG
+    DEMOD_TILE = 2048					# FOSPHOR_AMD_DEMOD_TILE
+    DEMOD_MODES = {"power": 0, "phase": 1, "fm": 2}	# FOSPHOR_AMD_DEMOD_*
+    DEMOD_JOB_DTYPE = np.dtype([("offset", "<i8"), ("out_offset", "<i8"), ("n", "<i4"), ("mode", "<i4"), ("avg", "<i4"),
+                                ("reserved", "<i4")])
+
+    @staticmethod
+    def _demod_mode(mode):
+        if isinstance(mode, str):
+            if mode not in Fosphor.DEMOD_MODES:
+                raise ValueError("mode must be one of %s" % ", ".join(Fosphor.DEMOD_MODES))
+            return Fosphor.DEMOD_MODES[mode]
+        return int(mode)
+
+    @staticmethod
+    def demod_n_out(mode, n, avg=1):
+        """fosphor_amd_demod_n_out: the outputs of a job of n samples, n_trace // avg (n_trace = n, or n - 1 for "fm")"""
+        rv = _lib.load().fosphor_amd_demod_n_out(Fosphor._demod_mode(mode), int(n), int(avg))
+        if rv < 0:
+            raise ValueError("fosphor_amd_demod_n_out -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return rv
+
+    @staticmethod
+    def demod_jobs(extract_jobs, mode="fm", avg=1):
+        """a DEMOD_JOB_DTYPE array from an EXTRACT_DTYPE array (fosphor_amd_demod_from_extract: each job demodulates what the
+        extract job wrote, offset = out_offset, n = n_out), the outputs placed back to back from out_offset 0 on"""
+        L = _lib.load()
+        ejobs = np.ascontiguousarray(np.atleast_1d(extract_jobs), dtype=Fosphor.EXTRACT_DTYPE)
+        out = np.zeros(ejobs.size, Fosphor.DEMOD_JOB_DTYPE)
+        at = 0
+        for i, e in enumerate(ejobs):
+            job = _lib.DemodJob()
+            rv = L.fosphor_amd_demod_from_extract(e.tobytes(), Fosphor._demod_mode(mode), int(avg), C.byref(job))
+            if rv:
+                raise ValueError("fosphor_amd_demod_from_extract -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            out[i] = (job.offset, at, job.n, job.mode, job.avg, job.reserved)
+            at += Fosphor.demod_n_out(job.mode, job.n, job.avg)
+        return out
+
+    @staticmethod
+    def _demod_outs(jobs):
+        """(n_out per job, the capacity the jobs need)"""
+        n_out = [Fosphor.demod_n_out(int(j["mode"]), int(j["n"]), int(j["avg"])) for j in jobs]
+        return n_out, max([int(j["out_offset"]) + n for j, n in zip(jobs, n_out)] + [0])
+
+    def demod(self, d_iq, jobs, n_samples=None):
+        """One float32 trace per job, up to 4096 jobs in one call (fosphor_amd_demod): power, phase in turns or the phase step
+        between consecutive samples in turns ("fm"), integrated and dumped over avg trace values, over float32 IQ that is already
+        in device memory.  d_iq: a contiguous device tensor (complex64 or float32 pairs; what extract() wrote) or a raw device
+        pointer with n_samples; jobs: a DEMOD_JOB_DTYPE array (out_offset is honoured; ranges must not overlap; demod_jobs()
+        makes one from extract jobs).  Returns a list with one torch float32 view per job, into one device buffer."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.DEMOD_JOB_DTYPE)
+        if n_samples is None:
+            if not hasattr(d_iq, "numel"):
+                raise ValueError("a raw device pointer needs n_samples")
+            if not d_iq.is_contiguous() or d_iq.dtype not in (torch.complex64, torch.float32):
+                raise ValueError("d_iq must be a contiguous complex64 or float32 tensor")
+            n_samples = d_iq.numel() if d_iq.is_complex() else d_iq.numel() // 2
+        n_out, cap = self._demod_outs(jobs)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 1), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()			# the caller's samples were written on torch's stream
+        rv = self.L.fosphor_amd_demod(self.h, _ptr(d_iq), int(n_samples), jobs.ctypes.data, int(jobs.size), d_out.data_ptr(), cap)
+        if rv:
+            raise RuntimeError("fosphor_amd_demod -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return [d_out[int(j["out_offset"]):int(j["out_offset"]) + n] for j, n in zip(jobs, n_out)]
+
+    @staticmethod
+    def demod_host(iq, jobs):
+        """fosphor_amd_demod_host: the same traces on the host, no GPU.  iq: complex64 or float32 pairs.  Returns a list with one
+        float32 array per job, views of one buffer"""
+        iq = np.ascontiguousarray(iq)
+        iq = iq.view(np.float32) if iq.dtype == np.complex64 else np.ascontiguousarray(iq, dtype=np.float32)
+        iq = iq.reshape(-1)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.DEMOD_JOB_DTYPE)
+        n_out, cap = Fosphor._demod_outs(jobs)
+        out = np.zeros(max(cap, 1), np.float32)
+        keep = iq if iq.size else np.zeros(2, np.float32)		# a pointer to pass when there are no samples
+        rv = _lib.load().fosphor_amd_demod_host(keep.ctypes.data, iq.size // 2, jobs.ctypes.data, int(jobs.size), out.ctypes.data, cap)
+        if rv:
+            raise ValueError("fosphor_amd_demod_host -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return [out[int(j["out_offset"]):int(j["out_offset"]) + n] for j, n in zip(jobs, n_out)]
+
+    @staticmethod
+    def atan2_turns(y, x):
+        """fosphor_amd_atan2_turns as the library compiled it: the angle of (x, y) in turns, float32, element-wise over float64"""
+        y, x = np.broadcast_arrays(np.asarray(y, np.float64), np.asarray(x, np.float64))
+        shape = y.shape
+        y, x = np.ascontiguousarray(y).reshape(-1), np.ascontiguousarray(x).reshape(-1)
+        out = np.zeros(max(y.size, 1), np.float32)
+        rv = _lib.load().fosphor_amd_demod_atan2_turns_n(y.ctypes.data, x.ctypes.data, int(y.size), out.ctypes.data)
+        if rv:
+            raise ValueError("fosphor_amd_demod_atan2_turns_n -> %d" % rv)
+        return out[:y.size].reshape(shape)
+
+    def demod_stats(self):
+        """fosphor_amd_demod_stats as a dict: calls, launches by kernel, jobs by form, samples, outputs (DEMOD_STATS)"""
+        st = (C.c_longlong * 7)()
+        rv = self.L.fosphor_amd_demod_stats(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("fosphor_amd_demod_stats -> %d" % rv)
+        return dict(zip(self.DEMOD_STATS, list(st)))
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

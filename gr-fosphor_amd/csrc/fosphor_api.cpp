@@ -200,6 +200,9 @@ struct fosphor
 	long long measure_stats[7];		/* measure calls, launches by kernel, jobs by form, samples (fosphor_measure.hip, fosphor_amd_measure_stats) */
 	void     *d_measure;			/* job table and SPLIT partials of fosphor_measure.hip, grown on demand; the instance never reads it */
 	size_t    measure_cap;
+	long long demod_stats[7];		/* demod calls, launches by kernel, jobs by form, samples, outputs (fosphor_demod.hip, fosphor_amd_demod_stats) */
+	void     *d_demod;			/* job table of fosphor_demod.hip, grown on demand; the instance never reads it */
+	size_t    demod_cap;
 	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
 	struct {
 		uint32_t *d_masks;		/* [mask_cap][rows / 32] presence bits, one part per rank */
@@ -453,6 +456,7 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_burst[0]); (void)hipFree(self->d_burst[1]);
 	(void)hipFree(self->d_extract);
 	(void)hipFree(self->d_measure);
+	(void)hipFree(self->d_demod);
 	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
 	(void)hipFree(self->wire.d_live); (void)hipFree(self->wire.d_words);
 	if (self->wire.h_live) (void)hipHostFree(self->wire.h_live);
@@ -2507,6 +2511,27 @@ extern "C" int fosphor_amd_priv_measure_scratch(struct fosphor *self, size_t byt
 		self->measure_cap = bytes;
 	}
 	*d_scratch = self->d_measure;
+	return 0;
+}
+
+/* private accessors for fosphor_demod.hip: its counters and its job table, which only grows (every call drains the stream before
+ * it returns, so no launch reads the old one) */
+extern "C" long long *fosphor_amd_priv_demod_stats(struct fosphor *self)
+{
+	return self->demod_stats;
+}
+
+extern "C" int fosphor_amd_priv_demod_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
+{
+	if (bytes > self->demod_cap) {
+		(void)hipFree(self->d_demod);
+		self->d_demod = nullptr;
+		self->demod_cap = 0;
+		if (hipMalloc(&self->d_demod, bytes) != hipSuccess)
+			return -EIO;
+		self->demod_cap = bytes;
+	}
+	*d_scratch = self->d_demod;
 	return 0;
 }
 

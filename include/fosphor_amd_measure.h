@@ -6,7 +6,7 @@
  * call is one range of float32 (re, im) pairs in device memory and gets one record of exact integers (how many samples are above a
  * threshold, the first and the last, how many times the envelope rises, where the peak is) and of double-precision sums (the mean,
  * the power and its square, y * y, and the lag-1 product).  Nothing transcendental runs on the device: fosphor_amd_measure_derive
- * turns a record into dB, Hz and ratios on the host.  Per-sample outputs (an envelope trace, a discriminator) are not this pass.
+ * turns a record into dB, Hz and ratios on the host.  Per-sample outputs (an envelope trace, a discriminator) are fosphor_amd_demod.h's.
  *
  * Conventions, those of fosphor_amd_extract.h: the device entry point waits for pending fosphor_process work first
  * (fosphor_amd_finish), runs on the instance's stream and returns when the records are complete; it writes no state of the
