@@ -158,6 +158,24 @@ class DemodJob(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class CorrelateJob(C.Structure):
+    """struct fosphor_amd_correlate_job (include/fosphor_amd_correlate.h)"""
+    _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("tpl_offset", C.c_int64), ("n", C.c_int32),
+                ("tpl_len", C.c_int32), ("trace", C.c_int32), ("threshold", C.c_float)]
+
+
+class CorrelateRecord(C.Structure):
+    """struct fosphor_amd_correlate_record"""
+    _fields_ = [("n_lags", C.c_int32), ("n_above", C.c_int32), ("first_above", C.c_int32), ("last_above", C.c_int32),
+                ("n_edges", C.c_int32), ("peak_lag", C.c_int32), ("peak_rho", C.c_float), ("tpl_len", C.c_int32),
+                ("peak_c_re", C.c_double), ("peak_c_im", C.c_double), ("peak_energy", C.c_double), ("tpl_energy", C.c_double)]
+
+
+class CorrelateValues(C.Structure):
+    """struct fosphor_amd_correlate_values"""
+    _fields_ = [(k, C.c_double) for k in ("time", "rho", "gain_re", "gain_im", "gain_db", "phase_turns", "snr_db", "detections")]
+
+
 class MeasureValues(C.Structure):
     """struct fosphor_amd_measure_values"""
     _fields_ = [(k, C.c_double) for k in ("mean_power", "mean_db", "peak_db", "papr_db", "freq_offset", "coherence", "kurtosis",
@@ -290,6 +308,15 @@ SIGNATURES = {
     "fosphor_amd_demod_atan2_turns": (C.c_float, [C.c_double, C.c_double]),
     "fosphor_amd_demod_atan2_turns_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "fosphor_amd_demod_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 7)]),
+    # include/fosphor_amd_correlate.h
+    "fosphor_amd_correlate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_int64]),
+    "fosphor_amd_correlate_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_int64]),
+    "fosphor_amd_correlate_n_out": (C.c_int, [C.c_int, C.c_int32, C.c_int]),
+    "fosphor_amd_correlate_from_extract": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_float, C.POINTER(CorrelateJob)]),
+    "fosphor_amd_correlate_derive": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(CorrelateValues)]),
+    "fosphor_amd_correlate_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 6)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

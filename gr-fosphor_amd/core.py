@@ -818,6 +818,158 @@ class Fosphor:
             raise RuntimeError("fosphor_amd_demod_stats -> %d" % rv)
         return dict(zip(self.DEMOD_STATS, list(st)))
 
+    CORRELATE_STATS = ("calls", "k_tile", "k_combine", "jobs", "lags", "macs")
+    CORRELATE_MAX_JOBS = 4096				# FOSPHOR_AMD_CORRELATE_MAX_JOBS (include/fosphor_amd_correlate.h)
+    CORRELATE_MAX_TPL = 1024				# FOSPHOR_AMD_CORRELATE_MAX_TPL
+    CORRELATE_TILE = 1024				# FOSPHOR_AMD_CORRELATE_TILE
+    CORRELATE_TRACES = {"none": 0, "rho": 1, "c": 2}	# FOSPHOR_AMD_CORRELATE_TRACE_*
+    CORRELATE_JOB_DTYPE = np.dtype([("offset", "<i8"), ("out_offset", "<i8"), ("tpl_offset", "<i8"), ("n", "<i4"),
+                                    ("tpl_len", "<i4"), ("trace", "<i4"), ("threshold", "<f4")])
+    CORRELATE_RECORD_DTYPE = np.dtype([("n_lags", "<i4"), ("n_above", "<i4"), ("first_above", "<i4"), ("last_above", "<i4"),
+                                       ("n_edges", "<i4"), ("peak_lag", "<i4"), ("peak_rho", "<f4"), ("tpl_len", "<i4"),
+                                       ("peak_c_re", "<f8"), ("peak_c_im", "<f8"), ("peak_energy", "<f8"), ("tpl_energy", "<f8")])
+    CORRELATE_VALUES = tuple(k for k, _ in _lib.CorrelateValues._fields_)
+
+    @staticmethod
+    def _correlate_trace(trace):
+        if isinstance(trace, str):
+            if trace not in Fosphor.CORRELATE_TRACES:
+                raise ValueError("trace must be one of %s" % ", ".join(Fosphor.CORRELATE_TRACES))
+            return Fosphor.CORRELATE_TRACES[trace]
+        return int(trace)
+
+    @staticmethod
+    def correlate_n_out(trace, n, tpl_len):
+        """fosphor_amd_correlate_n_out: the trace floats of a job of n samples: 0, n_lags or 2 * n_lags, n_lags = max(n - T + 1, 0)"""
+        rv = _lib.load().fosphor_amd_correlate_n_out(Fosphor._correlate_trace(trace), int(n), int(tpl_len))
+        if rv < 0:
+            raise ValueError("fosphor_amd_correlate_n_out -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return rv
+
+    @staticmethod
+    def correlate_jobs(extract_jobs, tpl_offset, tpl_len, trace="none", threshold=np.inf):
+        """a CORRELATE_JOB_DTYPE array from an EXTRACT_DTYPE array (fosphor_amd_correlate_from_extract: each job correlates what
+        the extract job wrote, offset = out_offset, n = n_out, against the template at tpl_offset), the traces placed back to back
+        from out_offset 0 on (a "c" trace has an even number of floats, so each begins on an even one)"""
+        L = _lib.load()
+        ejobs = np.ascontiguousarray(np.atleast_1d(extract_jobs), dtype=Fosphor.EXTRACT_DTYPE)
+        out = np.zeros(ejobs.size, Fosphor.CORRELATE_JOB_DTYPE)
+        code = Fosphor._correlate_trace(trace)
+        at = 0
+        for i, e in enumerate(ejobs):
+            job = _lib.CorrelateJob()
+            rv = L.fosphor_amd_correlate_from_extract(e.tobytes(), int(tpl_offset), int(tpl_len), code, float(threshold), C.byref(job))
+            if rv:
+                raise ValueError("fosphor_amd_correlate_from_extract -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            out[i] = (job.offset, at if code else 0, job.tpl_offset, job.n, job.tpl_len, job.trace, job.threshold)
+            at += Fosphor.correlate_n_out(code, job.n, job.tpl_len)
+        return out
+
+    @staticmethod
+    def _correlate_outs(jobs):
+        """(n_out per job, the capacity the jobs need)"""
+        n_out = [Fosphor.correlate_n_out(int(j["trace"]), int(j["n"]), int(j["tpl_len"])) for j in jobs]
+        return n_out, max([int(j["out_offset"]) + n for j, n in zip(jobs, n_out)] + [0])
+
+    @staticmethod
+    def _correlate_views(buf, jobs, n_out, complex_view):
+        views = []
+        for j, n in zip(jobs, n_out):
+            at, trace = int(j["out_offset"]), int(j["trace"])
+            if trace == 0:
+                views.append(None)
+            elif trace == 1:
+                views.append(buf[at:at + n])
+            else:
+                views.append(complex_view(buf[at:at + n]))
+        return views
+
+    def correlate(self, d_iq, jobs, tpl, n_samples=None, n_tpl=None):
+        """One record per job and, where the job asks for one, its trace, up to 4096 jobs in one call (fosphor_amd_correlate):
+        the sliding correlation of float32 IQ that is already in device memory against templates of up to 1024 samples, "valid"
+        lags only; rho = |c|^2 / (E Et) per lag, the peak, the lags above the job's threshold.  d_iq: a contiguous device tensor
+        (complex64 or float32 pairs; what extract() wrote) or a raw device pointer with n_samples; jobs: a CORRELATE_JOB_DTYPE
+        array (correlate_jobs() makes one from extract jobs); tpl: a numpy array of complex64 or float32 pairs (uploaded), such a
+        device tensor -- d_iq itself to correlate one burst against another -- or a raw device pointer with n_tpl.
+        Returns (records, views): a CORRELATE_RECORD_DTYPE array copied from the device, in job order, and a list with, per job,
+        a torch float32 view ("rho"), a complex64 view ("c") or None, into one device buffer.  A complex64 view begins on an
+        even float: a "c" job with an odd out_offset, which the C entry point takes, is a ValueError here."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.CORRELATE_JOB_DTYPE)
+        if np.any((jobs["trace"] == 2) & (jobs["out_offset"] & 1 != 0)):
+            raise ValueError("a \"c\" trace needs an even out_offset")
+
+        def count(x, n, name):
+            if n is not None:
+                return int(n)
+            if not hasattr(x, "numel"):
+                raise ValueError("a raw device pointer needs n_%s" % name)
+            if not x.is_contiguous() or x.dtype not in (torch.complex64, torch.float32):
+                raise ValueError("%s must be a contiguous complex64 or float32 tensor" % name)
+            return x.numel() if x.is_complex() else x.numel() // 2
+
+        if isinstance(tpl, np.ndarray):
+            tpl = np.ascontiguousarray(tpl)
+            tpl = tpl.view(np.float32) if tpl.dtype == np.complex64 else np.ascontiguousarray(tpl, dtype=np.float32)
+            tpl = torch.from_numpy(tpl.reshape(-1) if tpl.size else np.zeros(2, np.float32)).cuda()
+        n_samples = count(d_iq, n_samples, "samples")
+        n_tpl = count(tpl, n_tpl, "tpl")
+        n_out, cap = self._correlate_outs(jobs)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 1), dtype=torch.float32, device="cuda")
+        d_rec = torch.empty(max(jobs.size, 1) * self.CORRELATE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()			# the caller's samples were written on torch's stream
+        rv = self.L.fosphor_amd_correlate(self.h, _ptr(d_iq), n_samples, _ptr(tpl), n_tpl, jobs.ctypes.data, int(jobs.size),
+                                          d_rec.data_ptr(), d_out.data_ptr(), cap)
+        if rv:
+            raise RuntimeError("fosphor_amd_correlate -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        records = d_rec.cpu().numpy().view(self.CORRELATE_RECORD_DTYPE)[:jobs.size].copy()
+        return records, self._correlate_views(d_out, jobs, n_out, lambda v: v.view(torch.complex64))
+
+    @staticmethod
+    def correlate_host(iq, jobs, tpl):
+        """fosphor_amd_correlate_host: the same records and traces on the host, no GPU.  iq, tpl: complex64 or float32 pairs.
+        Returns (records, views), the views float32 ("rho") or complex64 ("c") arrays into one buffer, or None"""
+        def pairs(x):
+            x = np.ascontiguousarray(x)
+            x = x.view(np.float32) if x.dtype == np.complex64 else np.ascontiguousarray(x, dtype=np.float32)
+            return x.reshape(-1)
+        iq, tpl = pairs(iq), pairs(tpl)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.CORRELATE_JOB_DTYPE)
+        n_out, cap = Fosphor._correlate_outs(jobs)
+        out = np.zeros(max(cap, 2), np.float32)
+        records = np.zeros(max(jobs.size, 1), Fosphor.CORRELATE_RECORD_DTYPE)
+        keep = [x if x.size else np.zeros(2, np.float32) for x in (iq, tpl)]	# pointers to pass when there are no samples
+        rv = _lib.load().fosphor_amd_correlate_host(keep[0].ctypes.data, iq.size // 2, keep[1].ctypes.data, tpl.size // 2,
+                                                    jobs.ctypes.data, int(jobs.size), records.ctypes.data, out.ctypes.data, cap)
+        if rv:
+            raise ValueError("fosphor_amd_correlate_host -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+        return records[:jobs.size], Fosphor._correlate_views(out, jobs, n_out, lambda v: v.view(np.complex64))
+
+    @staticmethod
+    def correlate_derive(records, sample_rate):
+        """fosphor_amd_correlate_derive per record: a list of dicts of CORRELATE_VALUES (seconds, ratios, dB, turns; detections
+        an int)"""
+        L = _lib.load()
+        out = []
+        for r in np.ascontiguousarray(np.atleast_1d(records), dtype=Fosphor.CORRELATE_RECORD_DTYPE):
+            v = _lib.CorrelateValues()
+            rv = L.fosphor_amd_correlate_derive(r.tobytes(), float(sample_rate), C.byref(v))
+            if rv:
+                raise ValueError("fosphor_amd_correlate_derive -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            d = {k: getattr(v, k) for k in Fosphor.CORRELATE_VALUES}
+            d["detections"] = int(d["detections"])
+            out.append(d)
+        return out
+
+    def correlate_stats(self):
+        """fosphor_amd_correlate_stats as a dict: calls, launches by kernel, jobs, lags, complex multiply-adds (CORRELATE_STATS)"""
+        st = (C.c_longlong * 6)()
+        rv = self.L.fosphor_amd_correlate_stats(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("fosphor_amd_correlate_stats -> %d" % rv)
+        return dict(zip(self.CORRELATE_STATS, list(st)))
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

@@ -203,6 +203,9 @@ struct fosphor
 	long long demod_stats[7];		/* demod calls, launches by kernel, jobs by form, samples, outputs (fosphor_demod.hip, fosphor_amd_demod_stats) */
 	void     *d_demod;			/* job table of fosphor_demod.hip, grown on demand; the instance never reads it */
 	size_t    demod_cap;
+	long long correlate_stats[6];		/* correlate calls, launches by kernel, jobs, lags, multiply-adds (fosphor_correlate.hip, fosphor_amd_correlate_stats) */
+	void     *d_correlate;			/* job table and tile partials of fosphor_correlate.hip, grown on demand; the instance never reads it */
+	size_t    correlate_cap;
 	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
 	struct {
 		uint32_t *d_masks;		/* [mask_cap][rows / 32] presence bits, one part per rank */
@@ -457,6 +460,7 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_extract);
 	(void)hipFree(self->d_measure);
 	(void)hipFree(self->d_demod);
+	(void)hipFree(self->d_correlate);
 	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
 	(void)hipFree(self->wire.d_live); (void)hipFree(self->wire.d_words);
 	if (self->wire.h_live) (void)hipHostFree(self->wire.h_live);
@@ -2532,6 +2536,27 @@ extern "C" int fosphor_amd_priv_demod_scratch(struct fosphor *self, size_t bytes
 		self->demod_cap = bytes;
 	}
 	*d_scratch = self->d_demod;
+	return 0;
+}
+
+/* private accessors for fosphor_correlate.hip: its counters and its scratch, which only grows (every call drains the stream before
+ * it returns, so no launch reads the old one) */
+extern "C" long long *fosphor_amd_priv_correlate_stats(struct fosphor *self)
+{
+	return self->correlate_stats;
+}
+
+extern "C" int fosphor_amd_priv_correlate_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
+{
+	if (bytes > self->correlate_cap) {
+		(void)hipFree(self->d_correlate);
+		self->d_correlate = nullptr;
+		self->correlate_cap = 0;
+		if (hipMalloc(&self->d_correlate, bytes) != hipSuccess)
+			return -EIO;
+		self->correlate_cap = bytes;
+	}
+	*d_scratch = self->d_correlate;
 	return 0;
 }
 
