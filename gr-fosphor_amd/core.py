@@ -30,6 +30,44 @@ def _ptr(x):
     return int(x)
 
 
+def _fail(name, rv, exc):
+    """the library's `name` returned rv"""
+    raise exc("%s -> %d (%s)" % (name, rv, errno.errorcode.get(-rv, "?")))
+
+
+def _iq_count(x, n, name, floats=True):
+    """Samples of the device IQ x: n where given (a raw pointer needs it), else from the tensor, which must be contiguous and,
+    with floats, complex64 or float32 pairs"""
+    if n is not None:
+        return int(n)
+    if not hasattr(x, "numel"):
+        raise ValueError("a raw device pointer needs %s" % ("n_samples" if name == "d_iq" else "n_" + name))
+    if not floats:
+        if not x.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    elif not x.is_contiguous() or str(x.dtype) not in ("torch.complex64", "torch.float32"):
+        raise ValueError("%s must be a contiguous complex64 or float32 tensor" % name)
+    return x.numel() if x.is_complex() else x.numel() // 2
+
+
+def _float_pairs(x):
+    """complex64 or float32 pairs on the host -> flat float32"""
+    x = np.ascontiguousarray(x)
+    x = x.view(np.float32) if x.dtype == np.complex64 else np.ascontiguousarray(x, dtype=np.float32)
+    return x.reshape(-1)
+
+
+def _or_dummy(x):
+    """x, or something to point at when there are no samples (the caller holds it for as long as the pointer is in use)"""
+    return x if x.size else np.zeros(2, np.float32)
+
+
+def _outs(jobs, n_out_fn):
+    """(n_out per job, the capacity the jobs need)"""
+    n_out = [n_out_fn(j) for j in jobs]
+    return n_out, max([int(j["out_offset"]) + n for j, n in zip(jobs, n_out)] + [0])
+
+
 class Fosphor:
     """One fosphor instance (struct fosphor).  Reference geometry by default."""
 
@@ -69,6 +107,14 @@ class Fosphor:
             self.close()
         except Exception:
             pass
+
+    def _stats(self, fn, names):
+        """the counters a fosphor_amd_*_stats copies, as a dict"""
+        st = (C.c_longlong * len(names))()
+        rv = fn(self.h, C.byref(st))
+        if rv:
+            raise RuntimeError("%s -> %d" % (fn.__name__, rv))
+        return dict(zip(names, list(st)))
 
     # ---- reference API ---------------------------------------------------
     def process(self, samples):
@@ -190,11 +236,7 @@ class Fosphor:
     def wire_stats(self):
         """fosphor_amd_wire_stats as a dict: packs since the instance was made by the form they took (WIRE_STATS[:3]), live rows
         and wire bytes (masks included) of the last one"""
-        st = (C.c_longlong * 5)()
-        rv = self.L.fosphor_amd_wire_stats(self.h, C.byref(st))
-        if rv:
-            raise RuntimeError("fosphor_amd_wire_stats -> %d" % rv)
-        return dict(zip(self.WIRE_STATS, list(st)))
+        return self._stats(self.L.fosphor_amd_wire_stats, self.WIRE_STATS)
 
     def wire_kernel_times(self):
         """ms of the last k_wire_mask / k_wire_pack / k_wire_unpack launch made while profiling was on (-1: none)"""
@@ -315,7 +357,7 @@ class Fosphor:
             col.scale, col.offset = float(scale or 0.0), float(offset or 0.0)
         rv = self.L.fosphor_amd_view(self.h, C.byref(v), C.byref(o))
         if rv:
-            raise RuntimeError("fosphor_amd_view -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_view", rv, RuntimeError)
         for k in res:
             if k.endswith("_rgba"):
                 res[k] = res[k].view(torch.uint8).reshape(res[k].shape + (4,))
@@ -327,16 +369,12 @@ class Fosphor:
         v = _lib.View()
         rv = self.L.fosphor_amd_view_from_render(self.n, self.wf_rows, C.byref(render), int(width), int(wf_out_rows), C.byref(v))
         if rv:
-            raise RuntimeError("fosphor_amd_view_from_render -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_view_from_render", rv, RuntimeError)
         return self.view(v.first_bin, v.n_cols, v.width, v.wf_src_rows, v.wf_out_rows, detector=v.detector, **kw)
 
     def view_stats(self):
         """fosphor_amd_view_stats as a dict: view launches since the instance was made, by form (VIEW_FORMS)"""
-        st = (C.c_longlong * 4)()
-        rv = self.L.fosphor_amd_view_stats(self.h, C.byref(st))
-        if rv:
-            raise RuntimeError("fosphor_amd_view_stats -> %d" % rv)
-        return dict(zip(self.VIEW_FORMS, list(st)))
+        return self._stats(self.L.fosphor_amd_view_stats, self.VIEW_FORMS)
 
     TRACES = {"live": 0, "maxhold": 1}		# FOSPHOR_AMD_TRACE_* (include/fosphor_amd_detect.h)
     FLOOR_MODES = {"absolute": 0, "percentile": 1}	# FOSPHOR_AMD_FLOOR_*
@@ -356,7 +394,7 @@ class Fosphor:
         d_bin = torch.empty(shape, dtype=torch.int32, device="cuda") if bins else None
         rv = self.L.fosphor_amd_percentiles(self.h, qa.ctypes.data, qa.size, d_y.data_ptr(), d_bin.data_ptr() if bins else None)
         if rv:
-            raise RuntimeError("fosphor_amd_percentiles -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_percentiles", rv, RuntimeError)
         y = d_y.cpu().numpy()
         return (y, d_bin.cpu().numpy()) if bins else y
 
@@ -382,7 +420,7 @@ class Fosphor:
         d_bands = torch.empty(max(int(max_bands), 1) * self.BAND_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         rv = self.L.fosphor_amd_detect(self.h, C.byref(cfg), d_res.data_ptr(), d_bands.data_ptr(), int(max_bands))
         if rv:
-            raise RuntimeError("fosphor_amd_detect -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_detect", rv, RuntimeError)
         r = _lib.DetectResult.from_buffer_copy(d_res.cpu().numpy().tobytes())
         res = {k: getattr(r, k) for k, _ in _lib.DetectResult._fields_}
         bands = d_bands.cpu().numpy().view(self.BAND_DTYPE)[:res["n_written"]].copy()
@@ -390,11 +428,7 @@ class Fosphor:
 
     def detect_stats(self):
         """fosphor_amd_detect_stats as a dict: launches since the instance was made, by kernel (DETECT_STATS)"""
-        st = (C.c_longlong * 3)()
-        rv = self.L.fosphor_amd_detect_stats(self.h, C.byref(st))
-        if rv:
-            raise RuntimeError("fosphor_amd_detect_stats -> %d" % rv)
-        return dict(zip(self.DETECT_STATS, list(st)))
+        return self._stats(self.L.fosphor_amd_detect_stats, self.DETECT_STATS)
 
     MASK_STATS = ("scans", "from_trace", "form_rows", "form_shared")
     MASK_MAX_EVENTS = 65536				# FOSPHOR_AMD_MASK_MAX_EVENTS (include/fosphor_amd_mask.h)
@@ -438,7 +472,7 @@ class Fosphor:
                                           d_rows.data_ptr() if want_rows else None, d_ev.data_ptr() if d_ev is not None else None,
                                           int(max_events), d_pow.data_ptr() if channels else None)
         if rv:
-            raise RuntimeError("fosphor_amd_mask_scan -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_mask_scan", rv, RuntimeError)
         r = _lib.MaskResult.from_buffer_copy(d_res.cpu().numpy().tobytes())
         res = {k: getattr(r, k) for k, _ in _lib.MaskResult._fields_}
         recs = d_rows.cpu().numpy().view(self.MASK_ROW_DTYPE).copy() if want_rows else None
@@ -456,7 +490,7 @@ class Fosphor:
         d_out = torch.empty(self.n, dtype=torch.float32, device="cuda")
         rv = self.L.fosphor_amd_mask_from_trace(self.h, self.TRACES[trace], float(margin_db) / 20.0, int(spread_cols), d_out.data_ptr())
         if rv:
-            raise RuntimeError("fosphor_amd_mask_from_trace -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_mask_from_trace", rv, RuntimeError)
         return d_out
 
     def mask_from_points(self, cols, ys):
@@ -469,16 +503,12 @@ class Fosphor:
         out = np.empty(self.n, np.float32)
         rv = self.L.fosphor_amd_mask_from_points(self.n, c.ctypes.data, y.ctypes.data, c.size, out.ctypes.data)
         if rv:
-            raise RuntimeError("fosphor_amd_mask_from_points -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_mask_from_points", rv, RuntimeError)
         return out
 
     def mask_stats(self):
         """fosphor_amd_mask_stats as a dict: calls and launches since the instance was made, by kind and form (MASK_STATS)"""
-        st = (C.c_longlong * 4)()
-        rv = self.L.fosphor_amd_mask_stats(self.h, C.byref(st))
-        if rv:
-            raise RuntimeError("fosphor_amd_mask_stats -> %d" % rv)
-        return dict(zip(self.MASK_STATS, list(st)))
+        return self._stats(self.L.fosphor_amd_mask_stats, self.MASK_STATS)
 
     BURST_STATS = ("calls", "overflows", "k_count", "k_rows", "k_scan", "k_init", "k_write", "k_link", "k_reduce", "k_emit")
     BURST_MAX_RUNS = 1 << 20				# FOSPHOR_AMD_BURST_MAX_RUNS (include/fosphor_amd_burst.h)
@@ -523,7 +553,7 @@ class Fosphor:
         rv = self.L.fosphor_amd_bursts(self.h, C.byref(cfg), d_thr.data_ptr() if d_thr is not None else None, d_res.data_ptr(),
                                        d_out.data_ptr(), int(max_bursts))
         if rv:
-            raise RuntimeError("fosphor_amd_bursts -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_bursts", rv, RuntimeError)
         r = _lib.BurstResult.from_buffer_copy(d_res.cpu().numpy().tobytes())
         res = {k: getattr(r, k) for k, _ in _lib.BurstResult._fields_}
         recs = d_out.cpu().numpy().view(self.BURST_DTYPE)[:res["n_written"]].copy()
@@ -531,11 +561,7 @@ class Fosphor:
 
     def burst_stats(self):
         """fosphor_amd_burst_stats as a dict: calls, overflows and launches by kernel since the instance was made (BURST_STATS)"""
-        st = (C.c_longlong * 10)()
-        rv = self.L.fosphor_amd_burst_stats(self.h, C.byref(st))
-        if rv:
-            raise RuntimeError("fosphor_amd_burst_stats -> %d" % rv)
-        return dict(zip(self.BURST_STATS, list(st)))
+        return self._stats(self.L.fosphor_amd_burst_stats, self.BURST_STATS)
 
     EXTRACT_STATS = ("calls", "k_tile", "k_wave", "jobs_tile", "jobs_wave", "samples")
     EXTRACT_MAX_JOBS = 4096				# FOSPHOR_AMD_EXTRACT_MAX_JOBS (include/fosphor_amd_extract.h)
@@ -560,7 +586,7 @@ class Fosphor:
         out = np.empty(max(int(n_taps), 1), np.float32)
         rv = _lib.load().fosphor_amd_extract_design(int(decim), int(n_taps), float(guard), out.ctypes.data)
         if rv:
-            raise ValueError("fosphor_amd_extract_design -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_extract_design", rv, ValueError)
         return out
 
     def extract_from_burst(self, burst, newest_first_sample, row_hop, max_decim=64, guard=0.8):
@@ -572,7 +598,7 @@ class Fosphor:
         rv = self.L.fosphor_amd_extract_from_burst(C.byref(b), self.n, int(newest_first_sample), int(row_hop), int(max_decim),
                                                    float(guard), C.byref(job), C.byref(taps))
         if rv:
-            raise ValueError("fosphor_amd_extract_from_burst -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_extract_from_burst", rv, ValueError)
         return np.frombuffer(bytes(job), self.EXTRACT_DTYPE).copy(), taps.value
 
     def extract(self, d_iq, jobs, taps, iq_format=None, n_samples=None):
@@ -585,12 +611,7 @@ class Fosphor:
         import torch
         jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.EXTRACT_DTYPE)
         fmt = -1 if iq_format is None else IQ_FORMATS[iq_format] if isinstance(iq_format, str) else int(iq_format)
-        if n_samples is None:
-            if not hasattr(d_iq, "numel"):
-                raise ValueError("a raw device pointer needs n_samples")
-            if not d_iq.is_contiguous():
-                raise ValueError("d_iq must be contiguous")
-            n_samples = d_iq.numel() if d_iq.is_complex() else d_iq.numel() // 2
+        n_samples = _iq_count(d_iq, n_samples, "d_iq", floats=False)
         if hasattr(taps, "data_ptr"):
             d_taps = taps
             if d_taps.dtype != torch.float32 or not d_taps.is_cuda or not d_taps.is_contiguous():
@@ -604,16 +625,12 @@ class Fosphor:
         rv = self.L.fosphor_amd_extract(self.h, _ptr(d_iq), int(n_samples), fmt, jobs.ctypes.data, int(jobs.size),
                                         d_taps.data_ptr(), int(d_taps.numel()), d_out.data_ptr(), cap)
         if rv:
-            raise RuntimeError("fosphor_amd_extract -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_extract", rv, RuntimeError)
         return [d_out[int(j["out_offset"]):int(j["out_offset"]) + int(j["n_out"])] for j in jobs]
 
     def extract_stats(self):
         """fosphor_amd_extract_stats as a dict: calls, launches and jobs by kernel form, input samples spanned (EXTRACT_STATS)"""
-        st = (C.c_longlong * 6)()
-        rv = self.L.fosphor_amd_extract_stats(self.h, C.byref(st))
-        if rv:
-            raise RuntimeError("fosphor_amd_extract_stats -> %d" % rv)
-        return dict(zip(self.EXTRACT_STATS, list(st)))
+        return self._stats(self.L.fosphor_amd_extract_stats, self.EXTRACT_STATS)
 
     MEASURE_STATS = ("calls", "k_wave", "k_split", "k_combine", "jobs_wave", "jobs_split", "samples")
     MEASURE_MAX_JOBS = 4096				# FOSPHOR_AMD_MEASURE_MAX_JOBS (include/fosphor_amd_measure.h)
@@ -649,7 +666,7 @@ class Fosphor:
             job = _lib.MeasureJob()
             rv = L.fosphor_amd_measure_from_extract(e.tobytes(), float(threshold), C.byref(job))
             if rv:
-                raise ValueError("fosphor_amd_measure_from_extract -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+                _fail("fosphor_amd_measure_from_extract", rv, ValueError)
             out[i] = (job.offset, job.n, job.threshold)
         return out
 
@@ -661,32 +678,25 @@ class Fosphor:
         MEASURE_RECORD_DTYPE array copied from the device, in job order."""
         import torch
         jobs = self.measure_jobs(jobs, threshold)
-        if n_samples is None:
-            if not hasattr(d_iq, "numel"):
-                raise ValueError("a raw device pointer needs n_samples")
-            if not d_iq.is_contiguous() or d_iq.dtype not in (torch.complex64, torch.float32):
-                raise ValueError("d_iq must be a contiguous complex64 or float32 tensor")
-            n_samples = d_iq.numel() if d_iq.is_complex() else d_iq.numel() // 2
+        n_samples = _iq_count(d_iq, n_samples, "d_iq")
         # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
         d_rec = torch.empty(max(jobs.size, 1) * self.MEASURE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()			# the caller's samples were written on torch's stream
         rv = self.L.fosphor_amd_measure(self.h, _ptr(d_iq), int(n_samples), jobs.ctypes.data, int(jobs.size), d_rec.data_ptr())
         if rv:
-            raise RuntimeError("fosphor_amd_measure -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_measure", rv, RuntimeError)
         return d_rec.cpu().numpy().view(self.MEASURE_RECORD_DTYPE)[:jobs.size].copy()
 
     @staticmethod
     def measure_host(iq, jobs):
         """fosphor_amd_measure_host: the same records on the host, no GPU.  iq: complex64 or float32 pairs"""
-        iq = np.ascontiguousarray(iq)
-        iq = iq.view(np.float32) if iq.dtype == np.complex64 else np.ascontiguousarray(iq, dtype=np.float32)
-        iq = iq.reshape(-1)
+        iq = _float_pairs(iq)
         jobs = Fosphor.measure_jobs(jobs)
         out = np.zeros(max(jobs.size, 1), Fosphor.MEASURE_RECORD_DTYPE)
-        keep = iq if iq.size else np.zeros(2, np.float32)		# a pointer to pass when there are no samples
+        keep = _or_dummy(iq)
         rv = _lib.load().fosphor_amd_measure_host(keep.ctypes.data, iq.size // 2, jobs.ctypes.data, int(jobs.size), out.ctypes.data)
         if rv:
-            raise ValueError("fosphor_amd_measure_host -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_measure_host", rv, ValueError)
         return out[:jobs.size]
 
     @staticmethod
@@ -698,7 +708,7 @@ class Fosphor:
             v = _lib.MeasureValues()
             rv = L.fosphor_amd_measure_derive(r.tobytes(), float(sample_rate), C.byref(v))
             if rv:
-                raise ValueError("fosphor_amd_measure_derive -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+                _fail("fosphor_amd_measure_derive", rv, ValueError)
             d = {k: getattr(v, k) for k in Fosphor.MEASURE_VALUES}
             d["pulses"] = int(d["pulses"])
             out.append(d)
@@ -706,11 +716,7 @@ class Fosphor:
 
     def measure_stats(self):
         """fosphor_amd_measure_stats as a dict: calls, launches by kernel, jobs by form, samples (MEASURE_STATS)"""
-        st = (C.c_longlong * 7)()
-        rv = self.L.fosphor_amd_measure_stats(self.h, C.byref(st))
-        if rv:
-            raise RuntimeError("fosphor_amd_measure_stats -> %d" % rv)
-        return dict(zip(self.MEASURE_STATS, list(st)))
+        return self._stats(self.L.fosphor_amd_measure_stats, self.MEASURE_STATS)
 
     DEMOD_STATS = ("calls", "k_direct", "k_avg", "jobs_direct", "jobs_avg", "samples", "outputs")
     DEMOD_MAX_JOBS = 4096				# FOSPHOR_AMD_DEMOD_MAX_JOBS (include/fosphor_amd_demod.h)
@@ -733,7 +739,7 @@ class Fosphor:
         """fosphor_amd_demod_n_out: the outputs of a job of n samples, n_trace // avg (n_trace = n, or n - 1 for "fm")"""
         rv = _lib.load().fosphor_amd_demod_n_out(Fosphor._demod_mode(mode), int(n), int(avg))
         if rv < 0:
-            raise ValueError("fosphor_amd_demod_n_out -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_demod_n_out", rv, ValueError)
         return rv
 
     @staticmethod
@@ -748,16 +754,14 @@ class Fosphor:
             job = _lib.DemodJob()
             rv = L.fosphor_amd_demod_from_extract(e.tobytes(), Fosphor._demod_mode(mode), int(avg), C.byref(job))
             if rv:
-                raise ValueError("fosphor_amd_demod_from_extract -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+                _fail("fosphor_amd_demod_from_extract", rv, ValueError)
             out[i] = (job.offset, at, job.n, job.mode, job.avg, job.reserved)
             at += Fosphor.demod_n_out(job.mode, job.n, job.avg)
         return out
 
     @staticmethod
     def _demod_outs(jobs):
-        """(n_out per job, the capacity the jobs need)"""
-        n_out = [Fosphor.demod_n_out(int(j["mode"]), int(j["n"]), int(j["avg"])) for j in jobs]
-        return n_out, max([int(j["out_offset"]) + n for j, n in zip(jobs, n_out)] + [0])
+        return _outs(jobs, lambda j: Fosphor.demod_n_out(int(j["mode"]), int(j["n"]), int(j["avg"])))
 
     def demod(self, d_iq, jobs, n_samples=None):
         """One float32 trace per job, up to 4096 jobs in one call (fosphor_amd_demod): power, phase in turns or the phase step
@@ -767,35 +771,28 @@ class Fosphor:
         makes one from extract jobs).  Returns a list with one torch float32 view per job, into one device buffer."""
         import torch
         jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.DEMOD_JOB_DTYPE)
-        if n_samples is None:
-            if not hasattr(d_iq, "numel"):
-                raise ValueError("a raw device pointer needs n_samples")
-            if not d_iq.is_contiguous() or d_iq.dtype not in (torch.complex64, torch.float32):
-                raise ValueError("d_iq must be a contiguous complex64 or float32 tensor")
-            n_samples = d_iq.numel() if d_iq.is_complex() else d_iq.numel() // 2
+        n_samples = _iq_count(d_iq, n_samples, "d_iq")
         n_out, cap = self._demod_outs(jobs)
         # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
         d_out = torch.empty(max(cap, 1), dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()			# the caller's samples were written on torch's stream
         rv = self.L.fosphor_amd_demod(self.h, _ptr(d_iq), int(n_samples), jobs.ctypes.data, int(jobs.size), d_out.data_ptr(), cap)
         if rv:
-            raise RuntimeError("fosphor_amd_demod -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_demod", rv, RuntimeError)
         return [d_out[int(j["out_offset"]):int(j["out_offset"]) + n] for j, n in zip(jobs, n_out)]
 
     @staticmethod
     def demod_host(iq, jobs):
         """fosphor_amd_demod_host: the same traces on the host, no GPU.  iq: complex64 or float32 pairs.  Returns a list with one
         float32 array per job, views of one buffer"""
-        iq = np.ascontiguousarray(iq)
-        iq = iq.view(np.float32) if iq.dtype == np.complex64 else np.ascontiguousarray(iq, dtype=np.float32)
-        iq = iq.reshape(-1)
+        iq = _float_pairs(iq)
         jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.DEMOD_JOB_DTYPE)
         n_out, cap = Fosphor._demod_outs(jobs)
         out = np.zeros(max(cap, 1), np.float32)
-        keep = iq if iq.size else np.zeros(2, np.float32)		# a pointer to pass when there are no samples
+        keep = _or_dummy(iq)
         rv = _lib.load().fosphor_amd_demod_host(keep.ctypes.data, iq.size // 2, jobs.ctypes.data, int(jobs.size), out.ctypes.data, cap)
         if rv:
-            raise ValueError("fosphor_amd_demod_host -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_demod_host", rv, ValueError)
         return [out[int(j["out_offset"]):int(j["out_offset"]) + n] for j, n in zip(jobs, n_out)]
 
     @staticmethod
@@ -812,11 +809,7 @@ class Fosphor:
 
     def demod_stats(self):
         """fosphor_amd_demod_stats as a dict: calls, launches by kernel, jobs by form, samples, outputs (DEMOD_STATS)"""
-        st = (C.c_longlong * 7)()
-        rv = self.L.fosphor_amd_demod_stats(self.h, C.byref(st))
-        if rv:
-            raise RuntimeError("fosphor_amd_demod_stats -> %d" % rv)
-        return dict(zip(self.DEMOD_STATS, list(st)))
+        return self._stats(self.L.fosphor_amd_demod_stats, self.DEMOD_STATS)
 
     CORRELATE_STATS = ("calls", "k_tile", "k_combine", "jobs", "lags", "macs")
     CORRELATE_MAX_JOBS = 4096				# FOSPHOR_AMD_CORRELATE_MAX_JOBS (include/fosphor_amd_correlate.h)
@@ -843,7 +836,7 @@ class Fosphor:
         """fosphor_amd_correlate_n_out: the trace floats of a job of n samples: 0, n_lags or 2 * n_lags, n_lags = max(n - T + 1, 0)"""
         rv = _lib.load().fosphor_amd_correlate_n_out(Fosphor._correlate_trace(trace), int(n), int(tpl_len))
         if rv < 0:
-            raise ValueError("fosphor_amd_correlate_n_out -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_correlate_n_out", rv, ValueError)
         return rv
 
     @staticmethod
@@ -860,16 +853,14 @@ class Fosphor:
             job = _lib.CorrelateJob()
             rv = L.fosphor_amd_correlate_from_extract(e.tobytes(), int(tpl_offset), int(tpl_len), code, float(threshold), C.byref(job))
             if rv:
-                raise ValueError("fosphor_amd_correlate_from_extract -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+                _fail("fosphor_amd_correlate_from_extract", rv, ValueError)
             out[i] = (job.offset, at if code else 0, job.tpl_offset, job.n, job.tpl_len, job.trace, job.threshold)
             at += Fosphor.correlate_n_out(code, job.n, job.tpl_len)
         return out
 
     @staticmethod
     def _correlate_outs(jobs):
-        """(n_out per job, the capacity the jobs need)"""
-        n_out = [Fosphor.correlate_n_out(int(j["trace"]), int(j["n"]), int(j["tpl_len"])) for j in jobs]
-        return n_out, max([int(j["out_offset"]) + n for j, n in zip(jobs, n_out)] + [0])
+        return _outs(jobs, lambda j: Fosphor.correlate_n_out(int(j["trace"]), int(j["n"]), int(j["tpl_len"])))
 
     @staticmethod
     def _correlate_views(buf, jobs, n_out, complex_view):
@@ -898,22 +889,10 @@ class Fosphor:
         jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.CORRELATE_JOB_DTYPE)
         if np.any((jobs["trace"] == 2) & (jobs["out_offset"] & 1 != 0)):
             raise ValueError("a \"c\" trace needs an even out_offset")
-
-        def count(x, n, name):
-            if n is not None:
-                return int(n)
-            if not hasattr(x, "numel"):
-                raise ValueError("a raw device pointer needs n_%s" % name)
-            if not x.is_contiguous() or x.dtype not in (torch.complex64, torch.float32):
-                raise ValueError("%s must be a contiguous complex64 or float32 tensor" % name)
-            return x.numel() if x.is_complex() else x.numel() // 2
-
         if isinstance(tpl, np.ndarray):
-            tpl = np.ascontiguousarray(tpl)
-            tpl = tpl.view(np.float32) if tpl.dtype == np.complex64 else np.ascontiguousarray(tpl, dtype=np.float32)
-            tpl = torch.from_numpy(tpl.reshape(-1) if tpl.size else np.zeros(2, np.float32)).cuda()
-        n_samples = count(d_iq, n_samples, "samples")
-        n_tpl = count(tpl, n_tpl, "tpl")
+            tpl = torch.from_numpy(_or_dummy(_float_pairs(tpl))).cuda()
+        n_samples = _iq_count(d_iq, n_samples, "samples")
+        n_tpl = _iq_count(tpl, n_tpl, "tpl")
         n_out, cap = self._correlate_outs(jobs)
         # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
         d_out = torch.empty(max(cap, 1), dtype=torch.float32, device="cuda")
@@ -922,7 +901,7 @@ class Fosphor:
         rv = self.L.fosphor_amd_correlate(self.h, _ptr(d_iq), n_samples, _ptr(tpl), n_tpl, jobs.ctypes.data, int(jobs.size),
                                           d_rec.data_ptr(), d_out.data_ptr(), cap)
         if rv:
-            raise RuntimeError("fosphor_amd_correlate -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_correlate", rv, RuntimeError)
         records = d_rec.cpu().numpy().view(self.CORRELATE_RECORD_DTYPE)[:jobs.size].copy()
         return records, self._correlate_views(d_out, jobs, n_out, lambda v: v.view(torch.complex64))
 
@@ -930,20 +909,16 @@ class Fosphor:
     def correlate_host(iq, jobs, tpl):
         """fosphor_amd_correlate_host: the same records and traces on the host, no GPU.  iq, tpl: complex64 or float32 pairs.
         Returns (records, views), the views float32 ("rho") or complex64 ("c") arrays into one buffer, or None"""
-        def pairs(x):
-            x = np.ascontiguousarray(x)
-            x = x.view(np.float32) if x.dtype == np.complex64 else np.ascontiguousarray(x, dtype=np.float32)
-            return x.reshape(-1)
-        iq, tpl = pairs(iq), pairs(tpl)
+        iq, tpl = _float_pairs(iq), _float_pairs(tpl)
         jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.CORRELATE_JOB_DTYPE)
         n_out, cap = Fosphor._correlate_outs(jobs)
         out = np.zeros(max(cap, 2), np.float32)
         records = np.zeros(max(jobs.size, 1), Fosphor.CORRELATE_RECORD_DTYPE)
-        keep = [x if x.size else np.zeros(2, np.float32) for x in (iq, tpl)]	# pointers to pass when there are no samples
+        keep = _or_dummy(iq), _or_dummy(tpl)
         rv = _lib.load().fosphor_amd_correlate_host(keep[0].ctypes.data, iq.size // 2, keep[1].ctypes.data, tpl.size // 2,
                                                     jobs.ctypes.data, int(jobs.size), records.ctypes.data, out.ctypes.data, cap)
         if rv:
-            raise ValueError("fosphor_amd_correlate_host -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+            _fail("fosphor_amd_correlate_host", rv, ValueError)
         return records[:jobs.size], Fosphor._correlate_views(out, jobs, n_out, lambda v: v.view(np.complex64))
 
     @staticmethod
@@ -956,7 +931,7 @@ class Fosphor:
             v = _lib.CorrelateValues()
             rv = L.fosphor_amd_correlate_derive(r.tobytes(), float(sample_rate), C.byref(v))
             if rv:
-                raise ValueError("fosphor_amd_correlate_derive -> %d (%s)" % (rv, errno.errorcode.get(-rv, "?")))
+                _fail("fosphor_amd_correlate_derive", rv, ValueError)
             d = {k: getattr(v, k) for k in Fosphor.CORRELATE_VALUES}
             d["detections"] = int(d["detections"])
             out.append(d)
@@ -964,11 +939,7 @@ class Fosphor:
 
     def correlate_stats(self):
         """fosphor_amd_correlate_stats as a dict: calls, launches by kernel, jobs, lags, complex multiply-adds (CORRELATE_STATS)"""
-        st = (C.c_longlong * 6)()
-        rv = self.L.fosphor_amd_correlate_stats(self.h, C.byref(st))
-        if rv:
-            raise RuntimeError("fosphor_amd_correlate_stats -> %d" % rv)
-        return dict(zip(self.CORRELATE_STATS, list(st)))
+        return self._stats(self.L.fosphor_amd_correlate_stats, self.CORRELATE_STATS)
 
     @property
     def histo_scale(self):
@@ -1046,11 +1017,7 @@ class Fosphor:
     def merge_stats(self):
         """fosphor_amd_merge_stats as a dict: merge launches since the instance was made by form (MERGE_FORMS[:7]), how many of the
         long-batch ones read the rise/decay table from memory, the most batches one sparse launch of either kind merged, the rows the last sparse launch listed (-1: none yet; waits for it)"""
-        st = (C.c_longlong * 11)()
-        rv = self.L.fosphor_amd_merge_stats(self.h, C.byref(st))
-        if rv:
-            raise RuntimeError("fosphor_amd_merge_stats -> %d" % rv)
-        return dict(zip(self.MERGE_FORMS, list(st)))
+        return self._stats(self.L.fosphor_amd_merge_stats, self.MERGE_FORMS)
 
     def kernel_busy(self):
         """ms during which >= 1 kernel of each kind ran (call before kernel_times)"""

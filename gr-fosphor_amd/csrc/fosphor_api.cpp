@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "fosphor_internal.h"
+#include "fosphor_jobs.h"
 #include "../../include/fosphor_amd.h"
 #include "../../include/fosphor_amd_sink.h"
 #include "../../include/fosphor_amd_wire.h"
@@ -192,20 +193,14 @@ struct fosphor
 	long long mask_stats[4];		/* mask launches by kind and form (fosphor_mask.hip, fosphor_amd_mask_stats) */
 	void     *d_mask;			/* scratch of fosphor_mask.hip, allocated on first use; the instance never reads it */
 	long long burst_stats[10];		/* burst calls and launches by kernel (fosphor_burst.hip, fosphor_amd_burst_stats) */
-	void     *d_burst[2];			/* scratch of fosphor_burst.hip: [0] by rows and strips, [1] by runs; grown on demand, never read here */
-	size_t    burst_cap[2];
 	long long extract_stats[6];		/* extract calls, launches and jobs by form, samples (fosphor_extract.hip, fosphor_amd_extract_stats) */
-	void     *d_extract;			/* job table of fosphor_extract.hip, grown on demand; the instance never reads it */
-	size_t    extract_cap;
 	long long measure_stats[7];		/* measure calls, launches by kernel, jobs by form, samples (fosphor_measure.hip, fosphor_amd_measure_stats) */
-	void     *d_measure;			/* job table and SPLIT partials of fosphor_measure.hip, grown on demand; the instance never reads it */
-	size_t    measure_cap;
 	long long demod_stats[7];		/* demod calls, launches by kernel, jobs by form, samples, outputs (fosphor_demod.hip, fosphor_amd_demod_stats) */
-	void     *d_demod;			/* job table of fosphor_demod.hip, grown on demand; the instance never reads it */
-	size_t    demod_cap;
 	long long correlate_stats[6];		/* correlate calls, launches by kernel, jobs, lags, multiply-adds (fosphor_correlate.hip, fosphor_amd_correlate_stats) */
-	void     *d_correlate;			/* job table and tile partials of fosphor_correlate.hip, grown on demand; the instance never reads it */
-	size_t    correlate_cap;
+	struct {				/* scratch of fosphor_burst.hip (two) and of the passes over burst IQ (job tables, partials), by */
+		void  *d;			/* FOSPHOR_SCRATCH_* (fosphor_jobs.h); grown on demand, the instance never reads them */
+		size_t cap;
+	} scratch[FOSPHOR_SCRATCH_COUNT];
 	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
 	struct {
 		uint32_t *d_masks;		/* [mask_cap][rows / 32] presence bits, one part per rank */
@@ -456,11 +451,8 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_palette);
 	(void)hipFree(self->d_detect);
 	(void)hipFree(self->d_mask);
-	(void)hipFree(self->d_burst[0]); (void)hipFree(self->d_burst[1]);
-	(void)hipFree(self->d_extract);
-	(void)hipFree(self->d_measure);
-	(void)hipFree(self->d_demod);
-	(void)hipFree(self->d_correlate);
+	for (int i = 0; i < FOSPHOR_SCRATCH_COUNT; i++)
+		(void)hipFree(self->scratch[i].d);
 	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
 	(void)hipFree(self->wire.d_live); (void)hipFree(self->wire.d_words);
 	if (self->wire.h_live) (void)hipHostFree(self->wire.h_live);
@@ -2453,112 +2445,42 @@ extern "C" int fosphor_amd_priv_mask_scratch(struct fosphor *self, size_t bytes,
 	return 0;
 }
 
-/* private accessors for fosphor_burst.hip: its counters, and its two scratch buffers, which only grow (the caller has drained the
- * stream of every launch that used the old one before it asks for more) */
-extern "C" long long *fosphor_amd_priv_burst_stats(struct fosphor *self)
+/* The scratch buffers that only grow, by FOSPHOR_SCRATCH_* (fosphor_jobs.h): the two of fosphor_burst.hip, and one each for the
+ * job tables and partials of fosphor_extract / _measure / _demod / _correlate.hip.  Every user has drained the stream of the
+ * launches that used the old buffer before it asks for a larger one. */
+extern "C" int fosphor_amd_priv_scratch(struct fosphor *self, int which, size_t bytes, void **d_scratch)
 {
-	return self->burst_stats;
-}
-
-extern "C" int fosphor_amd_priv_burst_scratch(struct fosphor *self, int which, size_t bytes, void **d_scratch)
-{
-	if (which < 0 || which > 1)
+	if (which < 0 || which >= FOSPHOR_SCRATCH_COUNT)
 		return -EINVAL;
-	if (bytes > self->burst_cap[which]) {
-		(void)hipFree(self->d_burst[which]);
-		self->d_burst[which] = nullptr;
-		self->burst_cap[which] = 0;
-		if (hipMalloc(&self->d_burst[which], bytes) != hipSuccess)
+	if (bytes > self->scratch[which].cap) {
+		(void)hipFree(self->scratch[which].d);
+		self->scratch[which].d = nullptr;
+		self->scratch[which].cap = 0;
+		if (hipMalloc(&self->scratch[which].d, bytes) != hipSuccess)
 			return -EIO;
-		self->burst_cap[which] = bytes;
+		self->scratch[which].cap = bytes;
 	}
-	*d_scratch = self->d_burst[which];
+	*d_scratch = self->scratch[which].d;
 	return 0;
 }
 
-/* private accessors for fosphor_extract.hip: its counters, its job table, which only grows (every call drains the stream before it
- * returns, so no launch reads the old one), and the format -1 stands for */
-extern "C" long long *fosphor_amd_priv_extract_stats(struct fosphor *self)
+/* what every public fosphor_amd_*_stats does with its module's counters */
+extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, long long *(*counters)(struct fosphor *), int n, long long *stats)
 {
-	return self->extract_stats;
-}
-
-extern "C" int fosphor_amd_priv_extract_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
-{
-	if (bytes > self->extract_cap) {
-		(void)hipFree(self->d_extract);
-		self->d_extract = nullptr;
-		self->extract_cap = 0;
-		if (hipMalloc(&self->d_extract, bytes) != hipSuccess)
-			return -EIO;
-		self->extract_cap = bytes;
-	}
-	*d_scratch = self->d_extract;
+	if (!self)
+		return -EINVAL;
+	if (stats)
+		memcpy(stats, counters(self), sizeof(long long) * n);
 	return 0;
 }
 
-/* private accessors for fosphor_measure.hip: its counters and its scratch, which only grows (every call drains the stream before
- * it returns, so no launch reads the old one) */
-extern "C" long long *fosphor_amd_priv_measure_stats(struct fosphor *self)
-{
-	return self->measure_stats;
-}
-
-extern "C" int fosphor_amd_priv_measure_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
-{
-	if (bytes > self->measure_cap) {
-		(void)hipFree(self->d_measure);
-		self->d_measure = nullptr;
-		self->measure_cap = 0;
-		if (hipMalloc(&self->d_measure, bytes) != hipSuccess)
-			return -EIO;
-		self->measure_cap = bytes;
-	}
-	*d_scratch = self->d_measure;
-	return 0;
-}
-
-/* private accessors for fosphor_demod.hip: its counters and its job table, which only grows (every call drains the stream before
- * it returns, so no launch reads the old one) */
-extern "C" long long *fosphor_amd_priv_demod_stats(struct fosphor *self)
-{
-	return self->demod_stats;
-}
-
-extern "C" int fosphor_amd_priv_demod_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
-{
-	if (bytes > self->demod_cap) {
-		(void)hipFree(self->d_demod);
-		self->d_demod = nullptr;
-		self->demod_cap = 0;
-		if (hipMalloc(&self->d_demod, bytes) != hipSuccess)
-			return -EIO;
-		self->demod_cap = bytes;
-	}
-	*d_scratch = self->d_demod;
-	return 0;
-}
-
-/* private accessors for fosphor_correlate.hip: its counters and its scratch, which only grows (every call drains the stream before
- * it returns, so no launch reads the old one) */
-extern "C" long long *fosphor_amd_priv_correlate_stats(struct fosphor *self)
-{
-	return self->correlate_stats;
-}
-
-extern "C" int fosphor_amd_priv_correlate_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
-{
-	if (bytes > self->correlate_cap) {
-		(void)hipFree(self->d_correlate);
-		self->d_correlate = nullptr;
-		self->correlate_cap = 0;
-		if (hipMalloc(&self->d_correlate, bytes) != hipSuccess)
-			return -EIO;
-		self->correlate_cap = bytes;
-	}
-	*d_scratch = self->d_correlate;
-	return 0;
-}
+/* private accessors for the counters of fosphor_burst / _extract / _measure / _demod / _correlate.hip, and for the format that -1
+ * stands for in fosphor_amd_extract */
+extern "C" long long *fosphor_amd_priv_burst_stats(struct fosphor *self) { return self->burst_stats; }
+extern "C" long long *fosphor_amd_priv_extract_stats(struct fosphor *self) { return self->extract_stats; }
+extern "C" long long *fosphor_amd_priv_measure_stats(struct fosphor *self) { return self->measure_stats; }
+extern "C" long long *fosphor_amd_priv_demod_stats(struct fosphor *self) { return self->demod_stats; }
+extern "C" long long *fosphor_amd_priv_correlate_stats(struct fosphor *self) { return self->correlate_stats; }
 
 extern "C" int fosphor_amd_priv_iq_format(struct fosphor *self)
 {

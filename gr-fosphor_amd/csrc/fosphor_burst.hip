@@ -40,12 +40,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include "fosphor_jobs.h"					/* the scratch buffers and the copy of the counters */
 #include "../../include/fosphor_amd.h"
 #include "../../include/fosphor_amd_burst.h"
 
-/* accessors implemented next to struct fosphor (fosphor_api.cpp) */
+/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
 extern "C" long long *fosphor_amd_priv_burst_stats(struct fosphor *self);
-extern "C" int fosphor_amd_priv_burst_scratch(struct fosphor *self, int which, size_t bytes, void **d_scratch);
 
 namespace {
 
@@ -592,12 +592,7 @@ bool launched() { return hipGetLastError() == hipSuccess; }
 
 extern "C" int fosphor_amd_burst_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_BURST_STATS])
 {
-	if (!self)
-		return -EINVAL;
-	if (stats)
-		for (int i = 0; i < FOSPHOR_AMD_BURST_STATS; i++)
-			stats[i] = fosphor_amd_priv_burst_stats(self)[i];
-	return 0;
+	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_burst_stats, FOSPHOR_AMD_BURST_STATS, stats);
 }
 
 extern "C" int fosphor_amd_bursts_host(const float *ys, int rows, int n, const float *thr_or_null,
@@ -733,7 +728,7 @@ extern "C" int fosphor_amd_bursts(struct fosphor *self, const struct fosphor_amd
 	/* scratch by rows and strips: three summaries per row and strip, the rows' counts and offsets, the total */
 	const size_t cells = (size_t)rows * strips;
 	const size_t fixed_ints = 3 * cells + (size_t)rows + (size_t)rows + 1 + 1;
-	if (fosphor_amd_priv_burst_scratch(self, 0, fixed_ints * sizeof(int), &d))
+	if (fosphor_amd_priv_scratch(self, FOSPHOR_SCRATCH_BURST_ROWS, fixed_ints * sizeof(int), &d))
 		return -EIO;
 	int *ints = (int *)d;
 
@@ -794,7 +789,7 @@ extern "C" int fosphor_amd_bursts(struct fosphor *self, const struct fosphor_amd
 	size_t cap = 1024;
 	while (cap < (size_t)total)
 		cap <<= 1;
-	if (fosphor_amd_priv_burst_scratch(self, 1, cap * (sizeof(Run) + sizeof(Comp) + sizeof(int)), &d))
+	if (fosphor_amd_priv_scratch(self, FOSPHOR_SCRATCH_BURST_RUNS, cap * (sizeof(Run) + sizeof(Comp) + sizeof(int)), &d))
 		return -EIO;
 	Run *runs = (Run *)d;
 	Comp *comps = (Comp *)(runs + cap);

@@ -6,36 +6,25 @@
  * is on the process / merge path and no buffer of the instance is read or written but the scratch this file owns (the job table,
  * the prefix of work-group counts and the tile partials).
  *
- *   k_correlate_tile     a work-group of 256 lanes owns kTile consecutive lags of one job, which it finds by a bounded binary search
- *                        of the prefix (13 steps cover 4096 jobs).  It brings y[k0 .. k0 + lags + T - 1) and the template into LDS;
+ *   k_correlate_tile     a work-group of 256 lanes owns kTile consecutive lags of one job, which it finds in the prefix
+ *                        (fosphor_jobs.h).  It brings y[k0 .. k0 + lags + T - 1) and the template into LDS;
  *                        lane i owns lags i, i + 256, i + 512, i + 768: at step i of the template the 64 lanes of a wave read 64
  *                        consecutive samples (no bank conflict) and one template value (a broadcast), and each lane issues
  *                        26 fused multiply-adds in double for its 5 LDS reads.  Then rho, the trace, and the tile's partial.
  *   k_correlate_combine  a wave per job folds the job's partials and writes the record; lane l takes tiles l, l + 64, ...  Every
  *                        folded quantity is an integer, a minimum or a maximum, so the order of the fold does not matter; the
  *                        seam between tile c - 1 and tile c is settled by the lane that owns tile c.
- * The span is loaded as fosphor_demod.hip loads its: 16-byte loads, a pair of samples per lane, from the first 16-byte boundary of
- * the span on; the single samples before it and behind the last whole pair go one by one, so no byte outside the job's ranges is
- * read.  Every lag is computed by the operations of window() and rho_of(), on the device and in fosphor_amd_correlate_host alike.
+ * Both spans are loaded by load_span() of fosphor_jobs.h, which also has the table, the shared refusals and the tail of the call.
+ * Every lag is computed by the operations of window() and rho_of(), on the device and in fosphor_amd_correlate_host alike.
  * No atomics of any kind, no work-group waits for another, every loop carries its bound in its header.
  */
-#include <errno.h>
 #include <math.h>
-#include <stdint.h>
-#include <string.h>
 
-#include <algorithm>
-#include <utility>
-#include <vector>
-
-#include <hip/hip_runtime.h>
-
-#include "../../include/fosphor_amd.h"
+#include "fosphor_jobs.h"
 #include "../../include/fosphor_amd_correlate.h"
 
-/* accessors implemented next to struct fosphor (fosphor_api.cpp) */
+/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
 extern "C" long long *fosphor_amd_priv_correlate_stats(struct fosphor *self);
-extern "C" int fosphor_amd_priv_correlate_scratch(struct fosphor *self, size_t bytes, void **d_scratch);
 
 namespace {
 
@@ -54,11 +43,9 @@ constexpr int kSlots = kTile / kThreads;			/* lags of a lane */
 constexpr int kMaxTpl = FOSPHOR_AMD_CORRELATE_MAX_TPL;
 constexpr int kImageY = kTile + kMaxTpl;			/* a tile's span, kTile + T - 1 samples, and the slot before an odd start */
 constexpr int kImageT = kMaxTpl + 2;
-constexpr int kSearchSteps = 13;				/* 2^12 = MAX_JOBS */
-constexpr long long kMaxGroups = 0x7fffffffLL;
 constexpr int kNone = 0x7fffffff;				/* first_above of a partial without one, until the record is written */
 
-static_assert(FOSPHOR_AMD_CORRELATE_MAX_JOBS <= (1 << (kSearchSteps - 1)), "the job search is bounded");
+static_assert(FOSPHOR_AMD_CORRELATE_MAX_JOBS <= job_table::kMaxJobs, "the job search is bounded");
 static_assert(sizeof(Job) == 40, "the job is 40 bytes");
 static_assert(sizeof(Record) == 64, "the record is 64 bytes");
 static_assert(kTile % kThreads == 0 && kSlots == 4, "four lags a lane");
@@ -151,48 +138,6 @@ inline __host__ __device__ bool beats(float rho, int lag, float best, int best_l
 	return lag >= 0 && rho == rho && (best_lag < 0 || rho > best || (rho == best && lag < best_lag));
 }
 
-__device__ __forceinline__ LdsSample to_lds(float re, float im)
-{
-	LdsSample v;
-	v.x = re;
-	v.y = im;
-	return v;
-}
-
-/* Samples y[0 .. count) into the image, by the 256 lanes of a work-group of which this is lane t; count >= 1.
- * -> the image index of y[0] (0 or 1); y[m] lands at that index + m, at most at index count.  Reads y[0 .. count) and nothing else. */
-__device__ __forceinline__ int load_span(LdsSample *image, const float2 *y, int count, int t)
-{
-	const int head = min(count, (int)(((uintptr_t)y >> 3) & 1));	/* 0 or 1 sample before the 16-byte boundary */
-	const int pairs = (count - head) >> 1;
-	const int tail = head + 2 * pairs;					/* the single sample behind the last pair, if tail < count */
-	if (t == 0 && head)
-		image[1] = to_lds(y[0].x, y[0].y);
-	for (int g = t; g < pairs; g += kThreads) {
-		const float4 q = *reinterpret_cast<const float4 *>(y + head + 2 * g);
-		image[2 * head + 2 * g] = to_lds(q.x, q.y);
-		image[2 * head + 2 * g + 1] = to_lds(q.z, q.w);
-	}
-	if (t == kThreads - 1 && tail < count)
-		image[head + tail] = to_lds(y[tail].x, y[tail].y);
-	return head;
-}
-
-/* the job of work-group g: the largest j with prefix[j] <= g; a job without work-groups shares its prefix with the next and is
- * never the largest */
-__device__ __forceinline__ int find_job(const uint32_t *prefix, int n_jobs, uint32_t g)
-{
-	int lo = 0, hi = n_jobs;
-	for (int step = 0; step < kSearchSteps && hi - lo > 1; step++) {
-		const int mid = (lo + hi) >> 1;
-		if (prefix[mid] <= g)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
 /* what a lane, a wave, a tile or a job has seen of its lags */
 struct Acc {
 	int n_above, first, last, n_edges, peak_lag;
@@ -241,14 +186,14 @@ void k_correlate_tile(const Params p)
 	__shared__ unsigned char s_above[kTile];
 	__shared__ Acc s_acc[kWaves];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int j = find_job(p.prefix, p.n_jobs, blockIdx.x);
+	const int j = job_table::find_job(p.prefix, p.n_jobs, blockIdx.x);
 	const DevJob job = p.jobs[j];
 	const int c = (int)(blockIdx.x - p.prefix[j]);			/* the tile: c * kTile < n_lags by the prefix */
 	const int k0 = c * kTile;
 	const int lags = min(job.n_lags - k0, kTile);			/* 1 .. kTile */
 	const int T = job.tpl_len;					/* 1 .. kMaxTpl */
-	const int at_y = load_span(s_y, p.iq + job.offset + k0, lags + T - 1, tid);	/* the job has them: k0 + lags + T - 1 <= n */
-	const int at_t = load_span(s_t, p.tpl + job.tpl_offset, T, tid);
+	const int at_y = job_table::load_span<kThreads>(s_y, p.iq + job.offset + k0, lags + T - 1, tid);	/* the job has them: k0 + lags + T - 1 <= n */
+	const int at_t = job_table::load_span<kThreads>(s_t, p.tpl + job.tpl_offset, T, tid);
 	__syncthreads();
 
 	/* Lags tid + 256 s of the tile.  A lane beyond `lags` reads samples of the image that nobody loaded -- inside the array:
@@ -419,43 +364,36 @@ struct Plan {
 /* What both entry points refuse, but for the pointers. */
 int check_call(int64_t n_samples, int64_t n_tpl, const Job *jobs, int n_jobs, int64_t out_capacity, Plan *plan)
 {
-	if (!jobs || n_jobs < 1 || n_jobs > FOSPHOR_AMD_CORRELATE_MAX_JOBS || n_samples < 0 || n_tpl < 0 || out_capacity < 0)
+	if (!jobs || !job_table::count_ok(n_jobs, FOSPHOR_AMD_CORRELATE_MAX_JOBS) || n_samples < 0 || n_tpl < 0 || out_capacity < 0)
 		return -EINVAL;
 	Plan pl = { 0, 0, 0, false };
 	std::vector<std::pair<int64_t, int64_t> > ranges;
 	for (int i = 0; i < n_jobs; i++) {
 		const Job &b = jobs[i];
-		if (b.offset < 0 || b.n < 0 || b.offset > n_samples || b.n > n_samples - b.offset)
+		if (!job_table::inside(b.offset, b.n, n_samples))
 			return -EINVAL;
-		if (b.tpl_len < 1 || b.tpl_len > kMaxTpl || b.tpl_offset < 0 || b.tpl_offset > n_tpl || b.tpl_len > n_tpl - b.tpl_offset)
+		if (b.tpl_len < 1 || b.tpl_len > kMaxTpl || !job_table::inside(b.tpl_offset, b.tpl_len, n_tpl))
 			return -EINVAL;
-		if (!trace_ok(b.trace) || b.threshold != b.threshold || b.out_offset < 0)
+		if (!trace_ok(b.trace) || b.threshold != b.threshold)
 			return -EINVAL;
 		if (b.trace == FOSPHOR_AMD_CORRELATE_TRACE_NONE && b.out_offset != 0)
 			return -EINVAL;
 		const int n_lags = n_lags_of(b.n, b.tpl_len);
 		const int64_t n_out = n_out_of(b.trace, n_lags);
-		if (b.out_offset > out_capacity || n_out > out_capacity - b.out_offset)
+		if (!job_table::inside(b.out_offset, n_out, out_capacity) || !job_table::add_groups(pl.groups, n_lags, kTile))
 			return -EINVAL;
-		pl.groups += ((long long)n_lags + kTile - 1) / kTile;
 		pl.lags += n_lags;
 		pl.macs += (long long)n_lags * b.tpl_len;
 		pl.traces |= b.trace != FOSPHOR_AMD_CORRELATE_TRACE_NONE;
 		if (n_out > 0)
 			ranges.push_back(std::make_pair(b.out_offset, b.out_offset + n_out));
 	}
-	if (pl.groups > kMaxGroups)
+	if (!job_table::ranges_disjoint(ranges))
 		return -EINVAL;
-	std::sort(ranges.begin(), ranges.end());
-	for (size_t i = 1; i < ranges.size(); i++)
-		if (ranges[i].first < ranges[i - 1].second)
-			return -EINVAL;
 	if (plan)
 		*plan = pl;
 	return 0;
 }
-
-int launch_ok(void) { return hipGetLastError() == hipSuccess ? 0 : -EIO; }
 
 } // namespace
 
@@ -563,12 +501,7 @@ extern "C" int fosphor_amd_correlate_derive(const struct fosphor_amd_correlate_r
 
 extern "C" int fosphor_amd_correlate_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_CORRELATE_STATS])
 {
-	if (!self)
-		return -EINVAL;
-	if (stats)
-		for (int i = 0; i < FOSPHOR_AMD_CORRELATE_STATS; i++)
-			stats[i] = fosphor_amd_priv_correlate_stats(self)[i];
-	return 0;
+	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_correlate_stats, FOSPHOR_AMD_CORRELATE_STATS, stats);
 }
 
 extern "C" int fosphor_amd_correlate(struct fosphor *self, const void *d_iq, int64_t n_samples,
@@ -587,24 +520,21 @@ extern "C" int fosphor_amd_correlate(struct fosphor *self, const void *d_iq, int
 	if (plan.traces && !d_out)
 		return -EINVAL;
 
-	/* the table: every job in job order, the prefix; behind it, 8-byte aligned, the partials */
-	const size_t job_bytes = sizeof(DevJob) * (size_t)n_jobs;
-	const size_t table_bytes = (job_bytes + sizeof(uint32_t) * ((size_t)n_jobs + 1) + 7) & ~(size_t)7;
-	const size_t bytes = table_bytes + sizeof(Part) * (size_t)plan.groups;
-	std::vector<uint8_t> table(table_bytes);
-	DevJob *dj = reinterpret_cast<DevJob *>(table.data());
-	uint32_t *prefix = reinterpret_cast<uint32_t *>(table.data() + job_bytes);
-	prefix[0] = 0;
+	/* the table: every job in job order (one form), written where it goes, the prefix; behind it the partials */
+	const size_t n_form[2] = { (size_t)n_jobs, 0 }, n_prefix[2] = { (size_t)n_jobs + 1, 0 };
+	job_table::Table table = job_table::lay_table(sizeof(DevJob), n_form, n_prefix, (size_t)plan.groups, sizeof(Part));
+	DevJob *dj = reinterpret_cast<DevJob *>(table.image.data() + table.jobs_at[0]);
+	uint32_t *prefix = reinterpret_cast<uint32_t *>(table.image.data() + table.prefix_at[0]);
 	for (int i = 0; i < n_jobs; i++) {
-		const int n_lags = n_lags_of(jobs[i].n, jobs[i].tpl_len);
-		dj[i].offset = jobs[i].offset;
-		dj[i].out_offset = jobs[i].out_offset;
-		dj[i].tpl_offset = jobs[i].tpl_offset;
-		dj[i].n_lags = n_lags;
-		dj[i].tpl_len = jobs[i].tpl_len;
-		dj[i].trace = jobs[i].trace;
-		dj[i].threshold = jobs[i].threshold;
-		prefix[i + 1] = prefix[i] + (uint32_t)(((long long)n_lags + kTile - 1) / kTile);
+		DevJob &d = dj[i];
+		d.offset = jobs[i].offset;
+		d.out_offset = jobs[i].out_offset;
+		d.tpl_offset = jobs[i].tpl_offset;
+		d.n_lags = n_lags_of(jobs[i].n, jobs[i].tpl_len);
+		d.tpl_len = jobs[i].tpl_len;
+		d.trace = jobs[i].trace;
+		d.threshold = jobs[i].threshold;
+		prefix[i + 1] = prefix[i] + (uint32_t)job_table::groups_of(d.n_lags, kTile);
 	}
 
 	if (fosphor_amd_finish(self) < 0)
@@ -615,33 +545,24 @@ extern "C" int fosphor_amd_correlate(struct fosphor *self, const void *d_iq, int
 	stats[FOSPHOR_AMD_CORRELATE_LAGS] += plan.lags;
 	stats[FOSPHOR_AMD_CORRELATE_MACS] += plan.macs;
 
-	void *d;
-	if (fosphor_amd_priv_correlate_scratch(self, bytes, &d))
-		return -EIO;
-	const hipStream_t st = (hipStream_t)fosphor_amd_stream(self);
-	if (hipMemcpyAsync(d, table.data(), table_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+	uint8_t *d;
+	hipStream_t st;
+	if (job_table::upload_table(self, FOSPHOR_SCRATCH_CORRELATE, table, &d, &st))
 		return -EIO;
 	Params p;
 	p.iq = static_cast<const float2 *>(d_iq);
 	p.tpl = static_cast<const float2 *>(d_tpl);
-	p.jobs = static_cast<const DevJob *>(d);
-	p.prefix = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(d) + job_bytes);
-	p.parts = reinterpret_cast<Part *>(static_cast<uint8_t *>(d) + table_bytes);
+	p.jobs = reinterpret_cast<const DevJob *>(d + table.jobs_at[0]);
+	p.prefix = reinterpret_cast<const uint32_t *>(d + table.prefix_at[0]);
+	p.parts = reinterpret_cast<Part *>(d + table.parts_at);
 	p.records = d_records;
 	p.out = d_out;
 	p.n_jobs = n_jobs;
 	int rv = 0;
-	if (plan.groups) {
-		hipLaunchKernelGGL(k_correlate_tile, dim3((unsigned)plan.groups), dim3(kThreads), 0, st, p);
-		if (!(rv = launch_ok()))
-			stats[FOSPHOR_AMD_CORRELATE_K_TILE]++;
-	}
-	if (!rv) {
-		hipLaunchKernelGGL(k_correlate_combine, dim3((unsigned)((n_jobs + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, p);
-		if (!(rv = launch_ok()))
-			stats[FOSPHOR_AMD_CORRELATE_K_COMBINE]++;
-	}
-	if (hipStreamSynchronize(st) != hipSuccess)			/* the table on the host lives until here */
-		return -EIO;
-	return rv;
+	if (plan.groups)
+		rv = job_table::launch<kThreads>(k_correlate_tile, (unsigned)plan.groups, st, p, stats, FOSPHOR_AMD_CORRELATE_K_TILE);
+	if (!rv)
+		rv = job_table::launch<kThreads>(k_correlate_combine, (unsigned)job_table::groups_of(n_jobs, kWaves), st, p, stats,
+		                                 FOSPHOR_AMD_CORRELATE_K_COMBINE);
+	return job_table::drain(st, rv);
 }

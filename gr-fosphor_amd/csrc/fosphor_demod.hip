@@ -5,36 +5,24 @@
  * process / merge path and no buffer of the instance is read or written but the scratch this file owns (the job table and the
  * prefixes of work-group counts).
  *
- *   k_demod_direct  L = 1: a work-group of 256 lanes owns kTile consecutive trace values of one job, which it finds by a bounded
- *                   binary search of the prefix (13 steps cover 4096 jobs).  It brings their samples into LDS, computes value
- *                   i, i + 256, .. per lane and stores 4 bytes per lane, consecutive lanes to consecutive floats.
+ *   k_demod_direct  L = 1: a work-group of 256 lanes owns kTile consecutive trace values of one job, which it finds in the prefix
+ *                   (fosphor_jobs.h).  It brings their samples into LDS, computes value i, i + 256, .. per lane and stores 4 bytes
+ *                   per lane, consecutive lanes to consecutive floats.
  *   k_demod_avg     L > 1: a work-group owns kTile / L outputs.  The same load; the (kTile / L) * L trace values are computed one
  *                   per lane into LDS rows of L floats, row stride L | 1 (odd: the 32 lanes of a half wave that walk 32 rows read
  *                   32 banks); then one lane per output adds its row in ascending order in double.
- * Both load with one routine: 16-byte loads, a pair of samples per lane, from the first 16-byte boundary of the span on; the single
- * samples before it and behind the last whole pair go one by one, so no byte outside the job's range is read.  A pair lands on a
- * 16-byte boundary of the LDS image too (the image begins one slot in when the span begins off the boundary).  An FM span is one
- * sample longer than its trace values: v[m] needs y[m + 1], and n_trace = n - 1 says the job has it.
+ * Both load their span with load_span() of fosphor_jobs.h, which also has the table, the shared refusals and the tail of the call.
+ * An FM span is one sample longer than its trace values: v[m] needs y[m + 1], and n_trace = n - 1 says the job has it.
  * Every trace value is computed by trace_value() and every output by dump(), on the device and in fosphor_amd_demod_host alike.
  * No atomics of any kind, no work-group waits for another, every loop carries its bound in its header.
  */
-#include <errno.h>
 #include <math.h>
-#include <stdint.h>
-#include <string.h>
 
-#include <algorithm>
-#include <utility>
-#include <vector>
-
-#include <hip/hip_runtime.h>
-
-#include "../../include/fosphor_amd.h"
+#include "fosphor_jobs.h"
 #include "../../include/fosphor_amd_demod.h"
 
-/* accessors implemented next to struct fosphor (fosphor_api.cpp) */
+/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
 extern "C" long long *fosphor_amd_priv_demod_stats(struct fosphor *self);
-extern "C" int fosphor_amd_priv_demod_scratch(struct fosphor *self, size_t bytes, void **d_scratch);
 
 namespace {
 
@@ -45,10 +33,8 @@ constexpr int kTile = FOSPHOR_AMD_DEMOD_TILE;
 constexpr int kMaxAvg = FOSPHOR_AMD_DEMOD_MAX_AVG;
 constexpr int kImage = kTile + 2;				/* a tile's samples, FM's one more, and the slot before an odd start */
 constexpr int kRows = kTile / 2 * 3;				/* (kTile / L) * (L | 1) is largest at L = 2 */
-constexpr int kSearchSteps = 13;				/* 2^12 = MAX_JOBS */
-constexpr long long kMaxGroups = 0x7fffffffLL;
 
-static_assert(FOSPHOR_AMD_DEMOD_MAX_JOBS <= (1 << (kSearchSteps - 1)), "the job search is bounded");
+static_assert(FOSPHOR_AMD_DEMOD_MAX_JOBS <= job_table::kMaxJobs, "the job search is bounded");
 static_assert(sizeof(Job) == 32, "the job is 32 bytes");
 static_assert(kTile % 2 == 0 && kMaxAvg <= kTile, "a tile holds an output of every L");
 
@@ -103,48 +89,18 @@ inline __host__ __device__ float dump(const float *v, int L)
 	return quiet((float)(S / (double)L));
 }
 
-/* Samples y[0 .. count) into the image, by the 256 lanes of a work-group of which this is lane t; 1 <= count <= kTile + 1.
- * -> the image index of y[0] (0 or 1).  Reads y[0 .. count) and nothing else. */
-__device__ __forceinline__ int load_span(float2 *image, const float2 *y, int count, int t)
-{
-	const int head = min(count, (int)(((uintptr_t)y >> 3) & 1));	/* 0 or 1 sample before the 16-byte boundary */
-	const int pairs = (count - head) >> 1;
-	const int tail = head + 2 * pairs;					/* the single sample behind the last pair, if tail < count */
-	if (t == 0 && head)
-		image[1] = y[0];
-	for (int g = t; g < pairs; g += kThreads)
-		*reinterpret_cast<float4 *>(image + 2 * head + 2 * g) = *reinterpret_cast<const float4 *>(y + head + 2 * g);
-	if (t == kThreads - 1 && tail < count)
-		image[head + tail] = y[tail];
-	return head;
-}
-
-/* the job of work-group g: the largest j with prefix[j] <= g (every job of the table has a work-group) */
-__device__ __forceinline__ int find_job(const uint32_t *prefix, int n_jobs, uint32_t g)
-{
-	int lo = 0, hi = n_jobs;
-	for (int step = 0; step < kSearchSteps && hi - lo > 1; step++) {
-		const int mid = (lo + hi) >> 1;
-		if (prefix[mid] <= g)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
 __global__ __launch_bounds__(kThreads)
 void k_demod_direct(const Params p)
 {
 	__shared__ __align__(16) float2 s_y[kImage];
 	const int tid = threadIdx.x;
-	const int j = find_job(p.prefix, p.n_jobs, blockIdx.x);
+	const int j = job_table::find_job(p.prefix, p.n_jobs, blockIdx.x);
 	const DevJob job = p.jobs[j];
 	const int c = (int)(blockIdx.x - p.prefix[j]);			/* the tile: c * kTile < n_out by the prefix */
 	const int t0 = c * kTile;
 	const int count = min(job.n_out - t0, kTile);			/* 1 .. kTile trace values */
 	const int fm = job.mode == FOSPHOR_AMD_DEMOD_FM;
-	const int at = load_span(s_y, p.iq + job.offset + t0, count + fm, tid);
+	const int at = job_table::load_span<kThreads>(s_y, p.iq + job.offset + t0, count + fm, tid);
 	__syncthreads();
 	float *out = p.out + job.out_offset + t0;
 	const float2 *y = s_y + at;
@@ -166,7 +122,7 @@ void k_demod_avg(const Params p)
 	__shared__ __align__(16) float2 s_y[kImage];
 	__shared__ float s_v[kRows];
 	const int tid = threadIdx.x;
-	const int j = find_job(p.prefix, p.n_jobs, blockIdx.x);
+	const int j = job_table::find_job(p.prefix, p.n_jobs, blockIdx.x);
 	const DevJob job = p.jobs[j];
 	const int L = job.avg;						/* 2 .. kMaxAvg */
 	const int per = kTile / L;
@@ -175,7 +131,7 @@ void k_demod_avg(const Params p)
 	const int outs = min(job.n_out - o0, per);			/* 1 .. per outputs */
 	const int count = outs * L;					/* <= kTile trace values, from t0 = o0 * L <= n_trace - count */
 	const int fm = job.mode == FOSPHOR_AMD_DEMOD_FM;
-	const int at = load_span(s_y, p.iq + job.offset + (int64_t)o0 * L, count + fm, tid);
+	const int at = job_table::load_span<kThreads>(s_y, p.iq + job.offset + (int64_t)o0 * L, count + fm, tid);
 	__syncthreads();
 	const float2 *y = s_y + at;
 	const int stride = L | 1;
@@ -196,40 +152,32 @@ struct Plan {
 /* What both entry points refuse, but for the pointers. */
 int check_call(int64_t n_samples, const Job *jobs, int n_jobs, int64_t out_capacity, Plan *plan)
 {
-	if (!jobs || n_jobs < 1 || n_jobs > FOSPHOR_AMD_DEMOD_MAX_JOBS || n_samples < 0 || out_capacity < 0)
+	if (!jobs || !job_table::count_ok(n_jobs, FOSPHOR_AMD_DEMOD_MAX_JOBS) || n_samples < 0 || out_capacity < 0)
 		return -EINVAL;
 	Plan pl = { { 0, 0 }, { 0, 0 }, 0, 0 };
 	std::vector<std::pair<int64_t, int64_t> > ranges;
 	for (int i = 0; i < n_jobs; i++) {
 		const Job &b = jobs[i];
-		if (b.offset < 0 || b.n < 0 || b.offset > n_samples || b.n > n_samples - b.offset)
+		if (!job_table::inside(b.offset, b.n, n_samples))
 			return -EINVAL;
 		if (!mode_ok(b.mode) || b.avg < 1 || b.avg > kMaxAvg || b.reserved != 0)
 			return -EINVAL;
 		const int n_out = n_trace_of(b.mode, b.n) / b.avg;
-		if (b.out_offset < 0 || b.out_offset > out_capacity || n_out > out_capacity - b.out_offset)
-			return -EINVAL;
 		const int f = b.avg > 1;
-		const int per = per_group(b.avg);
-		pl.groups[f] += ((long long)n_out + per - 1) / per;
+		if (!job_table::inside(b.out_offset, n_out, out_capacity) || !job_table::add_groups(pl.groups[f], n_out, per_group(b.avg)))
+			return -EINVAL;
 		pl.jobs[f]++;
 		pl.samples += b.n;
 		pl.outputs += n_out;
 		if (n_out > 0)
 			ranges.push_back(std::make_pair(b.out_offset, b.out_offset + n_out));
 	}
-	if (pl.groups[0] > kMaxGroups || pl.groups[1] > kMaxGroups)
+	if (!job_table::ranges_disjoint(ranges))
 		return -EINVAL;
-	std::sort(ranges.begin(), ranges.end());
-	for (size_t i = 1; i < ranges.size(); i++)
-		if (ranges[i].first < ranges[i - 1].second)
-			return -EINVAL;
 	if (plan)
 		*plan = pl;
 	return 0;
 }
-
-int launch_ok(void) { return hipGetLastError() == hipSuccess ? 0 : -EIO; }
 
 } // namespace
 
@@ -296,12 +244,7 @@ extern "C" int fosphor_amd_demod_atan2_turns_n(const double *y, const double *x,
 
 extern "C" int fosphor_amd_demod_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_DEMOD_STATS])
 {
-	if (!self)
-		return -EINVAL;
-	if (stats)
-		for (int i = 0; i < FOSPHOR_AMD_DEMOD_STATS; i++)
-			stats[i] = fosphor_amd_priv_demod_stats(self)[i];
-	return 0;
+	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_demod_stats, FOSPHOR_AMD_DEMOD_STATS, stats);
 }
 
 extern "C" int fosphor_amd_demod(struct fosphor *self, const void *d_iq, int64_t n_samples,
@@ -316,7 +259,7 @@ extern "C" int fosphor_amd_demod(struct fosphor *self, const void *d_iq, int64_t
 	if (check_call(n_samples, jobs, n_jobs, out_capacity, &plan))
 		return -EINVAL;
 
-	/* the table: DIRECT jobs, AVG jobs, the DIRECT prefix, the AVG prefix; only jobs that write something */
+	/* the table: DIRECT and AVG jobs, their prefixes; only jobs that write something */
 	std::vector<DevJob> form[2];
 	std::vector<uint32_t> prefix[2] = { std::vector<uint32_t>(1, 0u), std::vector<uint32_t>(1, 0u) };
 	for (int i = 0; i < n_jobs; i++) {
@@ -324,7 +267,6 @@ extern "C" int fosphor_amd_demod(struct fosphor *self, const void *d_iq, int64_t
 		if (n_out == 0)
 			continue;
 		const int f = jobs[i].avg > 1;
-		const int per = per_group(jobs[i].avg);
 		DevJob d;
 		d.offset = jobs[i].offset;
 		d.out_offset = jobs[i].out_offset;
@@ -333,18 +275,9 @@ extern "C" int fosphor_amd_demod(struct fosphor *self, const void *d_iq, int64_t
 		d.avg = jobs[i].avg;
 		d.pad = 0;
 		form[f].push_back(d);
-		prefix[f].push_back(prefix[f].back() + (uint32_t)(((long long)n_out + per - 1) / per));
+		prefix[f].push_back(prefix[f].back() + (uint32_t)job_table::groups_of(n_out, per_group(jobs[i].avg)));
 	}
-	const size_t n_form[2] = { form[0].size(), form[1].size() };
-	const size_t job_bytes = sizeof(DevJob) * (n_form[0] + n_form[1]);
-	const size_t bytes = job_bytes + sizeof(uint32_t) * (prefix[0].size() + prefix[1].size());
-	std::vector<uint8_t> table(bytes);
-	for (int f = 0; f < 2; f++) {
-		if (n_form[f])
-			memcpy(table.data() + (f ? sizeof(DevJob) * n_form[0] : 0), form[f].data(), sizeof(DevJob) * n_form[f]);
-		memcpy(table.data() + job_bytes + (f ? sizeof(uint32_t) * prefix[0].size() : 0), prefix[f].data(),
-		       sizeof(uint32_t) * prefix[f].size());
-	}
+	const job_table::Table table = job_table::pack_table(form, prefix, 0, 0);
 
 	if (fosphor_amd_finish(self) < 0)
 		return -EIO;
@@ -354,36 +287,25 @@ extern "C" int fosphor_amd_demod(struct fosphor *self, const void *d_iq, int64_t
 	stats[FOSPHOR_AMD_DEMOD_JOBS_AVG] += plan.jobs[1];
 	stats[FOSPHOR_AMD_DEMOD_SAMPLES] += plan.samples;
 	stats[FOSPHOR_AMD_DEMOD_OUTPUTS] += plan.outputs;
-	if (!n_form[0] && !n_form[1])
+	if (form[0].empty() && form[1].empty())
 		return 0;						/* no job writes anything */
 
-	void *d;
-	if (fosphor_amd_priv_demod_scratch(self, bytes, &d))
-		return -EIO;
-	const hipStream_t st = (hipStream_t)fosphor_amd_stream(self);
-	if (hipMemcpyAsync(d, table.data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+	uint8_t *d;
+	hipStream_t st;
+	if (job_table::upload_table(self, FOSPHOR_SCRATCH_DEMOD, table, &d, &st))
 		return -EIO;
 	Params p;
 	p.iq = static_cast<const float2 *>(d_iq);
 	p.out = d_out;
 	int rv = 0;
-	if (n_form[0]) {
-		p.jobs = static_cast<const DevJob *>(d);
-		p.prefix = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(d) + job_bytes);
-		p.n_jobs = (int)n_form[0];
-		hipLaunchKernelGGL(k_demod_direct, dim3(prefix[0].back()), dim3(kThreads), 0, st, p);
-		if (!(rv = launch_ok()))
-			stats[FOSPHOR_AMD_DEMOD_K_DIRECT]++;
+	for (int f = 0; f < 2 && !rv; f++) {
+		if (form[f].empty())
+			continue;
+		p.jobs = reinterpret_cast<const DevJob *>(d + table.jobs_at[f]);
+		p.prefix = reinterpret_cast<const uint32_t *>(d + table.prefix_at[f]);
+		p.n_jobs = (int)form[f].size();
+		rv = job_table::launch<kThreads>(f ? k_demod_avg : k_demod_direct, prefix[f].back(), st, p, stats,
+		                                 f ? FOSPHOR_AMD_DEMOD_K_AVG : FOSPHOR_AMD_DEMOD_K_DIRECT);
 	}
-	if (n_form[1] && !rv) {
-		p.jobs = static_cast<const DevJob *>(d) + n_form[0];
-		p.prefix = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(d) + job_bytes) + prefix[0].size();
-		p.n_jobs = (int)n_form[1];
-		hipLaunchKernelGGL(k_demod_avg, dim3(prefix[1].back()), dim3(kThreads), 0, st, p);
-		if (!(rv = launch_ok()))
-			stats[FOSPHOR_AMD_DEMOD_K_AVG]++;
-	}
-	if (hipStreamSynchronize(st) != hipSuccess)			/* the table on the host lives until here */
-		return -EIO;
-	return rv;
+	return job_table::drain(st, rv);
 }

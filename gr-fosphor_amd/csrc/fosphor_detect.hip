@@ -34,6 +34,7 @@
 
 /* accessors implemented next to struct fosphor (fosphor_api.cpp) */
 extern "C" long long *fosphor_amd_priv_detect_stats(struct fosphor *self);
+extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, long long *(*counters)(struct fosphor *), int n, long long *stats);
 extern "C" int fosphor_amd_priv_detect_scratch(struct fosphor *self, size_t bytes, void **d_scratch);
 
 namespace {
@@ -454,12 +455,7 @@ extern "C" int fosphor_amd_detect_bands_host(const float *trace_y, int n, float 
 
 extern "C" int fosphor_amd_detect_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_DETECT_STATS])
 {
-	if (!self)
-		return -EINVAL;
-	if (stats)
-		for (int i = 0; i < FOSPHOR_AMD_DETECT_STATS; i++)
-			stats[i] = fosphor_amd_priv_detect_stats(self)[i];
-	return 0;
+	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_detect_stats, FOSPHOR_AMD_DETECT_STATS, stats);
 }
 
 extern "C" int fosphor_amd_percentiles(struct fosphor *self, const float *q, int n_q, float *d_y, int32_t *d_bin)

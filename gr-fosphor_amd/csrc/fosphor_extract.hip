@@ -4,10 +4,9 @@
  * A read-only pass over the CALLER's samples, in a file of its own: nothing here is on the process / merge path and no buffer of
  * the instance is read or written but the job table this file owns.
  *
- * The host checks the jobs, sorts them by form and uploads, per form, the jobs that write something and a prefix of their
- * work-group counts; a work-group finds its job by a bounded binary search of that prefix (13 steps cover 4096 jobs) and its place
- * in the job from what is left.  One launch per form present; no work-group waits for another; every loop carries its bound in its
- * header.
+ * The table of jobs, the search that gives a work-group its job, the refusals every pass over burst IQ shares and the tail of the
+ * call are those of fosphor_jobs.h; only jobs that write something are uploaded.  One launch per form present; no work-group waits
+ * for another; every loop carries its bound in its header.
  *
  *   k_extract_tile  small D: a work-group of 256 lanes owns kTileOut = 256 consecutive outputs of a job.  It loads their input span
  *                   (n - 1) * D + T samples coalesced, 16 bytes per lane where the address allows (the samples before the first
@@ -33,23 +32,13 @@
  * sincospif -- no fast intrinsic, whose absolute error near pi the tolerance does not allow.  float32 sums, explicit fmaf, no
  * atomics of any kind.
  */
-#include <errno.h>
 #include <math.h>
-#include <stdint.h>
-#include <string.h>
 
-#include <algorithm>
-#include <utility>
-#include <vector>
-
-#include <hip/hip_runtime.h>
-
-#include "../../include/fosphor_amd.h"
+#include "fosphor_jobs.h"
 #include "../../include/fosphor_amd_extract.h"
 
 /* accessors implemented next to struct fosphor (fosphor_api.cpp) */
 extern "C" long long *fosphor_amd_priv_extract_stats(struct fosphor *self);
-extern "C" int fosphor_amd_priv_extract_scratch(struct fosphor *self, size_t bytes, void **d_scratch);
 extern "C" int fosphor_amd_priv_iq_format(struct fosphor *self);
 
 namespace {
@@ -61,12 +50,10 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kTileOut = FOSPHOR_AMD_EXTRACT_TILE_OUT;	/* outputs of a TILE work-group: one per lane */
 constexpr int kTileLds = FOSPHOR_AMD_EXTRACT_TILE_LDS;	/* float2 of its LDS image: 52 KiB, three work-groups per CU */
 constexpr int kWaveOut = FOSPHOR_AMD_EXTRACT_WAVE_OUT;	/* outputs of a WAVE work-group: one per wave */
-constexpr int kSearchSteps = 13;			/* 2^12 = MAX_JOBS */
-constexpr long long kMaxGroups = 0x7fffffffLL;
 
 static_assert(kTileOut == kThreads, "a lane owns one output of the tile");
 static_assert(kWaveOut == kWaves, "a wave owns one output");
-static_assert(FOSPHOR_AMD_EXTRACT_MAX_JOBS <= (1 << (kSearchSteps - 1)), "the job search is bounded");
+static_assert(FOSPHOR_AMD_EXTRACT_MAX_JOBS <= job_table::kMaxJobs, "the job search is bounded");
 static_assert(sizeof(Job) == 40, "the job table is uploaded as it is");
 static_assert(kTileLds * sizeof(float2) <= 64 * 1024, "static LDS");
 
@@ -139,20 +126,6 @@ __device__ __forceinline__ float2 mix(float2 x, uint32_t phi)
 	return make_float2(fmaf(x.x, co, x.y * si), fmaf(x.y, co, -(x.x * si)));
 }
 
-/* the job of work-group g: the largest j with prefix[j] <= g (every job of the table has a work-group) */
-__device__ __forceinline__ int find_job(const uint32_t *prefix, int n_jobs, uint32_t g)
-{
-	int lo = 0, hi = n_jobs;
-	for (int step = 0; step < kSearchSteps && hi - lo > 1; step++) {
-		const int mid = (lo + hi) >> 1;
-		if (prefix[mid] <= g)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
 template <class IQ>
 __global__ __launch_bounds__(kThreads)
 void k_extract_tile(const Params p)
@@ -162,7 +135,7 @@ void k_extract_tile(const Params p)
 	constexpr int per = IQ::per;
 
 	const int tid = threadIdx.x;
-	const int j = find_job(p.prefix, p.n_jobs, blockIdx.x);
+	const int j = job_table::find_job(p.prefix, p.n_jobs, blockIdx.x);
 	const Job job = p.jobs[j];
 	const int D = job.decim, T = job.n_taps;
 	const int m0 = (int)(blockIdx.x - p.prefix[j]) * kTileOut;	/* first output of the tile */
@@ -225,7 +198,7 @@ void k_extract_wave(const Params p)
 {
 	typedef typename IQ::elem elem;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const int j = find_job(p.prefix, p.n_jobs, blockIdx.x);
+	const int j = job_table::find_job(p.prefix, p.n_jobs, blockIdx.x);
 	const Job job = p.jobs[j];
 	const int T = job.n_taps;
 	const int64_t m = (int64_t)(blockIdx.x - p.prefix[j]) * kWaveOut + wave;
@@ -252,13 +225,10 @@ void k_extract_wave(const Params p)
 }
 
 template <class IQ>
-int launch_form(bool tile, const Params &p, unsigned groups, hipStream_t st)
+int launch_form(int f, const Params &p, unsigned groups, hipStream_t st, long long *stats)
 {
-	if (tile)
-		hipLaunchKernelGGL(k_extract_tile<IQ>, dim3(groups), dim3(kThreads), 0, st, p);
-	else
-		hipLaunchKernelGGL(k_extract_wave<IQ>, dim3(groups), dim3(kThreads), 0, st, p);
-	return hipGetLastError() == hipSuccess ? 0 : -EIO;
+	return job_table::launch<kThreads>(f ? k_extract_wave<IQ> : k_extract_tile<IQ>, groups, st, p, stats,
+	                                   f ? FOSPHOR_AMD_EXTRACT_K_WAVE : FOSPHOR_AMD_EXTRACT_K_TILE);
 }
 
 int sample_bytes(int fmt) { return fmt == FOSPHOR_AMD_IQ_FP32 ? 8 : 4; }
@@ -266,7 +236,7 @@ int sample_bytes(int fmt) { return fmt == FOSPHOR_AMD_IQ_FP32 ? 8 : 4; }
 /* What both entry points refuse, but for the pointers.  fmt: 0, 1 or 2. */
 int check_call(int64_t n_samples, int fmt, const Job *jobs, int n_jobs, int n_taps_total, int64_t out_capacity)
 {
-	if (!jobs || n_jobs < 1 || n_jobs > FOSPHOR_AMD_EXTRACT_MAX_JOBS || n_samples < 0 || n_taps_total < 0 || out_capacity < 0)
+	if (!jobs || !job_table::count_ok(n_jobs, FOSPHOR_AMD_EXTRACT_MAX_JOBS) || n_samples < 0 || n_taps_total < 0 || out_capacity < 0)
 		return -EINVAL;
 	if (fmt != FOSPHOR_AMD_IQ_FP32 && fmt != FOSPHOR_AMD_IQ_FP16 && fmt != FOSPHOR_AMD_IQ_SC16)
 		return -EINVAL;
@@ -274,29 +244,22 @@ int check_call(int64_t n_samples, int fmt, const Job *jobs, int n_jobs, int n_ta
 	long long groups[2] = { 0, 0 };
 	for (int i = 0; i < n_jobs; i++) {
 		const Job &b = jobs[i];
-		if (b.first < 0 || b.out_offset < 0 || b.n_out < 0 || b.decim < 1 || b.decim > FOSPHOR_AMD_EXTRACT_MAX_DECIM ||
-		    b.n_taps < 1 || b.n_taps > FOSPHOR_AMD_EXTRACT_MAX_TAPS || b.taps_offset < 0 ||
-		    (int64_t)b.taps_offset + b.n_taps > n_taps_total)
+		if (b.first < 0 || b.decim < 1 || b.decim > FOSPHOR_AMD_EXTRACT_MAX_DECIM ||
+		    b.n_taps < 1 || b.n_taps > FOSPHOR_AMD_EXTRACT_MAX_TAPS || !job_table::inside(b.taps_offset, b.n_taps, n_taps_total))
 			return -EINVAL;
-		if (b.out_offset > out_capacity || b.n_out > out_capacity - b.out_offset)
+		if (!job_table::inside(b.out_offset, b.n_out, out_capacity))
 			return -EINVAL;
 		if (b.n_out == 0)
 			continue;
 		const int64_t need = (int64_t)(b.n_out - 1) * b.decim + b.n_taps;	/* < 2^41 */
-		if (b.first > n_samples || need > n_samples - b.first)
+		if (!job_table::inside(b.first, need, n_samples))
 			return -EINVAL;
 		ranges.emplace_back(b.out_offset, b.out_offset + b.n_out);
-		const bool tile = tile_form(b.decim, b.n_taps);
-		const int per = tile ? kTileOut : kWaveOut;
-		groups[tile ? 0 : 1] += ((long long)b.n_out + per - 1) / per;
-	}
-	if (groups[0] > kMaxGroups || groups[1] > kMaxGroups)
-		return -EINVAL;
-	std::sort(ranges.begin(), ranges.end());
-	for (size_t i = 1; i < ranges.size(); i++)
-		if (ranges[i].first < ranges[i - 1].second)
+		const int f = tile_form(b.decim, b.n_taps) ? 0 : 1;
+		if (!job_table::add_groups(groups[f], b.n_out, f ? kWaveOut : kTileOut))
 			return -EINVAL;
-	return 0;
+	}
+	return job_table::ranges_disjoint(ranges) ? 0 : -EINVAL;
 }
 
 float half_to_float(uint16_t h)
@@ -426,12 +389,7 @@ extern "C" int fosphor_amd_extract_from_burst(const struct fosphor_amd_burst *b,
 
 extern "C" int fosphor_amd_extract_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_EXTRACT_STATS])
 {
-	if (!self)
-		return -EINVAL;
-	if (stats)
-		for (int i = 0; i < FOSPHOR_AMD_EXTRACT_STATS; i++)
-			stats[i] = fosphor_amd_priv_extract_stats(self)[i];
-	return 0;
+	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_extract_stats, FOSPHOR_AMD_EXTRACT_STATS, stats);
 }
 
 extern "C" int fosphor_amd_extract(struct fosphor *self, const void *d_samples, int64_t n_samples, int iq_format,
@@ -451,30 +409,18 @@ extern "C" int fosphor_amd_extract(struct fosphor *self, const void *d_samples, 
 
 	/* the table: the jobs that write something, TILE jobs first, and behind them the two prefixes */
 	std::vector<Job> live[2];
-	std::vector<uint32_t> prefix[2];
+	std::vector<uint32_t> prefix[2] = { std::vector<uint32_t>(1, 0u), std::vector<uint32_t>(1, 0u) };
 	long long n_form[2] = { 0, 0 }, samples = 0;
 	for (int i = 0; i < n_jobs; i++) {
 		const int f = tile_form(jobs[i].decim, jobs[i].n_taps) ? 0 : 1;
 		n_form[f]++;
 		if (jobs[i].n_out == 0)
 			continue;
-		const int per = f ? kWaveOut : kTileOut;
-		if (prefix[f].empty())
-			prefix[f].push_back(0);
-		prefix[f].push_back(prefix[f].back() + (uint32_t)(((long long)jobs[i].n_out + per - 1) / per));
+		prefix[f].push_back(prefix[f].back() + (uint32_t)job_table::groups_of(jobs[i].n_out, f ? kWaveOut : kTileOut));
 		live[f].push_back(jobs[i]);
 		samples += (long long)(jobs[i].n_out - 1) * jobs[i].decim + jobs[i].n_taps;
 	}
-	const size_t n_live[2] = { live[0].size(), live[1].size() };
-	const size_t job_bytes = sizeof(Job) * (n_live[0] + n_live[1]);
-	const size_t bytes = job_bytes + sizeof(uint32_t) * (n_live[0] + n_live[1] + 2);
-	std::vector<uint8_t> table(bytes);
-	size_t pre_at[2] = { job_bytes, job_bytes + sizeof(uint32_t) * (n_live[0] + 1) };
-	for (int f = 0; f < 2; f++)
-		if (n_live[f]) {
-			memcpy(table.data() + (f ? sizeof(Job) * n_live[0] : 0), live[f].data(), sizeof(Job) * n_live[f]);
-			memcpy(table.data() + pre_at[f], prefix[f].data(), sizeof(uint32_t) * (n_live[f] + 1));
-		}
+	const job_table::Table table = job_table::pack_table(live, prefix, 0, 0);
 
 	if (fosphor_amd_finish(self) < 0)
 		return -EIO;
@@ -483,34 +429,28 @@ extern "C" int fosphor_amd_extract(struct fosphor *self, const void *d_samples, 
 	stats[FOSPHOR_AMD_EXTRACT_JOBS_TILE] += n_form[0];
 	stats[FOSPHOR_AMD_EXTRACT_JOBS_WAVE] += n_form[1];
 	stats[FOSPHOR_AMD_EXTRACT_SAMPLES] += samples;
-	if (!n_live[0] && !n_live[1])
+	if (live[0].empty() && live[1].empty())
 		return 0;						/* every job has n_out = 0 */
 
-	void *d;
-	if (fosphor_amd_priv_extract_scratch(self, bytes, &d))
+	uint8_t *d;
+	hipStream_t st;
+	if (job_table::upload_table(self, FOSPHOR_SCRATCH_EXTRACT, table, &d, &st))
 		return -EIO;
-	const hipStream_t st = (hipStream_t)fosphor_amd_stream(self);
-	if (hipMemcpyAsync(d, table.data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-		return -EIO;
+	Params p;
+	p.x = d_samples;
+	p.taps = d_taps;
+	p.out = static_cast<float2 *>(d_out);
 	int rv = 0;
 	for (int f = 0; f < 2 && !rv; f++) {
-		if (!n_live[f])
+		if (live[f].empty())
 			continue;
-		Params p;
-		p.x = d_samples;
-		p.taps = d_taps;
-		p.out = static_cast<float2 *>(d_out);
-		p.jobs = reinterpret_cast<const Job *>(static_cast<uint8_t *>(d) + (f ? sizeof(Job) * n_live[0] : 0));
-		p.prefix = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(d) + pre_at[f]);
-		p.n_jobs = (int)n_live[f];
+		p.jobs = reinterpret_cast<const Job *>(d + table.jobs_at[f]);
+		p.prefix = reinterpret_cast<const uint32_t *>(d + table.prefix_at[f]);
+		p.n_jobs = (int)live[f].size();
 		const unsigned groups = prefix[f].back();
-		rv = fmt == FOSPHOR_AMD_IQ_FP32 ? launch_form<iq_fp32>(f == 0, p, groups, st)
-		   : fmt == FOSPHOR_AMD_IQ_SC16 ? launch_form<iq_sc16>(f == 0, p, groups, st)
-		   :                              launch_form<iq_fp16>(f == 0, p, groups, st);
-		if (!rv)
-			stats[f ? FOSPHOR_AMD_EXTRACT_K_WAVE : FOSPHOR_AMD_EXTRACT_K_TILE]++;
+		rv = fmt == FOSPHOR_AMD_IQ_FP32 ? launch_form<iq_fp32>(f, p, groups, st, stats)
+		   : fmt == FOSPHOR_AMD_IQ_SC16 ? launch_form<iq_sc16>(f, p, groups, st, stats)
+		   :                              launch_form<iq_fp16>(f, p, groups, st, stats);
 	}
-	if (hipStreamSynchronize(st) != hipSuccess)			/* the table on the host lives until here */
-		return -EIO;
-	return rv;
+	return job_table::drain(st, rv);
 }

@@ -45,6 +45,7 @@
 
 /* accessors implemented next to struct fosphor (fosphor_api.cpp) */
 extern "C" long long *fosphor_amd_priv_mask_stats(struct fosphor *self);
+extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, long long *(*counters)(struct fosphor *), int n, long long *stats);
 extern "C" int fosphor_amd_priv_mask_scratch(struct fosphor *self, size_t bytes, void **d_scratch);
 
 namespace {
@@ -513,12 +514,7 @@ extern "C" int fosphor_amd_mask_from_points(int n, const double *col, const floa
 
 extern "C" int fosphor_amd_mask_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_MASK_STATS])
 {
-	if (!self)
-		return -EINVAL;
-	if (stats)
-		for (int i = 0; i < FOSPHOR_AMD_MASK_STATS; i++)
-			stats[i] = fosphor_amd_priv_mask_stats(self)[i];
-	return 0;
+	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_mask_stats, FOSPHOR_AMD_MASK_STATS, stats);
 }
 
 extern "C" int fosphor_amd_mask_from_trace(struct fosphor *self, int trace, float margin_y, int spread_cols, float *d_out)

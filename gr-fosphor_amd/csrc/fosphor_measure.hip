@@ -6,33 +6,25 @@
  * prefix of work-group counts and the SPLIT partials).
  *
  *   k_measure_wave     n <= kWaveMax: a wave owns a job, four jobs per work-group, no LDS.
- *   k_measure_split    longer jobs: a work-group of 256 lanes owns a chunk of kChunk samples of one job, which it finds by a bounded
- *                      binary search of the prefix (13 steps cover 4096 jobs), and writes the chunk's partial record.
+ *   k_measure_split    longer jobs: a work-group of 256 lanes owns a chunk of kChunk samples of one job, which it finds in the
+ *                      prefix (fosphor_jobs.h), and writes the chunk's partial record.
  *   k_measure_combine  a wave per SPLIT job folds the job's partials in ascending chunk order.
  * All three scan with one routine: a team of lanes (a wave, or the four waves of a work-group) strides a span of a job with
- * 16-byte loads, two samples per lane per load, from the first 16-byte boundary on; the single samples before it and behind the
- * last whole pair go one by one, so no byte outside the job's range is read.  A sample needs two things of its neighbours:
+ * 16-byte loads, two samples per lane per load, split as split_span() of fosphor_jobs.h splits it, so no byte outside the job's
+ * range is read; that header also has the table, the shared refusals and the tail of the call.  A sample needs two things of its neighbours:
  * above(m - 1) for the edge count and y[m + 1] for the lag-1 product.  Inside a pair both are at hand; between pairs they come from
  * the neighbouring lanes by a shuffle, and at the ends of a wave -- lane 0, and lane 63 or the team's last pair -- from one
  * 8-byte load of a sample the neighbouring wave reads anyway.  A lane sums its samples in ascending order; 64 partials meet by
  * xor-shuffles 32, 16, .. 1, which leave the same bits in every lane (a + b is b + a).  No atomics of any kind, no work-group
  * waits for another, every loop carries its bound in its header.
  */
-#include <errno.h>
 #include <math.h>
-#include <stdint.h>
-#include <string.h>
 
-#include <vector>
-
-#include <hip/hip_runtime.h>
-
-#include "../../include/fosphor_amd.h"
+#include "fosphor_jobs.h"
 #include "../../include/fosphor_amd_measure.h"
 
-/* accessors implemented next to struct fosphor (fosphor_api.cpp) */
+/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
 extern "C" long long *fosphor_amd_priv_measure_stats(struct fosphor *self);
-extern "C" int fosphor_amd_priv_measure_scratch(struct fosphor *self, size_t bytes, void **d_scratch);
 
 namespace {
 
@@ -43,11 +35,9 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;				/* jobs of a WAVE work-group */
 constexpr int kWaveMax = FOSPHOR_AMD_MEASURE_WAVE_MAX;
 constexpr int kChunk = FOSPHOR_AMD_MEASURE_CHUNK;
-constexpr int kSearchSteps = 13;				/* 2^12 = MAX_JOBS */
-constexpr long long kMaxGroups = 0x7fffffffLL;
 constexpr int kNone = 0x7fffffff;				/* first_above of a partial without one, until the record is written */
 
-static_assert(FOSPHOR_AMD_MEASURE_MAX_JOBS <= (1 << (kSearchSteps - 1)), "the job search is bounded");
+static_assert(FOSPHOR_AMD_MEASURE_MAX_JOBS <= job_table::kMaxJobs, "the job search is bounded");
 static_assert(sizeof(Job) == 16, "the job table is built from it");
 static_assert(sizeof(Record) == 96, "the record is 96 bytes");
 static_assert(kChunk % 2 == 0 && kChunk > kWaveMax, "a chunk is whole pairs, and a SPLIT job has two samples at least");
@@ -199,10 +189,10 @@ __device__ __forceinline__ void acc_wave_reduce(Acc &a)
 __device__ __forceinline__ void scan(Acc &a, const float2 *y, int n, int m0, int m1, float thr, int t, int team)
 {
 	const int lane = t & 63;
-	const int head = min(m1 - m0, (int)(((uintptr_t)(y + m0) >> 3) & 1));	/* 0 or 1 sample before the 16-byte boundary */
-	const int mb = m0 + head;
-	const int pairs = (m1 - mb) >> 1;
-	const int mt = mb + 2 * pairs;						/* the single sample behind the last pair, if mt < m1 */
+	const job_table::Span s = job_table::split_span(y + m0, m1 - m0);
+	const int head = s.head, pairs = s.pairs;
+	const int mb = m0 + head;						/* the first pair */
+	const int mt = m0 + s.tail;						/* the single sample behind the last pair, if mt < m1 */
 
 	if (t == 0 && head) {
 		const bool prev = m0 > 0 && power(y[m0 - 1]) >= thr;
@@ -241,20 +231,6 @@ __device__ __forceinline__ void scan(Acc &a, const float2 *y, int n, int m0, int
 	}
 }
 
-/* the job of work-group g: the largest j with prefix[j] <= g (every job of the table has a work-group) */
-__device__ __forceinline__ int find_job(const uint32_t *prefix, int n_jobs, uint32_t g)
-{
-	int lo = 0, hi = n_jobs;
-	for (int step = 0; step < kSearchSteps && hi - lo > 1; step++) {
-		const int mid = (lo + hi) >> 1;
-		if (prefix[mid] <= g)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
 __global__ __launch_bounds__(kThreads)
 void k_measure_wave(const Params p)
 {
@@ -276,7 +252,7 @@ void k_measure_split(const Params p)
 {
 	__shared__ Record s_part[kWaves];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int j = find_job(p.prefix, p.n_jobs, blockIdx.x);
+	const int j = job_table::find_job(p.prefix, p.n_jobs, blockIdx.x);
 	const DevJob job = p.jobs[j];
 	const int c = (int)(blockIdx.x - p.prefix[j]);			/* the chunk: c * kChunk < n by the prefix */
 	const int m0 = c * kChunk;
@@ -329,24 +305,18 @@ void k_measure_combine(const Params p)
 /* What both entry points refuse, but for the pointers. */
 int check_call(int64_t n_samples, const Job *jobs, int n_jobs)
 {
-	if (!jobs || n_jobs < 1 || n_jobs > FOSPHOR_AMD_MEASURE_MAX_JOBS || n_samples < 0)
+	if (!jobs || !job_table::count_ok(n_jobs, FOSPHOR_AMD_MEASURE_MAX_JOBS) || n_samples < 0)
 		return -EINVAL;
-	long long groups[2] = { 0, 0 };
+	long long chunks = 0;				/* of the SPLIT jobs; the WAVE jobs are kWaves to a work-group: MAX_JOBS / kWaves at most */
 	for (int i = 0; i < n_jobs; i++) {
 		const Job &b = jobs[i];
-		if (b.offset < 0 || b.n < 0 || b.offset > n_samples || b.n > n_samples - b.offset || b.threshold != b.threshold)
+		if (!job_table::inside(b.offset, b.n, n_samples) || b.threshold != b.threshold)
 			return -EINVAL;
-		if (form_of(b.n) == FOSPHOR_AMD_MEASURE_FORM_WAVE)
-			groups[0]++;
-		else
-			groups[1] += ((long long)b.n + kChunk - 1) / kChunk;
+		if (form_of(b.n) == FOSPHOR_AMD_MEASURE_FORM_SPLIT && !job_table::add_groups(chunks, b.n, kChunk))
+			return -EINVAL;
 	}
-	if ((groups[0] + kWaves - 1) / kWaves > kMaxGroups || groups[1] > kMaxGroups)
-		return -EINVAL;
 	return 0;
 }
-
-int launch_ok(void) { return hipGetLastError() == hipSuccess ? 0 : -EIO; }
 
 } // namespace
 
@@ -417,12 +387,7 @@ extern "C" int fosphor_amd_measure_derive(const struct fosphor_amd_measure_recor
 
 extern "C" int fosphor_amd_measure_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_MEASURE_STATS])
 {
-	if (!self)
-		return -EINVAL;
-	if (stats)
-		for (int i = 0; i < FOSPHOR_AMD_MEASURE_STATS; i++)
-			stats[i] = fosphor_amd_priv_measure_stats(self)[i];
-	return 0;
+	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_measure_stats, FOSPHOR_AMD_MEASURE_STATS, stats);
 }
 
 extern "C" int fosphor_amd_measure(struct fosphor *self, const void *d_iq, int64_t n_samples,
@@ -436,9 +401,11 @@ extern "C" int fosphor_amd_measure(struct fosphor *self, const void *d_iq, int64
 	if (check_call(n_samples, jobs, n_jobs))
 		return -EINVAL;
 
-	/* the table: WAVE jobs, SPLIT jobs, the SPLIT prefix; behind it, 8-byte aligned, the SPLIT partials */
+	/* the table: WAVE jobs, SPLIT jobs, the SPLIT prefix; behind it the SPLIT partials */
 	std::vector<DevJob> form[2];
-	std::vector<uint32_t> prefix(1, 0u);
+	std::vector<uint32_t> prefix[2];
+	std::vector<uint32_t> &chunks = prefix[FOSPHOR_AMD_MEASURE_FORM_SPLIT];
+	chunks.assign(1, 0u);
 	long long samples = 0;
 	for (int i = 0; i < n_jobs; i++) {
 		const int f = form_of(jobs[i].n);
@@ -449,62 +416,45 @@ extern "C" int fosphor_amd_measure(struct fosphor *self, const void *d_iq, int64
 		d.record = i;
 		d.part0 = 0;
 		if (f == FOSPHOR_AMD_MEASURE_FORM_SPLIT) {
-			d.part0 = (int32_t)prefix.back();
-			prefix.push_back(prefix.back() + (uint32_t)(((long long)jobs[i].n + kChunk - 1) / kChunk));
+			d.part0 = (int32_t)chunks.back();
+			chunks.push_back(chunks.back() + (uint32_t)job_table::groups_of(jobs[i].n, kChunk));
 		}
 		form[f].push_back(d);
 		samples += jobs[i].n;
 	}
-	const size_t n_form[2] = { form[0].size(), form[1].size() };
-	const size_t job_bytes = sizeof(DevJob) * (n_form[0] + n_form[1]);
-	const size_t table_bytes = (job_bytes + sizeof(uint32_t) * prefix.size() + 7) & ~(size_t)7;
-	const size_t bytes = table_bytes + sizeof(Record) * (size_t)prefix.back();
-	std::vector<uint8_t> table(table_bytes);
-	for (int f = 0; f < 2; f++)
-		if (n_form[f])
-			memcpy(table.data() + (f ? sizeof(DevJob) * n_form[0] : 0), form[f].data(), sizeof(DevJob) * n_form[f]);
-	memcpy(table.data() + job_bytes, prefix.data(), sizeof(uint32_t) * prefix.size());
+	const job_table::Table table = job_table::pack_table(form, prefix, chunks.back(), sizeof(Record));
 
 	if (fosphor_amd_finish(self) < 0)
 		return -EIO;
 	long long *stats = fosphor_amd_priv_measure_stats(self);
 	stats[FOSPHOR_AMD_MEASURE_CALLS]++;
-	stats[FOSPHOR_AMD_MEASURE_JOBS_WAVE] += (long long)n_form[0];
-	stats[FOSPHOR_AMD_MEASURE_JOBS_SPLIT] += (long long)n_form[1];
+	stats[FOSPHOR_AMD_MEASURE_JOBS_WAVE] += (long long)form[0].size();
+	stats[FOSPHOR_AMD_MEASURE_JOBS_SPLIT] += (long long)form[1].size();
 	stats[FOSPHOR_AMD_MEASURE_SAMPLES] += samples;
 
-	void *d;
-	if (fosphor_amd_priv_measure_scratch(self, bytes, &d))
-		return -EIO;
-	const hipStream_t st = (hipStream_t)fosphor_amd_stream(self);
-	if (hipMemcpyAsync(d, table.data(), table_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+	uint8_t *d;
+	hipStream_t st;
+	if (job_table::upload_table(self, FOSPHOR_SCRATCH_MEASURE, table, &d, &st))
 		return -EIO;
 	Params p;
 	p.iq = static_cast<const float2 *>(d_iq);
-	p.prefix = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(d) + job_bytes);
-	p.parts = reinterpret_cast<Record *>(static_cast<uint8_t *>(d) + table_bytes);
+	p.prefix = reinterpret_cast<const uint32_t *>(d + table.prefix_at[FOSPHOR_AMD_MEASURE_FORM_SPLIT]);
+	p.parts = reinterpret_cast<Record *>(d + table.parts_at);
 	p.records = d_records;
 	int rv = 0;
-	if (n_form[0]) {
-		p.jobs = static_cast<const DevJob *>(d);
-		p.n_jobs = (int)n_form[0];
-		hipLaunchKernelGGL(k_measure_wave, dim3((unsigned)((n_form[0] + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, p);
-		if (!(rv = launch_ok()))
-			stats[FOSPHOR_AMD_MEASURE_K_WAVE]++;
+	if (!form[0].empty()) {
+		p.jobs = reinterpret_cast<const DevJob *>(d + table.jobs_at[0]);
+		p.n_jobs = (int)form[0].size();
+		rv = job_table::launch<kThreads>(k_measure_wave, (unsigned)job_table::groups_of(p.n_jobs, kWaves), st, p, stats,
+		                                 FOSPHOR_AMD_MEASURE_K_WAVE);
 	}
-	if (n_form[1] && !rv) {
-		p.jobs = static_cast<const DevJob *>(d) + n_form[0];
-		p.n_jobs = (int)n_form[1];
-		hipLaunchKernelGGL(k_measure_split, dim3(prefix.back()), dim3(kThreads), 0, st, p);
-		if (!(rv = launch_ok()))
-			stats[FOSPHOR_AMD_MEASURE_K_SPLIT]++;
-		if (!rv) {
-			hipLaunchKernelGGL(k_measure_combine, dim3((unsigned)((n_form[1] + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, p);
-			if (!(rv = launch_ok()))
-				stats[FOSPHOR_AMD_MEASURE_K_COMBINE]++;
-		}
+	if (!form[1].empty() && !rv) {
+		p.jobs = reinterpret_cast<const DevJob *>(d + table.jobs_at[1]);
+		p.n_jobs = (int)form[1].size();
+		rv = job_table::launch<kThreads>(k_measure_split, chunks.back(), st, p, stats, FOSPHOR_AMD_MEASURE_K_SPLIT);
+		if (!rv)
+			rv = job_table::launch<kThreads>(k_measure_combine, (unsigned)job_table::groups_of(p.n_jobs, kWaves), st, p, stats,
+			                                 FOSPHOR_AMD_MEASURE_K_COMBINE);
 	}
-	if (hipStreamSynchronize(st) != hipSuccess)			/* the table on the host lives until here */
-		return -EIO;
-	return rv;
+	return job_table::drain(st, rv);
 }

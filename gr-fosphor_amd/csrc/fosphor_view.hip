@@ -31,6 +31,7 @@
 
 /* accessor implemented next to struct fosphor (fosphor_api.cpp) */
 extern "C" long long *fosphor_amd_priv_view_forms(struct fosphor *self);
+extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, long long *(*counters)(struct fosphor *), int n, long long *stats);
 
 namespace {
 
@@ -279,12 +280,7 @@ extern "C" int fosphor_amd_view_from_render(int fft_len, int wf_rows, const stru
 
 extern "C" int fosphor_amd_view_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_VIEW_STATS])
 {
-	if (!self)
-		return -EINVAL;
-	if (stats)
-		for (int i = 0; i < FOSPHOR_AMD_VIEW_STATS; i++)
-			stats[i] = fosphor_amd_priv_view_forms(self)[i];
-	return 0;
+	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_view_forms, FOSPHOR_AMD_VIEW_STATS, stats);
 }
 
 extern "C" int fosphor_amd_view(struct fosphor *self, const struct fosphor_amd_view *v, const struct fosphor_amd_view_out *out)

@@ -1,0 +1,194 @@
+"""The job tables of the four passes over burst IQ (gr-fosphor_amd/csrc/fosphor_jobs.h) on one instance: extract, then measure,
+demod and correlate over what extract wrote, three times with tables of 3, 300 and 2 jobs -- every scratch buffer of the instance
+grows once and is then reused larger than the table needs.
+
+A job's length comes from what can break the shared code: nothing (between live jobs and as the last job of a table), 1, one
+work-group's worth, one more, and two work-groups' worth plus 3 -- of extract's TILE_OUT 256 and WAVE_OUT 4 outputs, measure's CHUNK
+of 8192 samples (and WAVE_MAX 4096, the longest job a wave takes), demod's TILE of 2048 trace values at avg 1 and 3, correlate's TILE
+of 1024 lags with templates of 1, 2 and 33 samples.  Offsets walk through 0, 1, 2, 3, so spans begin on and off a 16-byte boundary.
+The single-module tests (tests/test_gpu_extract.py, _measure, _demod, _correlate) hold each pass's own seams at one table size; what
+is new here is the alternation of sizes on one instance, the chain, and jobs without work between and behind the live ones.
+
+What is compared: demod's traces and correlate's records and traces with fosphor_amd_demod_host and fosphor_amd_correlate_host over
+the same buffer, bit for bit; measure's integer fields and peak with fosphor_amd_measure_host bit for bit, its eight sums in double
+within measure_model.job_tolerance of the host's, because the header leaves the order of the additions open (rule 3) and the kernels
+use that; extract against the float64 model within extract_model.bound, as tests/test_gpu_extract.py does, because extract's host
+function is a float64 statement and no bit-exact twin.  Every stats delta is what the table predicts."""
+import os
+
+import numpy as np
+import pytest
+
+import correlate_model as cm
+import demod_model as dm
+import extract_model as em
+import measure_model as mm
+
+pytestmark = pytest.mark.gpu
+
+LONG = 18000				# outputs of the first extract job of every table: what the other passes read
+TILE_DT, WAVE_DT = (2, 9), (32, 257)	# (decim, taps) of the two extract forms
+TPL = 40
+
+
+@pytest.fixture(scope="module")
+def amd():
+    from _pkg import gr_fosphor_amd
+    if not os.path.exists(gr_fosphor_amd.LIB_PATH):
+        gr_fosphor_amd.build()
+    gr_fosphor_amd.load()
+    return gr_fosphor_amd
+
+
+def lengths(per):
+    return [0, 1, per, per + 1, 2 * per + 3]
+
+
+def pick(kinds, count, nothing):
+    """count rows out of kinds, in turn; kinds[1] is a job without work, which so lies between live jobs, and a table of more or
+    fewer than 3 jobs ends with one"""
+    rows = [kinds[k % len(kinds)] for k in range(count)]
+    if count != 3:
+        rows[-1] = nothing
+    return rows
+
+
+def extract_table(count):
+    """the long TILE job first; then both forms at every length, `first` walking through 0 .. 3"""
+    assert em.form(*TILE_DT) == "tile" and em.form(*WAVE_DT) == "wave"
+    kinds = [(0, LONG) + TILE_DT, (1, 0) + TILE_DT]
+    kinds += [(k % 4, n) + TILE_DT for k, n in enumerate(lengths(256)[1:])]
+    kinds += [(k % 4, n) + WAVE_DT for k, n in enumerate(lengths(4))]
+    rows = pick(kinds, count, (1, 0) + WAVE_DT)
+    return em.make_jobs([(first, n, d, (0x01234567 * (k + 1)) & 0xffffffff, 77 * k, 0 if t == TILE_DT[1] else TILE_DT[1], t)
+                         for k, (first, n, d, t) in enumerate(rows)])
+
+
+def measure_table(count, at, thr):
+    kinds = [(n, k % 4) for k, n in enumerate([mm.WAVE_MAX, 0, 1, mm.CHUNK, mm.CHUNK + 1, 2 * mm.CHUNK + 3])]
+    return mm.make_jobs([(at + off, n, thr) for n, off in pick(kinds, count, (0, 1))])
+
+
+def demod_table(count, at):
+    kinds = []
+    for avg in (1, 3):
+        for k, n_out in enumerate(lengths(dm.TILE // avg)):
+            mode = (dm.POWER, dm.PHASE, dm.FM)[(k + avg) % 3]
+            n = n_out * avg + (avg - 1 if n_out else 0) + (1 if mode == dm.FM and n_out else 0)	# a remainder that gives no output
+            kinds.append((at + k % 4, n, mode, avg))
+    kinds[0], kinds[1] = kinds[1], kinds[0]			# a live job first: kinds[1] is the one without outputs
+    assert [dm.n_out(mode, n, avg) for _, n, mode, avg in kinds[:3]] == [1, 0, dm.TILE]
+    return dm.place(pick(kinds, count, (at + 2, 1, dm.FM, 1)))
+
+
+def correlate_table(count, at):
+    kinds = []
+    for i, T in enumerate((33, 1, 2)):
+        for k, n_lags in enumerate(lengths(1024)):
+            n = n_lags + T - 1 if n_lags else (T - 1) * (k & 1)		# without lags: no samples, or one too few
+            kinds.append((at + (k + i) % 4, i & 1, n, T, (cm.RHO, cm.C, cm.NONE)[(k + i) % 3], 0.3))
+    kinds[0], kinds[1] = kinds[1], kinds[0]
+    assert [cm.n_lags(k[2], k[3]) for k in kinds[:3]] == [1, 0, 1024]
+    jobs = cm.place(pick(kinds, count, (at + 1, 0, 0, 2, cm.RHO, 0.3)))
+    odd = (jobs["trace"] == cm.C) & (jobs["out_offset"] & 1 != 0)
+    jobs["out_offset"][odd] -= 1				# a complex64 view begins on an even float; GUARD keeps the ranges apart
+    return jobs
+
+
+def delta(stats, before):
+    after = stats()
+    return {k: after[k] - before[k] for k in after}
+
+
+@pytest.fixture(scope="module")
+def stream():
+    rng = np.random.default_rng(1616)
+    x = (rng.standard_normal((2 * LONG + 4200, 2)) * 0.5).astype(np.float32)
+    taps = np.concatenate([em.design(*TILE_DT, 0.8), em.design(*WAVE_DT, 0.8)]).astype(np.float32)
+    tpl = (rng.standard_normal((TPL, 2)) * 0.5).astype(np.float32)
+    return x, taps, tpl
+
+
+def test_tables_of_3_300_2_jobs(amd, stream):
+    import torch
+    F = amd.Fosphor
+    x, taps, tpl = stream
+    xc = x.astype(np.float64) @ np.array([1.0, 1.0j])
+    d_x, d_tpl = torch.from_numpy(x).cuda(), torch.from_numpy(tpl).cuda()
+    f = F(n_bins=128, wf_rows=16)
+    try:
+        for count in (3, 300, 2):
+            # extract
+            ejobs = extract_table(count)
+            assert len(ejobs) == count and ejobs["n_out"][-1 if count != 3 else 1] == 0
+            before = f.extract_stats()
+            views = f.extract(d_x, ejobs, taps)
+            forms = np.array([em.form(int(j["decim"]), int(j["n_taps"])) for j in ejobs])
+            live = ejobs["n_out"] > 0
+            assert delta(f.extract_stats, before) == dict(
+                calls=1, k_tile=int((forms[live] == "tile").any()), k_wave=int((forms[live] == "wave").any()),
+                jobs_tile=int((forms == "tile").sum()), jobs_wave=int((forms == "wave").sum()),
+                samples=sum(em.need(int(j["n_out"]), int(j["decim"]), int(j["n_taps"])) for j in ejobs[live])), count
+            cap = int((ejobs["out_offset"] + ejobs["n_out"]).max())
+            y = np.zeros((cap, 2), np.float32)
+            for j, v in zip(ejobs, views):
+                got = v.cpu().numpy().view(np.float32).reshape(-1, 2)
+                assert len(got) == j["n_out"]
+                y[int(j["out_offset"]):int(j["out_offset"]) + int(j["n_out"])] = got
+                if j["n_out"]:
+                    want, tol = em.extract_job(xc, j, taps), em.bound(xc, j, taps)
+                    err = max(np.abs(got[:, 0] - want.real).max(), np.abs(got[:, 1] - want.imag).max())
+                    assert err <= tol, (count, j, err, tol)
+            base = views[0].data_ptr() - 8 * int(ejobs["out_offset"][0])	# extract()'s buffer: the views are slices of it
+            at = int(ejobs["out_offset"][0])					# the long job's outputs: what the others read
+            assert ejobs["n_out"][0] == LONG
+
+            # measure
+            thr = np.float32((y[at:at + LONG].astype(np.float64) ** 2).sum(axis=1).mean())
+            jobs = measure_table(count, at, thr)
+            before = f.measure_stats()
+            got = f.measure(base, jobs, n_samples=cap)
+            split = jobs["n"] > mm.WAVE_MAX
+            assert delta(f.measure_stats, before) == dict(
+                calls=1, k_wave=int((~split).any()), k_split=int(split.any()), k_combine=int(split.any()),
+                jobs_wave=int((~split).sum()), jobs_split=int(split.sum()), samples=int(jobs["n"].sum())), count
+            host = F.measure_host(y, jobs)
+            worst = 0.0
+            for i, (g, h, j) in enumerate(zip(got, host, jobs)):
+                for k in mm.INTS:
+                    assert g[k].tobytes() == h[k].tobytes(), (count, i, k, g[k], h[k])
+                tol = mm.job_tolerance(y, j)
+                for k in mm.SUMS:
+                    err = abs(float(g[k]) - float(h[k]))
+                    assert err <= tol[k], (count, i, k, float(g[k]), float(h[k]), tol[k])
+                    worst = max(worst, err / tol[k] if tol[k] else 0.0)
+            print("table of %d: measure's sums differ from the host's by at most %.3g of the tolerance" % (count, worst))
+
+            # demod
+            jobs = demod_table(count, at)
+            n_out = np.array([dm.n_out(int(j["mode"]), int(j["n"]), int(j["avg"])) for j in jobs])
+            before = f.demod_stats()
+            got = f.demod(base, jobs, n_samples=cap)
+            direct = jobs["avg"] == 1
+            assert delta(f.demod_stats, before) == dict(
+                calls=1, k_direct=int((direct & (n_out > 0)).any()), k_avg=int((~direct & (n_out > 0)).any()),
+                jobs_direct=int(direct.sum()), jobs_avg=int((~direct).sum()), samples=int(jobs["n"].sum()),
+                outputs=int(n_out.sum())), count
+            for i, (g, h) in enumerate(zip(got, F.demod_host(y, jobs))):
+                assert len(h) == n_out[i] and g.cpu().numpy().tobytes() == h.tobytes(), (count, i, tuple(jobs[i]))
+
+            # correlate
+            jobs = correlate_table(count, at)
+            lags = [cm.n_lags(int(j["n"]), int(j["tpl_len"])) for j in jobs]
+            before = f.correlate_stats()
+            rec, got = f.correlate(base, jobs, d_tpl, n_samples=cap)
+            assert delta(f.correlate_stats, before) == dict(calls=1, k_tile=int(any(lags)), k_combine=1, jobs=len(jobs),
+                                                            lags=sum(lags), macs=cm.macs(jobs)), count
+            hrec, hviews = F.correlate_host(y, jobs, tpl)
+            assert rec.tobytes() == hrec.tobytes(), (count, [i for i in range(len(jobs)) if rec[i] != hrec[i]][:4])
+            for i, (g, h) in enumerate(zip(got, hviews)):
+                assert (g is None) == (h is None) == (jobs["trace"][i] == cm.NONE)
+                if h is not None:
+                    assert g.cpu().numpy().tobytes() == h.tobytes(), (count, i, tuple(jobs[i]))
+    finally:
+        f.close()
