@@ -176,6 +176,12 @@ class CorrelateValues(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("time", "rho", "gain_re", "gain_im", "gain_db", "phase_turns", "snr_db", "detections")]
 
 
+class ResampleJob(C.Structure):
+    """struct fosphor_amd_resample_job (include/fosphor_amd_resample.h)"""
+    _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("phase0", C.c_int64), ("n", C.c_int32), ("n_out", C.c_int32),
+                ("up", C.c_int32), ("down", C.c_int32), ("taps_offset", C.c_int32), ("n_taps", C.c_int32)]
+
+
 class MeasureValues(C.Structure):
     """struct fosphor_amd_measure_values"""
     _fields_ = [(k, C.c_double) for k in ("mean_power", "mean_db", "peak_db", "papr_db", "freq_offset", "coherence", "kurtosis",
@@ -317,6 +323,17 @@ SIGNATURES = {
     "fosphor_amd_correlate_from_extract": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_float, C.POINTER(CorrelateJob)]),
     "fosphor_amd_correlate_derive": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(CorrelateValues)]),
     "fosphor_amd_correlate_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 6)]),
+    # include/fosphor_amd_resample.h
+    "fosphor_amd_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_int64]),
+    "fosphor_amd_resample_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_int64]),
+    "fosphor_amd_resample_n_out": (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "fosphor_amd_resample_design": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "fosphor_amd_resample_ratio": (C.c_int, [C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_double)]),
+    "fosphor_amd_resample_from_extract": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ResampleJob)]),
+    "fosphor_amd_resample_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 7)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

@@ -941,6 +941,119 @@ class Fosphor:
         """fosphor_amd_correlate_stats as a dict: calls, launches by kernel, jobs, lags, complex multiply-adds (CORRELATE_STATS)"""
         return self._stats(self.L.fosphor_amd_correlate_stats, self.CORRELATE_STATS)
 
+    RESAMPLE_STATS = ("calls", "k_tile", "k_direct", "jobs_tile", "jobs_direct", "outputs", "macs")
+    RESAMPLE_MAX_JOBS = 4096				# FOSPHOR_AMD_RESAMPLE_MAX_JOBS (include/fosphor_amd_resample.h)
+    RESAMPLE_MAX_UP = 256				# FOSPHOR_AMD_RESAMPLE_MAX_UP
+    RESAMPLE_MAX_DOWN = 256				# FOSPHOR_AMD_RESAMPLE_MAX_DOWN
+    RESAMPLE_MAX_BRANCH = 64				# FOSPHOR_AMD_RESAMPLE_MAX_BRANCH
+    RESAMPLE_TILE = 512					# FOSPHOR_AMD_RESAMPLE_TILE
+    RESAMPLE_TILE_LDS = 40960				# FOSPHOR_AMD_RESAMPLE_TILE_LDS
+    RESAMPLE_DIRECT_OUT = 256				# FOSPHOR_AMD_RESAMPLE_DIRECT_OUT
+    RESAMPLE_JOB_DTYPE = np.dtype([("offset", "<i8"), ("out_offset", "<i8"), ("phase0", "<i8"), ("n", "<i4"), ("n_out", "<i4"),
+                                   ("up", "<i4"), ("down", "<i4"), ("taps_offset", "<i4"), ("n_taps", "<i4")])
+
+    @staticmethod
+    def resample_form(up, down, n_taps):
+        """the kernel form of a job, "tile" or "direct": a function of (U, D, T) alone (include/fosphor_amd_resample.h)"""
+        up, down, n_taps = int(up), int(down), int(n_taps)
+        span = ((Fosphor.RESAMPLE_TILE - 1) * down + up - 1) // up + n_taps // up
+        return "tile" if 8 * (span + 1) + 4 * ((n_taps + 3) & ~3) <= Fosphor.RESAMPLE_TILE_LDS else "direct"
+
+    @staticmethod
+    def resample_n_out(n, up, down, n_taps, phase0=0):
+        """fosphor_amd_resample_n_out: the largest valid n_out of a job of n samples, ((n - Q) U - phase0) // D + 1 or 0"""
+        rv = _lib.load().fosphor_amd_resample_n_out(int(n), int(up), int(down), int(n_taps), int(phase0))
+        if rv < 0:
+            _fail("fosphor_amd_resample_n_out", rv, ValueError)
+        return rv
+
+    @staticmethod
+    def resample_design(up, down, branch_taps, guard=0.8):
+        """fosphor_amd_resample_design: the Hamming-windowed sinc prototype of branch_taps * up float32 taps for the ratio
+        up / down, cutoff guard / (2 * max(up, down)) cycles per sample of the up-sampled rate; the taps sum to up and are
+        symmetric; the group delay is (branch_taps * up - 1) / (2 * up) input samples"""
+        out = np.empty(max(int(branch_taps), 1) * max(int(up), 1), np.float32)
+        rv = _lib.load().fosphor_amd_resample_design(int(up), int(down), int(branch_taps), float(guard), out.ctypes.data)
+        if rv:
+            _fail("fosphor_amd_resample_design", rv, ValueError)
+        return out
+
+    @staticmethod
+    def resample_ratio(rate_in, rate_out, max_term=256):
+        """fosphor_amd_resample_ratio: (up, down, error): the best up / down for rate_out / rate_in with both terms at most
+        min(max_term, 256), and the achieved rate's relative error (rate_in * up / down - rate_out) / rate_out"""
+        up, down, err = C.c_int(0), C.c_int(0), C.c_double(0.0)
+        rv = _lib.load().fosphor_amd_resample_ratio(float(rate_in), float(rate_out), int(max_term), C.byref(up), C.byref(down),
+                                                    C.byref(err))
+        if rv:
+            _fail("fosphor_amd_resample_ratio", rv, ValueError)
+        return up.value, down.value, err.value
+
+    @staticmethod
+    def resample_jobs(extract_jobs, up, down, n_taps):
+        """a RESAMPLE_JOB_DTYPE array from an EXTRACT_DTYPE array (fosphor_amd_resample_from_extract: each job resamples what the
+        extract job wrote, offset = out_offset, n = n_out, phase0 = 0, the largest valid n_out, the taps at taps_offset 0), the
+        outputs placed back to back from out_offset 0 on"""
+        L = _lib.load()
+        ejobs = np.ascontiguousarray(np.atleast_1d(extract_jobs), dtype=Fosphor.EXTRACT_DTYPE)
+        out = np.zeros(ejobs.size, Fosphor.RESAMPLE_JOB_DTYPE)
+        at = 0
+        for i, e in enumerate(ejobs):
+            job = _lib.ResampleJob()
+            rv = L.fosphor_amd_resample_from_extract(e.tobytes(), int(up), int(down), int(n_taps), C.byref(job))
+            if rv:
+                _fail("fosphor_amd_resample_from_extract", rv, ValueError)
+            out[i] = (job.offset, at, job.phase0, job.n, job.n_out, job.up, job.down, job.taps_offset, job.n_taps)
+            at += job.n_out
+        return out
+
+    def resample(self, d_iq, jobs, taps, n_samples=None):
+        """Float32 IQ at up / down of its rate, up to 4096 jobs in one call (fosphor_amd_resample): a polyphase real FIR over
+        samples that are already in device memory, "valid" outputs only, every output bit-identical to resample_host().  d_iq:
+        a contiguous device tensor (complex64 or float32 pairs; what extract() wrote) or a raw device pointer with n_samples;
+        jobs: a RESAMPLE_JOB_DTYPE array (resample_jobs() makes one from extract jobs; out_offset is honoured, ranges must not
+        overlap); taps: float32 values (uploaded) or a float32 device tensor, addressed by the jobs' taps_offset / n_taps.
+        Returns a list with one torch complex64 view per job, into one device buffer that measure(), demod() and correlate()
+        read as they read extract()'s."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.RESAMPLE_JOB_DTYPE)
+        n_samples = _iq_count(d_iq, n_samples, "samples")
+        if hasattr(taps, "data_ptr"):
+            d_taps = taps
+            if d_taps.dtype != torch.float32 or not d_taps.is_cuda or not d_taps.is_contiguous():
+                raise ValueError("taps must be float32 values or a contiguous float32 device tensor")
+        else:
+            d_taps = torch.from_numpy(_or_dummy(np.ascontiguousarray(taps, dtype=np.float32).reshape(-1))).cuda()
+        cap = int((jobs["out_offset"] + jobs["n_out"]).max()) if jobs.size else 0
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 1), dtype=torch.complex64, device="cuda")
+        torch.cuda.synchronize()			# the taps (and the caller's samples) were written on torch's stream
+        rv = self.L.fosphor_amd_resample(self.h, _ptr(d_iq), n_samples, jobs.ctypes.data, int(jobs.size), d_taps.data_ptr(),
+                                         int(d_taps.numel()), d_out.data_ptr(), cap)
+        if rv:
+            _fail("fosphor_amd_resample", rv, RuntimeError)
+        return [d_out[int(j["out_offset"]):int(j["out_offset"]) + int(j["n_out"])] for j in jobs]
+
+    @staticmethod
+    def resample_host(iq, jobs, taps):
+        """fosphor_amd_resample_host: the same outputs on the host, no GPU.  iq: complex64 or float32 pairs; taps: float32.
+        Returns a list with one complex64 array per job, views into one buffer"""
+        iq = _float_pairs(iq)
+        taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.RESAMPLE_JOB_DTYPE)
+        cap = int((jobs["out_offset"] + jobs["n_out"]).max()) if jobs.size else 0
+        out = np.zeros(max(cap, 1), np.complex64)
+        keep = _or_dummy(iq), _or_dummy(taps)
+        rv = _lib.load().fosphor_amd_resample_host(keep[0].ctypes.data, iq.size // 2, jobs.ctypes.data, int(jobs.size),
+                                                   keep[1].ctypes.data, taps.size, out.ctypes.data, cap)
+        if rv:
+            _fail("fosphor_amd_resample_host", rv, ValueError)
+        return [out[int(j["out_offset"]):int(j["out_offset"]) + int(j["n_out"])] for j in jobs]
+
+    def resample_stats(self):
+        """fosphor_amd_resample_stats as a dict: calls, launches and jobs by form, outputs, multiply-adds (RESAMPLE_STATS)"""
+        return self._stats(self.L.fosphor_amd_resample_stats, self.RESAMPLE_STATS)
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

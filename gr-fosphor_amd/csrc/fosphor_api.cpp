@@ -197,6 +197,7 @@ struct fosphor
 	long long measure_stats[7];		/* measure calls, launches by kernel, jobs by form, samples (fosphor_measure.hip, fosphor_amd_measure_stats) */
 	long long demod_stats[7];		/* demod calls, launches by kernel, jobs by form, samples, outputs (fosphor_demod.hip, fosphor_amd_demod_stats) */
 	long long correlate_stats[6];		/* correlate calls, launches by kernel, jobs, lags, multiply-adds (fosphor_correlate.hip, fosphor_amd_correlate_stats) */
+	long long resample_stats[7];		/* resample calls, launches and jobs by form, outputs, multiply-adds (fosphor_resample.hip, fosphor_amd_resample_stats) */
 	struct {				/* scratch of fosphor_burst.hip (two) and of the passes over burst IQ (job tables, partials), by */
 		void  *d;			/* FOSPHOR_SCRATCH_* (fosphor_jobs.h); grown on demand, the instance never reads them */
 		size_t cap;
@@ -2446,7 +2447,7 @@ extern "C" int fosphor_amd_priv_mask_scratch(struct fosphor *self, size_t bytes,
 }
 
 /* The scratch buffers that only grow, by FOSPHOR_SCRATCH_* (fosphor_jobs.h): the two of fosphor_burst.hip, and one each for the
- * job tables and partials of fosphor_extract / _measure / _demod / _correlate.hip.  Every user has drained the stream of the
+ * job tables and partials of fosphor_extract / _measure / _demod / _correlate / _resample.hip.  Every user has drained the stream of the
  * launches that used the old buffer before it asks for a larger one. */
 extern "C" int fosphor_amd_priv_scratch(struct fosphor *self, int which, size_t bytes, void **d_scratch)
 {
@@ -2474,13 +2475,14 @@ extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, long long *(*co
 	return 0;
 }
 
-/* private accessors for the counters of fosphor_burst / _extract / _measure / _demod / _correlate.hip, and for the format that -1
+/* private accessors for the counters of fosphor_burst / _extract / _measure / _demod / _correlate / _resample.hip, and for the format that -1
  * stands for in fosphor_amd_extract */
 extern "C" long long *fosphor_amd_priv_burst_stats(struct fosphor *self) { return self->burst_stats; }
 extern "C" long long *fosphor_amd_priv_extract_stats(struct fosphor *self) { return self->extract_stats; }
 extern "C" long long *fosphor_amd_priv_measure_stats(struct fosphor *self) { return self->measure_stats; }
 extern "C" long long *fosphor_amd_priv_demod_stats(struct fosphor *self) { return self->demod_stats; }
 extern "C" long long *fosphor_amd_priv_correlate_stats(struct fosphor *self) { return self->correlate_stats; }
+extern "C" long long *fosphor_amd_priv_resample_stats(struct fosphor *self) { return self->resample_stats; }
 
 extern "C" int fosphor_amd_priv_iq_format(struct fosphor *self)
 {

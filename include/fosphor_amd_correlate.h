@@ -13,7 +13,8 @@
  *
  * Not this pass: a per-job derotator (a carrier offset inside the burst costs correlation gain; remove it by extracting at the
  * corrected centre, fosphor_amd_measure_derive's freq_offset), sub-sample interpolation of the peak, and FFT-based correlation
- * for templates beyond FOSPHOR_AMD_CORRELATE_MAX_TPL samples.
+ * for templates beyond FOSPHOR_AMD_CORRELATE_MAX_TPL samples.  A signal at another sample rate than the template's is brought to
+ * it first, on the device, by fosphor_amd_resample (fosphor_amd_resample.h); it is no longer a step for the host.
  *
  * Conventions, those of fosphor_amd_measure.h and fosphor_amd_demod.h: the device entry point waits for pending fosphor_process
  * work first (fosphor_amd_finish), runs on the instance's stream and returns when its outputs are complete; it writes no state of
