@@ -68,6 +68,18 @@ def _outs(jobs, n_out_fn):
     return n_out, max([int(j["out_offset"]) + n for j, n in zip(jobs, n_out)] + [0])
 
 
+def _check_f32(t, n, what, message="%s must be a contiguous float32 device tensor of %d elements"):
+    """t is a contiguous float32 device tensor of n elements, or ValueError(message % (what, n))"""
+    if str(t.dtype) != "torch.float32" or t.numel() != n or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(message % (what, n))
+
+
+def _result(d_res, Struct):
+    """a result struct on the device -> dict"""
+    r = Struct.from_buffer_copy(d_res.cpu().numpy().tobytes())
+    return {k: getattr(r, k) for k, _ in Struct._fields_}
+
+
 class Fosphor:
     """One fosphor instance (struct fosphor).  Reference geometry by default."""
 
@@ -107,6 +119,15 @@ class Fosphor:
             self.close()
         except Exception:
             pass
+
+    def _window(self, first_bin, n_cols, rows=None, most_rows=None):
+        """(n_cols, rows) of a window with the defaults filled in: every column from first_bin on, every waterfall row (at most
+        most_rows of them)"""
+        if n_cols is None:
+            n_cols = self.n - first_bin
+        if rows is None:
+            rows = self.wf_rows if most_rows is None else min(self.wf_rows, most_rows)
+        return n_cols, rows
 
     def _stats(self, fn, names):
         """the counters a fosphor_amd_*_stats copies, as a dict"""
@@ -317,12 +338,9 @@ class Fosphor:
         outputs: an iterable of those names instead, to produce exactly them.  Palettes, scales and offsets as in colorize();
         None = the reference's."""
         import torch
-        if n_cols is None:
-            n_cols = self.n - first_bin
+        n_cols, wf_src_rows = self._window(first_bin, n_cols, wf_src_rows)
         if width is None:
             width = n_cols
-        if wf_src_rows is None:
-            wf_src_rows = self.wf_rows
         if wf_out_rows is None:
             wf_out_rows = wf_src_rows
         if isinstance(detector, str):
@@ -411,8 +429,7 @@ class Fosphor:
             raise ValueError("trace must be one of %s" % ", ".join(self.TRACES))
         if floor not in self.FLOOR_MODES:
             raise ValueError("floor must be one of %s" % ", ".join(self.FLOOR_MODES))
-        if n_cols is None:
-            n_cols = self.n - first_bin
+        n_cols, _ = self._window(first_bin, n_cols)
         cfg = _lib.DetectCfg(self.TRACES[trace], int(first_bin), int(n_cols), self.FLOOR_MODES[floor], float(floor_q),
                              float(margin_db) / 20.0, float(threshold_y), int(max_gap), int(min_cols))
         # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
@@ -421,8 +438,7 @@ class Fosphor:
         rv = self.L.fosphor_amd_detect(self.h, C.byref(cfg), d_res.data_ptr(), d_bands.data_ptr(), int(max_bands))
         if rv:
             _fail("fosphor_amd_detect", rv, RuntimeError)
-        r = _lib.DetectResult.from_buffer_copy(d_res.cpu().numpy().tobytes())
-        res = {k: getattr(r, k) for k, _ in _lib.DetectResult._fields_}
+        res = _result(d_res, _lib.DetectResult)
         bands = d_bands.cpu().numpy().view(self.BAND_DTYPE)[:res["n_written"]].copy()
         return res, bands
 
@@ -447,16 +463,13 @@ class Fosphor:
         array (MASK_ROW_DTYPE), one record per scanned row, j = 0 the newest (None with want_rows=False); the int32 array of the
         n_written triggered j in ascending order; the float32 array [n_channels][rows] of channel power in y."""
         import torch
-        if n_cols is None:
-            n_cols = self.n - first_bin
-        if rows is None:
-            rows = self.wf_rows
+        n_cols, rows = self._window(first_bin, n_cols, rows)
         channels = [(int(a), int(b)) for a, b in channels]
         if len(channels) > self.MASK_MAX_CHANNELS:
             raise ValueError("at most %d channels" % self.MASK_MAX_CHANNELS)
         for name, t in (("upper", upper), ("lower", lower)):
-            if t is not None and (str(t.dtype) != "torch.float32" or t.numel() != self.n or not t.is_cuda or not t.is_contiguous()):
-                raise ValueError("%s must be a contiguous float32 device tensor of %d elements" % (name, self.n))
+            if t is not None:
+                _check_f32(t, self.n, name)
         cfg = _lib.MaskCfg(int(first_bin), int(n_cols), int(rows), int(min_cols), len(channels))
         for k, (a, b) in enumerate(channels):
             cfg.channels[k].first, cfg.channels[k].last = a, b
@@ -473,8 +486,7 @@ class Fosphor:
                                           int(max_events), d_pow.data_ptr() if channels else None)
         if rv:
             _fail("fosphor_amd_mask_scan", rv, RuntimeError)
-        r = _lib.MaskResult.from_buffer_copy(d_res.cpu().numpy().tobytes())
-        res = {k: getattr(r, k) for k, _ in _lib.MaskResult._fields_}
+        res = _result(d_res, _lib.MaskResult)
         recs = d_rows.cpu().numpy().view(self.MASK_ROW_DTYPE).copy() if want_rows else None
         events = d_ev.cpu().numpy()[:res["n_written"]].copy() if d_ev is not None else np.zeros(0, np.int32)
         power = d_pow.cpu().numpy() if channels else np.zeros((0, nr), np.float32)
@@ -529,10 +541,7 @@ class Fosphor:
         (BURST_DTYPE) of the n_written records in ascending root order (newest first).  overflow = 1 (more than max_runs runs: the
         threshold sits in the noise) gives no records."""
         import torch
-        if n_cols is None:
-            n_cols = self.n - first_bin
-        if rows is None:
-            rows = min(self.wf_rows, 65536)
+        n_cols, rows = self._window(first_bin, n_cols, rows, most_rows=65536)
         thr_y, d_thr = 0.0, None
         if hasattr(threshold, "data_ptr"):
             d_thr = threshold
@@ -540,9 +549,8 @@ class Fosphor:
             thr_y = float(threshold)
         else:
             d_thr = torch.from_numpy(np.ascontiguousarray(threshold, dtype=np.float32).reshape(-1)).cuda()
-        if d_thr is not None and (str(d_thr.dtype) != "torch.float32" or d_thr.numel() != self.n or not d_thr.is_cuda
-                                  or not d_thr.is_contiguous()):
-            raise ValueError("threshold must be a float, %d values, or a contiguous float32 device tensor of as many" % self.n)
+        if d_thr is not None:
+            _check_f32(d_thr, self.n, "threshold", "%s must be a float, %d values, or a contiguous float32 device tensor of as many")
         cfg = _lib.BurstCfg(int(first_bin), int(n_cols), int(rows), thr_y, int(max_gap_cols), int(max_gap_rows), int(min_rows),
                             int(min_cols), int(max_runs))
         nb = max(int(max_bursts), 1)
@@ -554,8 +562,7 @@ class Fosphor:
                                        d_out.data_ptr(), int(max_bursts))
         if rv:
             _fail("fosphor_amd_bursts", rv, RuntimeError)
-        r = _lib.BurstResult.from_buffer_copy(d_res.cpu().numpy().tobytes())
-        res = {k: getattr(r, k) for k, _ in _lib.BurstResult._fields_}
+        res = _result(d_res, _lib.BurstResult)
         recs = d_out.cpu().numpy().view(self.BURST_DTYPE)[:res["n_written"]].copy()
         return res, recs
 

@@ -187,19 +187,10 @@ struct fosphor
 	float    *d_chunk_sum, *d_chunk_max;	/* [max_spectra/16][N] */
 	long long *d_dbg;			/* K1_TIMING builds only (FOSPHOR_AMD_K1_TIMING=1) */
 	uint32_t *d_palette;			/* colour-map scratch (fosphor_cmap.hip), allocated on first use */
-	long long view_forms[4];		/* view launches by form (fosphor_view.hip, fosphor_amd_view_stats) */
-	long long detect_stats[3];		/* detect launches by kernel (fosphor_detect.hip, fosphor_amd_detect_stats) */
-	void     *d_detect;			/* scratch of fosphor_detect.hip, allocated on first use; the instance never reads it */
-	long long mask_stats[4];		/* mask launches by kind and form (fosphor_mask.hip, fosphor_amd_mask_stats) */
-	void     *d_mask;			/* scratch of fosphor_mask.hip, allocated on first use; the instance never reads it */
-	long long burst_stats[10];		/* burst calls and launches by kernel (fosphor_burst.hip, fosphor_amd_burst_stats) */
-	long long extract_stats[6];		/* extract calls, launches and jobs by form, samples (fosphor_extract.hip, fosphor_amd_extract_stats) */
-	long long measure_stats[7];		/* measure calls, launches by kernel, jobs by form, samples (fosphor_measure.hip, fosphor_amd_measure_stats) */
-	long long demod_stats[7];		/* demod calls, launches by kernel, jobs by form, samples, outputs (fosphor_demod.hip, fosphor_amd_demod_stats) */
-	long long correlate_stats[6];		/* correlate calls, launches by kernel, jobs, lags, multiply-adds (fosphor_correlate.hip, fosphor_amd_correlate_stats) */
-	long long resample_stats[7];		/* resample calls, launches and jobs by form, outputs, multiply-adds (fosphor_resample.hip, fosphor_amd_resample_stats) */
-	struct {				/* scratch of fosphor_burst.hip (two) and of the passes over burst IQ (job tables, partials), by */
-		void  *d;			/* FOSPHOR_SCRATCH_* (fosphor_jobs.h); grown on demand, the instance never reads them */
+	long long counters[FOSPHOR_COUNTERS_COUNT][FOSPHOR_COUNTERS_MAX];	/* launches, calls, jobs of the passes in files of their own, by FOSPHOR_COUNTERS_*
+						 * (fosphor_pass.h): host counters that only grow, behind every fosphor_amd_*_stats of theirs */
+	struct {				/* scratch of detect, mask, burst (two) and of the passes over burst IQ (job tables, partials), by */
+		void  *d;			/* FOSPHOR_SCRATCH_* (fosphor_pass.h); grown on demand, the instance never reads them */
 		size_t cap;
 	} scratch[FOSPHOR_SCRATCH_COUNT];
 	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
@@ -450,8 +441,6 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->d_chunk_sum); (void)hipFree(self->d_chunk_max);
 	(void)hipFree(self->d_rise);
 	(void)hipFree(self->d_palette);
-	(void)hipFree(self->d_detect);
-	(void)hipFree(self->d_mask);
 	for (int i = 0; i < FOSPHOR_SCRATCH_COUNT; i++)
 		(void)hipFree(self->scratch[i].d);
 	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
@@ -2412,41 +2401,8 @@ extern "C" void fosphor_amd_priv_power(struct fosphor *self, float *scale, float
 	*offset = self->power.offset;
 }
 
-/* private accessor for fosphor_view.hip: its launch counters (host counters that only grow; nothing on the submit path reads them) */
-extern "C" long long *fosphor_amd_priv_view_forms(struct fosphor *self)
-{
-	return self->view_forms;
-}
-
-/* private accessors for fosphor_detect.hip: its launch counters, and its scratch of a size that file fixes */
-extern "C" long long *fosphor_amd_priv_detect_stats(struct fosphor *self)
-{
-	return self->detect_stats;
-}
-
-extern "C" int fosphor_amd_priv_detect_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
-{
-	if (!self->d_detect && hipMalloc(&self->d_detect, bytes) != hipSuccess)
-		return -EIO;
-	*d_scratch = self->d_detect;
-	return 0;
-}
-
-/* private accessors for fosphor_mask.hip: its launch counters, and its scratch of a size that the instance's geometry fixes */
-extern "C" long long *fosphor_amd_priv_mask_stats(struct fosphor *self)
-{
-	return self->mask_stats;
-}
-
-extern "C" int fosphor_amd_priv_mask_scratch(struct fosphor *self, size_t bytes, void **d_scratch)
-{
-	if (!self->d_mask && hipMalloc(&self->d_mask, bytes) != hipSuccess)
-		return -EIO;
-	*d_scratch = self->d_mask;
-	return 0;
-}
-
-/* The scratch buffers that only grow, by FOSPHOR_SCRATCH_* (fosphor_jobs.h): the two of fosphor_burst.hip, and one each for the
+/* The scratch buffers that only grow, by FOSPHOR_SCRATCH_* (fosphor_pass.h): one each for fosphor_detect.hip and fosphor_mask.hip (of a
+ * size fixed for the life of the instance: allocated on first use, never again), the two of fosphor_burst.hip, and one each for the
  * job tables and partials of fosphor_extract / _measure / _demod / _correlate / _resample.hip.  Every user has drained the stream of the
  * launches that used the old buffer before it asks for a larger one. */
 extern "C" int fosphor_amd_priv_scratch(struct fosphor *self, int which, size_t bytes, void **d_scratch)
@@ -2465,25 +2421,23 @@ extern "C" int fosphor_amd_priv_scratch(struct fosphor *self, int which, size_t 
 	return 0;
 }
 
-/* what every public fosphor_amd_*_stats does with its module's counters */
-extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, long long *(*counters)(struct fosphor *), int n, long long *stats)
+/* the counters of pass `which` (FOSPHOR_COUNTERS_*, fosphor_pass.h); nothing on the submit path reads them */
+extern "C" long long *fosphor_amd_priv_counters(struct fosphor *self, int which)
 {
-	if (!self)
+	return self->counters[which];
+}
+
+/* what every public fosphor_amd_*_stats does with its pass's counters */
+extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, int which, int n, long long *stats)
+{
+	if (!self || which < 0 || which >= FOSPHOR_COUNTERS_COUNT || n < 0 || n > FOSPHOR_COUNTERS_MAX)
 		return -EINVAL;
 	if (stats)
-		memcpy(stats, counters(self), sizeof(long long) * n);
+		memcpy(stats, self->counters[which], sizeof(long long) * n);
 	return 0;
 }
 
-/* private accessors for the counters of fosphor_burst / _extract / _measure / _demod / _correlate / _resample.hip, and for the format that -1
- * stands for in fosphor_amd_extract */
-extern "C" long long *fosphor_amd_priv_burst_stats(struct fosphor *self) { return self->burst_stats; }
-extern "C" long long *fosphor_amd_priv_extract_stats(struct fosphor *self) { return self->extract_stats; }
-extern "C" long long *fosphor_amd_priv_measure_stats(struct fosphor *self) { return self->measure_stats; }
-extern "C" long long *fosphor_amd_priv_demod_stats(struct fosphor *self) { return self->demod_stats; }
-extern "C" long long *fosphor_amd_priv_correlate_stats(struct fosphor *self) { return self->correlate_stats; }
-extern "C" long long *fosphor_amd_priv_resample_stats(struct fosphor *self) { return self->resample_stats; }
-
+/* the format that -1 stands for in fosphor_amd_extract */
 extern "C" int fosphor_amd_priv_iq_format(struct fosphor *self)
 {
 	return self->iq_format;

@@ -5,10 +5,9 @@
  * between the stages is by kernel boundaries on the instance's stream: no work-group ever waits for another, nothing is polled, and
  * every loop has a bound that can be read off the code.
  *
- *   k_burst_runs    the streaming pass, with the access pattern of k_mask_scan: the columns of a call are cut, from (first column
- *                   & ~3) on, into strips of kStrip = 1024; a work-group of 256 lanes owns one strip of one row; lane t owns the
- *                   aligned group of 4 shifted columns at strip + 4t, one 16-byte load on either side of the N/2 wrap (the groups the
- *                   window cuts load column by column).  Gap closing needs, per cell, the nearest on cell before and after it
+ *   k_burst_runs    the streaming pass, by the strip read of the ring-pass substrate (fosphor_ring.h): a work-group of 256 lanes
+ *                   owns one strip of 1024 columns of one row, lane t the aligned group of 4 shifted columns at strip + 4t, one
+ *                   16-byte load.  Gap closing needs, per cell, the nearest on cell before and after it
  *                   (detect's k_bands takes them from a max and a min scan): here a lane finds them among its own 4 cells, then in
  *                   its wave with one ballot and one shuffle each way (lanes ascend with columns, so the nearest lane with an on cell
  *                   is the highest / lowest bit of the ballot on that side), then among the 4 waves through LDS, then from the other
@@ -23,7 +22,7 @@
  *   k_burst_rows    between the two: one wave per row, one lane per strip (at most 64): what precedes and follows each strip,
  *                   whether its first on cell is a start, the strip's place in the row, the row's count, and whether the strip holds
  *                   any cell of a run at all (if not, <true> returns before it loads anything: a sparse field is read once).
- *   k_burst_scan    exclusive scan of the rows' counts, one work-group as k_mask_events; the host reads the total, decides
+ *   k_burst_scan    exclusive scan of the rows' counts, one work-group (the substrate's block_scan); the host reads the total, decides
  *                   overflow and sizes the scratch that grows with the runs.
  *   k_burst_init    parent[r] = r, empty run and component records.
  *   k_burst_link    one lane per run: for each of the next max_gap_rows + 1 rows a binary search for the first run that can
@@ -40,26 +39,21 @@
 
 #include <hip/hip_runtime.h>
 
-#include "fosphor_jobs.h"					/* the scratch buffers and the copy of the counters */
-#include "../../include/fosphor_amd.h"
+#include "fosphor_ring.h"
 #include "../../include/fosphor_amd_burst.h"
-
-/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
-extern "C" long long *fosphor_amd_priv_burst_stats(struct fosphor *self);
 
 namespace {
 
-constexpr int kMaxCols = 65536;
+using namespace ring_pass;				/* kMaxCols, kStrip, kMaxStrips (k_burst_rows gives a strip a lane of one wave) */
+
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kStrip = FOSPHOR_AMD_BURST_STRIP;
-constexpr int kMaxStrips = kMaxCols / kStrip;		/* 64: k_burst_rows gives a strip a lane of one wave */
 constexpr int kScanLanes = 1024;
 constexpr int kSearchSteps = 17;			/* a binary search over at most 65536 + 1 entries */
 constexpr int kNone = INT32_MAX;
 
 static_assert(kStrip == kThreads * 4, "a lane owns 4 columns of the strip");
-static_assert(kMaxStrips == 64, "one lane per strip in k_burst_rows");
+static_assert(FOSPHOR_AMD_BURST_STATS <= FOSPHOR_COUNTERS_MAX, "the instance holds the counters");
 static_assert(FOSPHOR_AMD_BURST_MAX_ROWS <= 65536 && kMaxCols <= 65536, "16 bits each in the peak key");
 
 typedef unsigned long long u64;
@@ -96,16 +90,6 @@ struct RunParams {
 	int n_runs;
 };
 
-/* 10^(2 y) as an energy sum takes it (k_mask_scan's): 0 for a term that is not finite */
-__device__ __forceinline__ double power_term(float y)
-{
-	const float t = exp10f(2.0f * y);
-	if (t > 1e-30f && t < 1e30f)
-		return (double)t;
-	const double d = exp10(2.0 * (double)y);
-	return isfinite(d) ? d : 0.0;
-}
-
 /* y (not NaN) -> 32 bits that order as y does; -0 counts as +0; never 0 */
 __device__ __host__ __forceinline__ uint32_t order_bits(float y)
 {
@@ -120,16 +104,6 @@ __device__ __host__ __forceinline__ float order_value(uint32_t b)
 	c.u = (b & 0x80000000u) ? (b & 0x7fffffffu) : ~b;
 	return c.f;
 }
-
-__device__ __forceinline__ u64 shfl_up_u64(u64 v, int d)
-{
-	const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d);
-	const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d);
-	return ((u64)hi << 32) | lo;
-}
-
-__device__ __forceinline__ int low_lane(u64 m) { return __ffsll(m) - 1; }		/* m != 0 */
-__device__ __forceinline__ int top_lane(u64 m) { return 63 - __clzll((long long)m); }	/* m != 0 */
 
 __device__ __forceinline__ void run_send(const RunParams &p, int id, u64 key, double energy)
 {
@@ -156,9 +130,9 @@ void k_burst_runs(const RunParams p)
 		carry_next = p.sum_first[at];
 		carry_prev = p.sum_last[at];
 	}
-	const int s = (p.c0 & ~3) + strip * kStrip + 4 * tid;		/* this lane's shifted columns s .. s + 3 */
+	const int s = group_of(p.c0, strip, tid);			/* this lane's shifted columns s .. s + 3 */
 
-	uint32_t in = 0;
+	uint32_t in = 0;						/* the strip read, written out: fosphor_ring.h says why */
 #pragma unroll
 	for (int e = 0; e < 4; e++)
 		if (s + e >= p.c0 && s + e < p.c1)
@@ -167,8 +141,7 @@ void k_burst_runs(const RunParams p)
 	float4 v = make_float4(nan, nan, nan, nan);
 	float thr[4] = { nan, nan, nan, nan };
 	if (in) {							/* read where `in` says only */
-		const int row = (p.row_base - j) & p.row_mask;
-		const float *q = p.wf + (size_t)row * p.n + ((s ^ (p.n >> 1)) & (p.n - 1));
+		const float *q = p.wf + (size_t)ring_row(p.row_base, p.row_mask, j) * p.n + mem_col(s, p.n);
 		if (in == 15u) {
 			v = *reinterpret_cast<const float4 *>(q);
 		} else {						/* a group the window cuts: its columns one by one */
@@ -374,22 +347,13 @@ void k_burst_scan(const int *row_cnt, int n_rows, int *row_off, int *total)
 {
 	__shared__ long long s[kScanLanes];
 	const int t = threadIdx.x;
-	const int chunk = (n_rows + kScanLanes - 1) / kScanLanes;
-	const int g0 = min(t * chunk, n_rows), g1 = min(g0 + chunk, n_rows);
+	int g0, g1;
+	chunk_of<kScanLanes>(n_rows, t, g0, g1);
 
 	long long mine = 0;
 	for (int j = g0; j < g1; j++)
 		mine += row_cnt[j];
-	s[t] = mine;
-	__syncthreads();
-	for (int d = 1; d < kScanLanes; d <<= 1) {
-		long long w = s[t];
-		if (t >= d)
-			w += s[t - d];
-		__syncthreads();
-		s[t] = w;
-		__syncthreads();
-	}
+	block_scan<kScanLanes>(s, t, mine, OpAdd());
 	long long k = t ? s[t - 1] : 0;
 	for (int j = g0; j < g1; j++) {
 		row_off[j] = (int)(k < INT32_MAX ? k : INT32_MAX);
@@ -518,8 +482,8 @@ void k_burst_emit(const EmitParams p)
 	__shared__ int s[kScanLanes];
 	__shared__ int s_roots;
 	const int t = threadIdx.x;
-	const int chunk = (p.n_runs + kScanLanes - 1) / kScanLanes;
-	const int g0 = min(t * chunk, p.n_runs), g1 = min(g0 + chunk, p.n_runs);
+	int g0, g1;
+	chunk_of<kScanLanes>(p.n_runs, t, g0, g1);
 
 	if (t == 0)
 		s_roots = 0;
@@ -528,16 +492,7 @@ void k_burst_emit(const EmitParams p)
 		roots += p.parent[r] == r ? 1 : 0;
 		mine += kept(p, r) ? 1 : 0;
 	}
-	s[t] = mine;
-	__syncthreads();
-	for (int d = 1; d < kScanLanes; d <<= 1) {
-		int w = s[t];
-		if (t >= d)
-			w += s[t - d];
-		__syncthreads();
-		s[t] = w;
-		__syncthreads();
-	}
+	block_scan<kScanLanes>(s, t, mine, OpAdd());	/* its barriers order the initialisation above */
 	if (roots)
 		atomicAdd(&s_roots, roots);				/* LDS integer atomic: exact in any order */
 	int k = t ? s[t - 1] : 0;
@@ -573,7 +528,7 @@ void k_burst_emit(const EmitParams p)
 /* what both entry points refuse before they look at the data; n = columns of the buffer the window lies in */
 bool cfg_ok(const struct fosphor_amd_burst_cfg *cfg, int n, int max_rows, int max_bursts)
 {
-	if (cfg->first_bin < 0 || cfg->first_bin >= n || cfg->n_cols < 1 || cfg->n_cols > n - cfg->first_bin)
+	if (!window_ok(cfg->first_bin, cfg->n_cols, n))
 		return false;
 	if (cfg->rows < 1 || cfg->rows > max_rows || cfg->rows > FOSPHOR_AMD_BURST_MAX_ROWS)
 		return false;
@@ -586,13 +541,11 @@ bool cfg_ok(const struct fosphor_amd_burst_cfg *cfg, int n, int max_rows, int ma
 	return max_bursts >= 1 && max_bursts <= FOSPHOR_AMD_BURST_MAX_BURSTS;
 }
 
-bool launched() { return hipGetLastError() == hipSuccess; }
-
 } // namespace
 
 extern "C" int fosphor_amd_burst_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_BURST_STATS])
 {
-	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_burst_stats, FOSPHOR_AMD_BURST_STATS, stats);
+	return fosphor_amd_priv_copy_stats(self, FOSPHOR_COUNTERS_BURST, FOSPHOR_AMD_BURST_STATS, stats);
 }
 
 extern "C" int fosphor_amd_bursts_host(const float *ys, int rows, int n, const float *thr_or_null,
@@ -707,21 +660,19 @@ extern "C" int fosphor_amd_bursts(struct fosphor *self, const struct fosphor_amd
 		return -EINVAL;
 	if (!cfg_ok(cfg, kMaxCols, FOSPHOR_AMD_BURST_MAX_ROWS, max_bursts))	/* what needs no geometry, before the wait */
 		return -EINVAL;
-	if (fosphor_amd_finish(self) < 0)
-		return -EIO;
-	if (fosphor_amd_get_buffers_nohc(self, &b))			/* after the wait: the waterfall is one of two rings */
+	if (open(self, &b))
 		return -EIO;
 	const int n = b.fft_len;
-	if (n < 8 || n > kMaxCols || (n & (n - 1)) || b.wf_rows < 1 || (b.wf_rows & (b.wf_rows - 1)))
-		return -EINVAL;						/* what the aligned groups and the ring mask rely on */
+	if (!geometry_ok(b, 8))
+		return -EINVAL;
 	if (!cfg_ok(cfg, n, b.wf_rows, max_bursts))
 		return -EINVAL;
 
 	const hipStream_t st = (hipStream_t)fosphor_amd_stream(self);
-	long long *stats = fosphor_amd_priv_burst_stats(self);
+	long long *stats = fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_BURST);
 	const int rows = cfg->rows;
 	const int c0 = cfg->first_bin, c1 = cfg->first_bin + cfg->n_cols;
-	const int strips = (c1 - (c0 & ~3) + kStrip - 1) / kStrip;
+	const int strips = strips_of(c0, c1);
 	if (strips < 1 || strips > kMaxStrips)
 		return -EINVAL;
 
@@ -740,8 +691,8 @@ extern "C" int fosphor_amd_bursts(struct fosphor *self, const struct fosphor_amd
 	p.c0 = c0; p.c1 = c1;
 	p.gap = cfg->max_gap_cols;
 	p.n_rows = rows; p.strips = strips;
-	p.row_base = b.waterfall_pos - 1 + b.wf_rows;			/* kept non-negative before the mask */
-	p.row_mask = b.wf_rows - 1;
+	const Rows ring = waterfall_rows(b);
+	p.row_base = ring.base; p.row_mask = ring.mask;
 	p.sum_first = ints; p.sum_last = ints + cells; p.sum_cnt = ints + 2 * cells;
 	p.row_cnt = ints + 3 * cells;
 	int *row_off = p.row_cnt + rows;
@@ -753,17 +704,14 @@ extern "C" int fosphor_amd_bursts(struct fosphor *self, const struct fosphor_amd
 	stats[FOSPHOR_AMD_BURST_CALLS]++;
 	const dim3 block(kThreads);
 	hipLaunchKernelGGL(k_burst_runs<false>, dim3((unsigned)cells), block, 0, st, p);
-	if (!launched())
+	if (launch_counted(stats, FOSPHOR_AMD_BURST_K_COUNT))
 		return -EIO;
-	stats[FOSPHOR_AMD_BURST_K_COUNT]++;
 	hipLaunchKernelGGL(k_burst_rows, dim3((rows + kWaves - 1) / kWaves), block, 0, st, p);
-	if (!launched())
+	if (launch_counted(stats, FOSPHOR_AMD_BURST_K_ROWS))
 		return -EIO;
-	stats[FOSPHOR_AMD_BURST_K_ROWS]++;
 	hipLaunchKernelGGL(k_burst_scan, dim3(1), dim3(kScanLanes), 0, st, p.row_cnt, rows, row_off, d_total);
-	if (!launched())
+	if (launch_counted(stats, FOSPHOR_AMD_BURST_K_SCAN))
 		return -EIO;
-	stats[FOSPHOR_AMD_BURST_K_SCAN]++;
 
 	/* the one integer the host waits for between the two run passes: the call is synchronous anyway */
 	int total = 0;
@@ -798,22 +746,21 @@ extern "C" int fosphor_amd_bursts(struct fosphor *self, const struct fosphor_amd
 	p.n_runs = total;
 
 	const dim3 per_run((total + kThreads - 1) / kThreads);
-	int rv = 0;
 	hipLaunchKernelGGL(k_burst_init, per_run, block, 0, st, parent, runs, comps, total);
-	if (launched()) stats[FOSPHOR_AMD_BURST_K_INIT]++; else rv = -EIO;
+	int rv = launch_counted(stats, FOSPHOR_AMD_BURST_K_INIT);
 	if (!rv) {
 		hipLaunchKernelGGL(k_burst_runs<true>, dim3((unsigned)cells), block, 0, st, p);
-		if (launched()) stats[FOSPHOR_AMD_BURST_K_WRITE]++; else rv = -EIO;
+		rv = launch_counted(stats, FOSPHOR_AMD_BURST_K_WRITE);
 	}
 	if (!rv) {
 		hipLaunchKernelGGL(k_burst_link, per_run, block, 0, st, (const Run *)runs, (const int *)row_off, rows, total,
 		                   cfg->max_gap_rows, parent);
-		if (launched()) stats[FOSPHOR_AMD_BURST_K_LINK]++; else rv = -EIO;
+		rv = launch_counted(stats, FOSPHOR_AMD_BURST_K_LINK);
 	}
 	if (!rv) {
 		hipLaunchKernelGGL(k_burst_reduce, per_run, block, 0, st, (const Run *)runs, (const int *)row_off, rows, total,
 		                   (const int *)parent, comps);
-		if (launched()) stats[FOSPHOR_AMD_BURST_K_REDUCE]++; else rv = -EIO;
+		rv = launch_counted(stats, FOSPHOR_AMD_BURST_K_REDUCE);
 	}
 	if (!rv) {
 		EmitParams e;
@@ -822,9 +769,7 @@ extern "C" int fosphor_amd_bursts(struct fosphor *self, const struct fosphor_amd
 		e.min_rows = cfg->min_rows; e.min_cols = cfg->min_cols; e.max_bursts = max_bursts;
 		e.bursts = d_bursts; e.res = d_result;
 		hipLaunchKernelGGL(k_burst_emit, dim3(1), dim3(kScanLanes), 0, st, e);
-		if (launched()) stats[FOSPHOR_AMD_BURST_K_EMIT]++; else rv = -EIO;
+		rv = launch_counted(stats, FOSPHOR_AMD_BURST_K_EMIT);
 	}
-	if (hipStreamSynchronize(st) != hipSuccess)
-		return -EIO;
-	return rv;
+	return drain(st, rv);
 }

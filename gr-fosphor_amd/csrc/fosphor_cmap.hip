@@ -15,13 +15,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/fosphor_amd.h"
+#include "fosphor_ring.h"
 #include "../../include/fosphor_amd_cmap.h"
 #include "fosphor_cmap_dev.h"
-
-/* accessors implemented next to struct fosphor (fosphor_api.cpp) */
-extern "C" int  fosphor_amd_priv_palette(struct fosphor *self, int n, uint32_t **d_palette);
-extern "C" void fosphor_amd_priv_power(struct fosphor *self, float *scale, float *offset);
 
 namespace {
 
@@ -130,7 +126,7 @@ void k_colorize(const CmapParams p)
 	const int total = p.rows * quads;
 	for (int g = blockIdx.x * 256 + threadIdx.x; g < total; g += gridDim.x * 256) {
 		const int r = g / quads, c = (g - r * quads) << 2;
-		const int sr = (p.row_base - r) & p.row_mask;
+		const int sr = ring_pass::ring_row(p.row_base, p.row_mask, r);
 		const int sc = (c + (p.n >> 1)) & (p.n - 1);	/* fft-shift; stays 4-aligned and contiguous */
 		const float4 t = *reinterpret_cast<const float4 *>(p.src + (size_t)sr * p.n + sc);
 		uint4 o;
@@ -208,22 +204,17 @@ extern "C" int fosphor_amd_colorize(struct fosphor *self, int image, const uint3
 
 	p.dst = d_rgba;
 	p.n = b.fft_len; p.rows = rows;
-	if (image == FOSPHOR_AMD_IMG_WATERFALL) {
-		p.src = b.d_waterfall;
-		p.row_base = b.waterfall_pos - 1 + b.wf_rows;	/* kept non-negative before the mask */
-		p.row_mask = b.wf_rows - 1;
-	} else {
-		p.src = b.d_histogram;
-		p.row_base = b.n_bins - 1;
-		p.row_mask = 0x7fffffff;
-	}
+	const bool wf = image == FOSPHOR_AMD_IMG_WATERFALL;
+	const ring_pass::Rows rows_of = wf ? ring_pass::waterfall_rows(b) : ring_pass::histogram_rows(b);
+	p.src = wf ? b.d_waterfall : b.d_histogram;
+	p.row_base = rows_of.base; p.row_mask = rows_of.mask;
 	{
 		const int total = rows * (p.n >> 2);
 		int blocks = (total + 255) / 256;
 		if (blocks > 4096) blocks = 4096;
 		hipLaunchKernelGGL(k_colorize, dim3(blocks), dim3(256), sizeof(uint32_t) * p.lut.pal_n, st, p);
-		if (hipGetLastError() != hipSuccess)
+		if (ring_pass::launch_ok())
 			return -EIO;
 	}
-	return hipStreamSynchronize(st) == hipSuccess ? 0 : -EIO;
+	return ring_pass::drain(st, 0);
 }

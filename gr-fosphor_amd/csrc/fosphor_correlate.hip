@@ -23,9 +23,6 @@
 #include "fosphor_jobs.h"
 #include "../../include/fosphor_amd_correlate.h"
 
-/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
-extern "C" long long *fosphor_amd_priv_correlate_stats(struct fosphor *self);
-
 namespace {
 
 typedef struct fosphor_amd_correlate_job Job;
@@ -501,7 +498,7 @@ extern "C" int fosphor_amd_correlate_derive(const struct fosphor_amd_correlate_r
 
 extern "C" int fosphor_amd_correlate_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_CORRELATE_STATS])
 {
-	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_correlate_stats, FOSPHOR_AMD_CORRELATE_STATS, stats);
+	return fosphor_amd_priv_copy_stats(self, FOSPHOR_COUNTERS_CORRELATE, FOSPHOR_AMD_CORRELATE_STATS, stats);
 }
 
 extern "C" int fosphor_amd_correlate(struct fosphor *self, const void *d_iq, int64_t n_samples,
@@ -539,7 +536,7 @@ extern "C" int fosphor_amd_correlate(struct fosphor *self, const void *d_iq, int
 
 	if (fosphor_amd_finish(self) < 0)
 		return -EIO;
-	long long *stats = fosphor_amd_priv_correlate_stats(self);
+	long long *stats = fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_CORRELATE);
 	stats[FOSPHOR_AMD_CORRELATE_CALLS]++;
 	stats[FOSPHOR_AMD_CORRELATE_JOBS] += n_jobs;
 	stats[FOSPHOR_AMD_CORRELATE_LAGS] += plan.lags;

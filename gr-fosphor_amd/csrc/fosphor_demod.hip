@@ -21,9 +21,6 @@
 #include "fosphor_jobs.h"
 #include "../../include/fosphor_amd_demod.h"
 
-/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
-extern "C" long long *fosphor_amd_priv_demod_stats(struct fosphor *self);
-
 namespace {
 
 typedef struct fosphor_amd_demod_job Job;
@@ -244,7 +241,7 @@ extern "C" int fosphor_amd_demod_atan2_turns_n(const double *y, const double *x,
 
 extern "C" int fosphor_amd_demod_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_DEMOD_STATS])
 {
-	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_demod_stats, FOSPHOR_AMD_DEMOD_STATS, stats);
+	return fosphor_amd_priv_copy_stats(self, FOSPHOR_COUNTERS_DEMOD, FOSPHOR_AMD_DEMOD_STATS, stats);
 }
 
 extern "C" int fosphor_amd_demod(struct fosphor *self, const void *d_iq, int64_t n_samples,
@@ -281,7 +278,7 @@ extern "C" int fosphor_amd_demod(struct fosphor *self, const void *d_iq, int64_t
 
 	if (fosphor_amd_finish(self) < 0)
 		return -EIO;
-	long long *stats = fosphor_amd_priv_demod_stats(self);
+	long long *stats = fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_DEMOD);
 	stats[FOSPHOR_AMD_DEMOD_CALLS]++;
 	stats[FOSPHOR_AMD_DEMOD_JOBS_DIRECT] += plan.jobs[0];
 	stats[FOSPHOR_AMD_DEMOD_JOBS_AVG] += plan.jobs[1];

@@ -29,21 +29,18 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/fosphor_amd.h"
+#include "fosphor_ring.h"
 #include "../../include/fosphor_amd_detect.h"
-
-/* accessors implemented next to struct fosphor (fosphor_api.cpp) */
-extern "C" long long *fosphor_amd_priv_detect_stats(struct fosphor *self);
-extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, long long *(*counters)(struct fosphor *), int n, long long *stats);
-extern "C" int fosphor_amd_priv_detect_scratch(struct fosphor *self, size_t bytes, void **d_scratch);
 
 namespace {
 
-constexpr int kMaxCols = 65536;
+using namespace ring_pass;		/* kMaxCols, the lanes' helpers, block_scan and chunk_of, the host side of a call */
+
 constexpr int kMaxBins = 512;		/* fosphor_amd_init admits no more */
 constexpr int kPctLanes = 64;		/* one wave per work-group: 1024 work-groups at 65536 columns spread over every SIMD */
 constexpr int kPctRows = 32;		/* rows loaded ahead of the sum */
 constexpr int kLanes = FOSPHOR_AMD_DETECT_LANES;
+static_assert(FOSPHOR_AMD_DETECT_STATS <= FOSPHOR_COUNTERS_MAX, "the instance holds the counters");
 constexpr size_t kScratchBytes = sizeof(int32_t) * kMaxCols + sizeof(float) * kMaxBins;	/* floor bins [N], y table [n_bins] */
 
 struct PctParams {
@@ -138,10 +135,7 @@ int launch_percentiles(struct fosphor *self, hipStream_t st, const PctParams &p,
 	case 3: hipLaunchKernelGGL(k_percentiles<3>, grid, block, 0, st, p); break;
 	default: hipLaunchKernelGGL(k_percentiles<4>, grid, block, 0, st, p); break;
 	}
-	if (hipGetLastError() != hipSuccess)
-		return -EIO;
-	fosphor_amd_priv_detect_stats(self)[FOSPHOR_AMD_DETECT_PERCENTILES]++;
-	return 0;
+	return launch_counted(fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_DETECT), FOSPHOR_AMD_DETECT_PERCENTILES);
 }
 
 /* The lower median of the window's floor bins: element (m - 1) / 2 of the m bins that are >= 0, sorted. */
@@ -192,32 +186,12 @@ struct BandParams {
 	float threshold_y;
 };
 
-struct OpMax { __device__ int operator()(int a, int b) const { return max(a, b); } };
-struct OpMin { __device__ int operator()(int a, int b) const { return min(a, b); } };
-struct OpAdd { __device__ int operator()(int a, int b) const { return a + b; } };
-
-/* Inclusive scan of one value per lane over the work-group's kLanes lanes, left in s[] (position pos of this lane's value). */
-template <typename Op>
-__device__ void block_scan(int *s, int pos, int v, Op op)
-{
-	s[pos] = v;
-	__syncthreads();
-	for (int d = 1; d < kLanes; d <<= 1) {
-		int w = s[pos];
-		if (pos >= d)
-			w = op(s[pos - d], w);
-		__syncthreads();
-		s[pos] = w;
-		__syncthreads();
-	}
-}
-
 /* op over the values of the lanes below this one (ident for lane 0) */
 template <typename Op>
 __device__ int scan_below(int *s, int v, int ident, Op op)
 {
 	const int t = threadIdx.x;
-	block_scan(s, t, v, op);
+	block_scan<kLanes>(s, t, v, op);
 	const int r = t ? s[t - 1] : ident;
 	__syncthreads();
 	return r;
@@ -228,21 +202,18 @@ template <typename Op>
 __device__ int scan_above(int *s, int v, int ident, Op op)
 {
 	const int pos = kLanes - 1 - threadIdx.x;
-	block_scan(s, pos, v, op);
+	block_scan<kLanes>(s, pos, v, op);
 	const int r = pos ? s[pos - 1] : ident;
 	__syncthreads();
 	return r;
 }
-
-__device__ __forceinline__ int top_bit(uint64_t w) { return 63 - __clzll((long long)w); }	/* w != 0 */
-__device__ __forceinline__ int low_bit(uint64_t w) { return __ffsll((unsigned long long)w) - 1; }	/* w != 0 */
 
 __global__ __launch_bounds__(kLanes)
 void k_bands(const BandParams p)
 {
 	__shared__ int s[kLanes];
 	const int t = threadIdx.x, n = p.n_cols;
-	const int chunk = (n + kLanes - 1) / kLanes;			/* 1 .. 64 */
+	const int chunk = (n + kLanes - 1) / kLanes;			/* 1 .. 64; chunk_of() with g1 - g0 for len moved this kernel's listing */
 	const int g0 = min(t * chunk, n), len = min(chunk, n - g0);	/* this lane's window columns [g0, g0 + len); len may be 0 */
 	const float *y = p.trace + 2 * (size_t)p.first_bin + 1;	/* y of window column i: y[2 * i] */
 	const float thr = p.absolute ? p.threshold_y : p.res->threshold_y;
@@ -255,8 +226,8 @@ void k_bands(const BandParams p)
 			ab |= 1ull << j;
 
 	/* gap closing: the nearest above column on each side of a not-above one, inside the window or none (-1 / n) */
-	const int left_above  = scan_below(s, ab ? g0 + top_bit(ab) : -1, -1, OpMax());
-	const int right_above = scan_above(s, ab ? g0 + low_bit(ab) : n, n, OpMin());
+	const int left_above  = scan_below(s, ab ? g0 + top_lane(ab) : -1, -1, OpMax());
+	const int right_above = scan_above(s, ab ? g0 + low_lane(ab) : n, n, OpMin());
 	uint64_t m = ab;
 	int prev = left_above;
 	for (int j = 0; j < len; j++) {
@@ -265,15 +236,15 @@ void k_bands(const BandParams p)
 			continue;
 		}
 		const uint64_t rest = j < 63 ? ab >> (j + 1) : 0;
-		const int next = rest ? g0 + j + 1 + low_bit(rest) : right_above;
+		const int next = rest ? g0 + j + 1 + low_lane(rest) : right_above;
 		if (prev >= 0 && next < n && next - prev - 1 <= p.max_gap)
 			m |= 1ull << j;
 	}
 
 	/* runs of m: the nearest column outside a run on each side of this chunk (-1 / n: the window's edge) */
 	const uint64_t z = ~m & valid;
-	const int left_out  = scan_below(s, z ? g0 + top_bit(z) : -1, -1, OpMax());
-	const int right_out = scan_above(s, z ? g0 + low_bit(z) : n, n, OpMin());
+	const int left_out  = scan_below(s, z ? g0 + top_lane(z) : -1, -1, OpMax());
+	const int right_out = scan_above(s, z ? g0 + low_lane(z) : n, n, OpMin());
 	/* a run ends at bit j when bit j + 1 is clear; the column after the chunk is in a run unless it is right_out (or the edge) */
 	uint64_t ends = 0;
 	if (len) {
@@ -284,19 +255,19 @@ void k_bands(const BandParams p)
 	/* the bands that end in this chunk, and their numbers */
 	int mine = 0;
 	for (uint64_t e = ends; e; e &= e - 1) {
-		const int j = low_bit(e);
+		const int j = low_lane(e);
 		const uint64_t zb = z & ((1ull << j) - 1);
-		const int start = zb ? g0 + top_bit(zb) + 1 : left_out + 1;
+		const int start = zb ? g0 + top_lane(zb) + 1 : left_out + 1;
 		mine += g0 + j - start + 1 >= p.min_cols;
 	}
-	block_scan(s, t, mine, OpAdd());
+	block_scan<kLanes>(s, t, mine, OpAdd());
 	int k = t ? s[t - 1] : 0;
 	const int n_found = s[kLanes - 1];
 	const int n_written = min(n_found, p.max_bands);
 	for (uint64_t e = ends; e; e &= e - 1) {
-		const int j = low_bit(e);
+		const int j = low_lane(e);
 		const uint64_t zb = z & ((1ull << j) - 1);
-		const int start = zb ? g0 + top_bit(zb) + 1 : left_out + 1;
+		const int start = zb ? g0 + top_lane(zb) + 1 : left_out + 1;
 		if (g0 + j - start + 1 < p.min_cols)
 			continue;
 		if (k < p.max_bands) {
@@ -369,13 +340,11 @@ void bin_y(int n_bins, float histo_scale, float histo_offset, float *out)
 int prepare(struct fosphor *self, struct fosphor_amd_buffers *b, int32_t **d_bins, float **d_ytab)
 {
 	void *d;
-	if (fosphor_amd_finish(self) < 0)
+	if (open(self, b))
 		return -EIO;
-	if (fosphor_amd_get_buffers_nohc(self, b))
-		return -EIO;
-	if (b->fft_len < 4 || b->fft_len > kMaxCols || (b->fft_len & (b->fft_len - 1)) || b->n_bins < 1 || b->n_bins > kMaxBins)
+	if (!geometry_ok(*b, 4) || b->n_bins < 1 || b->n_bins > kMaxBins)
 		return -EINVAL;
-	if (fosphor_amd_priv_detect_scratch(self, kScratchBytes, &d))
+	if (fosphor_amd_priv_scratch(self, FOSPHOR_SCRATCH_DETECT, kScratchBytes, &d))
 		return -EIO;
 	*d_bins = (int32_t *)d;
 	*d_ytab = (float *)((int32_t *)d + kMaxCols);
@@ -455,7 +424,7 @@ extern "C" int fosphor_amd_detect_bands_host(const float *trace_y, int n, float 
 
 extern "C" int fosphor_amd_detect_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_DETECT_STATS])
 {
-	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_detect_stats, FOSPHOR_AMD_DETECT_STATS, stats);
+	return fosphor_amd_priv_copy_stats(self, FOSPHOR_COUNTERS_DETECT, FOSPHOR_AMD_DETECT_STATS, stats);
 }
 
 extern "C" int fosphor_amd_percentiles(struct fosphor *self, const float *q, int n_q, float *d_y, int32_t *d_bin)
@@ -487,10 +456,7 @@ extern "C" int fosphor_amd_percentiles(struct fosphor *self, const float *q, int
 	p.n = b.fft_len; p.n_bins = b.n_bins; p.c0 = 0; p.c1 = b.fft_len;
 	for (int k = 0; k < FOSPHOR_AMD_DETECT_MAX_Q; k++)
 		p.q[k] = k < n_q ? q[k] : 1.0f;
-	rv = launch_percentiles(self, st, p, n_q);
-	if (hipStreamSynchronize(st) != hipSuccess)
-		return -EIO;
-	return rv;
+	return drain(st, launch_percentiles(self, st, p, n_q));
 }
 
 extern "C" int fosphor_amd_detect(struct fosphor *self, const struct fosphor_amd_detect_cfg *cfg,
@@ -512,10 +478,10 @@ extern "C" int fosphor_amd_detect(struct fosphor *self, const struct fosphor_amd
 		return -EINVAL;
 	if ((rv = prepare(self, &b, &d_bins, &d_ytab)))
 		return rv;
-	if (cfg->first_bin < 0 || cfg->first_bin >= b.fft_len || cfg->n_cols < 1 || cfg->n_cols > b.fft_len - cfg->first_bin)
+	if (!window_ok(cfg->first_bin, cfg->n_cols, b.fft_len))
 		return -EINVAL;
 	const hipStream_t st = (hipStream_t)fosphor_amd_stream(self);
-	long long *stats = fosphor_amd_priv_detect_stats(self);
+	long long *stats = fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_DETECT);
 
 	std::vector<float> ytab(b.n_bins);		/* lives until the stream has been waited for */
 	rv = 0;
@@ -533,10 +499,7 @@ extern "C" int fosphor_amd_detect(struct fosphor *self, const struct fosphor_amd
 		if (!rv) {
 			hipLaunchKernelGGL(k_floor, dim3(1), dim3(kLanes), 0, st, d_bins, cfg->first_bin, cfg->n_cols, b.n_bins, d_ytab,
 			                   cfg->margin_y, d_result);
-			if (hipGetLastError() != hipSuccess)
-				rv = -EIO;
-			else
-				stats[FOSPHOR_AMD_DETECT_FLOOR]++;
+			rv = launch_counted(stats, FOSPHOR_AMD_DETECT_FLOOR);
 		}
 	}
 	if (!rv) {
@@ -547,12 +510,7 @@ extern "C" int fosphor_amd_detect(struct fosphor *self, const struct fosphor_amd
 		bp.max_gap = cfg->max_gap; bp.min_cols = cfg->min_cols; bp.max_bands = max_bands;
 		bp.absolute = !pct; bp.threshold_y = cfg->threshold_y;
 		hipLaunchKernelGGL(k_bands, dim3(1), dim3(kLanes), 0, st, bp);
-		if (hipGetLastError() != hipSuccess)
-			rv = -EIO;
-		else
-			stats[FOSPHOR_AMD_DETECT_BANDS]++;
+		rv = launch_counted(stats, FOSPHOR_AMD_DETECT_BANDS);
 	}
-	if (hipStreamSynchronize(st) != hipSuccess)
-		return -EIO;
-	return rv;
+	return drain(st, rv);
 }

@@ -37,8 +37,7 @@
 #include "fosphor_jobs.h"
 #include "../../include/fosphor_amd_extract.h"
 
-/* accessors implemented next to struct fosphor (fosphor_api.cpp) */
-extern "C" long long *fosphor_amd_priv_extract_stats(struct fosphor *self);
+/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
 extern "C" int fosphor_amd_priv_iq_format(struct fosphor *self);
 
 namespace {
@@ -389,7 +388,7 @@ extern "C" int fosphor_amd_extract_from_burst(const struct fosphor_amd_burst *b,
 
 extern "C" int fosphor_amd_extract_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_EXTRACT_STATS])
 {
-	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_extract_stats, FOSPHOR_AMD_EXTRACT_STATS, stats);
+	return fosphor_amd_priv_copy_stats(self, FOSPHOR_COUNTERS_EXTRACT, FOSPHOR_AMD_EXTRACT_STATS, stats);
 }
 
 extern "C" int fosphor_amd_extract(struct fosphor *self, const void *d_samples, int64_t n_samples, int iq_format,
@@ -424,7 +423,7 @@ extern "C" int fosphor_amd_extract(struct fosphor *self, const void *d_samples, 
 
 	if (fosphor_amd_finish(self) < 0)
 		return -EIO;
-	long long *stats = fosphor_amd_priv_extract_stats(self);
+	long long *stats = fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_EXTRACT);
 	stats[FOSPHOR_AMD_EXTRACT_CALLS]++;
 	stats[FOSPHOR_AMD_EXTRACT_JOBS_TILE] += n_form[0];
 	stats[FOSPHOR_AMD_EXTRACT_JOBS_WAVE] += n_form[1];

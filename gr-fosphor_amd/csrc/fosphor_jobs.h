@@ -7,12 +7,12 @@
  * what is left.  A pass supplies its device job struct, the work-group size of each form and its kernels.  It gets from here:
  *   device  find_job(), and load_span(): a span of float32 IQ into an LDS image by 16-byte loads that read no byte outside the span;
  *   host    the refusals every pass shares, the packer of the table, and the tail of a call: upload, launch, check, count, drain.
- * The scratch buffers that hold the tables belong to the instance (fosphor_api.cpp); their slots are named here.
+ * The scratch buffers that hold the tables belong to the instance (fosphor_api.cpp); fosphor_pass.h names their slots and holds the
+ * checked launch and the drain, which the passes over the plain buffers (fosphor_ring.h) end a call with as well.
  */
 #ifndef FOSPHOR_JOBS_H
 #define FOSPHOR_JOBS_H
 
-#include <errno.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -21,26 +21,7 @@
 #include <utility>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "../../include/fosphor_amd.h"
-
-/* the instance's scratch buffers that only grow, one per user (fosphor_burst.hip has two: by rows and strips, by runs) */
-enum {
-	FOSPHOR_SCRATCH_BURST_ROWS,
-	FOSPHOR_SCRATCH_BURST_RUNS,
-	FOSPHOR_SCRATCH_EXTRACT,
-	FOSPHOR_SCRATCH_MEASURE,
-	FOSPHOR_SCRATCH_DEMOD,
-	FOSPHOR_SCRATCH_CORRELATE,
-	FOSPHOR_SCRATCH_RESAMPLE,
-	FOSPHOR_SCRATCH_COUNT
-};
-
-/* implemented next to struct fosphor (fosphor_api.cpp): buffer `which`, at least `bytes` long -- its user has drained the stream of
- * every launch that used the old one before it asks for more -- and the copy behind every public fosphor_amd_*_stats */
-extern "C" int fosphor_amd_priv_scratch(struct fosphor *self, int which, size_t bytes, void **d_scratch);
-extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, long long *(*counters)(struct fosphor *), int n, long long *stats);
+#include "fosphor_pass.h"					/* the scratch slots, the counters, launch and drain */
 
 namespace job_table {
 
@@ -212,21 +193,10 @@ inline int upload_table(struct fosphor *self, int which, const Table &t, uint8_t
 	return 0;
 }
 
-inline int launch_ok(void) { return hipGetLastError() == hipSuccess ? 0 : -EIO; }
-
-/* one launch of `groups` work-groups of kThreads lanes, checked, and counted in stats[counter] if it went */
-template <int kThreads, class P>
-int launch(void (*kernel)(const P), unsigned groups, hipStream_t st, const P &p, long long *stats, int counter)
-{
-	hipLaunchKernelGGL(kernel, dim3(groups), dim3(kThreads), 0, st, p);
-	const int rv = launch_ok();
-	if (!rv)
-		stats[counter]++;
-	return rv;
-}
-
-/* the end of a call: rv of its launches once the stream is empty */
-inline int drain(hipStream_t st, int rv) { return hipStreamSynchronize(st) != hipSuccess ? -EIO : rv; }
+/* the checked launch and the drain: fosphor_pass.h */
+using pass::launch_ok;
+using pass::launch;
+using pass::drain;
 
 } // namespace job_table
 

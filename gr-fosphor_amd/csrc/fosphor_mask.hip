@@ -3,12 +3,9 @@
  *
  * Read-only passes over the instance's plain buffers, in a file of their own: nothing here is on the process / merge path.
  *
- *   k_mask_scan     the hot pass, a pure streaming read of rows x columns x 4 B.  The columns of a call are cut, from (first
- *                   column & ~3) on, into strips of kStrip = 1024; a work-group of 256 lanes owns one strip and a run of `rpg`
- *                   consecutive rows.  Lane t owns the aligned group of 4 shifted columns at strip + 4t, which is an aligned,
- *                   contiguous group of memory columns on either side of the N/2 wrap (N/2 is a multiple of 4): one 16-byte load
- *                   per lane and row, a coalesced 1 KiB per wave.  The groups that the window cuts (its head and tail) load their
- *                   columns one by one, so no byte outside the window is read.  What depends on the column only is fetched once
+ *   k_mask_scan     the hot pass, a pure streaming read of rows x columns x 4 B by the strip read of the ring-pass substrate
+ *                   (fosphor_ring.h): a work-group of 256 lanes owns one strip of 1024 columns and a run of `rpg` consecutive rows,
+ *                   one 16-byte load per lane and row, a coalesced 1 KiB per wave.  What depends on the column only is fetched once
  *                   per work-group and kept in registers for all its rows: the two limits of each column (NaN where there is none,
  *                   which no y violates, so the row loop carries no window test) and one bit per column and channel.  Rows are
  *                   loaded kUnroll at a time, independent of each other.
@@ -39,22 +36,16 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/fosphor_amd.h"
+#include "fosphor_ring.h"
 #include "../../include/fosphor_amd_detect.h"
 #include "../../include/fosphor_amd_mask.h"
 
-/* accessors implemented next to struct fosphor (fosphor_api.cpp) */
-extern "C" long long *fosphor_amd_priv_mask_stats(struct fosphor *self);
-extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, long long *(*counters)(struct fosphor *), int n, long long *stats);
-extern "C" int fosphor_amd_priv_mask_scratch(struct fosphor *self, size_t bytes, void **d_scratch);
-
 namespace {
 
-constexpr int kMaxCols = 65536;
+using namespace ring_pass;				/* kMaxCols, kStrip, kMaxStrips (k_mask_combine gives a strip a lane of one wave) */
+
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kStrip = FOSPHOR_AMD_MASK_STRIP;		/* columns of a work-group: one 16-byte load per lane */
-constexpr int kMaxStrips = kMaxCols / kStrip;		/* 64: k_mask_combine gives a strip a lane of one wave */
 constexpr int kMaxRpg = 32;				/* rows of a work-group at most (the size of its LDS) */
 constexpr int kUnroll = 4;				/* rows loaded ahead of their reduction */
 constexpr int kTargetGroups = 1024;			/* work-groups a call is cut into before they take more rows: 4 for each of the 256 CUs */
@@ -63,7 +54,7 @@ constexpr int kEvLanes = 1024;
 constexpr int kTraceTile = 256;
 
 static_assert(kStrip == kThreads * 4, "a lane owns 4 columns of the strip");
-static_assert(kMaxStrips == 64, "one lane per strip in k_mask_combine");
+static_assert(FOSPHOR_AMD_MASK_STATS <= FOSPHOR_COUNTERS_MAX, "the instance holds the counters");
 
 /* What a set of columns leaves of a row.  first / last: INT32_MAX / -1 when nothing violates; key: 0 when nothing is over, else
  * (bits of the excess) << 32 | (0xffffffff - column). */
@@ -122,27 +113,6 @@ __device__ __forceinline__ void emit_row(const ScanParams &p, int j, const Part 
 	p.flags[j] = (m.n_over + m.n_under >= p.min_cols) ? 1 : 0;
 }
 
-/* 10^(2 y) as a channel's sum takes it: 0 for a term that is not finite.  The float32 path covers every y a spectrum produces;
- * what it cannot represent (or a NaN) takes the fp64 path, which decides what is finite as fosphor_amd_detect does. */
-__device__ __forceinline__ double power_term(float y)
-{
-	const float t = exp10f(2.0f * y);
-	if (t > 1e-30f && t < 1e30f)
-		return (double)t;
-	const double d = exp10(2.0 * (double)y);
-	return isfinite(d) ? d : 0.0;
-}
-
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int d)
-{
-	const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d);
-	const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
-	return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ int low_lane(unsigned long long m) { return __ffsll(m) - 1; }		/* m != 0 */
-__device__ __forceinline__ int top_lane(unsigned long long m) { return 63 - __clzll((long long)m); }	/* m != 0 */
-
 __global__ __launch_bounds__(kThreads)
 void k_mask_scan(const ScanParams p)
 {
@@ -156,7 +126,7 @@ void k_mask_scan(const ScanParams p)
 	const int s = (p.c0 & ~3) + strip * kStrip + 4 * tid;		/* this lane's shifted columns s .. s + 3 */
 
 	/* what depends on the column only: which of the 4 are read, their limits, their channels */
-	uint32_t in = 0;
+	uint32_t in = 0;						/* the strip read, written out: fosphor_ring.h says why */
 #pragma unroll
 	for (int e = 0; e < 4; e++)
 		if (s + e >= p.c0 && s + e < p.c1)
@@ -197,8 +167,7 @@ void k_mask_scan(const ScanParams p)
 		for (int u = 0; u < kUnroll; u++) {
 			v[u] = make_float4(nan, nan, nan, nan);
 			if (r0 + u < nj && in) {
-				const int row = (p.row_base - (j0 + r0 + u)) & p.row_mask;
-				const float *q = base + (size_t)row * p.n;
+				const float *q = base + (size_t)((p.row_base - (j0 + r0 + u)) & p.row_mask) * p.n;
 				if (in == 15u) {
 					v[u] = *reinterpret_cast<const float4 *>(q);
 				} else {				/* a group the window cuts: its columns one by one */
@@ -345,22 +314,6 @@ void k_mask_combine(const ScanParams p)
 	}
 }
 
-/* Inclusive sum scan of one value per lane over the work-group's kEvLanes lanes, left in s[]. */
-__device__ void block_sum_scan(int *s, int v)
-{
-	const int t = threadIdx.x;
-	s[t] = v;
-	__syncthreads();
-	for (int d = 1; d < kEvLanes; d <<= 1) {
-		int w = s[t];
-		if (t >= d)
-			w += s[t - d];
-		__syncthreads();
-		s[t] = w;
-		__syncthreads();
-	}
-}
-
 /* The event list and the result.  Lane t owns the rows [t * chunk, (t + 1) * chunk), chunk = ceil(n_rows / 1024). */
 __global__ __launch_bounds__(kEvLanes)
 void k_mask_events(const uint8_t *flags, int n_rows, int32_t *events, int max_events, struct fosphor_amd_mask_result *res)
@@ -368,8 +321,8 @@ void k_mask_events(const uint8_t *flags, int n_rows, int32_t *events, int max_ev
 	__shared__ int s[kEvLanes];
 	__shared__ int s_newest, s_oldest;
 	const int t = threadIdx.x;
-	const int chunk = (n_rows + kEvLanes - 1) / kEvLanes;
-	const int g0 = min(t * chunk, n_rows), g1 = min(g0 + chunk, n_rows);
+	int g0, g1;
+	chunk_of<kEvLanes>(n_rows, t, g0, g1);
 
 	if (t == 0) {
 		s_newest = INT32_MAX;
@@ -382,7 +335,7 @@ void k_mask_events(const uint8_t *flags, int n_rows, int32_t *events, int max_ev
 			first = min(first, j);
 			last = j;
 		}
-	block_sum_scan(s, mine);				/* its barriers order the initialisation above */
+	block_scan<kEvLanes>(s, t, mine, OpAdd());		/* its barriers order the initialisation above */
 	if (mine) {
 		atomicMin(&s_newest, first);			/* LDS integer atomics: exact in any order */
 		atomicMax(&s_oldest, last);
@@ -425,31 +378,22 @@ void k_mask_trace(const float *trace, int n, int spread, float margin_y, float *
 	out[i] = m + margin_y;
 }
 
-struct Scratch {
-	uint8_t *flags;
-	Part    *parts;
-	double  *pows;
-};
-
 int launch_scan(struct fosphor *self, hipStream_t st, ScanParams &p)
 {
-	const int a0 = p.c0 & ~3;
-	p.strips = (p.c1 - a0 + kStrip - 1) / kStrip;
+	p.strips = strips_of(p.c0, p.c1);
 	if (p.strips < 1 || p.strips > kMaxStrips)
 		return -EINVAL;
 	long long rpg = (long long)p.n_rows * p.strips / kTargetGroups;
 	p.rpg = (int)(rpg < 1 ? 1 : rpg > kMaxRpg ? kMaxRpg : rpg);
 	const dim3 grid(p.strips, (p.n_rows + p.rpg - 1) / p.rpg), block(kThreads);
 	hipLaunchKernelGGL(k_mask_scan, grid, block, 0, st, p);
-	if (hipGetLastError() != hipSuccess)
-		return -EIO;
-	fosphor_amd_priv_mask_stats(self)[p.strips > 1 ? FOSPHOR_AMD_MASK_FORM_SHARED : FOSPHOR_AMD_MASK_FORM_ROWS]++;
-	if (p.strips > 1) {
+	int rv = launch_counted(fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_MASK),
+	                        p.strips > 1 ? FOSPHOR_AMD_MASK_FORM_SHARED : FOSPHOR_AMD_MASK_FORM_ROWS);
+	if (!rv && p.strips > 1) {
 		hipLaunchKernelGGL(k_mask_combine, dim3((p.n_rows + kWaves - 1) / kWaves), block, 0, st, p);
-		if (hipGetLastError() != hipSuccess)
-			return -EIO;
+		rv = launch_ok();
 	}
-	return 0;
+	return rv;
 }
 
 void row_rule(const float *y, const float *upper, const float *lower, int n, struct fosphor_amd_mask_row *out)
@@ -514,7 +458,7 @@ extern "C" int fosphor_amd_mask_from_points(int n, const double *col, const floa
 
 extern "C" int fosphor_amd_mask_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_MASK_STATS])
 {
-	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_mask_stats, FOSPHOR_AMD_MASK_STATS, stats);
+	return fosphor_amd_priv_copy_stats(self, FOSPHOR_COUNTERS_MASK, FOSPHOR_AMD_MASK_STATS, stats);
 }
 
 extern "C" int fosphor_amd_mask_from_trace(struct fosphor *self, int trace, float margin_y, int spread_cols, float *d_out)
@@ -525,24 +469,15 @@ extern "C" int fosphor_amd_mask_from_trace(struct fosphor *self, int trace, floa
 		return -EINVAL;
 	if (trace != FOSPHOR_AMD_TRACE_LIVE && trace != FOSPHOR_AMD_TRACE_MAXHOLD)
 		return -EINVAL;
-	if (fosphor_amd_finish(self) < 0)
-		return -EIO;
-	if (fosphor_amd_get_buffers_nohc(self, &b))
+	if (open(self, &b))
 		return -EIO;
 	if (b.fft_len < 1 || b.fft_len > kMaxCols)
 		return -EINVAL;
 	const hipStream_t st = (hipStream_t)fosphor_amd_stream(self);
 	const float *tr = b.d_spectrum + (trace == FOSPHOR_AMD_TRACE_MAXHOLD ? 2 * (size_t)b.fft_len : 0);
-	int rv = 0;
 	hipLaunchKernelGGL(k_mask_trace, dim3((b.fft_len + kTraceTile - 1) / kTraceTile), dim3(kTraceTile), 0, st,
 	                   tr, b.fft_len, spread_cols, margin_y, d_out);
-	if (hipGetLastError() != hipSuccess)
-		rv = -EIO;
-	else
-		fosphor_amd_priv_mask_stats(self)[FOSPHOR_AMD_MASK_FROM_TRACE]++;
-	if (hipStreamSynchronize(st) != hipSuccess)
-		return -EIO;
-	return rv;
+	return drain(st, launch_counted(fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_MASK), FOSPHOR_AMD_MASK_FROM_TRACE));
 }
 
 extern "C" int fosphor_amd_mask_scan(struct fosphor *self, const struct fosphor_amd_mask_cfg *cfg,
@@ -566,15 +501,12 @@ extern "C" int fosphor_amd_mask_scan(struct fosphor *self, const struct fosphor_
 	const bool masked = d_upper || d_lower;
 	if (!masked && cfg->n_channels == 0)
 		return -EINVAL;
-	if (fosphor_amd_finish(self) < 0)
-		return -EIO;
-	if (fosphor_amd_get_buffers_nohc(self, &b))		/* after the wait: the waterfall is one of two rings */
+	if (open(self, &b))
 		return -EIO;
 	const int n = b.fft_len;
-	if (n < 8 || n > kMaxCols || (n & (n - 1)) || b.wf_rows < 1 || (b.wf_rows & (b.wf_rows - 1)))
-		return -EINVAL;					/* what the aligned groups and the ring mask rely on */
-	if (cfg->first_bin < 0 || cfg->first_bin >= n || cfg->n_cols < 1 || cfg->n_cols > n - cfg->first_bin ||
-	    cfg->rows < 1 || cfg->rows > b.wf_rows)
+	if (!geometry_ok(b, 8))
+		return -EINVAL;
+	if (!window_ok(cfg->first_bin, cfg->n_cols, n) || cfg->rows < 1 || cfg->rows > b.wf_rows)
 		return -EINVAL;
 	for (int c = 0; c < cfg->n_channels; c++)
 		if (cfg->channels[c].first < 0 || cfg->channels[c].last >= n || cfg->channels[c].first > cfg->channels[c].last)
@@ -585,7 +517,7 @@ extern "C" int fosphor_amd_mask_scan(struct fosphor *self, const struct fosphor_
 	const size_t flag_bytes = ((size_t)b.wf_rows + 255) & ~(size_t)255;
 	const size_t part_bytes = sizeof(Part) * b.wf_rows * max_strips;
 	const size_t pow_bytes = sizeof(double) * kMaxCh * b.wf_rows * max_strips;
-	if (fosphor_amd_priv_mask_scratch(self, flag_bytes + part_bytes + pow_bytes, &d))
+	if (fosphor_amd_priv_scratch(self, FOSPHOR_SCRATCH_MASK, flag_bytes + part_bytes + pow_bytes, &d))
 		return -EIO;
 	const hipStream_t st = (hipStream_t)fosphor_amd_stream(self);
 
@@ -597,8 +529,8 @@ extern "C" int fosphor_amd_mask_scan(struct fosphor *self, const struct fosphor_
 	p.pows = (double *)((uint8_t *)d + flag_bytes + part_bytes);
 	p.n = n;
 	p.n_rows = cfg->rows;
-	p.row_base = b.waterfall_pos - 1 + b.wf_rows;		/* kept non-negative before the mask */
-	p.row_mask = b.wf_rows - 1;
+	const Rows ring = waterfall_rows(b);
+	p.row_base = ring.base; p.row_mask = ring.mask;
 	p.min_cols = cfg->min_cols;
 
 	/* the launch over the mask's window takes the channels that lie inside it; without a mask one launch takes them all */
@@ -624,8 +556,7 @@ extern "C" int fosphor_amd_mask_scan(struct fosphor *self, const struct fosphor_
 	p.c0 = masked ? w0 : h0;
 	p.c1 = masked ? w1 : h1;
 	p.emit_rows = 1;
-	long long *stats = fosphor_amd_priv_mask_stats(self);
-	stats[FOSPHOR_AMD_MASK_SCANS]++;
+	fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_MASK)[FOSPHOR_AMD_MASK_SCANS]++;
 	int rv = launch_scan(self, st, p);
 	if (!rv && n_rest) {
 		p.upper = p.lower = NULL;
@@ -641,10 +572,7 @@ extern "C" int fosphor_amd_mask_scan(struct fosphor *self, const struct fosphor_
 	}
 	if (!rv) {
 		hipLaunchKernelGGL(k_mask_events, dim3(1), dim3(kEvLanes), 0, st, p.flags, cfg->rows, d_events, max_events, d_result);
-		if (hipGetLastError() != hipSuccess)
-			rv = -EIO;
+		rv = launch_ok();
 	}
-	if (hipStreamSynchronize(st) != hipSuccess)
-		return -EIO;
-	return rv;
+	return drain(st, rv);
 }

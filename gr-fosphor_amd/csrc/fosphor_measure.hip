@@ -23,9 +23,6 @@
 #include "fosphor_jobs.h"
 #include "../../include/fosphor_amd_measure.h"
 
-/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
-extern "C" long long *fosphor_amd_priv_measure_stats(struct fosphor *self);
-
 namespace {
 
 typedef struct fosphor_amd_measure_job Job;
@@ -387,7 +384,7 @@ extern "C" int fosphor_amd_measure_derive(const struct fosphor_amd_measure_recor
 
 extern "C" int fosphor_amd_measure_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_MEASURE_STATS])
 {
-	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_measure_stats, FOSPHOR_AMD_MEASURE_STATS, stats);
+	return fosphor_amd_priv_copy_stats(self, FOSPHOR_COUNTERS_MEASURE, FOSPHOR_AMD_MEASURE_STATS, stats);
 }
 
 extern "C" int fosphor_amd_measure(struct fosphor *self, const void *d_iq, int64_t n_samples,
@@ -426,7 +423,7 @@ extern "C" int fosphor_amd_measure(struct fosphor *self, const void *d_iq, int64
 
 	if (fosphor_amd_finish(self) < 0)
 		return -EIO;
-	long long *stats = fosphor_amd_priv_measure_stats(self);
+	long long *stats = fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_MEASURE);
 	stats[FOSPHOR_AMD_MEASURE_CALLS]++;
 	stats[FOSPHOR_AMD_MEASURE_JOBS_WAVE] += (long long)form[0].size();
 	stats[FOSPHOR_AMD_MEASURE_JOBS_SPLIT] += (long long)form[1].size();

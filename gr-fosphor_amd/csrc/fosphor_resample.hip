@@ -25,9 +25,6 @@
 #include "fosphor_jobs.h"
 #include "../../include/fosphor_amd_resample.h"
 
-/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
-extern "C" long long *fosphor_amd_priv_resample_stats(struct fosphor *self);
-
 namespace {
 
 typedef struct fosphor_amd_resample_job Job;
@@ -345,7 +342,7 @@ extern "C" int fosphor_amd_resample_from_extract(const struct fosphor_amd_extrac
 
 extern "C" int fosphor_amd_resample_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_RESAMPLE_STATS])
 {
-	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_resample_stats, FOSPHOR_AMD_RESAMPLE_STATS, stats);
+	return fosphor_amd_priv_copy_stats(self, FOSPHOR_COUNTERS_RESAMPLE, FOSPHOR_AMD_RESAMPLE_STATS, stats);
 }
 
 extern "C" int fosphor_amd_resample(struct fosphor *self, const void *d_iq, int64_t n_samples,
@@ -375,7 +372,7 @@ extern "C" int fosphor_amd_resample(struct fosphor *self, const void *d_iq, int6
 
 	if (fosphor_amd_finish(self) < 0)
 		return -EIO;
-	long long *stats = fosphor_amd_priv_resample_stats(self);
+	long long *stats = fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_RESAMPLE);
 	stats[FOSPHOR_AMD_RESAMPLE_CALLS]++;
 	stats[FOSPHOR_AMD_RESAMPLE_JOBS_TILE] += plan.jobs[0];
 	stats[FOSPHOR_AMD_RESAMPLE_JOBS_DIRECT] += plan.jobs[1];

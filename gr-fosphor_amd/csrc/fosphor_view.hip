@@ -24,17 +24,16 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/fosphor_amd.h"
+#include "fosphor_ring.h"
 #include "../../include/fosphor_amd_cmap.h"
 #include "../../include/fosphor_amd_view.h"
 #include "fosphor_cmap_dev.h"
 
-/* accessor implemented next to struct fosphor (fosphor_api.cpp) */
-extern "C" long long *fosphor_amd_priv_view_forms(struct fosphor *self);
-extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, long long *(*counters)(struct fosphor *), int n, long long *stats);
-
 namespace {
 
+using namespace ring_pass;		/* ring_row, the host side of a call */
+
+static_assert(FOSPHOR_AMD_VIEW_STATS <= FOSPHOR_COUNTERS_MAX, "the instance holds the counters");
 constexpr int kThreads = 256;
 constexpr int kChunk = kThreads * 4;	/* columns of one strip: one 16-byte load per lane */
 constexpr int kRows = 4;		/* picture rows a work-group reduces at once (independent loads in flight per lane) */
@@ -144,7 +143,7 @@ void k_view(const ViewParams p)
 							const float4 u0 = b[0], u1 = b[1];
 							v = make_float4(u0.y, u0.w, u1.y, u1.w);
 						} else {
-							const int row = (p.row_base - (jlo[q] + j)) & p.row_mask;
+							const int row = ring_row(p.row_base, p.row_mask, jlo[q] + j);
 							v = *reinterpret_cast<const float4 *>(p.src + (size_t)row * p.n + col);
 						}
 						acc[q].x = det_op<DET>(acc[q].x, m0 ? v.x : ident);
@@ -195,7 +194,7 @@ void k_view(const ViewParams p)
 /* Shape -> form and launch geometry.  The form is a function of (n_cols, width) alone. */
 int launch_view(struct fosphor *self, hipStream_t st, ViewParams p, int detector, bool line)
 {
-	long long *forms = fosphor_amd_priv_view_forms(self);
+	long long *forms = fosphor_amd_priv_counters(self, FOSPHOR_COUNTERS_VIEW);
 	const long long span = ((long long)p.n_cols + p.width - 1) / p.width;	/* longest column span, cells (1 when magnifying) */
 
 	p.ppt = p.n_cols <= p.width ? kTileCols : (int)(((long long)kTileCols * p.width) / p.n_cols);
@@ -224,13 +223,8 @@ int launch_view(struct fosphor *self, hipStream_t st, ViewParams p, int detector
 		if (line) hipLaunchKernelGGL((k_view<FOSPHOR_AMD_DET_AVERAGE, true>), grid, block, lds, st, p);
 		else      hipLaunchKernelGGL((k_view<FOSPHOR_AMD_DET_AVERAGE, false>), grid, block, lds, st, p);
 	}
-	if (hipGetLastError() != hipSuccess)
-		return -EIO;
-	if (line)
-		forms[FOSPHOR_AMD_VIEW_LINES]++;
-	else
-		forms[p.wide ? FOSPHOR_AMD_VIEW_WIDE : (p.tlog ? FOSPHOR_AMD_VIEW_TILED_LANES : FOSPHOR_AMD_VIEW_TILED)]++;
-	return 0;
+	return launch_counted(forms, line ? FOSPHOR_AMD_VIEW_LINES
+	                                  : p.wide ? FOSPHOR_AMD_VIEW_WIDE : (p.tlog ? FOSPHOR_AMD_VIEW_TILED_LANES : FOSPHOR_AMD_VIEW_TILED));
 }
 
 bool color_ok(const struct fosphor_amd_view_color &c)
@@ -280,7 +274,7 @@ extern "C" int fosphor_amd_view_from_render(int fft_len, int wf_rows, const stru
 
 extern "C" int fosphor_amd_view_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_VIEW_STATS])
 {
-	return fosphor_amd_priv_copy_stats(self, fosphor_amd_priv_view_forms, FOSPHOR_AMD_VIEW_STATS, stats);
+	return fosphor_amd_priv_copy_stats(self, FOSPHOR_COUNTERS_VIEW, FOSPHOR_AMD_VIEW_STATS, stats);
 }
 
 extern "C" int fosphor_amd_view(struct fosphor *self, const struct fosphor_amd_view *v, const struct fosphor_amd_view_out *out)
@@ -300,14 +294,11 @@ extern "C" int fosphor_amd_view(struct fosphor *self, const struct fosphor_amd_v
 		return -EINVAL;
 	if ((out->d_waterfall_rgba && !color_ok(out->wf_color)) || (out->d_histogram_rgba && !color_ok(out->histo_color)))
 		return -EINVAL;
-	if (fosphor_amd_finish(self) < 0)			/* like fosphor_amd_colorize: wait for the compute side */
+	if (open(self, &b))
 		return -EIO;
-	if (fosphor_amd_get_buffers_nohc(self, &b))		/* after the wait: the waterfall is one of two rings */
-		return -EIO;
-	if (b.fft_len < 4 || b.fft_len > 65536 || (b.fft_len & (b.fft_len - 1)) || (b.wf_rows & (b.wf_rows - 1)))
-		return -EINVAL;					/* what span_cols and the ring mask rely on */
-	if (v->first_bin < 0 || v->first_bin >= b.fft_len || v->n_cols < 1 || v->n_cols > b.fft_len - v->first_bin ||
-	    v->width < 1 || v->width > 65536 ||
+	if (!geometry_ok(b, 4))					/* what span_cols and the ring mask rely on */
+		return -EINVAL;
+	if (!window_ok(v->first_bin, v->n_cols, b.fft_len) || v->width < 1 || v->width > 65536 ||
 	    v->wf_src_rows < 1 || v->wf_src_rows > b.wf_rows || v->wf_out_rows < 1 || v->wf_out_rows > b.wf_rows)
 		return -EINVAL;
 	st = (hipStream_t)fosphor_amd_stream(self);
@@ -320,8 +311,8 @@ extern "C" int fosphor_amd_view(struct fosphor *self, const struct fosphor_amd_v
 		p.src = b.d_waterfall;
 		p.dst_f = out->d_waterfall; p.dst_rgba = out->d_waterfall_rgba;
 		p.src_rows = v->wf_src_rows; p.out_rows = v->wf_out_rows;
-		p.row_base = b.waterfall_pos - 1 + b.wf_rows;	/* kept non-negative before the mask */
-		p.row_mask = b.wf_rows - 1;
+		const Rows ring = waterfall_rows(b);
+		p.row_base = ring.base; p.row_mask = ring.mask;
 		if (p.dst_rgba && (rv = fosphor_cmap_stage(self, FOSPHOR_AMD_IMG_WATERFALL, c.palette, c.n, c.use_defaults,
 		                                           c.scale, c.offset, 0, &p.lut)))
 			return rv;
@@ -333,8 +324,8 @@ extern "C" int fosphor_amd_view(struct fosphor *self, const struct fosphor_amd_v
 		p.src = b.d_histogram;
 		p.dst_f = out->d_histogram; p.dst_rgba = out->d_histogram_rgba;
 		p.src_rows = p.out_rows = b.n_bins;		/* never resampled */
-		p.row_base = b.n_bins - 1;
-		p.row_mask = 0x7fffffff;
+		const Rows bins = histogram_rows(b);
+		p.row_base = bins.base; p.row_mask = bins.mask;
 		if (p.dst_rgba && (rv = fosphor_cmap_stage(self, FOSPHOR_AMD_IMG_HISTOGRAM, c.palette, c.n, c.use_defaults,
 		                                           c.scale, c.offset, 1, &p.lut)))
 			return rv;
@@ -356,5 +347,5 @@ extern "C" int fosphor_amd_view(struct fosphor *self, const struct fosphor_amd_v
 		if ((rv = launch_view(self, st, p, v->detector, true)))
 			return rv;
 	}
-	return hipStreamSynchronize(st) == hipSuccess ? 0 : -EIO;
+	return drain(st, 0);
 }
