@@ -1,0 +1,698 @@
+"""The burst-IQ passes at the sizes their interface is built for: the input sets tests/test_job_scale_cpu.py,
+tests/test_gpu_job_scale.py and tests/test_gpu_job_far.py share, one view of the five passes over them, and the geometry of the far
+buffer.
+
+A case here is a Case: the pass, its jobs and the host copies of its buffers.  The five models stay what they are
+(tests/extract_model.py, resample_model.py, measure_model.py, demod_model.py, correlate_model.py); this file only names, per pass,
+the job field that places the input, the width of an output element, the stats a call must leave and the comparison the pass's
+contract allows: bit for bit where the contract pins the order of the operations (resample, demod, correlate), inside
+measure_model.job_tolerance and extract_model.bound where it leaves the order open.
+
+The long cases
+  measure    130 * CHUNK + 5 samples: k_measure_combine folds 64 partials a round, so three rounds.  Plants (LONG_MEASURE_PLANTS)
+             relative to the job's sample 0.
+  correlate  130 * TILE + 5 lags: k_correlate_combine gives lane l the tiles l, l + 64, l + 128.  An edges pattern with runs over
+             the seams 63|64 and 127|128, and a tie of bit-identical windows in tiles 3, 67 and 70 -- tile 67 is lane 3's second
+             tile, so the tie is met inside a lane in a later round as well as between lanes -- and, in a second job that begins
+             behind the first window, in tiles 64, 66 and 128: all beyond the first round, 64 and 128 in lane 0.
+  resample   U = 256 and an input of 2^24 + 64 samples of which only the tail is read: positions p = phase0 + m D of the up-sampled
+             rate around (n - Q) U, just beyond 2^32.
+The full tables: exactly MAX_JOBS jobs of tiny shapes in shuffled order, every 11th without work.
+The far buffer: FAR_SAMPLES float2 samples, about 16.01 GiB; bases and their aliases below.
+
+What these cases are aimed at: every expression of the kernels that forms an address or a position from offset, first, out_offset,
+tpl_offset, phase0, m0, k0, c or blockIdx.x, with the type it is evaluated in, as read in gr-fosphor_amd/csrc (all are 64-bit, or
+below 2^31 because the prefix gives a job no work-group beyond its n, n_out or n_lags, which are int32):
+  find_job (fosphor_jobs.h)  lo, hi, mid: int, below MAX_JOBS; prefix[] and g: uint32, at most 2^31 - 1 work-groups a launch
+  k_extract_tile    m0 = (int)(blockIdx.x - prefix[j]) * 256: int, < n_out.  base = (int64_t)m0 * D: int64.
+                    src = (elem *)x + first + base: pointer + int64 + int64.  phi0 = phase0 + (uint32_t)(uint64_t)base * phase_inc
+                    and phi0 + (uint32_t)i * inc: uint32 on purpose, the phase is taken mod 2^32.  span, head + g * per,
+                    tail0 + tid, r * R + q: int / uint32, below D * R <= 6656.  out[out_offset + m0 + tid]: int64 + int + int.
+  k_extract_wave    m = (int64_t)(blockIdx.x - prefix[j]) * 4 + wave, n0 = m * decim: int64.  src = x + first + n0: pointer +
+                    int64 + int64; src + k: k < T <= 8192.  phi0: uint32 as above.  out[out_offset + m]: int64.
+  k_resample_tile   m0 = (int)(..) * 512: int, < n_out.  p0 = phase0 + (int64_t)m0 * D, b0 = (p0 + U - 1) / U: int64.
+                    s0 = (int)(b0 * U - p0): an int64 difference in 0 .. U - 1.  iq + offset + b0: pointer + int64 + int64.
+                    span, pos = k * D - s0, db, db * U - pos: int, below 512 * 256 + 256.  out + out_offset + m0: pointer + int64.
+  k_resample_direct m = (int64_t)(..) * 256 + threadIdx.x, pos = phase0 + m * down, b: int64.  iq + offset + b: pointer + int64.
+                    taps + taps_offset + (int)(b * U - pos): an int64 difference below U.  out[out_offset + m]: int64.
+  k_measure_wave    j = blockIdx.x * 4 + wave: int, below MAX_JOBS.  iq + offset: pointer + int64.  scan(): m, m0 + 2 g: int, < n.
+  k_measure_split   c = (int)(blockIdx.x - prefix[j]), m0 = c * 8192: int, < n.  m1 = min(n - m0, 8192) + m0: int, <= n, written so
+                    that nothing passes n.  parts + part0 + c: pointer + int + int, each below the launch's 2^31 - 1 work-groups.
+  k_measure_combine parts + part0 + c0 + lane: pointer + int, c0 + lane < chunks.  records + record: below MAX_JOBS.
+  k_demod_direct    t0 = c * 2048: int, < n_out.  iq + offset + t0, out + out_offset + t0: pointer + int64 + int.
+  k_demod_avg       o0 = c * (2048 / L): int, < n_out.  iq + offset + (int64_t)o0 * L: int64 (o0 * L < n all the same).
+                    out + out_offset + o0: pointer + int64 + int.  row * stride + ..: int, below 3072.
+  k_correlate_tile  k0 = c * 1024: int, < n_lags.  iq + offset + k0, tpl + tpl_offset: pointer + int64 (+ int).
+                    out[out_offset + k0 + q]: int64 + int + int.  out + out_offset + 2 * (int64_t)k0: int64.
+                    parts + blockIdx.x: pointer + uint32.
+  k_correlate_combine  parts + prefix[j]: pointer + uint32; parts[c], parts[c - 1], parts[best_tile]: int, < tiles.
+                    records + j: below MAX_JOBS.  tpl + tpl_offset: pointer + int64.
+None is a 32-bit product or sum that can pass 2^31: nothing to fix."""
+import functools
+
+import numpy as np
+
+import correlate_model as cm
+import demod_model as dm
+import extract_model as em
+import measure_model as mm
+import resample_model as rm
+
+SENTINEL = 0x5a5a5a5a
+PASSES = ("extract", "resample", "measure", "demod", "correlate")
+MODELS = {"extract": em, "resample": rm, "measure": mm, "demod": dm, "correlate": cm}
+MAX_JOBS = 4096
+GUARD = 3						# every model's: output elements before, between and behind the jobs' ranges
+
+
+class Case:
+    """name: the pass; jobs; iq: float32 [n][2], or int16 / float16 [n][2] with fmt; taps: float32 (extract, resample); tpl:
+    float32 [n][2] or None where the templates lie in iq (correlate)"""
+
+    def __init__(self, name, jobs, iq, taps=None, tpl=None, fmt=em.FP32):
+        self.name, self.jobs, self.fmt = name, np.ascontiguousarray(jobs, MODELS[name].JOB_DTYPE), fmt
+        self.iq = np.ascontiguousarray(iq, em.RAW_DTYPE[fmt]).reshape(-1, 2)
+        self.taps = None if taps is None else np.ascontiguousarray(taps, np.float32)
+        self.tpl = None if tpl is None else np.ascontiguousarray(tpl, np.float32).reshape(-1, 2)
+
+    def with_jobs(self, jobs):
+        return Case(self.name, jobs, self.iq, self.taps, self.tpl, self.fmt)
+
+    def model_case(self):
+        """the case as its model's functions take it"""
+        return {"extract": (self.fmt, self.iq, self.jobs, self.taps), "resample": (self.iq, self.taps, self.jobs),
+                "measure": (self.iq, self.jobs), "demod": (self.iq, self.jobs), "correlate": (self.iq, self.tpl, self.jobs)}[self.name]
+
+
+def from_model(name, case):
+    """a case of one of the models' cases() as a Case"""
+    if name == "extract":
+        fmt, raw, jobs, taps = case
+        return Case(name, jobs, raw, taps=taps, fmt=fmt)
+    if name == "resample":
+        return Case(name, case[2], case[0], taps=case[1])
+    if name == "correlate":
+        return Case(name, case[2], case[0], tpl=case[1])
+    return Case(name, case[1], case[0])
+
+
+# ---- one view of the five passes --------------------------------------------------------------------------------------------------
+
+IN_FIELD = {"extract": "first", "resample": "offset", "measure": "offset", "demod": "offset", "correlate": "offset"}
+OUT_WORDS = {"extract": 2, "resample": 2, "measure": 0, "demod": 1, "correlate": 1}	# 32-bit words of an out_offset unit
+
+
+def sample_bytes(case):
+    return 8 if case.fmt == em.FP32 else 4
+
+
+def n_out(name, job):
+    """the output elements of a job, in units of its out_offset"""
+    if name in ("extract", "resample"):
+        return int(job["n_out"])
+    if name == "demod":
+        return dm.n_out(int(job["mode"]), int(job["n"]), int(job["avg"]))
+    if name == "correlate":
+        return cm.n_out(int(job["trace"]), int(job["n"]), int(job["tpl_len"]))
+    return 0
+
+
+def has_out(name, job):
+    """does out_offset of the job mean anything?  A correlate job without a trace must leave it 0"""
+    return name != "measure" and not (name == "correlate" and int(job["trace"]) == cm.NONE)
+
+
+def capacity(name, jobs):
+    """output elements of a case's buffer: the last one written and GUARD behind it"""
+    return max([int(j["out_offset"]) + n_out(name, j) for j in jobs if has_out(name, j)] + [0]) + GUARD
+
+
+def in_span(name, job):
+    """[begin, end) of the input samples a job may read"""
+    if name == "extract":
+        return int(job["first"]), int(job["first"]) + em.need(int(job["n_out"]), int(job["decim"]), int(job["n_taps"]))
+    return int(job["offset"]), int(job["offset"]) + int(job["n"])
+
+
+def out_ranges(name, jobs):
+    """[begin, end) of the output elements of the jobs that write some"""
+    return [(int(j["out_offset"]), int(j["out_offset"]) + n_out(name, j)) for j in jobs if has_out(name, j) and n_out(name, j)]
+
+
+def disjoint(ranges):
+    ranges = sorted(ranges)
+    return all(a[1] <= b[0] for a, b in zip(ranges, ranges[1:]))
+
+
+def forms(name, jobs):
+    """the kernel form of every job, as the pass's stats name it"""
+    if name == "extract":
+        return [em.form(int(j["decim"]), int(j["n_taps"])) for j in jobs]
+    if name == "resample":
+        return [rm.form(int(j["up"]), int(j["down"]), int(j["n_taps"])) for j in jobs]
+    if name == "measure":
+        return ["wave" if mm.form(int(j["n"])) == mm.FORM_WAVE else "split" for j in jobs]
+    if name == "demod":
+        return ["direct" if j["avg"] == 1 else "avg" for j in jobs]
+    return ["tile"] * len(jobs)
+
+
+def expected_stats(name, jobs):
+    """the stats delta one successful call leaves: the forms that ran, and what they were given"""
+    f = np.array(forms(name, jobs))
+    if name == "resample":
+        return rm.expected_stats(jobs)
+    if name == "extract":
+        live = jobs["n_out"] > 0
+        return dict(calls=1, k_tile=int((f[live] == "tile").any()), k_wave=int((f[live] == "wave").any()),
+                    jobs_tile=int((f == "tile").sum()), jobs_wave=int((f == "wave").sum()),
+                    samples=sum(em.need(int(j["n_out"]), int(j["decim"]), int(j["n_taps"])) for j in jobs[live]))
+    if name == "measure":
+        split = f == "split"
+        return dict(calls=1, k_wave=int((~split).any()), k_split=int(split.any()), k_combine=int(split.any()),
+                    jobs_wave=int((~split).sum()), jobs_split=int(split.sum()), samples=int(jobs["n"].astype(np.int64).sum()))
+    if name == "demod":
+        outs = np.array([n_out(name, j) for j in jobs])
+        direct = f == "direct"
+        return dict(calls=1, k_direct=int((direct & (outs > 0)).any()), k_avg=int((~direct & (outs > 0)).any()),
+                    jobs_direct=int(direct.sum()), jobs_avg=int((~direct).sum()), samples=int(jobs["n"].astype(np.int64).sum()),
+                    outputs=int(outs.sum()))
+    lags = [cm.n_lags(int(j["n"]), int(j["tpl_len"])) for j in jobs]
+    return dict(calls=1, k_tile=int(any(lags)), k_combine=1, jobs=len(jobs), lags=sum(lags), macs=cm.macs(jobs))
+
+
+class Model:
+    """what the model says of a case, computed once: records (measure, correlate), the image of the output buffer as uint32 words
+    with SENTINEL wherever no job writes (resample, demod, correlate), or the float64 outputs and bounds per job (extract)"""
+
+    def __init__(self, case):
+        name, jobs = case.name, case.jobs
+        self.case, self.records, self.image, self.tols, self.outs = case, None, None, None, None
+        if name == "measure":
+            self.records = mm.measure(case.iq, jobs)
+            self.tols = [mm.job_tolerance(case.iq, j) for j in jobs]
+        elif name == "demod":
+            self.image = dm.image(case.iq, jobs, SENTINEL)
+        elif name == "resample":
+            self.image = rm.image(case.model_case(), SENTINEL)
+        elif name == "correlate":
+            self.records, self.image = cm.image(case.model_case(), SENTINEL)
+        else:
+            x = em.widen(case.iq, case.fmt)
+            self.outs = [em.extract_job(x, j, case.taps) for j in jobs]
+            self.tols = [em.bound(x, j, case.taps) for j in jobs]
+
+    def check(self, rec, words, tag=""):
+        """rec: the records as the pass left them, or None; words: the whole output buffer as uint32 [OUT_WORDS * capacity]"""
+        name, jobs = self.case.name, self.case.jobs
+        if name == "measure":
+            mm.assert_records(rec, self.records, self.tols, tag)
+            return
+        assert len(words) == OUT_WORDS[name] * capacity(name, jobs), tag
+        if name == "correlate":
+            bad = [i for i in range(len(jobs)) if rec[i].tobytes() != self.records[i].tobytes()]
+            assert not bad, (tag, "records differ from the model's", bad[:4], rec[bad[:2]], self.records[bad[:2]])
+        if name != "extract":
+            bad = np.flatnonzero(words != self.image)
+            assert not len(bad), (tag, "words differ from the model's image", bad[:8], words[bad[:8]], self.image[bad[:8]])
+            return
+        out = words.reshape(-1, 2)
+        written = np.zeros(len(out), bool)
+        for j, want, tol in zip(jobs, self.outs, self.tols):
+            sl = slice(int(j["out_offset"]), int(j["out_offset"]) + int(j["n_out"]))
+            written[sl] = True
+            if j["n_out"]:
+                y = out[sl].view(np.float32).astype(np.float64)
+                err = max(np.abs(y[:, 0] - want.real).max(), np.abs(y[:, 1] - want.imag).max())
+                assert err <= tol, (tag, tuple(j), err, tol)
+        assert np.all(out[~written] == SENTINEL), (tag, "written outside the jobs' ranges")
+
+
+@functools.lru_cache(maxsize=None)
+def model_of(key):
+    """the Model of the case CASES[key]() builds; both computed once"""
+    return Model(case_of(key))
+
+
+@functools.lru_cache(maxsize=None)
+def case_of(key):
+    return CASES[key]()
+
+
+def host_twin(F, case):
+    """the case through fosphor_amd_*_host -> (records or None, the output buffer as uint32 words or None), laid out as a device
+    run lays them out but for the words no job writes.  extract's host function is a float64 statement, no twin: not here."""
+    name, jobs = case.name, case.jobs
+    if name == "measure":
+        return F.measure_host(case.iq, jobs), None
+    words = np.full(OUT_WORDS[name] * capacity(name, jobs), SENTINEL, np.uint32)
+    rec = None
+    if name == "demod":
+        views = F.demod_host(case.iq, jobs)
+    elif name == "resample":
+        views = F.resample_host(case.iq, jobs, case.taps)
+    else:
+        rec, views = F.correlate_host(case.iq, jobs, case.iq if case.tpl is None else case.tpl)
+    for j, v in zip(jobs, views):
+        if v is not None and v.size:
+            w = np.ascontiguousarray(v).view(np.uint32).reshape(-1)
+            at = OUT_WORDS[name] * int(j["out_offset"])
+            words[at:at + len(w)] = w
+    return rec, words
+
+
+# ---- the long cases -----------------------------------------------------------------------------------------------------------------
+
+LONG_PARTS = 130
+LONG_MEASURE_N = LONG_PARTS * mm.CHUNK + 5
+LONG_MEASURE_CUT = 64 * mm.CHUNK
+LONG_MEASURE_THRESHOLD = 0.5
+# name -> (first sample, last sample, is it the maximum?), relative to the job's sample 0
+LONG_MEASURE_PLANTS = {
+    "top in part 5": (5 * mm.CHUNK + 100, 5 * mm.CHUNK + 100, True),
+    "run over the round boundary": (64 * mm.CHUNK - 3, 64 * mm.CHUNK + 2, False),
+    "top in part 70": (70 * mm.CHUNK + 17, 70 * mm.CHUNK + 17, True),
+    "rising edge at a part's first sample": (128 * mm.CHUNK, 128 * mm.CHUNK + 8, False),
+    "top in part 129": (129 * mm.CHUNK + 40, 129 * mm.CHUNK + 40, True),
+    "the last sample": (LONG_MEASURE_N - 1, LONG_MEASURE_N - 1, False),
+}
+
+
+def long_measure_case():
+    """quiet noise (p around 2e-4) with LONG_MEASURE_PLANTS, twice: from sample 1 and from an even sample.  The jobs: the whole at
+    the odd and at the even offset; exactly 64 parts, one sample more, 65 parts; and what is left of the whole behind
+    LONG_MEASURE_CUT, which with the job of 64 parts is the whole cut in two."""
+    rng = np.random.default_rng(6464)
+    n, cut, thr = LONG_MEASURE_N, LONG_MEASURE_CUT, LONG_MEASURE_THRESHOLD
+    base = (rng.standard_normal((n, 2)) * 0.01).astype(np.float32)
+    big, top = np.float32([0.75, -0.5]), np.float32([1.5, 0.25])
+    for first, last, is_top in LONG_MEASURE_PLANTS.values():
+        base[first:last + 1] = top if is_top else big
+    even = n + 3 + ((n + 3) & 1)
+    iq = np.zeros((even + n, 2), np.float32)
+    iq[1:1 + n] = base
+    iq[even:even + n] = base
+    rows = [(1, n, thr), (even, n, thr), (1, cut, thr), (even, cut + 1, thr), (1, 65 * mm.CHUNK, thr), (1 + cut, n - cut, thr)]
+    return Case("measure", mm.make_jobs(rows), iq)
+
+
+def assert_long_measure_cut(case, rec, tol):
+    """the cut rule over the records of long_measure_case(): the whole against the two jobs it is cut into at LONG_MEASURE_CUT, as
+    tests/test_measure_cpu.py cuts -- the edge at the cut counted once, r1 after the one term at the cut is put back.  tol: the
+    whole job's mm.job_tolerance"""
+    cut, n, thr = LONG_MEASURE_CUT, LONG_MEASURE_N, np.float32(LONG_MEASURE_THRESHOLD)
+    w, a, b = rec[0], rec[2], rec[5]
+    assert (a["n"], b["n"]) == (cut, n - cut)
+    y = case.iq[1:1 + n]
+    p = mm.power(y[cut - 1:cut + 1])
+    both = bool(p[0] >= thr) and bool(p[1] >= thr)
+    assert both, "the cut lies inside a run"
+    assert w["n_above"] == a["n_above"] + b["n_above"] and w["n_edges"] == a["n_edges"] + b["n_edges"] - int(both)
+    y = y[cut - 1:cut + 1].astype(np.float64)
+    at = {"r1_re": y[1, 0] * y[0, 0] + y[1, 1] * y[0, 1], "r1_im": y[1, 1] * y[0, 0] - y[1, 0] * y[0, 1]}
+    for k in mm.SUMS:
+        assert abs(float(w[k]) - (float(a[k]) + float(b[k]) + at.get(k, 0.0))) <= tol[k], k
+
+
+LONG_TILES = 130
+LONG_LAGS =LONG_TILES * cm.TILE + 5
+
+
+def long_edges_pattern():
+    """which of LONG_LAGS lags are above, for T = 1: cm.edges_pattern()'s kinds at the seams a later round of the combine settles"""
+    T = cm.TILE
+    on = np.zeros(LONG_LAGS, bool)
+    on[0] = True
+    on[5:9] = True
+    on[3 * T] = True						# a tile ends below, the next begins above
+    on[64 * T - 1:64 * T + 1] = True				# one edge over the seam 63|64: lane 0's second tile
+    on[65 * T - 1] = True					# tile 64 ends above, tile 65 begins below
+    on[128 * T - 2:128 * T + 3] = True				# one edge over the seam 127|128: lane 0's third tile
+    on[129 * T] = True						# tile 128 ends below, tile 129 begins above
+    on[LONG_LAGS - 3:] = True					# up to the last lag
+    rng = np.random.default_rng(41)
+    for tile in (1, 100):
+        on[tile * T + 50:(tile + 1) * T - 50] = rng.random(T - 100) < 0.3
+    return on
+
+
+def long_edges_case():
+    """T = 1 with the template (1, 0), as cm.edges_case(): `above` is long_edges_pattern() at the threshold 0.5.  All three traces;
+    the C job begins one sample in, so its seams cut the pattern one lag earlier."""
+    on = long_edges_pattern()
+    iq = cm.noise(len(on), 40)
+    iq[~on] = 0.0
+    tpl = np.array([(1.0, 0.0), (0.6, -0.8)], np.float32)
+    n = len(on)
+    rows = [(0, 0, n, 1, cm.RHO, 0.5), (0, 0, n, 1, cm.NONE, 0.5), (1, 0, n - 1, 1, cm.C, 0.5)]
+    return Case("correlate", cm.place(rows), iq, tpl=tpl)
+
+
+TIE_T = 48
+TIE_LAGS = tuple(t * cm.TILE + k for t, k in ((3, 100), (67, 333), (70, 137), (131, 277)))	# where the window lies in iq
+TIE_SECOND = 3 * cm.TILE + 200				# the second job's first sample: behind the first window's first sample
+TIE_SECOND_LAGS = 128 * cm.TILE + 300
+
+
+def long_tie_case():
+    """cm.tie_case() extended: the template is iq[TIE_LAGS[0] ..] itself and the same T samples lie at the other TIE_LAGS, so rho
+    is the same float at those lags and the largest of all; the smallest lag wins.  Job 0 (rho trace) and job 1 (no trace) have
+    LONG_LAGS lags and see the windows in tiles 3, 67 and 70; job 2 (C trace) begins at TIE_SECOND and sees those of tiles 67, 70
+    and the fourth in its tiles 64, 66 and 128."""
+    total = TIE_SECOND + TIE_SECOND_LAGS + TIE_T - 1
+    iq = cm.noise(total, 30)
+    for at in TIE_LAGS[1:]:
+        iq[at:at + TIE_T] = iq[TIE_LAGS[0]:TIE_LAGS[0] + TIE_T]
+    n = LONG_LAGS + TIE_T - 1
+    rows = [(0, TIE_LAGS[0], n, TIE_T, cm.RHO, 0.5), (0, TIE_LAGS[0], n, TIE_T, cm.NONE, 0.5),
+            (TIE_SECOND, TIE_LAGS[0], TIE_SECOND_LAGS + TIE_T - 1, TIE_T, cm.C, 0.5)]
+    return Case("correlate", cm.place(rows), iq)
+
+
+RS_N = 2 ** 24 + 64					# input samples of the long resample case
+RS_UP = 256
+RS_TAIL = 4096						# the samples that are not zero: the last ones
+RS_TILE = (255, 2)					# (D, Q) of the TILE form
+RS_DIRECT = (251, rm.seam_of(RS_UP, down=251) + 1)	# of the DIRECT form: with U = 256 the form is DIRECT from this Q on, whatever D
+
+
+def rs_rows():
+    """(phase0, n_out, D, Q, taps_offset) of the long resample jobs: per form, the outputs that end at (n - Q) U exactly for
+    k = 1, 2, 40, the one output at (n - Q) U, and a job of 570 outputs whose second TILE tile begins beyond 2^32 while its first
+    begins below"""
+    rows, at = [], 1
+    for D, Q in (RS_TILE, RS_DIRECT):
+        room = (RS_N - Q) * RS_UP
+        for k in (1, 2, 40):
+            rows.append((room - 3 * D * k, 3 * k + 1, D, Q, at))
+        rows.append((room, 1, D, Q, at))
+        rows.append((room - 569 * D, 570, D, Q, at))
+        at += Q * RS_UP + 3
+    return rows
+
+
+def long_resample_case():
+    """U = 256 over RS_N samples of which the last RS_TAIL are noise and the rest zero; the jobs of rs_rows(), offset 0 and the
+    whole buffer each"""
+    iq = np.zeros((RS_N, 2), np.float32)
+    iq[RS_N - RS_TAIL:] = rm.noise(RS_TAIL, 90)
+    rows = [(0, ph, RS_N, n_out, RS_UP, D, toff, Q * RS_UP) for ph, n_out, D, Q, toff in rs_rows()]
+    taps = rm.some_taps(1 + (RS_TILE[1] + RS_DIRECT[1]) * RS_UP + 6, 91)
+    return Case("resample", rm.place(rows), iq, taps=taps)
+
+
+# ---- the full tables ----------------------------------------------------------------------------------------------------------------
+
+def shuffled(jobs, seed):
+    """the jobs in another order: their outputs are then out of order"""
+    return jobs[np.random.default_rng(seed).permutation(len(jobs))]
+
+
+def full_extract_case():
+    """MAX_JOBS sc16 jobs: TILE (2, 9) and (3, 25), WAVE (32, 70), up to 12 and 5 outputs; every 11th writes nothing"""
+    rng = np.random.default_rng(4096)
+    shapes = [(2, 9), (32, 70), (3, 25)]
+    taps, where = em.one_tap_set(rng, shapes)
+    n, rows = 3000, []
+    for i in range(MAX_JOBS):
+        d, t = shapes[i % 3]
+        k = 0 if i % 11 == 0 else int(rng.integers(1, 6 if em.form(d, t) == "wave" else 13))
+        rows.append((int(rng.integers(0, n - em.need(k, d, t) + 1)), k, d, int(rng.integers(0, 1 << 32)), int(rng.integers(0, 1 << 32)),
+                     where[(d, t)], t))
+    return Case("extract", shuffled(em.make_jobs(rows), 1), em.stream(em.SC16, n, 4097), taps=taps, fmt=em.SC16)
+
+
+def full_resample_case():
+    """MAX_JOBS jobs of rm.COUNT_FORMS -- TILE (3, 2, 4) and DIRECT (1, 16, 5) -- up to 12 outputs; every 11th writes nothing"""
+    rng = np.random.default_rng(4098)
+    total, rows = 3000, []
+    for i in range(MAX_JOBS):
+        U, D, Q = rm.COUNT_FORMS[i % 2]
+        k = 0 if i % 11 == 0 else int(rng.integers(1, 13))
+        ph = int(rng.integers(0, 3 * U))
+        n = rm.need(U, D, Q, ph, k) + int(rng.integers(0, 3))
+        rows.append((int(rng.integers(0, total - n + 1)), ph, n, k, U, D, int(rng.integers(0, 4)), Q * U))
+    return Case("resample", shuffled(rm.place(rows), 2), rm.noise(total, 4099), taps=rm.some_taps(64, 4100))
+
+
+def full_measure_case():
+    """MAX_JOBS jobs: up to 120 samples (WAVE), every 64th a few samples more than WAVE_MAX (SPLIT, one chunk) and every 11th none"""
+    rng = np.random.default_rng(4101)
+    total, rows = mm.WAVE_MAX + 1500, []
+    for i in range(MAX_JOBS):
+        n = 0 if i % 11 == 0 else mm.WAVE_MAX + 1 + int(rng.integers(0, 100)) if i % 64 == 5 else int(rng.integers(1, 121))
+        rows.append((int(rng.integers(0, total - n + 1)), n, 0.3))
+    return Case("measure", shuffled(mm.make_jobs(rows), 3), mm.bursty(total, 4102))
+
+
+def full_demod_case():
+    """MAX_JOBS jobs of all modes, L = 1 (DIRECT) and 2, 3, 7 (AVG), up to 40 samples; every 11th has none"""
+    rng = np.random.default_rng(4103)
+    total, rows = 3000, []
+    for i in range(MAX_JOBS):
+        n = 0 if i % 11 == 0 else int(rng.integers(1, 41))
+        rows.append((int(rng.integers(0, total - n + 1)), n, i % 3, (1, 2, 1, 3, 7)[i % 5]))
+    return Case("demod", shuffled(dm.place(rows), 4), dm.noise(total, 4104))
+
+
+def full_correlate_case():
+    """MAX_JOBS jobs of all traces, T = 1, 2, 7, 16, up to 30 lags; every 11th has too few samples for a lag"""
+    rng = np.random.default_rng(4105)
+    total, rows = 3000, []
+    for i in range(MAX_JOBS):
+        T = (1, 2, 7, 16)[i % 4]
+        n = (T - 1) * (i & 1) if i % 11 == 0 else T - 1 + int(rng.integers(1, 31))
+        rows.append((int(rng.integers(0, total - n + 1)), int(rng.integers(0, 40 - T + 1)), n, T, i % 3, 1.5 / T))
+    jobs = cm.place(rows)
+    odd = (jobs["trace"] == cm.C) & (jobs["out_offset"] & 1 != 0)
+    jobs["out_offset"][odd] -= 1				# GUARD keeps the ranges apart all the same
+    return Case("correlate", shuffled(jobs, 5), cm.noise(total, 4106), tpl=cm.noise(40, 4107))
+
+
+FULL = {"extract": full_extract_case, "resample": full_resample_case, "measure": full_measure_case, "demod": full_demod_case,
+        "correlate": full_correlate_case}
+
+
+def one_job_of(case):
+    """the first job of a full table that has work, alone: the small call before and behind the full one"""
+    name = case.name
+    work = [i for i, j in enumerate(case.jobs) if (int(j["n"]) if name == "measure" else n_out(name, j)) > 0]
+    return case.with_jobs(case.jobs[work[0]:work[0] + 1])
+
+
+# ---- the relocation cases and the far buffer ------------------------------------------------------------------------------------------
+
+FAR_SAMPLES = 2 ** 31 + 2 ** 20				# float2 samples of the far buffer
+FAR_BYTES = 8 * FAR_SAMPLES
+FAR_FREE_NEEDED = 20 * 2 ** 30
+FAR_GUARD = 4096					# sentinel elements either side of a far output range
+BASES_FP32 = (2 ** 29 + 16, 2 ** 31 + 16)		# in float2 samples: byte offset beyond 2^32; sample index beyond int32
+BASES_16 = BASES_FP32 + (2 ** 32 + 32,)			# in 4-byte samples
+OUT_BASE = {2: 2 ** 31 + 16, 1: 2 ** 32 + 32}		# by OUT_WORDS: beyond 2^31 complex outputs, beyond 2^32 floats
+TPL_BASE = 2 ** 31 + 48
+
+RELOCATE = {
+    "extract n_out_seams": lambda: from_model("extract", em.cases()["n_out_seams"]),
+    "extract first1_fp32": lambda: from_model("extract", em.cases()["first1_fp32"]),
+    "extract first3_fp16": lambda: from_model("extract", em.cases()["first3_fp16"]),
+    "extract first5_sc16": lambda: from_model("extract", em.cases()["first5_sc16"]),
+    "resample counts": lambda: from_model("resample", rm.counts_case()),
+    "demod seams": lambda: from_model("demod", dm.seams_case()),
+    "correlate lag_counts": lambda: from_model("correlate", cm.lag_counts_case()),
+    "measure split_n": lambda: from_model("measure", mm.split_n_case()),
+    "measure planted": lambda: from_model("measure", mm.planted_case()),
+}
+
+
+def bases_of(case):
+    return BASES_FP32 if sample_bytes(case) == 8 else BASES_16
+
+
+def aliases(base, unit):
+    """where an element at `base` (in units of `unit` bytes) is looked for by code that truncates: the index to 32 and to 31 bits,
+    the byte offset to 32 bits -> the distinct element indices other than base itself"""
+    found = {base % 2 ** 32, base % 2 ** 31, (base * unit) % 2 ** 32 // unit}
+    return sorted(found - {base})
+
+
+def shifted(case, field, by):
+    """the case with `field` of every job (of every job that has an output, for out_offset) moved by `by`"""
+    jobs = case.jobs.copy()
+    for j in jobs:
+        if field != "out_offset" or has_out(case.name, j):
+            j[field] += by
+    return case.with_jobs(jobs)
+
+
+# ---- the long extract jobs of the far buffer --------------------------------------------------------------------------------------------
+
+HASH_MUL, HASH_HIGH, HASH_ADD = 0x2545F491, 0x3C6EF35F, 0x7F4A7C15
+
+
+def hash_words(index):
+    """the 32-bit word (an sc16 sample: re in the low half) at 4-byte index `index` of the far buffer, from int64 arithmetic that
+    numpy arrays and torch tensors perform alike: index < 2^33 and HASH_MUL < 2^30, so nothing overflows"""
+    v = (index * HASH_MUL + (index >> 31) * HASH_HIGH + HASH_ADD) & 0xffffffff	# the bits from 2^31 up count: no alias has the same word
+    v = v ^ (v >> 15)
+    return (v * 0x9E5 + (v >> 7)) & 0xffffffff
+
+
+class HashedStream:
+    """the sc16 stream of hash_words as extract_model indexes it: x[indices] -> complex128, without the 2^32 samples in memory"""
+
+    def __getitem__(self, index):
+        w = hash_words(np.asarray(index, np.int64))
+        re, im = (w & 0xffff).astype(np.uint16).view(np.int16), (w >> 16).astype(np.uint16).view(np.int16)
+        return re.astype(np.float64) * 2.0 ** -15 + 1j * (im.astype(np.float64) * 2.0 ** -15)
+
+
+def hashed_bound(job, taps):
+    """em.bound with max|x| = sqrt(2), which no sc16 sample exceeds: the stream is too long to look at"""
+    t = int(job["n_taps"])
+    h = np.asarray(taps, np.float32)[int(job["taps_offset"]):int(job["taps_offset"]) + t].astype(np.float64)
+    return (t + 16) * 2.0 ** -24 * np.abs(h).sum() * np.sqrt(2.0)
+
+
+def advanced(job, m):
+    """the job that computes outputs m .. of `job` as its outputs 0 ..: first and phase0 advanced (the cut rule of em.split_case)"""
+    out = np.array(job, em.JOB_DTYPE).copy().reshape(1)
+    d = int(job["decim"])
+    out["first"] = int(job["first"]) + m * d
+    out["phase0"] = (int(job["phase0"]) + m * d * int(job["phase_inc"])) % (1 << 32)
+    out["n_out"] = int(job["n_out"]) - m
+    return out
+
+
+WAVE_LONG = dict(decim=1024, n_taps=3, n_out=2 ** 22 + 9, first=5, phase_inc=0x1234567b, phase0=0xfffffff0)
+TILE_LONG = dict(decim=25, n_taps=33, n_out=-(-2 ** 31 // 25) + 600, first=3, phase_inc=0x0f1e2d3d, phase0=0xdeadbeef)
+
+
+def long_extract_job(spec, out_offset):
+    job = np.zeros(1, em.JOB_DTYPE)
+    for k, v in spec.items():
+        job[k] = v
+    job["out_offset"] = out_offset
+    return job
+
+
+CASES = dict(RELOCATE)
+CASES.update({"long measure": long_measure_case, "long edges": long_edges_case, "long tie": long_tie_case,
+              "long resample": long_resample_case})
+CASES.update({"full " + k: v for k, v in FULL.items()})
+
+
+# ---- driving the passes on the device (torch is imported where it is used: the CPU tests import this file too) ----------------------
+
+class Dev:
+    """an instance, torch views of its waterfall ring and spectrum, and the five passes through the C ABI by raw device pointers"""
+
+    def __init__(self, amd, wf_rows=16):
+        self.f = amd.Fosphor(n_bins=128, wf_rows=wf_rows)
+        self.n, self.wf_rows = self.f.n, wf_rows
+        assert self.f.finish() >= 0			# a new instance fills its buffers at its first wait
+
+    def views(self):
+        import torch
+        from gr_fosphor_amd.dist import wrap_device_array
+        b = self.f.buffers(False)
+        assert (b.fft_len, b.wf_rows) == (self.n, self.wf_rows)
+        self.pos = b.waterfall_pos
+        self.wf = wrap_device_array(b.d_waterfall, (self.wf_rows, self.n), torch.float32)
+        self.spec = wrap_device_array(b.d_spectrum, (2, self.n, 2), torch.float32)
+
+    def save(self):
+        import torch
+        assert self.f.finish() >= 0
+        self.views()
+        self.saved = (self.wf.view(torch.int32).clone(), self.spec.view(torch.int32).clone(), self.pos)
+        torch.cuda.synchronize()
+
+    def assert_untouched(self):
+        import torch
+        torch.cuda.synchronize()
+        self.views()
+        assert self.pos == self.saved[2], "the ring position moved"
+        assert torch.equal(self.wf.view(torch.int32), self.saved[0]), "the waterfall was written"
+        assert torch.equal(self.spec.view(torch.int32), self.saved[1]), "the spectrum lines were written"
+
+    def call(self, name, jobs, fmt, iq, n_iq, out=None, cap=0, taps=None, n_taps=0, tpl=None, n_tpl=0, rec=None, tag=""):
+        """one call that must succeed, every buffer a device pointer: the ring, the waterfall and the spectrum untouched and the
+        stats delta what the jobs predict"""
+        import torch
+        jobs = np.ascontiguousarray(jobs, MODELS[name].JOB_DTYPE)
+        self.save()
+        torch.cuda.synchronize()			# the fills and uploads run on torch's stream, the pass on the instance's
+        L, h, stats = self.f.L, self.f.h, getattr(self.f, name + "_stats")
+        before = stats()
+        if name == "extract":
+            rv = L.fosphor_amd_extract(h, iq, n_iq, fmt, jobs.ctypes.data, len(jobs), taps, n_taps, out, cap)
+        elif name == "resample":
+            rv = L.fosphor_amd_resample(h, iq, n_iq, jobs.ctypes.data, len(jobs), taps, n_taps, out, cap)
+        elif name == "measure":
+            rv = L.fosphor_amd_measure(h, iq, n_iq, jobs.ctypes.data, len(jobs), rec)
+        elif name == "demod":
+            rv = L.fosphor_amd_demod(h, iq, n_iq, jobs.ctypes.data, len(jobs), out, cap)
+        else:
+            rv = L.fosphor_amd_correlate(h, iq, n_iq, tpl, n_tpl, jobs.ctypes.data, len(jobs), rec, out, cap)
+        after = stats()
+        self.assert_untouched()
+        assert rv == 0, (tag, name, rv)
+        delta = {k: after[k] - before[k] for k in after}
+        assert delta == expected_stats(name, jobs), (tag, name, delta)
+
+    def run(self, case, tag="", iq_at=None, out_at=None, tpl_at=None):
+        """the case in sentinel-filled buffers of its own -> (records or None, the whole output buffer as uint32 words or None);
+        inputs and taps are compared with their host copies afterwards.
+        iq_at, tpl_at: (device pointer, samples there, base): the case's samples or templates lie there from `base` on already --
+        the jobs' offsets are moved by base, and the caller looks after that buffer.
+        out_at: (device pointer, capacity there, base): the outputs go there, out_offset moved by base; no words are returned."""
+        import torch
+        name, jobs = case.name, case.jobs
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int32 if a.dtype.itemsize == 4 else np.int16)).cuda()
+        held = {}
+        if iq_at is None:
+            held["iq"] = (up(case.iq if len(case.iq) else np.zeros((1, 2), case.iq.dtype)), case.iq)
+            iq, n_iq = held["iq"][0].data_ptr(), len(case.iq)
+        else:
+            iq, n_iq = iq_at[0], iq_at[1]
+            jobs = shifted(case, IN_FIELD[name], iq_at[2]).jobs
+        taps = n_taps = tpl = n_tpl = rec = d_rec = out = d_out = None
+        if case.taps is not None:
+            held["taps"] = (up(case.taps), case.taps)
+            taps, n_taps = held["taps"][0].data_ptr(), len(case.taps)
+        if name == "correlate":
+            if tpl_at is not None:
+                tpl, n_tpl = tpl_at[0], tpl_at[1]
+                jobs = shifted(case.with_jobs(jobs), "tpl_offset", tpl_at[2]).jobs
+            elif case.tpl is None:
+                tpl, n_tpl = iq, n_iq
+                if iq_at is not None:
+                    jobs = shifted(case.with_jobs(jobs), "tpl_offset", iq_at[2]).jobs
+            else:
+                held["tpl"] = (up(case.tpl), case.tpl)
+                tpl, n_tpl = held["tpl"][0].data_ptr(), len(case.tpl)
+        if name in ("measure", "correlate"):
+            words = MODELS[name].RECORD_DTYPE.itemsize // 4
+            d_rec = torch.full(((len(jobs) + 2 * GUARD) * words,), SENTINEL, dtype=torch.int32, device="cuda")
+            rec = d_rec.data_ptr() + 4 * GUARD * words
+        cap = capacity(name, jobs)
+        if out_at is not None:
+            out, cap = out_at[0], out_at[1]
+            jobs = shifted(case.with_jobs(jobs), "out_offset", out_at[2]).jobs
+        elif OUT_WORDS[name]:
+            d_out = torch.full((OUT_WORDS[name] * cap + 2,), SENTINEL, dtype=torch.int32, device="cuda")
+            out = d_out.data_ptr()
+        self.call(name, jobs, case.fmt, iq, n_iq, out=out, cap=cap, taps=taps, n_taps=n_taps or 0, tpl=tpl, n_tpl=n_tpl or 0, rec=rec,
+                  tag=tag)
+        for k, (d, host) in held.items():
+            assert d.cpu().numpy().tobytes() == host.tobytes(), (tag, "the %s buffer was written" % k)
+        got = words_out = None
+        if d_rec is not None:
+            r = d_rec.cpu().numpy().view(np.uint32).reshape(len(jobs) + 2 * GUARD, -1)
+            assert np.all(r[:GUARD] == SENTINEL) and np.all(r[-GUARD:] == SENTINEL), (tag, "written outside the records")
+            got = r[GUARD:-GUARD].copy().view(MODELS[name].RECORD_DTYPE).reshape(-1)
+        if d_out is not None:
+            w = d_out.cpu().numpy().view(np.uint32)
+            assert np.all(w[-2:] == SENTINEL), (tag, "written behind the capacity")
+            words_out = w[:-2].copy()
+        return got, words_out

@@ -1,0 +1,260 @@
+"""The passes over burst IQ far into a buffer: inputs, outputs and templates beyond byte 2^32 and beyond sample 2^31, and extract
+jobs whose positions inside the job pass 2^31 and 2^32 (the input sets and the geometry are tests/job_scale_cases.py;
+tests/test_job_scale_cpu.py holds the conditions on them).
+
+One module-scoped device buffer of 2^31 + 2^20 float2 samples, about 16.01 GiB, allocated uninitialised; the module is skipped
+only where less than 20 GiB of device memory is free, with both numbers in the reason.
+
+  relocation    a case of every pass runs near, in buffers of its own, and far: the same bytes copied into the buffer at a base
+                (a multiple of 16 samples, so every head / tail split of the loads is the one of the near run) and every job's
+                input offset moved by the base.  Decoy data lies where a truncated index or byte offset would look
+                (jc.aliases).  The far results are bit-identical to the near ones -- also for extract and measure: their kernels
+                have no atomics, and no order of their additions depends on an address beyond its low four bits -- and the near
+                ones are held to the model as everywhere.
+  far outputs   the buffer as d_out with a small input of its own: out_offset beyond 2^31 complex outputs (extract, resample) and
+                beyond 2^32 floats (demod, correlate); FAR_GUARD sentinel elements either side of the range and the same at the
+                aliases of the output offset, all checked afterwards.  One run with the buffer as correlate's d_tpl.
+  long extract  WAVE: D = 1024, T = 3 over a span of 2^32 + 8195 sc16 samples, phase0 near 2^32; exactly the samples it reads
+                are written, from a hash of the index that numpy recomputes.  TILE: D = 25, T = 33, base = m0 * D beyond 2^31,
+                input and output in disjoint regions of the buffer; the tiles at the ends and on both sides of 2^31 against the
+                model, every output word written (a sentinel count on the device), the last outputs bit-identical to a short
+                job advanced to there (the cut rule of extract_model.split_case)."""
+import os
+
+import numpy as np
+import pytest
+
+import extract_model as em
+import job_scale_cases as jc
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = jc.SENTINEL
+G = jc.FAR_GUARD
+WITH_OUTPUT = sorted(k for k in jc.RELOCATE if jc.OUT_WORDS[k.split()[0]])
+
+
+@pytest.fixture(scope="module")
+def amd():
+    from _pkg import gr_fosphor_amd
+    if not os.path.exists(gr_fosphor_amd.LIB_PATH):
+        gr_fosphor_amd.build()
+    gr_fosphor_amd.load()
+    return gr_fosphor_amd
+
+
+@pytest.fixture(scope="module")
+def dev(amd):
+    d = jc.Dev(amd)
+    yield d
+    d.f.close()
+
+
+class Far:
+    """the far buffer as 32-bit words"""
+
+    def __init__(self, torch):
+        self.torch = torch
+        self.big = torch.empty((jc.FAR_SAMPLES, 2), dtype=torch.float32, device="cuda")
+        self.words = self.big.view(torch.int32).view(-1)
+        self.ptr = self.big.data_ptr()
+        assert self.words.numel() == jc.FAR_BYTES // 4 and self.ptr % 16 == 0
+
+    def put(self, at, host):
+        """host words (uint32) to words at ..."""
+        self.words[at:at + len(host)].copy_(self.torch.from_numpy(host.view(np.int32)).cuda())
+
+    def get(self, at, n):
+        return self.words[at:at + n].cpu().numpy().view(np.uint32)
+
+    def fill(self, at, n, value=SENTINEL):
+        self.words[at:at + n].fill_(value)
+
+    def count(self, at, n, value=SENTINEL):
+        return int((self.words[at:at + n] == value).sum().item())
+
+    def hashed(self, at, n):
+        """jc.hash_words of the word indices at .. at + n, as int32"""
+        torch = self.torch
+        v = jc.hash_words(torch.arange(at, at + n, dtype=torch.int64, device="cuda"))
+        return torch.where(v >= 2 ** 31, v - 2 ** 32, v).to(torch.int32)
+
+
+@pytest.fixture(scope="module")
+def far():
+    import torch
+    free, total = torch.cuda.mem_get_info()
+    if free < jc.FAR_FREE_NEEDED:
+        pytest.skip("the far buffer takes %d bytes and wants %d free: %d of %d bytes are" % (jc.FAR_BYTES, jc.FAR_FREE_NEEDED, free, total))
+    print("device memory: %d of %d bytes free; the far buffer takes %d" % (free, total, jc.FAR_BYTES))
+    f = Far(torch)
+    yield f
+    f.words = f.big = None
+    torch.cuda.empty_cache()
+
+
+def words_of(a):
+    return np.ascontiguousarray(a).reshape(-1).view(np.uint32)
+
+
+def decoy_of(data):
+    """other samples of the same kind: the case's in reverse order with one bit of every 16 flipped"""
+    return np.ascontiguousarray(data[::-1]) ^ np.uint32(0x00100010)
+
+
+def same(a, b):
+    return all((x is None and y is None) or x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("key", sorted(jc.RELOCATE))
+def test_relocated_input(dev, far, key):
+    case, model = jc.case_of(key), jc.model_of(key)
+    near = dev.run(case, tag=key)
+    model.check(*near, tag=key)
+    unit = jc.sample_bytes(case)
+    per = unit // 4						# words of a sample
+    data = words_of(case.iq)
+    decoy = decoy_of(data)
+    assert not np.array_equal(decoy, data)
+    for base in jc.bases_of(case):
+        found = jc.aliases(base, unit)
+        for a in found:
+            far.put(a * per, decoy)
+        far.put(base * per, data)
+        got = dev.run(case, tag="%s at %d" % (key, base), iq_at=(far.ptr, jc.FAR_BYTES // unit, base))
+        assert same(got, near), (key, base, "the far run differs from the near one")
+        model.check(*got, tag=key)
+        assert far.get(base * per, len(data)).tobytes() == data.tobytes(), "the input was written"
+        for a in found:
+            assert far.get(a * per, len(decoy)).tobytes() == decoy.tobytes(), "a decoy was written"
+
+
+@pytest.mark.parametrize("key", WITH_OUTPUT)
+def test_relocated_output(dev, far, key):
+    case = jc.case_of(key)
+    near = dev.run(case, tag=key)
+    jc.model_of(key).check(*near, tag=key)
+    per = jc.OUT_WORDS[case.name]				# words of an output element
+    base, cap = jc.OUT_BASE[per], jc.capacity(case.name, case.jobs)
+    spans = [(max(a - G, 0), a + cap + G) for a in jc.aliases(base, 4 * per)]
+    for a, b in spans + [(base - G, base + cap + G)]:
+        far.fill(a * per, (b - a) * per)
+    rec, _ = dev.run(case, tag=key + " far out", out_at=(far.ptr, jc.FAR_BYTES // (4 * per), base))
+    got = far.get((base - G) * per, (cap + 2 * G) * per)
+    assert np.all(got[:G * per] == SENTINEL) and np.all(got[-G * per:] == SENTINEL), "written beside the far range"
+    assert got[G * per:-G * per].tobytes() == near[1].tobytes(), "the far outputs differ from the near ones"
+    assert same((rec,), near[:1])
+    for a, b in spans:
+        assert far.count(a * per, (b - a) * per) == (b - a) * per, "written at an alias of the output offset"
+
+
+def test_relocated_templates(dev, far):
+    key = "correlate lag_counts"
+    case = jc.case_of(key)
+    near = dev.run(case, tag=key)
+    data = words_of(case.tpl)
+    decoy = decoy_of(data)
+    found = jc.aliases(jc.TPL_BASE, 8)
+    for a in found:
+        far.put(2 * a, decoy)
+    far.put(2 * jc.TPL_BASE, data)
+    got = dev.run(case, tag=key + " far templates", tpl_at=(far.ptr, jc.FAR_SAMPLES, jc.TPL_BASE))
+    assert same(got, near)
+    assert far.get(2 * jc.TPL_BASE, len(data)).tobytes() == data.tobytes(), "the templates were written"
+
+
+def worst(got, want):
+    y = got.view(np.float32).reshape(-1, 2).astype(np.float64)
+    return max(np.abs(y[:, 0] - want.real).max(), np.abs(y[:, 1] - want.imag).max())
+
+
+def test_long_wave_job(dev, far):
+    import torch
+    spec = jc.WAVE_LONG
+    n_out, D, T, first = spec["n_out"], spec["decim"], spec["n_taps"], spec["first"]
+    taps = em.lowpass(np.random.default_rng(77), T)
+    d_taps = torch.from_numpy(taps).cuda()
+    # exactly the samples the job reads: rows of T words, D words apart
+    rows = far.words.as_strided((n_out, T), (D, 1), first)
+    index = first + torch.arange(n_out, dtype=torch.int64, device="cuda")[:, None] * D + torch.arange(T, dtype=torch.int64, device="cuda")
+    v = jc.hash_words(index)
+    vals = torch.where(v >= 2 ** 31, v - 2 ** 32, v).to(torch.int32)
+    rows.copy_(vals)
+    del index, v
+
+    job = jc.long_extract_job(spec, jc.GUARD)
+    cap = n_out + 2 * jc.GUARD
+    d_out = torch.full((2 * cap,), SENTINEL, dtype=torch.int32, device="cuda")
+    dev.call("extract", job, em.SC16, far.ptr, 2 * jc.FAR_SAMPLES, out=d_out.data_ptr(), cap=cap, taps=d_taps.data_ptr(), n_taps=T,
+             tag="long wave")
+    out = d_out.cpu().numpy().view(np.uint32).reshape(-1, 2)
+    assert np.all(out[:jc.GUARD] == SENTINEL) and np.all(out[-jc.GUARD:] == SENTINEL), "written outside the job's range"
+    assert torch.equal(rows, vals), "the input was written"
+    assert d_taps.cpu().numpy().tobytes() == taps.tobytes()
+    got = out[jc.GUARD:-jc.GUARD]
+    x, tol, err = jc.HashedStream(), jc.hashed_bound(job[0], taps), 0.0
+    step = 2 ** 19
+    for m0 in range(0, n_out, step):				# the model over all outputs, a piece at a time
+        sub = jc.advanced(job[0], m0)
+        sub["n_out"] = min(step, n_out - m0)
+        err = max(err, worst(got[m0:m0 + step], em.extract_job(x, sub[0], taps)))
+    print("long wave: err %.3g of %.3g" % (err, tol))
+    assert err <= tol
+
+    # the cut rule: the last 64 outputs as a job of their own, first and phase0 advanced
+    tail = jc.advanced(job[0], n_out - 64)
+    tail["out_offset"] = jc.GUARD
+    assert 2 ** 31 < tail["first"][0] < 2 ** 32 < tail["first"][0] + 63 * D
+    d_tail = torch.full((2 * (64 + 2 * jc.GUARD),), SENTINEL, dtype=torch.int32, device="cuda")
+    dev.call("extract", tail, em.SC16, far.ptr, 2 * jc.FAR_SAMPLES, out=d_tail.data_ptr(), cap=64 + 2 * jc.GUARD, taps=d_taps.data_ptr(),
+             n_taps=T, tag="long wave, the tail")
+    short = d_tail.cpu().numpy().view(np.uint32).reshape(-1, 2)
+    assert np.all(short[:jc.GUARD] == SENTINEL) and np.all(short[-jc.GUARD:] == SENTINEL)
+    assert short[jc.GUARD:-jc.GUARD].tobytes() == got[-64:].tobytes(), "the last 64 outputs do not depend on the cut"
+
+
+def test_long_tile_job(dev, far):
+    import torch
+    spec = jc.TILE_LONG
+    n_out, D, T, first = spec["n_out"], spec["decim"], spec["n_taps"], spec["first"]
+    taps = em.lowpass(np.random.default_rng(78), T)
+    d_taps = torch.from_numpy(taps).cuda()
+    end = first + em.need(n_out, D, T)				# the words the job reads end here
+    out_offset = jc.FAR_SAMPLES - n_out - G - 1
+    assert end <= 2 * (out_offset - G), "input and output lie in disjoint regions"
+    piece = 2 ** 26
+    for at in range(0, end, piece):
+        far.words[at:min(at + piece, end)].copy_(far.hashed(at, min(piece, end - at)))
+    far.fill(2 * (out_offset - G), 2 * (n_out + 2 * G))
+
+    job = jc.long_extract_job(spec, out_offset)
+    dev.call("extract", job, em.SC16, far.ptr, 2 * jc.FAR_SAMPLES, out=far.ptr, cap=jc.FAR_SAMPLES, taps=d_taps.data_ptr(), n_taps=T,
+             tag="long tile")
+    assert far.count(2 * (out_offset - G), 2 * G) == 2 * G and far.count(2 * (out_offset + n_out), 2 * G) == 2 * G, "written beside the range"
+    assert far.count(2 * out_offset, 2 * n_out) == 0, "an output word was not written"
+    for at in range(0, end, piece):
+        assert torch.equal(far.words[at:min(at + piece, end)], far.hashed(at, min(piece, end - at))), "the input was written"
+
+    x, tol = jc.HashedStream(), jc.hashed_bound(job[0], taps)
+    tiles = -(-n_out // em.TILE_OUT)
+    k = 2 ** 31 // (D * em.TILE_OUT)				# the last tile whose base m0 * D is below 2^31
+    assert k + 1 == tiles - 2
+    for t in (0, k - 1, k + 1):					# two tiles each: the first, below 2^31, and from 2^31 on: the last, one short
+        m0 = t * em.TILE_OUT
+        sub = jc.advanced(job[0], m0)
+        sub["n_out"] = min(2 * em.TILE_OUT, n_out - m0)
+        got = far.get(2 * (out_offset + m0), 2 * int(sub["n_out"][0]))
+        err = worst(got, em.extract_job(x, sub[0], taps))
+        print("long tile: tiles %d and %d: err %.3g of %.3g" % (t, t + 1, err, tol))
+        assert err <= tol, (t, err, tol)
+
+    # the cut rule: the last 300 outputs as a job of their own, first and phase0 advanced
+    tail = jc.advanced(job[0], n_out - 300)
+    tail["out_offset"] = jc.GUARD
+    assert tail["first"][0] > 2 ** 31
+    d_tail = torch.full((2 * (300 + 2 * jc.GUARD),), SENTINEL, dtype=torch.int32, device="cuda")
+    dev.call("extract", tail, em.SC16, far.ptr, 2 * jc.FAR_SAMPLES, out=d_tail.data_ptr(), cap=300 + 2 * jc.GUARD, taps=d_taps.data_ptr(),
+             n_taps=T, tag="long tile, the tail")
+    short = d_tail.cpu().numpy().view(np.uint32).reshape(-1, 2)
+    assert np.all(short[:jc.GUARD] == SENTINEL) and np.all(short[-jc.GUARD:] == SENTINEL)
+    assert short[jc.GUARD:-jc.GUARD].reshape(-1).tobytes() == far.get(2 * (out_offset + n_out - 300), 600).tobytes()

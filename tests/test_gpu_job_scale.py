@@ -1,0 +1,108 @@
+"""The passes over burst IQ on long jobs and full tables (the input sets are tests/job_scale_cases.py; tests/test_job_scale_cpu.py
+holds the conditions on them and runs the host twins over them).
+
+The single-module tests (tests/test_gpu_extract.py, _resample, _measure, _demod, _correlate) work in buffers of a few tens of
+thousands of samples: no job there has more than four partials and no call more than 257 jobs.  Here
+  long jobs    measure over 131 chunks and correlate over 131 tiles: k_measure_combine and k_correlate_combine fold 64 partials a
+               round, so their second and third rounds run -- a lane that holds several partials, the seam rule at partials 64 and
+               128, the peak's tie inside a lane across rounds and between lanes, best_tile chosen in a later round.  The cut rule
+               of measure at the round boundary.  Resample at positions of the up-sampled rate around 2^32, in both forms.
+  full tables  every pass with exactly MAX_JOBS jobs in shuffled order, every 11th without work: the deepest search of the prefix
+               and the largest table; and on a fresh instance a call of one job, the full table and the one job again, so the
+               scratch slot of the pass grows behind a first, smaller call.
+Every call goes through the C ABI into sentinel-filled buffers that are compared whole: bit for bit with demod_model,
+correlate_model and resample_model, inside measure_model.job_tolerance and extract_model.bound for the two passes whose contracts
+leave the order of the additions open.  Inputs and taps are compared with their host copies after the call, the ring position, the
+waterfall and the spectrum with what they were before, and the stats delta with what the jobs predict.  The same call twice is
+bit-identical."""
+import os
+
+import numpy as np
+import pytest
+
+import job_scale_cases as jc
+import measure_model as mm
+
+pytestmark = pytest.mark.gpu
+
+LONG = ("long measure", "long edges", "long tie", "long resample")
+
+
+@pytest.fixture(scope="module")
+def amd():
+    from _pkg import gr_fosphor_amd
+    if not os.path.exists(gr_fosphor_amd.LIB_PATH):
+        gr_fosphor_amd.build()
+    gr_fosphor_amd.load()
+    return gr_fosphor_amd
+
+
+@pytest.fixture(scope="module")
+def dev(amd):
+    d = jc.Dev(amd)
+    yield d
+    d.f.close()
+
+
+def same(a, b):
+    """two results of Dev.run: records and words bit-identical"""
+    return all((x is None and y is None) or x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+
+def assert_host(amd, case, rec, words, tag):
+    """against fosphor_amd_*_host: bit for bit, but measure's sums (rule 3 leaves their order open: the model's tolerance holds them)"""
+    if case.name == "extract":
+        return							# its host function is a float64 statement, no twin
+    host_rec, host_words = jc.host_twin(amd.Fosphor, case)
+    if case.name == "measure":
+        for k in mm.INTS:
+            assert np.array_equal(rec[k], host_rec[k]), (tag, k)
+        return
+    assert words.tobytes() == host_words.tobytes(), (tag, "words differ from the host's")
+    if host_rec is not None:
+        assert rec.tobytes() == host_rec.tobytes(), (tag, "records differ from the host's")
+
+
+@pytest.mark.parametrize("key", LONG)
+def test_long_jobs(amd, dev, key):
+    case, model = jc.case_of(key), jc.model_of(key)
+    got = dev.run(case, tag=key)
+    model.check(*got, tag=key)
+    assert_host(amd, case, *got, tag=key)
+    assert same(dev.run(case, tag=key + " again"), got), "the same call twice is bit-identical"
+    if key == "long measure":
+        rec = got[0]
+        assert list(rec["peak_index"][:2]) == [jc.LONG_MEASURE_PLANTS["top in part 5"][0]] * 2
+        assert list(rec["n_edges"][:2]) == [len(jc.LONG_MEASURE_PLANTS)] * 2
+        jc.assert_long_measure_cut(case, rec, model.tols[0])
+    if key == "long tie":
+        assert list(got[0]["peak_lag"]) == [jc.TIE_LAGS[0], jc.TIE_LAGS[0], jc.TIE_LAGS[1] - jc.TIE_SECOND]
+
+
+@pytest.mark.parametrize("name", jc.PASSES)
+def test_full_table(amd, dev, name):
+    key = "full " + name
+    case, model = jc.case_of(key), jc.model_of(key)
+    assert len(case.jobs) == jc.MAX_JOBS
+    got = dev.run(case, tag=key)
+    model.check(*got, tag=key)
+    assert_host(amd, case, *got, tag=key)
+    assert same(dev.run(case, tag=key + " again"), got), "the same call twice is bit-identical"
+
+
+@pytest.mark.parametrize("name", jc.PASSES)
+def test_the_scratch_grows_behind_a_small_call(amd, name):
+    """a fresh instance: one job, the full table, the one job again"""
+    key = "full " + name
+    case = jc.case_of(key)
+    one = jc.one_job_of(case)
+    d = jc.Dev(amd)
+    try:
+        first = d.run(one, tag=key + ": one job")
+        full = d.run(case, tag=key + ": the full table")
+        third = d.run(one, tag=key + ": one job again")
+    finally:
+        d.f.close()
+    jc.Model(one).check(*first, tag=key + ": one job")
+    jc.model_of(key).check(*full, tag=key + ": the full table behind a small call")
+    assert same(first, third), "the one job gives the same bits before and behind the full table"
