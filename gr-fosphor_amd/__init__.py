@@ -11,7 +11,7 @@ core.py (host-side mirror of the reference's libfosphor interface), dist.py (mul
 """
 from . import _lib
 from ._lib import LIB_PATH, Buffers, Config, Partials, Render, build, load
-from .core import FFT_LEN, FFT_LEN_LOG, MAX_BATCH, MULT_BATCH, Fosphor
+from .core import FFT_LEN, FFT_LEN_LOG, MAX_BATCH, MULT_BATCH, Fosphor, plan_k1
 
-__all__ = ["Fosphor", "build", "load", "LIB_PATH", "Config", "Buffers", "Partials", "Render",
+__all__ = ["Fosphor", "plan_k1", "build", "load", "LIB_PATH", "Config", "Buffers", "Partials", "Render",
            "FFT_LEN", "FFT_LEN_LOG", "MAX_BATCH", "MULT_BATCH"]

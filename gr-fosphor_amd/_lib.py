@@ -38,6 +38,12 @@ class CountPlan(C.Structure):
                 ("table", C.c_int), ("merge_form", C.c_int), ("table_in_memory", C.c_int)]
 
 
+class K1Plan(C.Structure):
+    """struct fosphor_amd_k1_plan"""
+    _fields_ = [("kernel", C.c_int), ("tile", C.c_int), ("tiles", C.c_int), ("units", C.c_int), ("max_tiles", C.c_int),
+                ("min_tiles", C.c_int)]
+
+
 class Channel(C.Structure):
     _fields_ = [("enabled", C.c_int), ("center", C.c_float), ("width", C.c_float)]
 
@@ -254,6 +260,7 @@ SIGNATURES = {
     "fosphor_amd_tune_placement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "fosphor_amd_plan_piece_batches": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong]),
     "fosphor_amd_plan_count": (C.c_int, [C.c_int] * 8 + [C.POINTER(CountPlan)]),
+    "fosphor_amd_plan_k1": (C.c_int, [C.c_int] * 10 + [C.POINTER(K1Plan)]),
     "fosphor_amd_share_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "fosphor_amd_launch_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "fosphor_amd_merge_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 11)]),

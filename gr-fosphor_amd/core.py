@@ -23,6 +23,25 @@ WIRE_FORMS = {"packed16": 1, "sparse16": 2}	# FOSPHOR_AMD_WIRE_* (include/fospho
 WIRE_MAX_BATCH = 65535
 
 
+K1_KERNELS = ("k1_fft_bin", "k1v2_fft_bin", "k1big_fft_bin", "k1w_fft_bin", "k1h_fused")	# FOSPHOR_AMD_K1_* (include/fosphor_amd.h)
+
+
+def plan_k1(fft_len_log, n_bins, iq_format, hop, iq_align, total, batch, tile_knob=0, k1_knob=1, n_cus=256):
+    """fosphor_amd_plan_k1 (host arithmetic, no device): the FFT launch of one piece of `total` spectra in batches of `batch` as a
+    dict -- kernel (a K1_KERNELS name), tile, tiles, units, max_tiles, min_tiles.  iq_format: "fp32" / "fp16" / "sc16" or a
+    FOSPHOR_AMD_IQ_* number; hop: samples between spectrum starts; iq_align: byte address of the first sample (modulo 16 is what
+    counts); tile_knob / k1_knob: the FOSPHOR_AMD_TILE / FOSPHOR_AMD_K1 settings the instance was made under."""
+    fmt = IQ_FORMATS[iq_format] if isinstance(iq_format, str) else int(iq_format)
+    p = _lib.K1Plan()
+    rv = _lib.load().fosphor_amd_plan_k1(fft_len_log, n_bins, fmt, hop, int(iq_align) & 15, tile_knob, k1_knob, n_cus, total, batch,
+                                         C.byref(p))
+    if rv:
+        _fail("fosphor_amd_plan_k1", rv, ValueError)
+    out = {k: getattr(p, k) for k, _ in _lib.K1Plan._fields_}
+    out["kernel"] = K1_KERNELS[p.kernel]
+    return out
+
+
 def _ptr(x):
     """Device pointer of a torch tensor / anything with data_ptr(), or a raw integer."""
     if hasattr(x, "data_ptr"):

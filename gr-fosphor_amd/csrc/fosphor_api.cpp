@@ -837,44 +837,25 @@ error:
 	return -EIO;
 }
 
-/* Spectra per K1 wave (N = 1024) / per work-group pass (other lengths).  One tile = one row of live / max
- * partials (8 B per column), so longer tiles mean fewer intermediate bytes: 64 spectra per wave is 0.125 B per
- * sample written and read back, 16 was 0.5.  A tile never straddles a batch (K2 weights whole tiles). */
+/* The FFT launch of `total` spectra in batches of `batch` on this instance, as k1_plan (fosphor_kernels.hip) lays it out: hop 0 = the
+ * FFT length; tile 0 = the plan's own choice */
+static K1Shape k1_shape(const struct fosphor *self, const void *d_iq, int hop, int total, int batch, int tile)
+{
+	K1Shape s = {};
+	s.log2n = self->log2n; s.n_bins = self->n_bins; s.iq_format = self->iq_format;
+	s.hop = hop ? hop : self->n;
+	s.align = (int)((uintptr_t)d_iq & 15);
+	s.tile_knob = self->kn_tile; s.k1_knob = self->k1_variant;
+	s.n_cus = self->n_cus;
+	s.total = total; s.batch = batch; s.tile = tile;
+	return s;
+}
+
+/* Spectra per tile of an FFT launch (the rule is k1_plan's; the tile depends on neither the hop nor the sample pointer) */
 static int pick_tile(const struct fosphor *self, int total, int batch)
 {
-	const int v = self->kn_tile;
-	if (v >= (self->log2n == 13 ? 8 : 4) && v <= (self->log2n == 16 ? 32 : 128) && !(v & (v - 1)) && batch % v == 0 && total % v == 0)
-		return v;
-	if (self->log2n == 16) {
-		/* a cluster owns whole tiles: the largest tile that still gives each of the 32 clusters one (at most 32 spectra: the
-		 * 9th bits of a tile's bin indices share one dword per column) */
-		for (int t = 32; t >= 8; t >>= 1)
-			if (batch % t == 0 && total / t >= 32)
-				return t;
-		return 4;
-	}
-	if (self->log2n == 13) {
-		assert(batch % 16 == 0);	/* (every entry point asks for it: the fallback tile of 8 divides the batch) */
-		/* one work-group per CU walks whole tiles; inside a tile the overlapped half of a window is reused from registers,
-		 * so long tiles fetch less (tile 64 at 50 % overlap: 65 half-windows for 64 spectra) and leave fewer partial rows;
-		 * every CU gets a tile (measured, 16384 spectra per launch: tile 16 / 32 / 64 -> 279 / 288 / 289 GSamples/s) */
-		for (int t = 64; t >= 8; t >>= 1)
-			if (batch % t == 0 && total / t >= 256)
-				return t;
-		return 8;		/* (at least 8: the 9th bits of a tile's bin indices go out as one byte per column and eight spectra) */
-	}
-	if (self->log2n != 10 || self->bins16) {
-		/* largest tile that still gives every resident wave (256 CUs x 8) a tile */
-		if (total / 16 >= 2048) return 16;
-		if (total / 8 >= 2048) return 8;
-		return 4;
-	}
-	/* 1024 waves (one 4-wave work-group per CU) per launch: consecutive launches overlap on alternating
-	 * streams, so two of them fill the chip's 512 work-group slots */
-	for (int t = 64; t >= 8; t >>= 1)
-		if (batch % t == 0 && total / t >= 1024)
-			return t;
-	return 4;
+	assert(self->log2n != 13 || batch % 16 == 0);	/* (every entry point asks for it: the fallback tile of 8 divides the batch) */
+	return k1_plan(k1_shape(self, NULL, 0, total, batch, 0)).tile;
 }
 
 static void fill_k1(struct fosphor *self, K1Params *k1, const void *d_iq, int total, int tile,
@@ -915,7 +896,9 @@ static void fill_k1(struct fosphor *self, K1Params *k1, const void *d_iq, int to
 	k1->amb = 0.5f - delta0;
 	k1->kappa = kappa;
 	k1->w = 1.0f - self->alpha;		/* display.cl:99 */
-	k1->variant = (self->log2n == 10 && !self->bins16) ? self->k1_variant : (self->log2n == 16 ? 4 : 3);
+	/* (the two-wave kernel where FOSPHOR_AMD_K1 asks for it, and where the wave-per-spectrum kernel cannot load: odd hops, sc16 on a
+	 * start that is not 8-byte aligned) */
+	k1->variant = k1_variant_of(k1_plan(k1_shape(self, d_iq, hop, total, total, tile)).kernel);
 	k1->scratch = self->d_scratch;
 	k1->sync = (self->log2n == 16) ? self->d_k1h_sync : NULL;
 	k1->sync_err = self->h_k1h_err;
@@ -930,10 +913,6 @@ static void fill_k1(struct fosphor *self, K1Params *k1, const void *d_iq, int to
 		if (k1->cus && !(self->f.tail.recorded && hipEventQuery(self->f.tail.ev) == hipErrorNotReady))
 			k1->cus = 0;
 	}
-	if (k1->variant == 1 && (k1->hop & 1))
-		k1->variant = 2;		/* 16-byte IQ loads of variant 1 need an even hop */
-	if (k1->variant == 1 && self->iq_format == FOSPHOR_AMD_IQ_SC16 && ((uintptr_t)d_iq & 7))
-		k1->variant = 2;		/* ... and its 8-byte sc16 loads an 8-byte aligned start (variant 2 loads one 4-byte sample per lane) */
 }
 
 static int gcd_int(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
@@ -1003,6 +982,27 @@ extern "C" int fosphor_amd_plan_count(int log2n, int n_bins, int slab_chunks, in
 	if (!out || n_batches < 1 || batch < 1 || log2n < 1 || log2n > 30 || n_bins < 1 || slab_chunks < 0)
 		return -EINVAL;
 	*out = plan_count(log2n, n_bins, slab_chunks, rowmask_off != 0, no_sum16 != 0, n_batches, batch, pipelined != 0);
+	return 0;
+}
+
+/* The FFT launch of one piece, exported for the CPU test suite (include/fosphor_amd.h): k1_plan, which pick_tile, fill_k1 and the
+ * launch itself take their values from, for a launch that finds the chip idle (the full-chip form at N = 8192). */
+extern "C" int fosphor_amd_plan_k1(int log2n, int n_bins, int iq_format, int hop, int iq_align, int tile_knob, int k1_knob,
+                                   int n_cus, int total, int batch, struct fosphor_amd_k1_plan *out)
+{
+	if (!out || (log2n != 10 && log2n != 13 && log2n != 16) || n_bins < 1 || n_bins > 512 || hop < 1 || iq_align < 0 || n_cus < 0 ||
+	    iq_format < FOSPHOR_AMD_IQ_FP32 || iq_format > FOSPHOR_AMD_IQ_SC16 || (iq_format == FOSPHOR_AMD_IQ_FP16 && log2n != 16) ||
+	    batch < 4 || total < batch || total % batch || (batch & (log2n == 13 ? 15 : 3)))
+		return -EINVAL;
+	static_assert(K1_WAVE == FOSPHOR_AMD_K1_WAVE && K1_V2 == FOSPHOR_AMD_K1_V2 && K1_BIG == FOSPHOR_AMD_K1_BIG &&
+	              K1_WIDE == FOSPHOR_AMD_K1_WIDE && K1_FUSED == FOSPHOR_AMD_K1_FUSED, "the public names of K1Kernel");
+	K1Shape s = {};
+	s.log2n = log2n; s.n_bins = n_bins; s.iq_format = iq_format; s.hop = hop; s.align = iq_align & 15;
+	s.tile_knob = tile_knob; s.k1_knob = k1_knob == 2 ? 2 : 1;
+	s.n_cus = n_cus; s.total = total; s.batch = batch;
+	const K1Plan pl = k1_plan(s);
+	out->kernel = pl.kernel; out->tile = pl.tile; out->tiles = pl.tiles; out->units = pl.units;
+	out->max_tiles = pl.max_tiles; out->min_tiles = pl.min_tiles;
 	return 0;
 }
 

@@ -135,6 +135,32 @@ struct K3Params {
 	int   rowlist_cnt;		/* ... which of the two counts this launch uses: 0, or 1 + rows (alternating) */
 };
 
+/* The shape of one FFT launch: which kernel runs, on which tile, over how many persistent units -- waves (k1_fft_bin) or work-groups
+ * (the others) -- and how many tiles the busiest and the idlest of them walk.  What decides it: the instance's geometry and knobs,
+ * the call (hop, alignment of the sample pointer, total, batch) and the device's CU count, never the data.  pick_tile and fill_k1
+ * (fosphor_api.cpp), launch_k1_as and fosphor_amd_plan_k1 (include/fosphor_amd.h) all take their values from k1_plan. */
+enum K1Kernel { K1_WAVE, K1_V2, K1_BIG, K1_WIDE, K1_FUSED };	/* FOSPHOR_AMD_K1_WAVE .. _FUSED */
+struct K1Shape {
+	int log2n, n_bins;
+	int iq_format;			/* FOSPHOR_AMD_IQ_* */
+	int hop;			/* samples between spectrum starts */
+	int align;			/* byte address of the first sample, modulo 16 */
+	int tile_knob, k1_knob;		/* FOSPHOR_AMD_TILE (0: none), FOSPHOR_AMD_K1 (1 or 2) */
+	int n_cus;			/* CUs of the device (0: 256) */
+	int share;			/* N = 8192: CUs the launch would keep when it leaves the rest to the count / merge kernels (K1Params.cus), 0 = all */
+	int total, batch;		/* spectra of the launch, spectra per batch */
+	int tile;			/* 0: the plan chooses (tile_knob, or the default rule); else the tile the launch was given */
+};
+struct K1Plan {
+	int kernel;			/* K1Kernel */
+	int tile, tiles;
+	int grid;			/* work-groups launched */
+	int units;			/* waves / work-groups that take at least one tile (N = 65536: the clusters; they claim tiles dynamically) */
+	int max_tiles, min_tiles;	/* tiles the busiest / the idlest of those units walks (N = 65536: 0, the claim is dynamic) */
+};
+K1Plan k1_plan(const K1Shape &s);
+inline int k1_variant_of(int kernel) { return kernel == K1_WAVE ? 1 : kernel == K1_V2 ? 2 : kernel == K1_FUSED ? 4 : 3; }	/* K1Params.variant */
+
 hipError_t launch_k1(const K1Params &p, hipStream_t s);
 hipError_t launch_k1_traffic_twin(const K1Params &p, hipStream_t s);
 hipError_t launch_k2(const K2Params &p, int n_chunks, hipStream_t s);

@@ -899,18 +899,128 @@ static hipError_t launch_k1h(const K1Params &p0, hipStream_t s)
 	     : p0.iq_format == kIqFp16 ? launch_k1h_form<iq_fp16, 8>(p0, s) : launch_k1h_form<iq_fp32, 8>(p0, s);
 }
 
+/* Spectra per K1 wave (N = 1024) / per work-group pass (other lengths).  One tile = one row of live / max
+ * partials (8 B per column), so longer tiles mean fewer intermediate bytes: 64 spectra per wave is 0.125 B per
+ * sample written and read back, 16 was 0.5.  A tile never straddles a batch (K2 weights whole tiles). */
+static int k1_tile(const K1Shape &s)
+{
+	const int v = s.tile_knob, total = s.total, batch = s.batch;
+	const bool bins16 = s.n_bins > 256 || s.log2n != 10;
+	if (v >= (s.log2n == 13 ? 8 : 4) && v <= (s.log2n == 16 ? 32 : 128) && !(v & (v - 1)) && batch % v == 0 && total % v == 0)
+		return v;
+	if (s.log2n == 16) {
+		/* a cluster owns whole tiles: the largest tile that still gives each of the 32 clusters one (at most 32 spectra: the
+		 * 9th bits of a tile's bin indices share one dword per column) */
+		for (int t = 32; t >= 8; t >>= 1)
+			if (batch % t == 0 && total / t >= 32)
+				return t;
+		return 4;
+	}
+	if (s.log2n == 13) {
+		/* one work-group per CU walks whole tiles; inside a tile the overlapped half of a window is reused from registers,
+		 * so long tiles fetch less (tile 64 at 50 % overlap: 65 half-windows for 64 spectra) and leave fewer partial rows;
+		 * every CU gets a tile (measured, 16384 spectra per launch: tile 16 / 32 / 64 -> 279 / 288 / 289 GSamples/s) */
+		for (int t = 64; t >= 8; t >>= 1)
+			if (batch % t == 0 && total / t >= 256)
+				return t;
+		return 8;		/* (at least 8: the 9th bits of a tile's bin indices go out as one byte per column and eight spectra) */
+	}
+	if (s.log2n != 10 || bins16) {
+		/* largest tile that still gives every resident wave (256 CUs x 8) a tile */
+		if (total / 16 >= 2048) return 16;
+		if (total / 8 >= 2048) return 8;
+		return 4;
+	}
+	/* 1024 waves (one 4-wave work-group per CU) per launch: consecutive launches overlap on alternating
+	 * streams, so two of them fill the chip's 512 work-group slots */
+	for (int t = 64; t >= 8; t >>= 1)
+		if (batch % t == 0 && total / t >= 1024)
+			return t;
+	return 4;
+}
+
+/* `units` persistent units walk `tiles` tiles, unit u taking u, u + units, ... */
+static void k1_walk(K1Plan *pl, int cap)
+{
+	pl->units = pl->tiles < cap ? pl->tiles : cap;
+	pl->max_tiles = pl->units > 0 ? (pl->tiles + pl->units - 1) / pl->units : 0;
+	pl->min_tiles = pl->units > 0 ? pl->tiles / pl->units : 0;
+}
+
+K1Plan k1_plan(const K1Shape &s)
+{
+	K1Plan pl;
+	const bool bins16 = s.n_bins > 256 || s.log2n != 10;
+	pl.tile = s.tile > 0 ? s.tile : k1_tile(s);
+	pl.tiles = s.total / pl.tile;
+	if (s.log2n == 16) {
+		/* 32 clusters: 8 work-groups of 8 waves, one per CU; a cluster claims its next tile when it is done with the last */
+		pl.kernel = K1_FUSED;
+		pl.grid = 256;
+		pl.units = 32;
+		pl.max_tiles = pl.min_tiles = 0;
+		return pl;
+	}
+	if (bins16 && s.log2n == 10) {
+		/* N = 1024 with 16-bit bin indices (more than 256 bins): the general kernel at 128 threads per spectrum */
+		pl.kernel = K1_BIG;
+		k1_walk(&pl, 4096);
+		pl.grid = pl.units;
+		return pl;
+	}
+	if (bins16) {
+		/* one 8-wave work-group per CU -- or per CU of the share the host leaves to this kernel (K1Params.cus: the count and
+		 * merge kernels of the previous launch run on the rest) */
+		const int all_cus = s.n_cus > 0 ? s.n_cus : 256;
+		pl.kernel = K1_WIDE;
+		k1_walk(&pl, (s.share > 0 && s.share < all_cus && pl.tiles % s.share == 0) ? s.share : all_cus);
+		pl.grid = pl.units;
+		return pl;
+	}
+	/* 16-byte IQ loads of the wave-per-spectrum kernel need an even hop, its 8-byte sc16 loads an 8-byte aligned start (the
+	 * two-wave kernel loads one 4-byte sample per lane) */
+	if (s.k1_knob == 2 || (s.hop & 1) || (s.iq_format == kIqSc16 && (s.align & 7))) {
+		pl.kernel = K1_V2;
+		k1_walk(&pl, 256 * 2 * kK1v2WavesPerSimd);	/* resident 2-wave work-groups on 256 CUs */
+		pl.grid = pl.units;
+		return pl;
+	}
+	/* FOSPHOR_AMD_K1_BLOCKS: debugging aid (e.g. 256 = one wave per SIMD, for phase timing) */
+	static const int max_blocks = [] { const char *e = getenv("FOSPHOR_AMD_K1_BLOCKS"); const int v = e ? atoi(e) : 0;
+	                                   return (v > 0 && v < kK1MaxBlocks) ? v : kK1MaxBlocks; }();
+	pl.kernel = K1_WAVE;
+	pl.grid = (pl.tiles + 3) / 4;
+	if (pl.grid > max_blocks)
+		pl.grid = max_blocks;		/* persistent: 2 work-groups per CU */
+	k1_walk(&pl, 4 * pl.grid);		/* (the waves of the grid; a wave without a tile leaves at once) */
+	return pl;
+}
+
+/* ... of the launch that p describes */
+static K1Plan k1_plan(const K1Params &p)
+{
+	K1Shape s = {};
+	s.log2n = p.log2n; s.n_bins = p.n_bins; s.iq_format = p.iq_format; s.hop = p.hop;
+	s.align = (int)((uintptr_t)p.iq & 15);
+	s.k1_knob = p.variant == 2 ? 2 : 1;
+	s.n_cus = p.n_cus; s.share = p.cus;
+	s.total = p.total; s.batch = p.total; s.tile = p.tile;
+	return k1_plan(s);
+}
+
 /* The 1024- and 8192-point kernels of one format; each kernel's options are chosen here, once */
 template <typename IQ>
 static hipError_t launch_k1_as(const K1Params &p, hipStream_t s)
 {
-	const int tiles = p.total / p.tile;
+	const K1Plan pl = k1_plan(p);
+	if (k1_variant_of(pl.kernel) != p.variant)
+		return hipErrorInvalidValue;		/* (fill_k1 takes the variant from the same plan) */
 	if (p.variant == 3) {
 		if (p.log2n == 10) {
 			/* N = 1024 with 16-bit bin indices (more than 256 bins): the general kernel at 128 threads per spectrum */
 			constexpr int N = 1024;
 			constexpr int lds = (N + ((N / 2 - 8) / 7) * 7 + N / 2) * 8 + N * 4;		/* exchange slab + the reference's twiddles + window */
-			const int blocks = tiles < 4096 ? tiles : 4096;
-			hipLaunchKernelGGL((p.fft_out ? k1big_fft_bin<IQ, 10, true> : k1big_fft_bin<IQ, 10, false>), dim3(blocks), dim3(N / 8), lds, s, p);
+			hipLaunchKernelGGL((p.fft_out ? k1big_fft_bin<IQ, 10, true> : k1big_fft_bin<IQ, 10, false>), dim3(pl.grid), dim3(N / 8), lds, s, p);
 			return hipGetLastError();
 		}
 		if (p.log2n != 13 || (p.tile & 7) || (p.total & 7))	/* (the kernel packs the 9th bits of spectra 8 u .. 8 u + 7 of a tile into one byte per column) */
@@ -924,28 +1034,15 @@ static hipError_t launch_k1_as(const K1Params &p, hipStream_t s)
 			return ae;
 		/* rows of 512 samples the next window of a tile shares with this one: hop = 8192 / R, R = 2, 4, 8, 16; any other hop: none */
 		const int which = (p.hop == 4096) ? 0 : (p.hop == 2048) ? 1 : (p.hop == 1024) ? 2 : (p.hop == 512) ? 3 : 4;
-		/* one 8-wave work-group per CU -- or per CU of the share the host leaves to this kernel (K1Params.cus: the count and
-		 * merge kernels of the previous launch run on the rest) */
-		const int all_cus = p.n_cus > 0 ? p.n_cus : 256;
-		const int cus = (p.cus > 0 && p.cus < all_cus && tiles % p.cus == 0) ? p.cus : all_cus;
-		const int bw = tiles < cus ? tiles : cus;
-		hipLaunchKernelGGL(fns[which], dim3(bw), dim3(512), ldsw, s, p);
+		hipLaunchKernelGGL(fns[which], dim3(pl.grid), dim3(512), ldsw, s, p);
 		return hipGetLastError();
 	}
 	if (p.variant == 2) {
-		const int maxb = 256 * 2 * kK1v2WavesPerSimd;	/* resident 2-wave work-groups on 256 CUs */
-		int blocks = tiles < maxb ? tiles : maxb;
-		hipLaunchKernelGGL((p.fft_out ? k1v2_fft_bin<IQ, true> : k1v2_fft_bin<IQ, false>), dim3(blocks), dim3(128), 0, s, p);
+		hipLaunchKernelGGL((p.fft_out ? k1v2_fft_bin<IQ, true> : k1v2_fft_bin<IQ, false>), dim3(pl.grid), dim3(128), 0, s, p);
 		return hipGetLastError();
 	}
-	int blocks = (tiles + 3) / 4;
-	/* FOSPHOR_AMD_K1_BLOCKS: debugging aid (e.g. 256 = one wave per SIMD, for phase timing) */
-	static const int max_blocks = [] { const char *e = getenv("FOSPHOR_AMD_K1_BLOCKS"); const int v = e ? atoi(e) : 0;
-	                                   return (v > 0 && v < kK1MaxBlocks) ? v : kK1MaxBlocks; }();
-	if (blocks > max_blocks)
-		blocks = max_blocks;		/* persistent: 2 work-groups per CU */
 	hipLaunchKernelGGL((p.fft_out ? k1_fft_bin<IQ, true, false> : p.n_bins == 256 ? k1_fft_bin<IQ, false, true> : k1_fft_bin<IQ, false, false>),
-	                   dim3(blocks), dim3(256), 0, s, p);
+	                   dim3(pl.grid), dim3(256), 0, s, p);
 	return hipGetLastError();
 }
 

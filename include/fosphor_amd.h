@@ -309,6 +309,35 @@ struct fosphor_amd_count_plan
 int fosphor_amd_plan_count(int fft_len_log, int n_bins, int slab_chunks, int rowmask_off, int no_sum16,
                            int n_batches, int batch, int pipelined, struct fosphor_amd_count_plan *out);
 
+/* Host-logic test hook (no device needed): the shape of the FFT launch of ONE piece (fosphor_amd_plan_piece_batches) of `total` spectra
+ * in batches of `batch` -- which kernel runs, on which tile, how many persistent units (waves of the wave-per-spectrum kernel,
+ * work-groups of the others) take tiles and how many tiles the busiest and the idlest of them walk: unit u takes tiles u, u + units,
+ * ...  Tests use it to prove that a case makes a kernel walk several tiles per unit.  Inputs: the instance's fft_len_log, n_bins and
+ * iq_format; hop = samples between spectrum starts (the FFT length, or FFT length / overlap); iq_align = byte address of the first
+ * sample modulo 16; tile_knob / k1_knob = the FOSPHOR_AMD_TILE (0: unset) / FOSPHOR_AMD_K1 (1 or 2) settings; n_cus = the device's
+ * compute units (0: 256).  The debugging aid FOSPHOR_AMD_K1_BLOCKS, read once per process, is honoured.  At fft_len_log = 13 this is the
+ * full-chip form, which a launch that finds the chip idle takes.  At fft_len_log = 16 tiles are claimed dynamically by `units` clusters:
+ * max_tiles and min_tiles are 0.  The library's tile choice, kernel choice and grid sizes come from the same function.  0, or -EINVAL
+ * for a shape no entry point accepts. */
+enum {
+	FOSPHOR_AMD_K1_WAVE,		/* k1_fft_bin: N = 1024, up to 256 bins, one wave per spectrum; units are waves */
+	FOSPHOR_AMD_K1_V2,		/* k1v2_fft_bin: N = 1024, two waves per spectrum (FOSPHOR_AMD_K1=2, odd hops, sc16 on a start that is not 8-byte aligned) */
+	FOSPHOR_AMD_K1_BIG,		/* k1big_fft_bin: N = 1024 with more than 256 bins */
+	FOSPHOR_AMD_K1_WIDE,		/* k1w_fft_bin: N = 8192, one work-group per CU */
+	FOSPHOR_AMD_K1_FUSED		/* k1h_fused: N = 65536, 32 clusters */
+};
+struct fosphor_amd_k1_plan
+{
+	int kernel;		/* FOSPHOR_AMD_K1_* */
+	int tile;		/* spectra per tile */
+	int tiles;		/* total / tile */
+	int units;		/* waves / work-groups / clusters that take tiles */
+	int max_tiles;		/* tiles the busiest unit walks */
+	int min_tiles;		/* tiles the idlest unit that has one walks */
+};
+int fosphor_amd_plan_k1(int fft_len_log, int n_bins, int iq_format, int hop, int iq_align, int tile_knob, int k1_knob,
+                        int n_cus, int total, int batch, struct fosphor_amd_k1_plan *out);
+
 /* FFT launches made in the space-sharing form (*cus work-groups, the count / merge kernels of the launch before on the CUs they
  * leave) and in the full-chip form since the instance was made: counted at fft_len_log = 13 only (the one length that shares; both
  * counters stay 0 otherwise).  *cus is the device's share whatever the length: 224 on a 256-CU device, 0 on any other (this device
