@@ -424,7 +424,19 @@ static __device__ __forceinline__ uint32_t bin_exact(float re, float im, float l
 		} else if (sd != sd) {
 			*l2_out = __builtin_nanf("");
 		} else {
-			const unsigned long long u = (unsigned long long)__double_as_longlong(sd);
+			/* A float hypot below 2^-126 is a subnormal float, k * 2^-149 with few bits, and the reference takes the logarithm of
+			 * THAT (display.cl:136): with k = 8 the rounding moves log10 by up to 0.03.  re and im are then subnormal themselves,
+			 * so m = sd * 2^298 is an integer below 2^47 and exact; (k + 1/2)^2 is no integer, so no tie exists and k is the
+			 * integer with k^2 - k < m <= k^2 + k: a float estimate of sqrt(m), within 2 of it, corrected twice. */
+			double sl = sd;
+			if (sd < 0x1p-252) {
+				const double m = sd * 0x1p298;
+				double k = __builtin_rint((double)__builtin_sqrtf((float)m));
+				for (int it = 0; it < 2; it++)
+					k += (m > __builtin_fma(k, k, k)) ? 1.0 : (m <= __builtin_fma(k, k, -k)) ? -1.0 : 0.0;
+				sl = (k * k) * 0x1p-298;
+			}
+			const unsigned long long u = (unsigned long long)__double_as_longlong(sl);
 			const int e = (int)((u >> 52) & 0x7ff) - 1023;
 			const double m = __longlong_as_double((long long)((u & 0x000fffffffffffffULL) | 0x3ff0000000000000ULL));
 			*l2_out = (float)e + __builtin_amdgcn_logf((float)m);
