@@ -8,384 +8,21 @@
  * tri-state BOOTING/PENDING/READY (cl.c:92-96), errno-style returns.
  *
  * There is no CPU fallback: without a HIP device fosphor_init() fails loudly.
+ *
+ * This file: the instance and the K1 -> K2 -> K3 pipeline.  struct fosphor is in fosphor_instance.h; the host tables, the
+ * sharded-frame path and the measurement hooks are in fosphor_tables.cpp, fosphor_shard.cpp and fosphor_prof.cpp.
  */
 #include <assert.h>
 #include <errno.h>
 #include <math.h>
-#include <stddef.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <algorithm>
-#include <utility>
-#include <vector>
-
-#include "fosphor_internal.h"
-#include "fosphor_jobs.h"
-#include "../../include/fosphor_amd.h"
+#include "fosphor_instance.h"
 #include "../../include/fosphor_amd_sink.h"
-#include "../../include/fosphor_amd_wire.h"
 #include "../../include/fosphor_portable_math.h"
 
-using namespace fosphor_amd;
-
 #define FOSPHOR_AMD_VERSION "fosphor_amd 0.1 gfx950"
-
-#define HIP_TRY(expr, what) do { \
-		hipError_t _e = (expr); \
-		if (_e != hipSuccess) { \
-			fprintf(stderr, "[!] fosphor_amd: %s: %s\n", what, hipGetErrorString(_e)); \
-			goto error; \
-		} \
-	} while (0)
-
-enum { ST_BOOTING = 0, ST_PENDING = 1, ST_READY = 2 };	/* cl.c:92-96 */
-
-static const int kMaxN = 65536;
-static const int kSets = 5;		/* intermediate (bin index / partial) sets in rotation */
-static const int kMaxK1Streams = 4;	/* `stream` + up to three more FFT streams */
-/* N = 8192, space sharing: the FFT kernel (one work-group per CU, every register of it) takes 224 CUs when a launch's tiles divide
- * evenly among them, and the count / merge kernels of the launch before run on the 32 it leaves free -- the dispatcher fills CUs it
- * finds empty, no CU mask involved (hardware masks that remove CUs unevenly from the shader engines unbalance a grid of CU-sized
- * work-groups: tools/ubench/cu_mask_big.hip).  Measured at BASELINE C3: 333 -> 367-371 GSamples/s with 28 batches per call, 358
- * with 14, 345 with 7; 232 / 240 CUs leave the tail too little (it becomes the longer side), 216: 356 (DESIGN.md sections 4-5; DESIGN_HISTORY.md section 8). */
-static const int kK1wShareCus = 224;	/* (208 / 240 with 26 / 30 batches per call measured no better, profiles/r06_c3.md) */
-static const int kSubSamplesLog2 = 26;	/* default sub-launch: 64 Mi samples (64 reference batches of 1024 x 1024) */
-
-static const int kRiseMax = 8192;	/* largest batch served by the rise/decay table */
-
-/* An event that may not have been recorded yet: the work queued on one stream that work on another must follow.  Nothing waits
- * for a fence that was never recorded (or that was forgotten: `recorded = 0`). */
-struct Fence
-{
-	hipEvent_t  ev;
-	int         recorded;
-	hipStream_t stream;			/* the stream it was last recorded on */
-
-	hipError_t create(unsigned flags) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }	/* (no-op when it exists) */
-	/* behind everything queued on st so far */
-	hipError_t record(hipStream_t st)
-	{
-		const hipError_t e = hipEventRecord(ev, st);
-		if (e == hipSuccess) { recorded = 1; stream = st; }
-		return e;
-	}
-	/* what is queued on st next follows the record; unless_same: not when st is the stream of the record (stream order does it) */
-	hipError_t wait(hipStream_t st, bool unless_same = false) const
-	{
-		if (!recorded || (unless_same && stream == st))
-			return hipSuccess;
-		return hipStreamWaitEvent(st, ev, 0);
-	}
-};
-
-/* Every fence of an instance (nothing but Fence members: fosphor_amd_init and fosphor_release walk them as an array) */
-struct Fences
-{
-	/* made by fosphor_amd_init, with dep_event_flags() */
-	Fence wf[2];				/* last K1 that stored rows into ring b */
-	Fence in;				/* what the caller queued on `stream` before a call, for the other FFT streams */
-	Fence k1_done[kSets];			/* K1 wrote set pp */
-	Fence set_free[kSets];			/* K2 finished reading set pp */
-	Fence k2_done[2];			/* K2 wrote hit-count set h */
-	Fence h_free[2];			/* K3 finished reading hit-count set h */
-	Fence k3_done;				/* orders K3s that are issued on different streams */
-	Fence tail;				/* N = 8192: behind the merge kernel of the last launch (is there a tail to share the chip with?) */
-	/* made with the stream or the staging slot they belong to */
-	Fence k1s_done[kMaxK1Streams];
-	Fence stage_free[2];
-	Fence upload_slot[2];			/* upload into d_stage[k] done: the instance's stream waits for it before the FFT kernel */
-	Fence upload_done;			/* H2D of the last fosphor_amd_process_pinned */
-};
-static const int kInitFences = offsetof(Fences, k1s_done) / sizeof(Fence);
-static const int kFences = sizeof(Fences) / sizeof(Fence);
-static_assert(sizeof(Fences) == kFences * sizeof(Fence) && offsetof(Fences, upload_done) == (kFences - 1) * sizeof(Fence), "Fences is an array of Fence");
-
-struct fosphor
-{
-	/* geometry / constants */
-	int log2n, n, n_bins, wf_rows;
-	int bins16;				/* bin indices are 16-bit (2 spectra per dword) */
-	int tw_len, tw_off[8];
-	float t0r, t0d, alpha;
-	int max_spectra, max_batches;
-	int iq_format;				/* FOSPHOR_AMD_IQ_*: fp32, fp16 (N = 65536 only) or sc16 pairs */
-	size_t sample_bytes;			/* bytes per sample of that format: 8, 4, 4 */
-	size_t stage_samples;			/* capacity of one host staging slot, samples */
-
-	/* reference-visible settings (private.h:44-54) */
-	float fft_win[kMaxN];
-	int   win_dirty;
-	struct { int db_ref, db_per_div; float scale, offset; } power;
-	struct { double center, span; } frequency;
-	float histo_scale, histo_offset;	/* cl.c:1087-1088 */
-	int   thr_dirty;
-
-	/* device */
-	int device;
-	hipStream_t stream;
-	int own_stream;
-	float    *d_win;
-	float2   *d_tw;
-	double   *d_thr;
-	float    *d_wf_pp[2], *d_hist;		/* two waterfall rings: a call that rewrites every row targets the other one,
-						 * so its K1s need not wait for the previous call's (see run()) */
-	int       wf_cur;			/* ring the results are in */
-	Fences    f;
-	float2   *d_spectrum;
-	uint32_t *d_bins_pp[kSets];		/* rotating sets: K1 of launch i+1 overlaps K2/K3 of launch i */
-	float2   *d_partial_pp[kSets];
-	uint32_t *d_bins;			/* current set */
-	float2   *d_partial;
-	int       pp;
-	hipStream_t k1_streams[kMaxK1Streams];	/* [0] = `stream`; the K1s of consecutive sub-launches of a device-resident call rotate over
-						 * n_k1_streams of them: the next K1s are already queued when work-groups of the current one exit */
-	int       n_sets;			/* intermediate sets in use (3, <= kSets) */
-	int       n_k1_streams;			/* FOSPHOR_AMD_K1_STREAMS (default 2) */
-	int       alt;				/* FOSPHOR_AMD_ALT=0 keeps every K1 on `stream` */
-	int       k1_seq;
-	int       relaxed;			/* fosphor_amd_set_input_ordering(self, 0) */
-	long long sub_samples;			/* samples per sub-launch of a device-resident call */
-	hipStream_t stream2;			/* K2 (and K3 unless pipe3) of the multi-batch path */
-	hipStream_t stream3;			/* K3 of the multi-batch path: K3 of launch i beside K2 of launch i+1 */
-	int       pipe3;			/* FOSPHOR_AMD_PIPE3=0 keeps K3 on stream2 */
-	int       hset;				/* hit-count / live-sum set of the next launch (two, like the bin sets) */
-	hipStream_t last_k3_stream;
-	hipStream_t k2_stream_last;		/* stream of the most recent count kernel */
-	int       overlap;			/* 1: two-stream pipeline for process paths */
-	int       k1_variant;			/* FOSPHOR_AMD_K1: 1 (default) = wave per spectrum, 2 = two waves per spectrum (what odd hops use) */
-	/* tuning / test knobs, read from the environment ONCE, at init (nothing on the submit path calls getenv) */
-	int       kn_tile;			/* FOSPHOR_AMD_TILE: spectra per tile, 0 = pick_tile's choice */
-	int       kn_rowmask_off;		/* FOSPHOR_AMD_ROWMASK=0: dense count hand-off at N = 65536 */
-	int       kn_no_sum16;			/* FOSPHOR_AMD_NO_SUM16 */
-	int       kn_frame_group;		/* FOSPHOR_AMD_FRAME_GROUP: chunks per count work-group of a sharded frame (default 4) */
-	int       kn_k1w_share_off;		/* FOSPHOR_AMD_K1W_SHARE=0: no space sharing at N = 8192 */
-	int       n_cus;			/* hipDeviceProp_t::multiProcessorCount */
-	int       share_cus;			/* N = 8192: work-groups of an FFT launch that leaves CUs to the count / merge kernels (0: never) */
-	long long k1w_shared, k1w_full;		/* N = 8192: FFT launches made in the shared / the full-chip form (fosphor_amd_share_stats) */
-	long long k3_forms[K3_FORMS], k3_rise_mem;	/* merge launches by form; long-batch launches that read the (d, e) table from memory (fosphor_amd_merge_stats) */
-	const uint32_t *k3_listed;		/* device word holding the row count of the last sparse launch's list, and the stream it ran on */
-	hipStream_t k3_listed_stream;
-	int       k3_sparse_max[2];		/* most batches in one sparse launch: batches up to 1024 spectra / longer ones */
-	long long acc_pieces, n_k2c, n_k2b;	/* FFT pieces launched by accumulate(); chunk sums (k2c) / chunk reduces (k2b) launched (fosphor_amd_launch_stats) */
-	uint32_t *d_hc;
-	uint32_t *d_hc_export;			/* [n_bins][N] last batch, written by K3 on the 16-bit path */
-	const uint16_t *export_src;		/* ... made from the last batch's slabs when fosphor_amd_get_buffers asks */
-	const uint32_t *export_mask;
-	hipStream_t export_stream;		/* the stream the K2 that wrote export_src ran on */
-	uint32_t *d_rowmask;			/* K2 -> K3: one bit per (batch, slab, bin row) "this row has counts and is stored"; 2 sets */
-	int       mask_words;			/* ceil(n_bins / 32) */
-	uint8_t  *d_hot;			/* [N/64][n_bins]: some cell of the row is above the fast-exit level (K3 maintains it) */
-	uint32_t *d_rowlist;			/* [2 + rows]: the live rows of a merge (sparse form) between two counts used alternately */
-	int       rowlist_flip;
-	int       hot_valid;			/* 0 after anything but the 16-bit K3 wrote the histogram */
-	uint16_t *d_slab16;			/* per-chunk packed 16-bit count slabs of batches longer than 1024 spectra / of a shard */
-	int       slab_chunks;			/* capacity of d_slab16 in 1024-spectrum chunks */
-	const uint32_t *hc_view;		/* the hit counts of the last batch merged, as fosphor_amd_get_buffers shows them */
-	float    *d_live_sum, *d_vmax;
-	float    *d_chunk_sum, *d_chunk_max;	/* [max_spectra/16][N] */
-	long long *d_dbg;			/* K1_TIMING builds only (FOSPHOR_AMD_K1_TIMING=1) */
-	uint32_t *d_palette;			/* colour-map scratch (fosphor_cmap.hip), allocated on first use */
-	long long counters[FOSPHOR_COUNTERS_COUNT][FOSPHOR_COUNTERS_MAX];	/* launches, calls, jobs of the passes in files of their own, by FOSPHOR_COUNTERS_*
-						 * (fosphor_pass.h): host counters that only grow, behind every fosphor_amd_*_stats of theirs */
-	struct {				/* scratch of detect, mask, burst (two) and of the passes over burst IQ (job tables, partials), by */
-		void  *d;			/* FOSPHOR_SCRATCH_* (fosphor_pass.h); grown on demand, the instance never reads them */
-		size_t cap;
-	} scratch[FOSPHOR_SCRATCH_COUNT];
-	/* compact wire of the sharded frame (fosphor_wire.hip, include/fosphor_amd_wire.h); every buffer is allocated on first use */
-	struct {
-		uint32_t *d_masks;		/* [mask_cap][rows / 32] presence bits, one part per rank */
-		int       mask_cap;		/* parts d_masks holds */
-		int       world;		/* parts it is laid out for (the last mask stage's world) */
-		int       masked;		/* world of a mask stage no sparse pack has consumed yet, else 0 */
-		int       masked_slot, packed_slot;	/* the slot that mask stage read; the slot the last pack read */
-		uint32_t *d_union, *d_prefix;	/* [rows / 32] union mask, live rows in the words before each */
-		uint32_t *d_live;		/* the union's live-row count, for the row copies ... */
-		uint32_t *h_live;		/* ... and in pinned host memory, for the host (the one wait of the sparse form) */
-		uint32_t *d_words;		/* [cells / 2] wire words */
-		int       form;			/* form the last pack took, 0 once it is unpacked */
-		int       n_words, live_rows;	/* of the last pack */
-		long long stats[FOSPHOR_AMD_WIRE_STATS];
-		hipEvent_t ev[6];		/* (start, stop) of the last mask / pack / unpack launch made while profiling was on */
-		int       ev_rec[3];
-	} wire;
-	float2   *d_rise;			/* [kRiseMax+1] (d, e) per hit count */
-	float2   *h_rise;			/* pinned */
-	int       rise_batch;			/* batch the table was built for (0 = none) */
-	float     rise_t0r, rise_t0d;
-	int       slot;				/* partial-array slot used by accumulate/merge */
-	float2   *d_scratch;			/* N = 65536: [max_spectra][N] spectrum between the two FFT stages */
-	uint32_t *d_k1h_sync;			/* N = 65536 (both levels of the plan in one kernel, the intermediate in the XCDs' L2): its cluster counters */
-	uint32_t *h_k1h_err;			/* ... and its error word (host memory the kernel writes: work-groups of a cluster on different XCDs) */
-
-	/* host->device staging for fosphor_process (pinned ring of 2) */
-	float2   *h_stage[2];
-	float2   *d_stage[2];
-	hipStream_t copy_stream;		/* the H2D of fosphor_amd_process_pinned is queued here, so that the upload of one batch runs beside
-						 * the kernels of the batch before (created by the first fosphor_amd_process_pinned) */
-	size_t    d_stage_cap[2];		/* samples d_stage[k] holds */
-	int       pend_slot[2], pend_len[2], pend_head, pend_n;	/* uploads queued by fosphor_amd_upload_pinned, kernels not yet */
-	int       stage_idx;
-	double   *h_thr;			/* pinned, n_bins+1 */
-	float    *h_win;			/* pinned, N */
-
-	/* state */
-	int state;
-	int wf_pos;
-
-	/* where a launch's count hand-off lives */
-	size_t cells() const { return (size_t)n_bins * n; }
-	uint32_t *hc_slot(int slot) const { return d_hc + (size_t)slot * cells(); }				/* 32-bit counts of one batch */
-	uint16_t *hc16_set(int hset) const { return (uint16_t *)d_hc + (size_t)hset * max_batches * cells(); }	/* 16-bit counts of a launch */
-	int       live_slot(int slot, int hset) const { return slot + hset * max_batches; }			/* live-sum / max slot ... */
-	float    *live_sum_at(int lslot) const { return d_live_sum + (size_t)lslot * n; }			/* ... and its arrays */
-	float    *vmax_at(int lslot) const { return d_vmax + (size_t)lslot * n; }
-	uint32_t *rowmask_set(int hset) const { return d_rowmask + (size_t)hset * max_batches * (n / 64) * mask_words; }
-
-	/* profiling */
-	int prof;				/* 0 off, 1 every kernel, 2 K1 only (fewer events beside K2/K3) */
-	int prof_open;
-	std::vector<hipEvent_t> ev_pool;
-	std::vector<int> ev_kind;		/* kernel index per (start, stop) pair */
-	size_t ev_used;
-	std::vector<hipEvent_t> xev_pool;	/* (start, stop) pairs around the exchanges of the multi-GPU path, while profiling is on */
-	size_t xev_used;
-};
-
-/* ------------------------------------------------------------------------ */
-/* Host-side tables                                                         */
-/* ------------------------------------------------------------------------ */
-
-/* Twiddles.  N = 1024: exactly as the reference forms them (fft.cl:62-68,162-166,286-297), native_sin / native_cos pinned to
- * fosphor_portable_math.h; one block per radix-8 pass with p = 8, 64 ([k < p][n = 1..7]), then the final radix-2 pass
- * ([k < N/2]): the kTw2Off / kTw3Off / kTw4Off layout of fosphor_internal.h.
- *
- * N = 8192 and N = 65536 run this build's own plans (no reference behaviour exists at these lengths; oracle/fosphor_oracle.c,
- * o_pass_radix8_fma / o_pass_radix16_fma / o_pass_radix2_fma, restates them): the reference's Stockham passes with the twiddles
- * ON the radix-2 butterflies of a pass instead of on its inputs, so an item needs the twiddles of its stages -- every one of them
- * exp(-j pi q / den) for integers q, den, formed like the reference's (one float expression, pinned sin / cos): tw_long().
- *   both:       block  0    the constants W16, W8, W16^3 (first pass)
- *   N = 8192:   blocks 1-2  passes p = 16, 256: [k < p][8] = w^8, w^4, w^2, w^2 W8, w, w W16, w W8, w W16^3   (w = exp(-j pi k / (8 p)))
- *               block  3    the radix-2 pass: [k < 4096] = exp(-j pi k / 4096)
- *   N = 65536:  blocks 1-3  passes p = 16, 256, 4096: [k < p][8], as above */
-static float2 tw_long(int q, int den)
-{
-	const float PI_F = 3.141592653589f;		/* fft.cl:26 */
-	const float arg = -PI_F * (float)q / (float)den;
-	return make_float2(fpm_cosf(arg), fpm_sinf(arg));
-}
-
-static int build_twiddles16(float2 *tw, int *offsets /* [8] or NULL */)
-{
-	int pos = 0, q = 0;
-	if (offsets) offsets[q] = pos;
-	q++;
-	for (int m = 1; m <= 3; m++) {
-		if (tw) tw[pos] = tw_long(m, 8);
-		pos++;
-	}
-	for (int p = 16; p <= 4096; p *= 16, q++) {
-		if (offsets) offsets[q] = pos;
-		const int d = 8 * p;
-		for (int k = 0; k < p; k++) {
-			const int qs[8] = { 8 * k, 4 * k, 2 * k, 2 * k + 2 * p, k, k + p, k + 2 * p, k + 3 * p };
-			for (int f = 0; f < 8; f++) {
-				if (tw) tw[pos] = tw_long(qs[f], d);
-				pos++;
-			}
-		}
-	}
-	return pos;
-}
-
-static int build_twiddles13(float2 *tw, int *offsets /* [8] or NULL */)
-{
-	const int n = 8192;
-	int pos = 0, q = 0;
-	if (offsets) offsets[q] = pos;
-	q++;
-	for (int m = 1; m <= 3; m++) {
-		if (tw) tw[pos] = tw_long(m, 8);
-		pos++;
-	}
-	for (int p = 16; p <= 256; p *= 16, q++) {
-		if (offsets) offsets[q] = pos;
-		const int d = 8 * p;
-		for (int k = 0; k < p; k++) {
-			const int qs[8] = { 8 * k, 4 * k, 2 * k, 2 * k + 2 * p, k, k + p, k + 2 * p, k + 3 * p };
-			for (int f = 0; f < 8; f++) {
-				if (tw) tw[pos] = tw_long(qs[f], d);
-				pos++;
-			}
-		}
-	}
-	if (offsets) offsets[q] = pos;
-	for (int k = 0; k < n / 2; k++) {
-		if (tw) tw[pos] = tw_long(k, n / 2);
-		pos++;
-	}
-	return pos;
-}
-
-static int build_twiddles(float2 *tw, int log2n, int *offsets /* [8] or NULL */)
-{
-	const float PI_F = 3.141592653589f;		/* fft.cl:26 */
-	const int n = 1 << log2n;
-	int pos = 0, q = 0;
-	if (log2n == 16)
-		return build_twiddles16(tw, offsets);
-	if (log2n == 13)
-		return build_twiddles13(tw, offsets);
-	for (int p = 8; p < n / 2; p *= 8, q++) {
-		if (offsets) offsets[q] = pos;
-		for (int k = 0; k < p; k++) {
-			const float alpha = -PI_F * (float)k / (float)(4 * p);
-			for (int f = 1; f < 8; f++) {
-				const float arg = (float)f * alpha;
-				if (tw) tw[pos] = make_float2(fpm_cosf(arg), fpm_sinf(arg));
-				pos++;
-			}
-		}
-	}
-	if (offsets) offsets[q] = pos;
-	for (int k = 0; k < n / 2; k++) {
-		const float alpha = -PI_F * (float)k / (float)(n / 2);
-		const float arg = (float)1 * alpha;
-		if (tw) tw[pos] = make_float2(fpm_cosf(arg), fpm_sinf(arg));
-		pos++;
-	}
-	return pos;
-}
-
-/* Exact bin thresholds on the double squared magnitude: thr[b] = smallest s >= 0 with
- * oracle bin(s) >= b.  bin(s) is monotone while hypot(s) is finite (checked exhaustively by
- * oracle/tools/pm_check.c); thr[nb] = smallest s whose hypot overflows float. */
-static void build_thresholds(double *thr, int nb, float hs, float ho)
-{
-	/* largest s with finite (float)sqrt(s) */
-	uint64_t lo = 0, hi = fpm_d2u(1.0e80);
-	while (hi - lo > 1) {
-		uint64_t mid = lo + (hi - lo) / 2;
-		if (isinf(fpm_hypot_from_sqmag(fpm_u2d(mid)))) hi = mid; else lo = mid;
-	}
-	const uint64_t s_inf = hi;
-	thr[0] = -1.0;
-	thr[nb] = fpm_u2d(s_inf);
-	for (int b = 1; b < nb; b++) {
-		/* invariant: bin(lo) < b <= bin(hi) on [0, s_inf) */
-		if (fpm_bin_from_sqmag(fpm_u2d(s_inf - 1), hs, ho, nb) < b) {
-			thr[b] = fpm_u2d(s_inf);	/* unreachable bin */
-			continue;
-		}
-		lo = 0; hi = s_inf - 1;
-		while (hi - lo > 1) {
-			uint64_t mid = lo + (hi - lo) / 2;
-			if (fpm_bin_from_sqmag(fpm_u2d(mid), hs, ho, nb) >= b) hi = mid; else lo = mid;
-		}
-		thr[b] = fpm_u2d(hi);
-	}
-}
 
 /* ------------------------------------------------------------------------ */
 /* Init / release                                                           */
@@ -408,7 +45,7 @@ static hipError_t alloc_output(void **p, size_t bytes, bool uncached)
 	return hipMalloc(p, bytes);
 }
 
-static unsigned dep_event_flags(void)
+unsigned fosphor_amd::dep_event_flags(void)
 {
 	/* (no system fence: the events order kernels of this device among its own streams, nothing the host or another device reads) */
 	return hipEventDisableTiming | hipEventDisableSystemFence;
@@ -446,8 +83,6 @@ extern "C" void fosphor_release(struct fosphor *self)
 	(void)hipFree(self->wire.d_masks); (void)hipFree(self->wire.d_union); (void)hipFree(self->wire.d_prefix);
 	(void)hipFree(self->wire.d_live); (void)hipFree(self->wire.d_words);
 	if (self->wire.h_live) (void)hipHostFree(self->wire.h_live);
-	for (hipEvent_t e : self->wire.ev)
-		if (e) (void)hipEventDestroy(e);
 	(void)hipFree(self->d_scratch);
 	(void)hipFree(self->d_k1h_sync);
 	if (self->h_k1h_err) (void)hipHostFree(self->h_k1h_err);
@@ -459,8 +94,7 @@ extern "C" void fosphor_release(struct fosphor *self)
 	}
 	if (self->h_thr) (void)hipHostFree(self->h_thr);
 	if (self->h_win) (void)hipHostFree(self->h_win);
-	for (hipEvent_t e : self->ev_pool) (void)hipEventDestroy(e);
-	for (hipEvent_t e : self->xev_pool) (void)hipEventDestroy(e);
+	for (EventTimer &t : self->timers) t.destroy();
 	if (self->own_stream && self->stream)
 		(void)hipStreamDestroy(self->stream);
 	delete self;
@@ -735,41 +369,13 @@ extern "C" void fosphor_set_frequency_range(struct fosphor *self, double center,
 /* Launch sequence                                                          */
 /* ------------------------------------------------------------------------ */
 
-static void prof_begin(struct fosphor *self, int kind, hipStream_t st)
-{
-	self->prof_open = 0;
-	if (!self->prof || (self->prof == 2 && kind != 0)) return;
-	if (self->ev_used + 2 > self->ev_pool.size()) {
-		for (int i = 0; i < 2; i++) {
-			hipEvent_t e;
-			if (hipEventCreateWithFlags(&e, dep_event_flags() & ~hipEventDisableTiming) != hipSuccess) return;
-			self->ev_pool.push_back(e);
-		}
-	}
-	if (hipEventRecord(self->ev_pool[self->ev_used], st) != hipSuccess)
-		return;				/* this launch goes untimed */
-	self->prof_open = 1;
-	self->ev_kind.push_back(kind);
-}
-
-static void prof_end(struct fosphor *self, hipStream_t st)
-{
-	if (!self->prof_open) return;
-	self->prof_open = 0;
-	if (self->ev_used + 2 > self->ev_pool.size() || hipEventRecord(self->ev_pool[self->ev_used + 1], st) != hipSuccess) {
-		self->ev_kind.pop_back();	/* drop the half-recorded pair */
-		return;
-	}
-	self->ev_used += 2;
-}
-
 /* The stream K2 / K3 and the exchanges run on: a second stream when the two-stream pipeline is on, else the main one */
-static hipStream_t count_stream(const struct fosphor *self)
+hipStream_t fosphor_amd::count_stream(const struct fosphor *self)
 {
 	return self->overlap ? self->stream2 : self->stream;
 }
 
-static int sync_all(struct fosphor *self)
+int fosphor_amd::sync_all(struct fosphor *self)
 {
 	int rv = 0;
 	if (self->stream  && hipStreamSynchronize(self->stream)  != hipSuccess) rv = -EIO;
@@ -783,7 +389,7 @@ static int sync_all(struct fosphor *self)
 /* K3s update the persistent state in launch order.  They normally follow each other on one
  * stream; when the stream changes (pipelined process path <-> accumulate/merge path) the new
  * stream waits for the last K3 of the old one. */
-static int k3_stream_enter(struct fosphor *self, hipStream_t st)
+int fosphor_amd::k3_stream_enter(struct fosphor *self, hipStream_t st)
 {
 	if (self->last_k3_stream && self->last_k3_stream != st) {
 		if (self->f.k3_done.record(self->last_k3_stream) != hipSuccess || self->f.k3_done.wait(st) != hipSuccess)
@@ -795,7 +401,7 @@ static int k3_stream_enter(struct fosphor *self, hipStream_t st)
 
 /* Before anything else than the pipelined 16-bit path writes d_hc / live sums: K3s still
  * reading the two hit-count sets must be done. */
-static int drain_h_sets(struct fosphor *self, hipStream_t st)
+int fosphor_amd::drain_h_sets(struct fosphor *self, hipStream_t st)
 {
 	for (int h = 0; h < 2; h++) {
 		if (self->f.h_free[h].wait(st) != hipSuccess)
@@ -806,7 +412,7 @@ static int drain_h_sets(struct fosphor *self, hipStream_t st)
 }
 
 /* Upload lazily-changed tables (cl.c:889-900) and boot fills (cl.c:406-465, 930-934) */
-static int prepare(struct fosphor *self)
+int fosphor_amd::prepare(struct fosphor *self)
 {
 	if (self->win_dirty || self->thr_dirty) {
 		/* The tables are read by every K1 still queued -- with relaxed input ordering those of the previous call may be
@@ -852,14 +458,14 @@ static K1Shape k1_shape(const struct fosphor *self, const void *d_iq, int hop, i
 }
 
 /* Spectra per tile of an FFT launch (the rule is k1_plan's; the tile depends on neither the hop nor the sample pointer) */
-static int pick_tile(const struct fosphor *self, int total, int batch)
+int fosphor_amd::pick_tile(const struct fosphor *self, int total, int batch)
 {
 	assert(self->log2n != 13 || batch % 16 == 0);	/* (every entry point asks for it: the fallback tile of 8 divides the batch) */
 	return k1_plan(k1_shape(self, NULL, 0, total, batch, 0)).tile;
 }
 
-static void fill_k1(struct fosphor *self, K1Params *k1, const void *d_iq, int total, int tile,
-                    int wf_pos0, int wf_first, int hop = 0)
+void fosphor_amd::fill_k1(struct fosphor *self, K1Params *k1, const void *d_iq, int total, int tile,
+                          int wf_pos0, int wf_first, int hop)
 {
 	const double A = (double)self->histo_scale * 0.150514997831990597606869447362;
 	const double C = (double)self->histo_scale * (double)self->histo_offset;
@@ -1007,14 +613,14 @@ extern "C" int fosphor_amd_plan_k1(int log2n, int n_bins, int iq_format, int hop
 }
 
 /* ... of a launch of this instance */
-static struct fosphor_amd_count_plan plan_count(const struct fosphor *self, int n_batches, int batch, int pipelined)
+struct fosphor_amd_count_plan fosphor_amd::plan_count(const struct fosphor *self, int n_batches, int batch, int pipelined)
 {
-	return plan_count(self->log2n, self->n_bins, self->slab_chunks, self->kn_rowmask_off, self->kn_no_sum16, n_batches, batch, pipelined);
+	return ::plan_count(self->log2n, self->n_bins, self->slab_chunks, self->kn_rowmask_off, self->kn_no_sum16, n_batches, batch, pipelined);
 }
 
 /* The count-kernel fields every K2 launch sets alike: `total` spectra of the current set's bin indices / tile partials in batches of
  * `batch`, counted `chunk` spectra per work-group; the first of them is spectrum t_offset of a batch of weight_batch (live-sum weights) */
-static void fill_k2(const struct fosphor *self, K2Params *k2, int total, int batch, int chunk, int tile, int t_offset, int weight_batch)
+void fosphor_amd::fill_k2(const struct fosphor *self, K2Params *k2, int total, int batch, int chunk, int tile, int t_offset, int weight_batch)
 {
 	memset(k2, 0, sizeof(*k2));
 	k2->bins = self->d_bins; k2->partial = self->d_partial;
@@ -1028,7 +634,7 @@ static void fill_k2(const struct fosphor *self, K2Params *k2, int total, int bat
 
 /* The per-chunk float partials of n_batches batches of cpb chunks each, reduced into live-sum / max slot lslot; sum16: the chunks'
  * 16-bit count slabs in d_slab16 added into the 32-bit hit counts of slot slot0 as well (k2c_sum) */
-static hipError_t launch_chunk_sum(struct fosphor *self, int n_batches, int cpb, int slot0, int lslot, int sum16, hipStream_t st)
+hipError_t fosphor_amd::launch_chunk_sum(struct fosphor *self, int n_batches, int cpb, int slot0, int lslot, int sum16, hipStream_t st)
 {
 	K2bParams k2b;
 	memset(&k2b, 0, sizeof(k2b));
@@ -1048,8 +654,8 @@ static hipError_t launch_chunk_sum(struct fosphor *self, int n_batches, int cpb,
 /* K2 (+K2b) for n_batches batches of `batch` spectra whose bin indices / tile partials are in
  * d_bins / d_partial, handed off as `plan` says; results land in slot `slot0`.. of hc / live_sum / vmax (pipelined launches: of
  * hit-count set hset). */
-static int run_count(struct fosphor *self, const struct fosphor_amd_count_plan &plan, int n_batches, int batch, int tile, int slot0,
-                     int hset, int t_offset, int weight_batch, hipStream_t st)
+int fosphor_amd::run_count(struct fosphor *self, const struct fosphor_amd_count_plan &plan, int n_batches, int batch, int tile, int slot0,
+                           int hset, int t_offset, int weight_batch, hipStream_t st)
 {
 	K2Params k2;
 	const int cpb = plan.cpb;
@@ -1109,8 +715,8 @@ static int ensure_rise_table(struct fosphor *self, int batch, hipStream_t st)
 	return 1;
 }
 
-static int run_merge(struct fosphor *self, const struct fosphor_amd_count_plan &plan, int n_batches, int batch, int slot0, int hset,
-                     hipStream_t st, int cell_begin = 0, int cell_end = 0)
+int fosphor_amd::run_merge(struct fosphor *self, const struct fosphor_amd_count_plan &plan, int n_batches, int batch, int slot0, int hset,
+                           hipStream_t st, int cell_begin, int cell_end)
 {
 	K3Params k3;
 	const int lslot = self->live_slot(slot0, hset);
@@ -1174,7 +780,7 @@ error:
 }
 
 /* the other FFT streams see what the caller (and prepare()) queued on `stream` ... */
-static int k1_streams_fork(struct fosphor *self)
+int fosphor_amd::k1_streams_fork(struct fosphor *self)
 {
 	if (self->f.in.record(self->stream) != hipSuccess)
 		return -EIO;
@@ -1185,7 +791,7 @@ static int k1_streams_fork(struct fosphor *self)
 }
 
 /* ... and what the caller queues on `stream` next follows every K1 queued on them */
-static int k1_streams_join(struct fosphor *self)
+int fosphor_amd::k1_streams_join(struct fosphor *self)
 {
 	for (int i = 1; i < self->n_k1_streams; i++)
 		if (self->f.k1s_done[i].record(self->k1_streams[i]) != hipSuccess || self->f.k1s_done[i].wait(self->stream) != hipSuccess)
@@ -1197,7 +803,7 @@ static int k1_streams_join(struct fosphor *self)
  * time frame (its row goes to ring position wf_pos + t), and rows are stored for the spectra from first_row on (same frame).  The
  * piece writes the next intermediate set of the rotation once the count kernel that read that set last is done, and the count
  * stream waits for the piece.  Returns the set (k1_set_release() behind the count kernel that reads it), -1 on error. */
-static int k1_piece(struct fosphor *self, hipStream_t ks, const void *d_iq, int t, int sub_total, int tile, int first_row, int hop)
+int fosphor_amd::k1_piece(struct fosphor *self, hipStream_t ks, const void *d_iq, int t, int sub_total, int tile, int first_row, int hop)
 {
 	K1Params k1;
 	const int set = self->pp;
@@ -1234,7 +840,7 @@ error:
 }
 
 /* ... behind the count kernel (queued on the count stream) that read intermediate set `set`: the set is free again */
-static int k1_set_release(struct fosphor *self, int set)
+int fosphor_amd::k1_set_release(struct fosphor *self, int set)
 {
 	if (self->overlap)
 		HIP_TRY(self->f.set_free[set].record(count_stream(self)), "record set free");
@@ -1333,7 +939,7 @@ error:
 /* The checks of every call that reads the caller's device samples: `spectra` spectra from d_samples, their windows advancing
  * N / overlap samples (1: back to back).  sc16 samples are dwords: a device pointer to them must be 4-byte aligned (fp32 / fp16
  * callers are not checked here). */
-static int device_call_ok(const struct fosphor *self, const void *d_samples, long long spectra, int overlap)
+int fosphor_amd::device_call_ok(const struct fosphor *self, const void *d_samples, long long spectra, int overlap)
 {
 	return self && d_samples && spectra <= self->max_spectra && overlap >= 1 && overlap <= self->n && self->n % overlap == 0 &&
 	       !(self->iq_format == FOSPHOR_AMD_IQ_SC16 && ((uintptr_t)d_samples & 3));
@@ -1651,721 +1257,6 @@ extern "C" int fosphor_amd_bin(struct fosphor *self, const void *d_fft, void *d_
 	return hipStreamSynchronize(self->stream) == hipSuccess ? 0 : -EIO;
 }
 
-/* ------------------------------------------------------------------------ */
-/* Multi-GPU split                                                          */
-/* ------------------------------------------------------------------------ */
-
-/* Spectra [t_offset, t_offset + n_local) of a batch of total_batch spectra (a time shard of a display frame), windows advancing
- * N / overlap samples, counted into partial slot `slot`; rows are stored for the spectra that survive in the ring */
-static int accumulate(struct fosphor *self, const void *d_samples, int n_local, int t_offset, int total_batch, int overlap)
-{
-	if (!device_call_ok(self, d_samples, n_local, overlap) || n_local < 16 || (n_local & 15) || (t_offset & 15) ||
-	    t_offset < 0 || t_offset + n_local > total_batch)
-		return -EINVAL;
-	const int did_prep = self->win_dirty || self->thr_dirty || self->state == ST_BOOTING;
-	const int hop = self->n / overlap;
-	const int first_row = total_batch - self->wf_rows;	/* spectrum t_offset + t stores its row iff t_offset + t >= first_row */
-	hipStream_t st2 = count_stream(self);
-	const struct fosphor_amd_count_plan plan = plan_count(self, 1, n_local, 0);
-	const int cpb = plan.cpb;
-	const int chunked = plan.handoff == FOSPHOR_AMD_COUNT_SUM16;	/* whole 1024-spectrum chunks, and room for their slabs */
-	const int sub_c = self->sub_samples / (1024LL * self->n) > 1 ? (int)(self->sub_samples / (1024LL * self->n)) : 1;
-
-	if (prepare(self))
-		return -EIO;
-	if (chunked && cpb > sub_c) {
-		/* A shard of several whole 1024-spectrum chunks runs like a device-resident call: sub-launches of
-		 * sub_samples samples, K1s alternating between two streams, K2 of piece j beside K1 of piece j + 1.
-		 * Each K2 leaves its chunks' packed 16-bit count slabs and float partials at the chunks' places;
-		 * one k2c_sum at the end adds all of them into the 32-bit slot that is exchanged. */
-		const size_t cells = self->cells();
-		const int use_alt = self->overlap && self->alt && self->log2n != 16;
-		/* K2 counts G consecutive 1024-spectrum chunks per work-group (16-bit counters hold 65535 spectra): 1 / G of the
-		 * slab traffic, as long as enough work-groups are left to keep the bin-index reads in flight */
-		int G = 1;
-		/* measured, N = 1024, 256 batches per frame: G = 1 / 2 / 4 / 8 -> 486 / 510 / 528 / 450 GSamples/s (at 8 the
-		 * count kernel's 128 work-groups no longer keep up with the FFT kernel) */
-		for (int want = self->kn_frame_group; want >= 1; want >>= 1)
-			if (want <= 32 && !(want & (want - 1)) && sub_c % want == 0 && cpb % want == 0) {
-				G = want;
-				break;
-			}
-		if (drain_h_sets(self, st2) || (use_alt && (did_prep || !self->relaxed) && k1_streams_fork(self)))
-			return -EIO;
-		for (int c0 = 0; c0 < cpb; c0 += sub_c) {
-			const int nc = (cpb - c0 < sub_c) ? cpb - c0 : sub_c;
-			const int t0 = c0 * 1024, sub_total = nc * 1024;
-			const int tile = pick_tile(self, sub_total, 1024);
-			hipStream_t ks = use_alt ? self->k1_streams[self->k1_seq++ % self->n_k1_streams] : self->stream;
-			const int set = k1_piece(self, ks, (const char *)d_samples + (size_t)t0 * hop * self->sample_bytes, t_offset + t0,
-			                         sub_total, tile, first_row, hop);
-			K2Params k2;
-
-			if (set < 0)
-				return -EIO;
-			self->acc_pieces++;
-			fill_k2(self, &k2, sub_total, sub_total, 1024 * G, tile, t_offset + t0, total_batch);
-			k2.hc = self->hc_slot(self->slot);
-			k2.hc16 = self->d_slab16 + (size_t)(c0 / G) * cells;
-			k2.chunk_sum = self->d_chunk_sum + (size_t)(c0 / G) * self->n;
-			k2.chunk_max = self->d_chunk_max + (size_t)(c0 / G) * self->n;
-			prof_begin(self, 1, st2);
-			HIP_TRY(launch_k2(k2, nc / G, st2), "launch count");
-			prof_end(self, st2);
-			if (k1_set_release(self, set))
-				return -EIO;
-		}
-		HIP_TRY(launch_chunk_sum(self, 1, cpb / G, self->slot, self->slot, 1, st2), "launch chunk sum");
-		if (use_alt && !self->relaxed && k1_streams_join(self))
-			return -EIO;
-	} else {
-		/* one K1 launch: same two-stream pipeline as run(): K1 on `stream`, K2 (and later the exchange and
-		 * fosphor_amd_merge's K3) on the count stream, intermediates rotating between the sets */
-		const int tile = pick_tile(self, n_local, n_local);
-		const int set = k1_piece(self, self->stream, d_samples, t_offset, n_local, tile, first_row, hop);
-		if (set < 0)
-			return -EIO;
-		self->acc_pieces++;
-		if (drain_h_sets(self, st2) || run_count(self, plan, 1, n_local, tile, self->slot, 0, t_offset, total_batch, st2) ||
-		    k1_set_release(self, set))
-			return -EIO;
-	}
-	/* the ring advances with the data (host state), so the next frame can be accumulated
-	 * before this one is merged */
-	self->wf_pos = (self->wf_pos + total_batch) & (self->wf_rows - 1);
-	self->state = ST_PENDING;
-	return 0;
-error:
-	return -EIO;
-}
-
-extern "C" int fosphor_amd_accumulate_device(struct fosphor *self, const void *d_samples,
-                                             int n_local, int t_offset, int total_batch)
-{
-	return accumulate(self, d_samples, n_local, t_offset, total_batch, 1);
-}
-
-/* the same with overlap_cc fused into the read (see fosphor_amd_process_device_overlap): d_samples is this rank's part
- * of the UNEXPANDED stream, (n_local - 1) * N / overlap + N samples starting at the first sample of its first spectrum */
-extern "C" int fosphor_amd_accumulate_device_overlap(struct fosphor *self, const void *d_samples,
-                                                     int n_local, int t_offset, int total_batch, int overlap)
-{
-	return accumulate(self, d_samples, n_local, t_offset, total_batch, overlap);
-}
-
-extern "C" int fosphor_amd_set_partial_slot(struct fosphor *self, int slot)
-{
-	if (!self || slot < 0 || slot >= self->max_batches)
-		return -EINVAL;
-	self->slot = slot;
-	return 0;
-}
-
-extern "C" int fosphor_amd_get_partials(struct fosphor *self, struct fosphor_amd_partials *out)
-{
-	if (!self || !out)
-		return -EINVAL;
-	out->d_hc = self->hc_slot(self->slot);
-	out->d_live_sum = self->live_sum_at(self->slot);
-	out->d_max = self->vmax_at(self->slot);
-	out->n_hc = self->n_bins * self->n;
-	out->n_cols = self->n;
-	return 0;
-}
-
-/* K3 on the partial arrays of the current slot (a batch of total_batch spectra), for the cells [cell_begin, cell_end) of the
- * histogram (0, 0: all of them) */
-static int merge_slot(struct fosphor *self, int total_batch, int cell_begin, int cell_end)
-{
-	if (prepare(self) || run_merge(self, plan_count(self, 1, total_batch, 0), 1, total_batch, self->slot, 0, count_stream(self), cell_begin, cell_end))
-		return -EIO;
-	self->state = ST_PENDING;
-	return 0;
-}
-
-extern "C" int fosphor_amd_merge(struct fosphor *self, int total_batch)
-{
-	if (!self || total_batch < 16)
-		return -EINVAL;
-	return merge_slot(self, total_batch, 0, 0);
-}
-
-/* ---- native exchange (RCCL over xGMI), fosphor_exchange.cpp --------------- */
-
-/* 1 when the RCCL library can be bound in this process (no communicator, no collective: purely local) */
-extern "C" int fosphor_amd_comm_available(void)
-{
-	return xchg_available();
-}
-
-/* ncclCommCount of a communicator made by fosphor_amd_comm_init */
-extern "C" int fosphor_amd_comm_count(void *comm)
-{
-	return comm ? xchg_comm_count(comm) : -EINVAL;
-}
-
-/* events around an exchange on its stream, while profiling is on (fosphor_amd_exchange_time) */
-static void xprof_begin(struct fosphor *self, hipStream_t st)
-{
-	if (!self->prof)
-		return;
-	while (self->xev_used + 2 > self->xev_pool.size()) {
-		hipEvent_t e;
-		if (hipEventCreateWithFlags(&e, dep_event_flags() & ~hipEventDisableTiming) != hipSuccess)
-			return;
-		self->xev_pool.push_back(e);
-	}
-	(void)hipEventRecord(self->xev_pool[self->xev_used], st);
-}
-
-static void xprof_end(struct fosphor *self, hipStream_t st)
-{
-	if (!self->prof || self->xev_used + 2 > self->xev_pool.size())
-		return;
-	if (hipEventRecord(self->xev_pool[self->xev_used + 1], st) == hipSuccess)
-		self->xev_used += 2;
-}
-
-/* Sum of the durations of the exchanges recorded since the last call (hipEvents on the count/merge stream around the
- * ncclGroup), and how many there were; resets.  0 exchanges when profiling was off. */
-extern "C" int fosphor_amd_exchange_time(struct fosphor *self, float *ms_total, int *count)
-{
-	if (!self || !ms_total || !count)
-		return -EINVAL;
-	if (sync_all(self))
-		return -EIO;
-	*ms_total = 0.0f; *count = 0;
-	for (size_t i = 0; i + 1 < self->xev_used; i += 2) {
-		float t = 0.0f;
-		if (hipEventElapsedTime(&t, self->xev_pool[i], self->xev_pool[i + 1]) == hipSuccess) {
-			*ms_total += t;
-			(*count)++;
-		}
-	}
-	self->xev_used = 0;
-	return 0;
-}
-
-extern "C" int fosphor_amd_comm_unique_id(void *id128)
-{
-	return id128 ? xchg_unique_id(id128) : -EINVAL;
-}
-
-extern "C" int fosphor_amd_comm_init(void **comm, int world, int rank, const void *id128)
-{
-	if (!comm || !id128 || world < 1 || rank < 0 || rank >= world)
-		return -EINVAL;
-	return xchg_comm_init(comm, world, rank, id128);
-}
-
-extern "C" int fosphor_amd_comm_destroy(void *comm)
-{
-	return comm ? xchg_comm_destroy(comm) : -EINVAL;
-}
-
-/* Between fosphor_amd_accumulate_device and fosphor_amd_merge: one ncclGroup of three all-reduces over the
- * partial arrays of the current slot, queued on the count/merge stream (behind K2, in front of K3). */
-extern "C" int fosphor_amd_exchange(struct fosphor *self, void *comm)
-{
-	if (!self || !comm)
-		return -EINVAL;
-	hipStream_t st = count_stream(self);
-	xprof_begin(self, st);
-	const int rv = xchg_allreduce3(comm, st, self->hc_slot(self->slot), self->cells(),
-	                               self->live_sum_at(self->slot), self->vmax_at(self->slot), (size_t)self->n);
-	xprof_end(self, st);
-	return rv;
-}
-
-/* Frequency-sliced form for large states (128 MiB of counts at 65536 x 512): the counts are
- * reduce-scattered -- rank r owns cells [r C / world, (r + 1) C / world) of the [bin][x] array -- and
- * fosphor_amd_merge_sliced updates only that slice of the histogram; fosphor_amd_gather_state all-gathers the
- * slices when a complete histogram is wanted on every rank (once per draw, not once per exchange). */
-static int slice_ok(const struct fosphor *self, int world, int rank)
-{
-	return self && world >= 1 && rank >= 0 && rank < world && (size_t)self->n_bins * self->n % (size_t)world == 0;
-}
-
-extern "C" int fosphor_amd_exchange_sliced(struct fosphor *self, void *comm, int world, int rank)
-{
-	if (!comm || !slice_ok(self, world, rank))
-		return -EINVAL;
-	hipStream_t st = count_stream(self);
-	xprof_begin(self, st);
-	const int rv = xchg_reduce_scatter(comm, st, self->hc_slot(self->slot), self->cells(), world, rank,
-	                                   self->live_sum_at(self->slot), self->vmax_at(self->slot), (size_t)self->n);
-	xprof_end(self, st);
-	return rv;
-}
-
-extern "C" int fosphor_amd_merge_sliced(struct fosphor *self, int total_batch, int world, int rank)
-{
-	if (!slice_ok(self, world, rank) || total_batch < 16)
-		return -EINVAL;
-	const int per = self->n_bins * self->n / world;
-	return merge_slot(self, total_batch, per * rank, per * (rank + 1));
-}
-
-extern "C" int fosphor_amd_gather_state(struct fosphor *self, void *comm, int world, int rank)
-{
-	if (!comm || !slice_ok(self, world, rank))
-		return -EINVAL;
-	const size_t cells = (size_t)self->n_bins * self->n;
-	hipStream_t st = count_stream(self);
-	if (k3_stream_enter(self, st))
-		return -EIO;
-	self->hot_valid = 0;		/* other ranks' cells arrive: the hot-row flags of the sparse merge no longer describe d_hist */
-	return xchg_allgather_f32(comm, st, self->d_hist, cells, world, rank);
-}
-
-/* ---- compact wire formats (include/fosphor_amd_wire.h, kernels in fosphor_wire.hip) ---- */
-
-static unsigned wire_rows(const struct fosphor *self)
-{
-	return (unsigned)(self->cells() / FOSPHOR_AMD_WIRE_ROW_CELLS);
-}
-
-/* what every entry point refuses before it does anything */
-static int wire_args_ok(const struct fosphor *self, int total_batch, int form, int world, int rank)
-{
-	return self && total_batch >= 16 && total_batch <= FOSPHOR_AMD_WIRE_MAX_BATCH &&
-	       (form == FOSPHOR_AMD_WIRE_PACKED16 || form == FOSPHOR_AMD_WIRE_SPARSE16) &&
-	       world >= 1 && rank >= 0 && rank < world && self->cells() % (FOSPHOR_AMD_WIRE_ROW_CELLS * 32) == 0;
-}
-
-/* hipEvents around the last launch of wire kernel `kind` (0 mask, 1 pack, 2 unpack), while profiling is on */
-static void wire_prof(struct fosphor *self, int kind, int end, hipStream_t st)
-{
-	hipEvent_t *e = &self->wire.ev[2 * kind + end];
-	if (!self->prof)
-		return;
-	if (!end)
-		self->wire.ev_rec[kind] = 0;
-	if (!*e && hipEventCreateWithFlags(e, dep_event_flags() & ~hipEventDisableTiming) != hipSuccess)
-		return;
-	if (hipEventRecord(*e, st) == hipSuccess && end && self->wire.ev[2 * kind])
-		self->wire.ev_rec[kind] = 1;
-}
-
-/* work is queued on the count stream: fosphor_amd_finish has something to wait for again (an instance that is still booting
- * stays so: its boot fills are yet to be queued) */
-static void wire_queued(struct fosphor *self)
-{
-	if (self->state == ST_READY)
-		self->state = ST_PENDING;
-}
-
-static void wire_fill(const struct fosphor *self, struct fosphor_amd_wire *out)
-{
-	out->d_masks = self->wire.d_masks;
-	out->mask_words = (int)(wire_rows(self) / 32);
-	out->world = self->wire.world;
-	out->d_words = self->wire.d_words;
-	out->n_words = self->wire.form ? self->wire.n_words : 0;
-	out->form = self->wire.form;
-	out->live_rows = self->wire.live_rows;
-	out->rows = (int)wire_rows(self);
-}
-
-static int wire_mask_stage(struct fosphor *self, int world, int rank, hipStream_t st)
-{
-	const unsigned rows = wire_rows(self);
-	const size_t part = rows / 32;
-	if (world > self->wire.mask_cap) {
-		/* (kernels of an earlier frame may still read the old buffer) */
-		HIP_TRY(hipStreamSynchronize(st), "drain the count stream before the mask buffer grows");
-		(void)hipFree(self->wire.d_masks);
-		self->wire.d_masks = nullptr;
-		self->wire.mask_cap = 0;
-		HIP_TRY(hipMalloc((void **)&self->wire.d_masks, sizeof(uint32_t) * part * world), "alloc wire masks");
-		self->wire.mask_cap = world;
-	}
-	self->wire.world = world;
-	wire_prof(self, 0, 0, st);
-	HIP_TRY(launch_wire_mask(self->hc_slot(self->slot), self->wire.d_masks + part * rank, rows, st), "launch wire mask");
-	wire_prof(self, 0, 1, st);
-	wire_queued(self);
-	self->wire.masked = world;
-	self->wire.masked_slot = self->slot;
-	return 0;
-error:
-	return -EIO;
-}
-
-static int wire_pack_stage(struct fosphor *self, int form, int world, hipStream_t st)
-{
-	const unsigned rows = wire_rows(self);
-	const size_t cells = self->cells();
-	int taken = form;
-	if (!self->wire.d_words)
-		HIP_TRY(hipMalloc((void **)&self->wire.d_words, sizeof(uint32_t) * (cells / 2)), "alloc wire words");
-	self->wire.form = 0;
-	if (form == FOSPHOR_AMD_WIRE_SPARSE16) {
-		if (!self->wire.d_union)
-			HIP_TRY(hipMalloc((void **)&self->wire.d_union, sizeof(uint32_t) * (rows / 32)), "alloc wire union mask");
-		if (!self->wire.d_prefix)
-			HIP_TRY(hipMalloc((void **)&self->wire.d_prefix, sizeof(uint32_t) * (rows / 32)), "alloc wire prefix counts");
-		if (!self->wire.d_live)
-			HIP_TRY(hipMalloc((void **)&self->wire.d_live, sizeof(uint32_t)), "alloc wire live-row count");
-		if (!self->wire.h_live)
-			HIP_TRY(hipHostMalloc((void **)&self->wire.h_live, 64, hipHostMallocMapped), "alloc wire live-row word");
-		self->wire.masked = 0;
-		wire_prof(self, 1, 0, st);
-		HIP_TRY(launch_wire_pack_sparse(self->hc_slot(self->slot), self->wire.d_masks, world, self->wire.d_union, self->wire.d_prefix,
-		                                self->wire.d_live, self->wire.h_live, self->wire.d_words, rows, st), "launch wire pack (sparse)");
-		wire_prof(self, 1, 1, st);
-		/* THE host wait of the sparse form: the all-reduce is sized by the union's live rows */
-		HIP_TRY(hipStreamSynchronize(st), "wait for the live-row count");
-		self->wire.live_rows = (int)self->wire.h_live[0];
-		if ((unsigned)self->wire.live_rows > rows / 2)
-			taken = FOSPHOR_AMD_WIRE_PACKED16;
-	} else {
-		self->wire.live_rows = -1;
-	}
-	if (taken == FOSPHOR_AMD_WIRE_PACKED16) {
-		wire_prof(self, 1, 0, st);		/* (of a frame that fell back, the dense pack is the one timed) */
-		HIP_TRY(launch_wire_pack_dense(self->hc_slot(self->slot), self->wire.d_words, cells, st), "launch wire pack (dense)");
-		wire_prof(self, 1, 1, st);
-	}
-	wire_queued(self);
-	self->wire.form = taken;
-	self->wire.packed_slot = self->slot;
-	self->wire.n_words = taken == FOSPHOR_AMD_WIRE_PACKED16 ? (int)(cells / 2) : self->wire.live_rows * FOSPHOR_AMD_WIRE_ROW_WORDS;
-	self->wire.stats[form == FOSPHOR_AMD_WIRE_PACKED16 ? FOSPHOR_AMD_WIRE_FRAMES_PACKED16 :
-	                 taken == form ? FOSPHOR_AMD_WIRE_FRAMES_SPARSE16 : FOSPHOR_AMD_WIRE_FRAMES_FELL_BACK]++;
-	self->wire.stats[FOSPHOR_AMD_WIRE_LAST_LIVE_ROWS] = self->wire.live_rows;
-	self->wire.stats[FOSPHOR_AMD_WIRE_LAST_WIRE_BYTES] = 4LL * self->wire.n_words +
-		(form == FOSPHOR_AMD_WIRE_SPARSE16 ? 4LL * world * (rows / 32) : 0);
-	return 0;
-error:
-	return -EIO;
-}
-
-static int wire_unpack_stage(struct fosphor *self, hipStream_t st)
-{
-	wire_prof(self, 2, 0, st);
-	if (self->wire.form == FOSPHOR_AMD_WIRE_PACKED16)
-		HIP_TRY(launch_wire_unpack_dense(self->wire.d_words, self->hc_slot(self->slot), self->cells(), st), "launch wire unpack (dense)");
-	else
-		HIP_TRY(launch_wire_unpack_sparse(self->wire.d_words, self->wire.d_union, self->wire.d_prefix, self->wire.d_live,
-		                                  self->hc_slot(self->slot), wire_rows(self), st), "launch wire unpack (sparse)");
-	wire_prof(self, 2, 1, st);
-	wire_queued(self);
-	self->wire.form = 0;
-	return 0;
-error:
-	return -EIO;
-}
-
-extern "C" int fosphor_amd_wire_mask(struct fosphor *self, int total_batch, int world, int rank)
-{
-	if (!wire_args_ok(self, total_batch, FOSPHOR_AMD_WIRE_SPARSE16, world, rank))
-		return -EINVAL;
-	return wire_mask_stage(self, world, rank, count_stream(self));
-}
-
-extern "C" int fosphor_amd_wire_pack(struct fosphor *self, int total_batch, int form, int world, struct fosphor_amd_wire *out)
-{
-	if (!out || !wire_args_ok(self, total_batch, form, world, 0) ||
-	    (form == FOSPHOR_AMD_WIRE_SPARSE16 && (self->wire.masked != world || self->wire.masked_slot != self->slot)))
-		return -EINVAL;
-	const int rv = wire_pack_stage(self, form, world, count_stream(self));
-	wire_fill(self, out);
-	return rv;
-}
-
-extern "C" int fosphor_amd_wire_unpack(struct fosphor *self)
-{
-	if (!self || !self->wire.form || self->wire.packed_slot != self->slot)
-		return -EINVAL;
-	return wire_unpack_stage(self, count_stream(self));
-}
-
-extern "C" int fosphor_amd_wire_get(struct fosphor *self, struct fosphor_amd_wire *out)
-{
-	if (!self || !out)
-		return -EINVAL;
-	wire_fill(self, out);
-	return 0;
-}
-
-extern "C" int fosphor_amd_exchange_compact(struct fosphor *self, void *comm, int total_batch, int form, int world, int rank)
-{
-	if (!comm || !wire_args_ok(self, total_batch, form, world, rank))
-		return -EINVAL;
-	hipStream_t st = count_stream(self);
-	int rv = 0;
-	xprof_begin(self, st);
-	if (form == FOSPHOR_AMD_WIRE_SPARSE16) {
-		rv = wire_mask_stage(self, world, rank, st);
-		rv = rv ? rv : xchg_allgather_u32(comm, st, self->wire.d_masks, wire_rows(self) / 32, rank);
-	}
-	rv = rv ? rv : wire_pack_stage(self, form, world, st);
-	rv = rv ? rv : xchg_allreduce3(comm, st, self->wire.d_words, (size_t)self->wire.n_words,
-	                               self->live_sum_at(self->slot), self->vmax_at(self->slot), (size_t)self->n);
-	rv = rv ? rv : wire_unpack_stage(self, st);
-	xprof_end(self, st);
-	return rv;
-}
-
-extern "C" int fosphor_amd_wire_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_WIRE_STATS])
-{
-	if (!self || !stats)
-		return -EINVAL;
-	for (int i = 0; i < FOSPHOR_AMD_WIRE_STATS; i++)
-		stats[i] = self->wire.stats[i];
-	return 0;
-}
-
-extern "C" int fosphor_amd_wire_kernel_times(struct fosphor *self, float ms[3])
-{
-	if (!self || !ms)
-		return -EINVAL;
-	if (hipStreamSynchronize(count_stream(self)) != hipSuccess)
-		return -EIO;
-	for (int k = 0; k < 3; k++) {
-		ms[k] = -1.0f;
-		if (self->wire.ev_rec[k] && hipEventElapsedTime(&ms[k], self->wire.ev[2 * k], self->wire.ev[2 * k + 1]) != hipSuccess)
-			ms[k] = -1.0f;
-	}
-	return 0;
-}
-
-/* ------------------------------------------------------------------------ */
-/* Measurement                                                              */
-/* ------------------------------------------------------------------------ */
-
-extern "C" void fosphor_amd_profile(struct fosphor *self, int enable)
-{
-	self->prof = enable == 2 ? 2 : (enable ? 1 : 0);
-}
-
-extern "C" int fosphor_amd_kernel_times(struct fosphor *self, float ms[3], int launches[3])
-{
-	if (!self)
-		return -EINVAL;
-	if (sync_all(self))
-		return -EIO;
-	for (int i = 0; i < 3; i++) { ms[i] = 0.0f; launches[i] = 0; }
-	for (size_t i = 0; i + 1 < self->ev_used; i += 2) {
-		float t = 0.0f;
-		int kind = self->ev_kind[i / 2];
-		if (hipEventElapsedTime(&t, self->ev_pool[i], self->ev_pool[i + 1]) == hipSuccess) {
-			ms[kind] += t;
-			launches[kind]++;
-		}
-	}
-	self->ev_used = 0;
-	self->ev_kind.clear();
-	return 0;
-}
-
-/* Time during which at least one kernel of each kind was running (union of the recorded intervals), from the
- * same events fosphor_amd_kernel_times sums.  K1s of consecutive sub-launches overlap on two streams, so the sum
- * of their individual durations counts the shared time twice; the union is what a launch costs.  Call before
- * fosphor_amd_kernel_times (which resets). */
-extern "C" int fosphor_amd_kernel_busy(struct fosphor *self, float busy_ms[3])
-{
-	if (!self)
-		return -EINVAL;
-	if (sync_all(self))
-		return -EIO;
-	for (int kind = 0; kind < 3; kind++) {
-		std::vector<std::pair<float, float> > iv;
-		for (size_t i = 0; i + 1 < self->ev_used; i += 2) {
-			float a = 0.0f, b = 0.0f;
-			if (self->ev_kind[i / 2] != kind)
-				continue;
-			if (hipEventElapsedTime(&a, self->ev_pool[0], self->ev_pool[i]) != hipSuccess ||
-			    hipEventElapsedTime(&b, self->ev_pool[0], self->ev_pool[i + 1]) != hipSuccess)
-				continue;
-			iv.push_back(std::make_pair(a, b));
-		}
-		std::sort(iv.begin(), iv.end());
-		float busy = 0.0f, cur_a = 0.0f, cur_b = -1.0f;
-		for (size_t i = 0; i < iv.size(); i++) {
-			if (cur_b < cur_a || iv[i].first > cur_b) {
-				if (cur_b >= cur_a) busy += cur_b - cur_a;
-				cur_a = iv[i].first; cur_b = iv[i].second;
-			} else if (iv[i].second > cur_b) {
-				cur_b = iv[i].second;
-			}
-		}
-		if (cur_b >= cur_a) busy += cur_b - cur_a;
-		busy_ms[kind] = busy;
-	}
-	return 0;
-}
-
-/* Measurement hook: the memory traffic of one K1 launch (same loads, same stores, same order)
- * without its arithmetic, on this instance's buffers; average of `reps` launches in ms.  The
- * intermediates of the current set are overwritten (call between launches, results unaffected:
- * every launch rewrites them before reading). */
-extern "C" int fosphor_amd_traffic_twin(struct fosphor *self, const void *d_samples, int n_batches, int batch,
-                                        int reps, float *ms_out)
-{
-	K1Params k1;
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	const int total = n_batches * batch;
-	float ms = 0.0f;
-	if (!self || !d_samples || !ms_out || reps < 1 || total < 16 || total > self->max_spectra || self->log2n != 10 || self->bins16 ||
-	    self->iq_format != FOSPHOR_AMD_IQ_FP32)
-		return -EINVAL;
-	if (fosphor_amd_finish(self) < 0 || prepare(self))
-		return -EIO;
-	fill_k1(self, &k1, d_samples, total, pick_tile(self, total, batch), 0, total);
-	hipError_t le = hipEventCreate(&e0);
-	if (le == hipSuccess) le = hipEventCreate(&e1);
-	for (int i = 0; i < 3 && le == hipSuccess; i++)
-		le = launch_k1_traffic_twin(k1, self->stream);
-	if (le == hipSuccess) le = hipEventRecord(e0, self->stream);
-	for (int i = 0; i < reps && le == hipSuccess; i++)
-		le = launch_k1_traffic_twin(k1, self->stream);
-	if (le == hipSuccess) le = hipEventRecord(e1, self->stream);
-	if (le == hipSuccess) le = hipEventSynchronize(e1);
-	if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
-	if (e0) (void)hipEventDestroy(e0);
-	if (e1) (void)hipEventDestroy(e1);
-	if (le != hipSuccess)
-		return -EIO;
-	*ms_out = ms / (float)reps;
-	return 0;
-}
-
-/* Placement tuning.  On MI355X the same FFT launch runs in one of two states -- its bare memory traffic takes 98 or 109 us per 512 MiB of
- * IQ -- and which one is a property of the ALLOCATIONS involved: the caller's IQ buffer against this instance's intermediate sets (bin
- * indices + tile partials).  Re-allocating either re-rolls it (about even odds; offsets inside an allocation do not matter: measured up to
- * 1 GiB; tools/twin_state.py).  This call measures the memory twin of the FFT kernel against `d_samples` for every intermediate set and
- * re-allocates a set (keeping the rejected allocations until the end, so that the allocator hands out different memory) until its traffic
- * runs at >= 6.0 TB/s or `max_tries` allocations have been tried, keeping the fastest.  us_before / us_after: the slowest set before and
- * after (NULL allowed).  Returns the number of re-allocations made, or -EINVAL / -EIO.  Results never depend on it. */
-extern "C" int fosphor_amd_tune_placement(struct fosphor *self, const void *d_samples, int n_batches, int batch, int max_tries,
-                                          float *us_before, float *us_after)
-{
-	const int total = n_batches * batch;
-	if (!self || !d_samples || total < 16 || total > self->max_spectra || self->log2n != 10 || self->bins16 || max_tries < 1 ||
-	    self->iq_format != FOSPHOR_AMD_IQ_FP32)
-		return -EINVAL;
-	if (fosphor_amd_finish(self) < 0)
-		return -EIO;
-	const size_t bins_bytes = (size_t)self->max_spectra * self->n * (self->bins16 ? 2 : 1);
-	size_t tiles_max = (size_t)self->max_spectra / 4;
-	const size_t part_bytes = sizeof(float2) * tiles_max * self->n;
-	/* what the twin moves per launch: the IQ, one byte of bin index per sample, the tile partials */
-	const double bytes = (double)total * self->n * 9.0 + (double)(total / pick_tile(self, total, batch)) * self->n * 8.0;
-	/* (a launch of less than 128 MiB is timed by its launch overhead, not by the memory behind it: measured, nothing replaced) */
-	if (bytes < 128.0 * 1048576.0)
-		max_tries = 1;
-	const float good_ms = (float)(bytes / 6.0e12 * 1e3);
-	std::vector<void *> rejected;
-	int reallocs = 0;
-	float worst_before = 0.0f, worst_after = 0.0f;
-	uint32_t *const cur_bins = self->d_bins;
-	int cur_set = 0;
-	for (int i = 0; i < kSets; i++)
-		if (self->d_bins_pp[i] == cur_bins) cur_set = i;
-	for (int i = 0; i < self->n_sets; i++) {
-		float best = 0.0f;
-		for (int t = 0; t < max_tries; t++) {
-			uint32_t *nb = self->d_bins_pp[i];
-			float2 *np = self->d_partial_pp[i];
-			if (t > 0) {
-				if (hipMalloc((void **)&nb, bins_bytes) != hipSuccess)
-					break;
-				if (hipMalloc((void **)&np, part_bytes) != hipSuccess) {
-					(void)hipFree(nb);
-					break;
-				}
-			}
-			uint32_t *const ob = self->d_bins_pp[i];
-			float2 *const op = self->d_partial_pp[i];
-			self->d_bins_pp[i] = nb; self->d_partial_pp[i] = np;
-			self->d_bins = nb; self->d_partial = np;
-			float ms = 0.0f;
-			if (fosphor_amd_traffic_twin(self, d_samples, n_batches, batch, 8, &ms) != 0) {
-				self->d_bins_pp[i] = ob; self->d_partial_pp[i] = op;
-				if (t > 0) { (void)hipFree(nb); (void)hipFree(np); }
-				break;
-			}
-			if (t == 0) {
-				best = ms;
-				if (ms > worst_before) worst_before = ms;
-			} else if (ms < best) {
-				rejected.push_back(ob); rejected.push_back(op);		/* the new pair is the better one */
-				best = ms;
-				reallocs++;
-			} else {
-				self->d_bins_pp[i] = ob; self->d_partial_pp[i] = op;	/* keep what we had */
-				rejected.push_back(nb); rejected.push_back(np);
-			}
-			if (best <= good_ms)
-				break;
-		}
-		if (best > worst_after) worst_after = best;
-	}
-	for (void *q : rejected)
-		(void)hipFree(q);
-	self->d_bins = self->d_bins_pp[cur_set];
-	self->d_partial = self->d_partial_pp[cur_set];
-	if (us_before) *us_before = worst_before * 1e3f;
-	if (us_after) *us_after = worst_after * 1e3f;
-	return reallocs;
-}
-
-/* N = 8192: how many FFT launches ran in the space-sharing form (share_cus work-groups, beside the previous launch's count / merge
- * kernels) and how many took every CU, since the instance was made; cus = the shared form's work-group count (0: this device never
- * shares).  The form is chosen from the state of the queue at submit time, so two runs of the same calls may differ here -- never in
- * their results. */
-extern "C" int fosphor_amd_share_stats(struct fosphor *self, long long *shared, long long *full, int *cus)
-{
-	if (!self)
-		return -EINVAL;
-	if (shared) *shared = self->k1w_shared;
-	if (full) *full = self->k1w_full;
-	if (cus) *cus = self->share_cus;
-	return 0;
-}
-
-/* What the calls so far launched, since the instance was made: FFT pieces of fosphor_amd_accumulate_device[_overlap] (1 per call on
- * the single-launch path, one per sub-launch otherwise), chunk sums over 16-bit slabs (k2c_sum) and chunk reduces beside 32-bit
- * counts (k2b_reduce), the latter two by any entry point.  Host counters that only grow; nothing on the submit path reads them. */
-extern "C" int fosphor_amd_launch_stats(struct fosphor *self, long long *pieces, long long *k2c, long long *k2b)
-{
-	if (!self)
-		return -EINVAL;
-	if (pieces) *pieces = self->acc_pieces;
-	if (k2c) *k2c = self->n_k2c;
-	if (k2b) *k2b = self->n_k2b;
-	return 0;
-}
-
-/* Merge launches since the instance was made, by the form launch_k3 chose (k3_form): stats[0..6] in the order of K3Form, stats[7] =
- * how many of the long-batch launches (forms 1, 2, 6) read the (d, e) table from memory, stats[8] / stats[9] = the most batches one
- * launch of form 5 / form 6 merged, stats[10] = the rows the last sparse launch listed (read back from the device behind that launch;
- * -1: none yet).  The others are host counters that only grow; nothing on the submit path reads them. */
-extern "C" int fosphor_amd_merge_stats(struct fosphor *self, long long stats[FOSPHOR_AMD_MERGE_STATS])
-{
-	if (!self)
-		return -EINVAL;
-	if (!stats)
-		return 0;
-	for (int i = 0; i < K3_FORMS; i++)
-		stats[i] = self->k3_forms[i];
-	stats[FOSPHOR_AMD_MERGE_TABLE_IN_MEMORY] = self->k3_rise_mem;
-	stats[FOSPHOR_AMD_MERGE_SPARSE_MAX_BATCHES] = self->k3_sparse_max[0];
-	stats[FOSPHOR_AMD_MERGE_SPARSE_LONG_MAX_BATCHES] = self->k3_sparse_max[1];
-	stats[FOSPHOR_AMD_MERGE_SPARSE_LISTED_ROWS] = -1;
-	if (self->k3_listed) {
-		/* (the word stays as the launch left it until the scan after the next one zeroes it: k3_scan) */
-		uint32_t listed = 0;
-		if (hipMemcpyAsync(&listed, self->k3_listed, sizeof(listed), hipMemcpyDeviceToHost, self->k3_listed_stream) != hipSuccess ||
-		    hipStreamSynchronize(self->k3_listed_stream) != hipSuccess)
-			return -EIO;
-		stats[FOSPHOR_AMD_MERGE_SPARSE_LISTED_ROWS] = listed;
-	}
-	return 0;
-}
-
 extern "C" void *fosphor_amd_stream(struct fosphor *self)
 {
 	return self ? (void *)self->stream : NULL;
@@ -2441,39 +1332,6 @@ extern "C" int fosphor_amd_priv_copy_stats(struct fosphor *self, int which, int 
 extern "C" int fosphor_amd_priv_iq_format(struct fosphor *self)
 {
 	return self->iq_format;
-}
-
-/* ------------------------------------------------------------------------ */
-/* Host-side tables (no GPU)                                                */
-/* ------------------------------------------------------------------------ */
-
-extern "C" int fosphor_amd_host_thresholds(int n_bins, float histo_scale, float histo_offset, double *out)
-{
-	if (!out || n_bins < 2 || n_bins > 65536)
-		return -EINVAL;
-	build_thresholds(out, n_bins, histo_scale, histo_offset);
-	return 0;
-}
-
-
-extern "C" int fosphor_amd_host_twiddle_count(void) { return build_twiddles(NULL, 10, NULL); }
-
-extern "C" int fosphor_amd_host_twiddles(float *out)
-{
-	if (!out)
-		return -EINVAL;
-	build_twiddles((float2 *)out, 10, NULL);
-	return 0;
-}
-
-/* debug: copy the K1 phase-timing accumulators (K1_TIMING builds) to the host */
-extern "C" int fosphor_amd_debug_k1_timing(struct fosphor *self, long long *out, int n)
-{
-	if (!self || !self->d_dbg || !out || n > 16 * 4 * kK1MaxBlocks)
-		return -EINVAL;
-	if (fosphor_amd_finish(self) < 0)
-		return -EIO;
-	return hipMemcpy(out, self->d_dbg, sizeof(long long) * n, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -EIO;
 }
 
 /* Two-stream pipelining of the process paths on (1, default) or off (0: K1, K2, K3 in order on

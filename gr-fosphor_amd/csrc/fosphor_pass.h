@@ -44,7 +44,7 @@ enum {
 };
 #define FOSPHOR_COUNTERS_MAX 10		/* counters of one pass at most (FOSPHOR_AMD_BURST_STATS) */
 
-/* implemented next to struct fosphor (fosphor_api.cpp): scratch buffer `which`, at least `bytes` long -- its user has drained the
+/* implemented in fosphor_api.cpp, on struct fosphor (fosphor_instance.h, which no pass includes): scratch buffer `which`, at least `bytes` long -- its user has drained the
  * stream of every launch that used the old one before it asks for more; the counters of pass `which`; the copy behind every public
  * fosphor_amd_*_stats (n <= FOSPHOR_COUNTERS_MAX); and what fosphor_cmap.hip needs of the instance */
 extern "C" int fosphor_amd_priv_scratch(struct fosphor *self, int which, size_t bytes, void **d_scratch);

@@ -8,7 +8,7 @@ CSRC=$ROOT/gr-fosphor_amd/csrc
 for spec in "$@"; do
 	name=${spec%%:*}; flags=${spec#*:}
 	hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -fPIC -pthread -Wno-unused-function $flags -x hip -shared \
-		-o "$ROOT/build/ab/lib_$name.so" $CSRC/fosphor_kernels.hip $CSRC/fosphor_cmap.hip $CSRC/fosphor_api.cpp $CSRC/fosphor_render.cpp \
+		-o "$ROOT/build/ab/lib_$name.so" $CSRC/fosphor_kernels.hip $CSRC/fosphor_cmap.hip $CSRC/fosphor_api.cpp $CSRC/fosphor_shard.cpp $CSRC/fosphor_prof.cpp $CSRC/fosphor_tables.cpp $CSRC/fosphor_render.cpp \
 		$CSRC/fosphor_sink.cpp $CSRC/fosphor_exchange.cpp -ldl 2>&1 | grep -E "error|spill" || true &
 done
 wait
