@@ -182,6 +182,26 @@ class CorrelateValues(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("time", "rho", "gain_re", "gain_im", "gain_db", "phase_turns", "snr_db", "detections")]
 
 
+class PsdJob(C.Structure):
+    """struct fosphor_amd_psd_job (include/fosphor_amd_psd.h)"""
+    _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("win_offset", C.c_int64), ("n", C.c_int32),
+                ("fft_len_log", C.c_int32), ("hop", C.c_int32), ("pre", C.c_int32), ("trace", C.c_int32),
+                ("obw_fraction", C.c_float), ("xdb_ratio", C.c_float), ("reserved", C.c_int32)]
+
+
+class PsdRecord(C.Structure):
+    """struct fosphor_amd_psd_record"""
+    _fields_ = [("n_seg", C.c_int32), ("fft_len", C.c_int32), ("peak_bin", C.c_int32), ("peak_power", C.c_float),
+                ("obw_lo", C.c_int32), ("obw_hi", C.c_int32), ("xdb_lo", C.c_int32), ("xdb_hi", C.c_int32),
+                ("total", C.c_double), ("m1", C.c_double), ("m2", C.c_double), ("win_energy", C.c_double)]
+
+
+class PsdValues(C.Structure):
+    """struct fosphor_amd_psd_values"""
+    _fields_ = [(k, C.c_double) for k in ("mean_power", "peak_freq", "peak_db", "centroid", "rms_width", "obw", "obw_centre",
+                                          "xdb_bandwidth")]
+
+
 class ResampleJob(C.Structure):
     """struct fosphor_amd_resample_job (include/fosphor_amd_resample.h)"""
     _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("phase0", C.c_int64), ("n", C.c_int32), ("n_out", C.c_int32),
@@ -341,6 +361,19 @@ SIGNATURES = {
                                              C.POINTER(C.c_double)]),
     "fosphor_amd_resample_from_extract": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ResampleJob)]),
     "fosphor_amd_resample_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 7)]),
+    # include/fosphor_amd_psd.h
+    "fosphor_amd_psd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_int64]),
+    "fosphor_amd_psd_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_int64]),
+    "fosphor_amd_psd_n_seg": (C.c_int, [C.c_int32, C.c_int, C.c_int]),
+    "fosphor_amd_psd_window": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
+    "fosphor_amd_psd_twiddles": (C.c_int, [C.c_void_p]),
+    "fosphor_amd_psd_from_extract": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                               C.POINTER(PsdJob)]),
+    "fosphor_amd_psd_ratio_from_db": (C.c_double, [C.c_double]),
+    "fosphor_amd_psd_derive": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(PsdValues)]),
+    "fosphor_amd_psd_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 6)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

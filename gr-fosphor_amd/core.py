@@ -967,6 +967,161 @@ class Fosphor:
         """fosphor_amd_correlate_stats as a dict: calls, launches by kernel, jobs, lags, complex multiply-adds (CORRELATE_STATS)"""
         return self._stats(self.L.fosphor_amd_correlate_stats, self.CORRELATE_STATS)
 
+    PSD_STATS = ("calls", "k_group", "k_wave", "k_combine", "jobs", "segments")
+    PSD_MAX_JOBS = 4096					# FOSPHOR_AMD_PSD_MAX_JOBS (include/fosphor_amd_psd.h)
+    PSD_MIN_LOG, PSD_MAX_LOG = 6, 10			# FOSPHOR_AMD_PSD_MIN_LOG, FOSPHOR_AMD_PSD_MAX_LOG
+    PSD_TILE = 32					# FOSPHOR_AMD_PSD_TILE
+    PSD_PRES = {"none": 0, "square": 1, "fourth": 2, "magsq": 3}	# FOSPHOR_AMD_PSD_PRE_*
+    PSD_TRACES = {"none": 0, "power": 1}		# FOSPHOR_AMD_PSD_TRACE_*
+    PSD_WINDOWS = {"rect": 0, "hann": 1, "blackman_harris": 2}	# FOSPHOR_AMD_PSD_WINDOW_*
+    PSD_LDS = {"group": 37904, "wave": 19008, "combine": 22528}	# FOSPHOR_AMD_PSD_LDS_*
+    PSD_JOB_DTYPE = np.dtype([("offset", "<i8"), ("out_offset", "<i8"), ("win_offset", "<i8"), ("n", "<i4"), ("fft_len_log", "<i4"),
+                              ("hop", "<i4"), ("pre", "<i4"), ("trace", "<i4"), ("obw_fraction", "<f4"), ("xdb_ratio", "<f4"),
+                              ("reserved", "<i4")])
+    PSD_RECORD_DTYPE = np.dtype([("n_seg", "<i4"), ("fft_len", "<i4"), ("peak_bin", "<i4"), ("peak_power", "<f4"), ("obw_lo", "<i4"),
+                                 ("obw_hi", "<i4"), ("xdb_lo", "<i4"), ("xdb_hi", "<i4"), ("total", "<f8"), ("m1", "<f8"),
+                                 ("m2", "<f8"), ("win_energy", "<f8")])
+    PSD_VALUES = tuple(k for k, _ in _lib.PsdValues._fields_)
+
+    @staticmethod
+    def _psd_code(table, what, v):
+        if isinstance(v, str):
+            if v not in table:
+                raise ValueError("%s must be one of %s" % (what, ", ".join(table)))
+            return table[v]
+        return int(v)
+
+    @staticmethod
+    def psd_n_seg(n, fft_len_log, hop):
+        """fosphor_amd_psd_n_seg: the segments of a job of n samples, n < L ? 0 : (n - L) // hop + 1"""
+        rv = _lib.load().fosphor_amd_psd_n_seg(int(n), int(fft_len_log), int(hop))
+        if rv < 0:
+            _fail("fosphor_amd_psd_n_seg", rv, ValueError)
+        return rv
+
+    @staticmethod
+    def psd_window(kind, fft_len_log):
+        """fosphor_amd_psd_window: "rect", "hann" or "blackman_harris" in periodic form, float32 [2^fft_len_log]"""
+        if not Fosphor.PSD_MIN_LOG <= int(fft_len_log) <= Fosphor.PSD_MAX_LOG:
+            raise ValueError("fft_len_log must be %d .. %d" % (Fosphor.PSD_MIN_LOG, Fosphor.PSD_MAX_LOG))
+        out = np.zeros(1 << int(fft_len_log), np.float32)
+        rv = _lib.load().fosphor_amd_psd_window(Fosphor._psd_code(Fosphor.PSD_WINDOWS, "kind", kind), int(fft_len_log), out.ctypes.data)
+        if rv:
+            _fail("fosphor_amd_psd_window", rv, ValueError)
+        return out
+
+    @staticmethod
+    def psd_twiddles():
+        """fosphor_amd_psd_twiddles: the table of the pass, e^(-2 pi i m / 1024) for m < 512, complex128 [512]"""
+        out = np.zeros(512, np.complex128)
+        rv = _lib.load().fosphor_amd_psd_twiddles(out.ctypes.data)
+        if rv:
+            _fail("fosphor_amd_psd_twiddles", rv, ValueError)
+        return out
+
+    @staticmethod
+    def psd_ratio_from_db(db):
+        """fosphor_amd_psd_ratio_from_db: 10^(db / 10) for db <= 0: what a job's xdb_ratio wants"""
+        return _lib.load().fosphor_amd_psd_ratio_from_db(float(db))
+
+    @staticmethod
+    def psd_jobs(extract_jobs, fft_len_log, hop=None, win_offset=0, pre="none", trace="none", obw_fraction=0.99, xdb=-26.0):
+        """a PSD_JOB_DTYPE array from an EXTRACT_DTYPE array (fosphor_amd_psd_from_extract: each job takes the spectrum of what the
+        extract job wrote, offset = out_offset, n = n_out), the traces placed back to back from out_offset 0 on.  hop: L // 2 by
+        default; xdb: dB below the peak, at most 0"""
+        L = _lib.load()
+        ejobs = np.ascontiguousarray(np.atleast_1d(extract_jobs), dtype=Fosphor.EXTRACT_DTYPE)
+        out = np.zeros(ejobs.size, Fosphor.PSD_JOB_DTYPE)
+        pre, trace = Fosphor._psd_code(Fosphor.PSD_PRES, "pre", pre), Fosphor._psd_code(Fosphor.PSD_TRACES, "trace", trace)
+        hop = (1 << int(fft_len_log)) // 2 if hop is None else int(hop)
+        ratio = Fosphor.psd_ratio_from_db(xdb)
+        at = 0
+        for i, e in enumerate(ejobs):
+            job = _lib.PsdJob()
+            rv = L.fosphor_amd_psd_from_extract(e.tobytes(), int(win_offset), int(fft_len_log), hop, pre, trace, float(obw_fraction),
+                                                ratio, C.byref(job))
+            if rv:
+                _fail("fosphor_amd_psd_from_extract", rv, ValueError)
+            out[i] = (job.offset, at if trace else 0, job.win_offset, job.n, job.fft_len_log, job.hop, job.pre, job.trace,
+                      job.obw_fraction, job.xdb_ratio, 0)
+            at += Fosphor._psd_n_out(out[i])
+        return out
+
+    @staticmethod
+    def _psd_n_out(j):
+        """the trace floats of a job: L with a trace and a segment, else 0"""
+        return (1 << int(j["fft_len_log"])) if int(j["trace"]) and Fosphor.psd_n_seg(j["n"], j["fft_len_log"], j["hop"]) > 0 else 0
+
+    @staticmethod
+    def _psd_views(buf, jobs, n_out):
+        return [buf[int(j["out_offset"]):int(j["out_offset"]) + n] if n else None for j, n in zip(jobs, n_out)]
+
+    def psd(self, d_iq, jobs, win, n_samples=None, n_win=None):
+        """One record per job and, where the job asks for one, its trace, up to 4096 jobs in one call (fosphor_amd_psd): Welch's
+        averaged power spectrum of float32 IQ that is already in device memory, segments of L = 64 .. 1024 samples, hop apart,
+        windowed, transformed in double; peak, occupied bandwidth, x-dB bandwidth and moments in the record.  d_iq: a contiguous
+        device tensor (complex64 or float32 pairs; what extract() wrote) or a raw device pointer with n_samples; jobs: a
+        PSD_JOB_DTYPE array (psd_jobs() makes one from extract jobs); win: a float32 numpy array (uploaded; psd_window() makes
+        one), such a device tensor, or a raw device pointer with n_win.
+        Returns (records, views): a PSD_RECORD_DTYPE array copied from the device, in job order, and a list with, per job, a
+        torch float32 view of L values in ascending frequency, DC at L // 2, or None, into one device buffer."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.PSD_JOB_DTYPE)
+        if isinstance(win, np.ndarray):
+            win = torch.from_numpy(np.ascontiguousarray(win if win.size else np.zeros(1), dtype=np.float32).reshape(-1)).cuda()
+        n_samples = _iq_count(d_iq, n_samples, "samples")
+        if n_win is None:
+            if not hasattr(win, "numel"):
+                raise ValueError("a raw device pointer needs n_win")
+            if not win.is_contiguous() or str(win.dtype) != "torch.float32":
+                raise ValueError("win must be a contiguous float32 tensor")
+            n_win = win.numel()
+        n_out, cap = _outs(jobs, self._psd_n_out)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 1), dtype=torch.float32, device="cuda")
+        d_rec = torch.empty(max(jobs.size, 1) * self.PSD_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()			# the caller's samples were written on torch's stream
+        rv = self.L.fosphor_amd_psd(self.h, _ptr(d_iq), n_samples, _ptr(win), int(n_win), jobs.ctypes.data, int(jobs.size),
+                                    d_rec.data_ptr(), d_out.data_ptr(), cap)
+        if rv:
+            _fail("fosphor_amd_psd", rv, RuntimeError)
+        records = d_rec.cpu().numpy().view(self.PSD_RECORD_DTYPE)[:jobs.size].copy()
+        return records, self._psd_views(d_out, jobs, n_out)
+
+    @staticmethod
+    def psd_host(iq, jobs, win):
+        """fosphor_amd_psd_host: the same records and traces on the host, no GPU.  iq: complex64 or float32 pairs; win: float32.
+        Returns (records, views), the views float32 arrays into one buffer, or None"""
+        iq = _float_pairs(iq)
+        win = np.ascontiguousarray(win, dtype=np.float32).reshape(-1)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.PSD_JOB_DTYPE)
+        n_out, cap = _outs(jobs, Fosphor._psd_n_out)
+        out = np.zeros(max(cap, 1), np.float32)
+        records = np.zeros(max(jobs.size, 1), Fosphor.PSD_RECORD_DTYPE)
+        keep = _or_dummy(iq), _or_dummy(win)
+        rv = _lib.load().fosphor_amd_psd_host(keep[0].ctypes.data, iq.size // 2, keep[1].ctypes.data, win.size, jobs.ctypes.data,
+                                              int(jobs.size), records.ctypes.data, out.ctypes.data, cap)
+        if rv:
+            _fail("fosphor_amd_psd_host", rv, ValueError)
+        return records[:jobs.size], Fosphor._psd_views(out, jobs, n_out)
+
+    @staticmethod
+    def psd_derive(records, sample_rate):
+        """fosphor_amd_psd_derive per record: a list of dicts of PSD_VALUES (Hz relative to the burst's centre, dB, power)"""
+        L = _lib.load()
+        out = []
+        for r in np.ascontiguousarray(np.atleast_1d(records), dtype=Fosphor.PSD_RECORD_DTYPE):
+            v = _lib.PsdValues()
+            rv = L.fosphor_amd_psd_derive(r.tobytes(), float(sample_rate), C.byref(v))
+            if rv:
+                _fail("fosphor_amd_psd_derive", rv, ValueError)
+            out.append({k: getattr(v, k) for k in Fosphor.PSD_VALUES})
+        return out
+
+    def psd_stats(self):
+        """fosphor_amd_psd_stats as a dict: calls, launches by kernel, jobs, segments (PSD_STATS)"""
+        return self._stats(self.L.fosphor_amd_psd_stats, self.PSD_STATS)
+
     RESAMPLE_STATS = ("calls", "k_tile", "k_direct", "jobs_tile", "jobs_direct", "outputs", "macs")
     RESAMPLE_MAX_JOBS = 4096				# FOSPHOR_AMD_RESAMPLE_MAX_JOBS (include/fosphor_amd_resample.h)
     RESAMPLE_MAX_UP = 256				# FOSPHOR_AMD_RESAMPLE_MAX_UP
