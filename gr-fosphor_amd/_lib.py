@@ -202,6 +202,25 @@ class PsdValues(C.Structure):
                                           "xdb_bandwidth")]
 
 
+class SymbolsJob(C.Structure):
+    """struct fosphor_amd_symbols_job (include/fosphor_amd_symbols.h)"""
+    _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("n", C.c_int32), ("sps", C.c_int32), ("mode", C.c_int32),
+                ("tau", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class SymbolsRecord(C.Structure):
+    """struct fosphor_amd_symbols_record"""
+    _fields_ = [("n_sym", C.c_int32), ("first", C.c_int32), ("tau", C.c_float), ("status", C.c_int32), ("mu", C.c_double),
+                ("x_re", C.c_double), ("x_im", C.c_double), ("a0", C.c_double), ("m2", C.c_double), ("m4", C.c_double),
+                ("z2_re", C.c_double), ("z2_im", C.c_double), ("z4_re", C.c_double), ("z4_im", C.c_double)]
+
+
+class SymbolsValues(C.Structure):
+    """struct fosphor_amd_symbols_values"""
+    _fields_ = [(k, C.c_double) for k in ("tau", "t_first", "symbol_rate", "timing_depth", "sym_power", "snr_db", "phase2", "lock2",
+                                          "phase4", "lock4")]
+
+
 class ResampleJob(C.Structure):
     """struct fosphor_amd_resample_job (include/fosphor_amd_resample.h)"""
     _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("phase0", C.c_int64), ("n", C.c_int32), ("n_out", C.c_int32),
@@ -374,6 +393,15 @@ SIGNATURES = {
     "fosphor_amd_psd_ratio_from_db": (C.c_double, [C.c_double]),
     "fosphor_amd_psd_derive": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(PsdValues)]),
     "fosphor_amd_psd_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 6)]),
+    # include/fosphor_amd_symbols.h
+    "fosphor_amd_symbols": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
+    "fosphor_amd_symbols_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
+    "fosphor_amd_symbols_max_out": (C.c_int, [C.c_int32, C.c_int]),
+    "fosphor_amd_symbols_twiddles": (C.c_int, [C.c_int, C.c_void_p]),
+    "fosphor_amd_symbols_from_extract": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(SymbolsJob)]),
+    "fosphor_amd_symbols_from_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(SymbolsJob)]),
+    "fosphor_amd_symbols_derive": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(SymbolsValues)]),
+    "fosphor_amd_symbols_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 9)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

@@ -1235,6 +1235,133 @@ class Fosphor:
         """fosphor_amd_resample_stats as a dict: calls, launches and jobs by form, outputs, multiply-adds (RESAMPLE_STATS)"""
         return self._stats(self.L.fosphor_amd_resample_stats, self.RESAMPLE_STATS)
 
+    SYMBOLS_STATS = ("calls", "k_fold", "k_time", "k_pick", "k_record", "jobs_estimate", "jobs_fixed", "samples", "symbols")
+    SYMBOLS_MAX_JOBS = 4096				# FOSPHOR_AMD_SYMBOLS_MAX_JOBS (include/fosphor_amd_symbols.h)
+    SYMBOLS_MIN_SPS, SYMBOLS_MAX_SPS = 2, 64		# FOSPHOR_AMD_SYMBOLS_MIN_SPS, FOSPHOR_AMD_SYMBOLS_MAX_SPS
+    SYMBOLS_BLOCK, SYMBOLS_TILE = 64, 4096		# FOSPHOR_AMD_SYMBOLS_BLOCK, FOSPHOR_AMD_SYMBOLS_TILE
+    SYMBOLS_STAGE_SPS = 8				# FOSPHOR_AMD_SYMBOLS_STAGE_SPS
+    SYMBOLS_MODES = {"estimate": 0, "fixed": 1}		# FOSPHOR_AMD_SYMBOLS_ESTIMATE, FOSPHOR_AMD_SYMBOLS_FIXED
+    SYMBOLS_STATUS = {"ok": 0, "no_timing": 1}		# FOSPHOR_AMD_SYMBOLS_OK, FOSPHOR_AMD_SYMBOLS_NO_TIMING
+    SYMBOLS_LDS = {"fold": 33792, "time": 2048, "pick": 31968, "record": 0}	# FOSPHOR_AMD_SYMBOLS_LDS_*
+    SYMBOLS_JOB_DTYPE = np.dtype([("offset", "<i8"), ("out_offset", "<i8"), ("n", "<i4"), ("sps", "<i4"), ("mode", "<i4"),
+                                  ("tau", "<f4"), ("reserved", "<i4", (2,))])
+    SYMBOLS_RECORD_DTYPE = np.dtype([("n_sym", "<i4"), ("first", "<i4"), ("tau", "<f4"), ("status", "<i4"), ("mu", "<f8"),
+                                     ("x_re", "<f8"), ("x_im", "<f8"), ("a0", "<f8"), ("m2", "<f8"), ("m4", "<f8"), ("z2_re", "<f8"),
+                                     ("z2_im", "<f8"), ("z4_re", "<f8"), ("z4_im", "<f8")])
+    SYMBOLS_VALUES = tuple(k for k, _ in _lib.SymbolsValues._fields_)
+
+    @staticmethod
+    def _symbols_mode(mode):
+        if isinstance(mode, str):
+            if mode not in Fosphor.SYMBOLS_MODES:
+                raise ValueError("mode must be one of %s" % ", ".join(Fosphor.SYMBOLS_MODES))
+            return Fosphor.SYMBOLS_MODES[mode]
+        return int(mode)
+
+    @staticmethod
+    def symbols_max_out(n, sps):
+        """fosphor_amd_symbols_max_out: the outputs a job of n samples reserves, n < 4 ? 0 : (n - 4) // sps + 1"""
+        rv = _lib.load().fosphor_amd_symbols_max_out(int(n), int(sps))
+        if rv < 0:
+            _fail("fosphor_amd_symbols_max_out", rv, ValueError)
+        return rv
+
+    @staticmethod
+    def symbols_twiddles(sps):
+        """fosphor_amd_symbols_twiddles: the table of the pass for one sps, e^(-2 pi i k / sps) for k < sps, complex128 [sps]"""
+        out = np.zeros(max(int(sps), 1), np.complex128)
+        rv = _lib.load().fosphor_amd_symbols_twiddles(int(sps), out.ctypes.data)
+        if rv:
+            _fail("fosphor_amd_symbols_twiddles", rv, ValueError)
+        return out
+
+    @staticmethod
+    def symbols_jobs(source_jobs, sps, mode="estimate", tau=0.0):
+        """a SYMBOLS_JOB_DTYPE array from an EXTRACT_DTYPE or a RESAMPLE_JOB_DTYPE array (fosphor_amd_symbols_from_extract,
+        fosphor_amd_symbols_from_resample: each job reads what the source job wrote, offset = out_offset, n = n_out), the reserved
+        outputs placed back to back from out_offset 0 on"""
+        L = _lib.load()
+        src = np.atleast_1d(source_jobs)
+        if src.dtype == Fosphor.RESAMPLE_JOB_DTYPE:
+            make, name = L.fosphor_amd_symbols_from_resample, "fosphor_amd_symbols_from_resample"
+        else:
+            src = np.ascontiguousarray(src, dtype=Fosphor.EXTRACT_DTYPE)
+            make, name = L.fosphor_amd_symbols_from_extract, "fosphor_amd_symbols_from_extract"
+        out = np.zeros(src.size, Fosphor.SYMBOLS_JOB_DTYPE)
+        code = Fosphor._symbols_mode(mode)
+        at = 0
+        for i, s in enumerate(src):
+            job = _lib.SymbolsJob()
+            rv = make(s.tobytes(), int(sps), code, float(tau), C.byref(job))
+            if rv:
+                _fail(name, rv, ValueError)
+            out[i] = (job.offset, at, job.n, job.sps, job.mode, job.tau, (0, 0))
+            at += Fosphor.symbols_max_out(job.n, job.sps)
+        return out
+
+    @staticmethod
+    def _symbols_outs(jobs):
+        return _outs(jobs, lambda j: Fosphor.symbols_max_out(int(j["n"]), int(j["sps"])))
+
+    def symbols(self, d_iq, jobs, n_samples=None):
+        """One record and one run of symbol-rate samples per job, up to 4096 jobs in one call (fosphor_amd_symbols): the symbol
+        phase from the symbol-rate line of |y|^2 (or the job's own tau), a cubic Lagrange fractional delay and a decimation by
+        sps, over float32 IQ that is already in device memory.  d_iq: a contiguous device tensor (complex64 or float32 pairs; what
+        extract() or resample() wrote) or a raw device pointer with n_samples; jobs: a SYMBOLS_JOB_DTYPE array (symbols_jobs()
+        makes one from extract or resample jobs; out_offset is honoured, the reserved ranges must not overlap).
+        Returns (records, views): a SYMBOLS_RECORD_DTYPE array copied from the device, in job order, and a list with one torch
+        complex64 view of n_sym symbols per job, into one device buffer."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.SYMBOLS_JOB_DTYPE)
+        n_samples = _iq_count(d_iq, n_samples, "samples")
+        _, cap = self._symbols_outs(jobs)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 1), dtype=torch.complex64, device="cuda")
+        d_rec = torch.empty(max(jobs.size, 1) * self.SYMBOLS_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()			# the caller's samples were written on torch's stream
+        rv = self.L.fosphor_amd_symbols(self.h, _ptr(d_iq), n_samples, jobs.ctypes.data, int(jobs.size), d_rec.data_ptr(),
+                                        d_out.data_ptr(), cap)
+        if rv:
+            _fail("fosphor_amd_symbols", rv, RuntimeError)
+        records = d_rec.cpu().numpy().view(self.SYMBOLS_RECORD_DTYPE)[:jobs.size].copy()
+        return records, [d_out[int(j["out_offset"]):int(j["out_offset"]) + int(r["n_sym"])] for j, r in zip(jobs, records)]
+
+    @staticmethod
+    def symbols_host(iq, jobs):
+        """fosphor_amd_symbols_host: the same records and symbols on the host, no GPU.  iq: complex64 or float32 pairs.  Returns
+        (records, views), the views complex64 arrays into one buffer"""
+        iq = _float_pairs(iq)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.SYMBOLS_JOB_DTYPE)
+        _, cap = Fosphor._symbols_outs(jobs)
+        out = np.zeros(max(cap, 1), np.complex64)
+        records = np.zeros(max(jobs.size, 1), Fosphor.SYMBOLS_RECORD_DTYPE)
+        keep = _or_dummy(iq)
+        rv = _lib.load().fosphor_amd_symbols_host(keep.ctypes.data, iq.size // 2, jobs.ctypes.data, int(jobs.size),
+                                                  records.ctypes.data, out.ctypes.data, cap)
+        if rv:
+            _fail("fosphor_amd_symbols_host", rv, ValueError)
+        records = records[:jobs.size]
+        return records, [out[int(j["out_offset"]):int(j["out_offset"]) + int(r["n_sym"])] for j, r in zip(jobs, records)]
+
+    @staticmethod
+    def symbols_derive(records, sps, sample_rate):
+        """fosphor_amd_symbols_derive per record: a list of dicts of SYMBOLS_VALUES (symbols, seconds, Hz, dB, radians).  sps: one
+        value for all the records or one per record"""
+        L = _lib.load()
+        records = np.ascontiguousarray(np.atleast_1d(records), dtype=Fosphor.SYMBOLS_RECORD_DTYPE)
+        out = []
+        for r, s in zip(records, np.broadcast_to(np.asarray(sps), records.shape)):
+            v = _lib.SymbolsValues()
+            rv = L.fosphor_amd_symbols_derive(r.tobytes(), int(s), float(sample_rate), C.byref(v))
+            if rv:
+                _fail("fosphor_amd_symbols_derive", rv, ValueError)
+            out.append({k: getattr(v, k) for k in Fosphor.SYMBOLS_VALUES})
+        return out
+
+    def symbols_stats(self):
+        """fosphor_amd_symbols_stats as a dict: calls, launches by kernel, jobs by mode, samples, symbols (SYMBOLS_STATS)"""
+        return self._stats(self.L.fosphor_amd_symbols_stats, self.SYMBOLS_STATS)
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

@@ -8,7 +8,8 @@
  * the angle, and it is pinned the way fosphor_portable_math.h pins log10: fosphor_amd_atan2_turns below is a fixed sequence of
  * IEEE double operations rounded once to float32, so the device, fosphor_amd_demod_host and the numpy model
  * (tests/demod_model.py) agree to the bit.  No sqrt, no libm call and no float32 division anywhere in the pass: magnitude and dB
- * traces, which would need a pinned sqrt / log10 on the device, are not this pass; neither are phase unwrapping or symbol timing.
+ * traces, which would need a pinned sqrt / log10 on the device, are not this pass; neither is phase unwrapping, and symbol timing
+ * is fosphor_amd_symbols' work (fosphor_amd_symbols.h), which takes its angle from fosphor_amd_atan2_turns below.
  * The whole number of samples per symbol that integrate-and-dump wants is fosphor_amd_resample's work (fosphor_amd_resample.h).
  *
  * Conventions, those of fosphor_amd_measure.h: the device entry point waits for pending fosphor_process work first

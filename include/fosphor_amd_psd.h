@@ -13,7 +13,7 @@
  *
  * Not this pass: transforms beyond FOSPHOR_AMD_PSD_MAX_LOG (average shorter segments, or decimate further), detrending, a
  * logarithmic trace (10 log10 of a float is the caller's), and the symbol timing itself, which starts from the line that
- * FOSPHOR_AMD_PSD_PRE_MAGSQ shows.
+ * FOSPHOR_AMD_PSD_PRE_MAGSQ shows: fosphor_amd_symbols (fosphor_amd_symbols.h) takes that one line and gives the symbols.
  *
  * Conventions, those of fosphor_amd_correlate.h: the device entry point waits for pending fosphor_process work first
  * (fosphor_amd_finish), runs on the instance's stream and returns when its outputs are complete; it writes no state of the
