@@ -1,12 +1,12 @@
 """The burst-IQ passes at the sizes their interface is built for: the input sets tests/test_job_scale_cpu.py,
-tests/test_gpu_job_scale.py and tests/test_gpu_job_far.py share, one view of the five passes over them, and the geometry of the far
+tests/test_gpu_job_scale.py and tests/test_gpu_job_far.py share, one view of the seven passes over them, and the geometry of the far
 buffer.
 
-A case here is a Case: the pass, its jobs and the host copies of its buffers.  The five models stay what they are
-(tests/extract_model.py, resample_model.py, measure_model.py, demod_model.py, correlate_model.py); this file only names, per pass,
-the job field that places the input, the width of an output element, the stats a call must leave and the comparison the pass's
-contract allows: bit for bit where the contract pins the order of the operations (resample, demod, correlate), inside
-measure_model.job_tolerance and extract_model.bound where it leaves the order open.
+A case here is a Case: the pass, its jobs and the host copies of its buffers.  The seven models stay what they are
+(tests/extract_model.py, resample_model.py, measure_model.py, demod_model.py, correlate_model.py, psd_model.py, symbols_model.py);
+this file only names, per pass, the job field that places the input, the width of an output element, the stats a call must leave
+and the comparison the pass's contract allows: bit for bit where the contract pins the order of the operations (resample, demod,
+correlate, psd, symbols), inside measure_model.job_tolerance and extract_model.bound where it leaves the order open.
 
 The long cases
   measure    130 * CHUNK + 5 samples: k_measure_combine folds 64 partials a round, so three rounds.  Plants (LONG_MEASURE_PLANTS)
@@ -17,8 +17,21 @@ The long cases
              behind the first window, in tiles 64, 66 and 128: all beyond the first round, 64 and 128 in lane 0.
   resample   U = 256 and an input of 2^24 + 64 samples of which only the tail is read: positions p = phase0 + m D of the up-sampled
              rate around (n - Q) U, just beyond 2^32.
-The full tables: exactly MAX_JOBS jobs of tiny shapes in shuffled order, every 11th without work.
+  psd        130 * TILE + 5 segments at L = 64 (hop 1, WAVE), 256 (hop 3) and 1024 (hop 7, GROUP): k_psd_combine adds 131 tiles one
+             after the other, the last of 5 segments; copies cut to 64 * TILE and 64 * TILE + 1 segments (64 and 65 tiles) with a
+             job without a segment between them; FOURTH, and a job without a trace.
+  symbols    R = 19 * TILE + 5 symbols at sps 3 and 64 (ESTIMATE) and 2 (FIXED): 20 fold tiles and 20 pick tiles, which
+             k_sym_time and k_sym_record add under `#pragma unroll 8` -- two unrolled bodies and a remainder of 4; sps 8 with
+             8 * TILE (one body exactly) and 8 * TILE + 1 symbols; a job of n = 0 in between.
+The full tables: exactly MAX_JOBS jobs of tiny shapes in shuffled order, every 11th without work (psd's and symbols' are their
+models' own full_table_case()).
 The far buffer: FAR_SAMPLES float2 samples, about 16.01 GiB; bases and their aliases below.
+The long far jobs of psd and symbols read n = 2^31 - 1 samples, which no model can hold: the far buffer is one noise block of
+PERIOD samples repeated, PERIOD a multiple of the job's tile stride (TILE hop, TILE sps), so tile c of the job sees the samples of
+tile c mod (PERIOD / stride).  periodic_psd and periodic_symbols compute those PERIOD / stride distinct full tiles and the last,
+partial one with the models' own functions and add them in the pinned serial order: the whole record, the whole trace, and the
+symbols of the first period and of the last tile, bit for bit.  PERIOD = 3 * 2^18 divides neither 2^31 nor 2^32 (both leave
+2^18 or 2^19 samples), so a position truncated to 31 or 32 bits reads other samples.
 
 What these cases are aimed at: every expression of the kernels that forms an address or a position from offset, first, out_offset,
 tpl_offset, phase0, m0, k0, c or blockIdx.x, with the type it is evaluated in, as read in gr-fosphor_amd/csrc (all are 64-bit, or
@@ -47,6 +60,26 @@ below 2^31 because the prefix gives a job no work-group beyond its n, n_out or n
                     parts + blockIdx.x: pointer + uint32.
   k_correlate_combine  parts + prefix[j]: pointer + uint32; parts[c], parts[c - 1], parts[best_tile]: int, < tiles.
                     records + j: below MAX_JOBS.  tpl + tpl_offset: pointer + int64.
+  psd_tile          (k_psd_group: c = (int)(blockIdx.x - prefix[j]); k_psd_wave: g = blockIdx.x * 4 + wave: uint32, below the
+                    form's tiles, c = (int)(g - prefix[j]))  s0 = c * 32, s1 = min(s0 + 32, n_seg): int, s0 < n_seg <= 2^31 - 64.
+                    y = iq + offset: pointer + int64.  y + (int64_t)s * hop: int64 (s hop + L <= n all the same).
+                    win + win_offset: pointer + int64; w[i], i < L.  parts + part0 + (int64_t)c * L: pointer + int64 + int64, up to
+                    2^29 doubles in one job and 2^41 in a call.  bitrev, pad, i0, i1, j << (kLog - tt): int, below 1088.
+  k_psd_combine     j = blockIdx.x * 4 + wave: int, below MAX_JOBS.  tiles = (n_seg + 31) / 32: int, n_seg + 31 < 2^31.
+                    T = parts + part0 + ((i + half) & (L - 1)): pointer + int64 + int; T[(int64_t)c * L]: int64.
+                    out[out_offset + i]: int64 + int.  records[record]: below MAX_JOBS.  (double)n_seg: exact.
+  k_sym_fold        c = (int)(blockIdx.x - fold_prefix[j]); n / sps - c * 4096: int, c * 4096 <= n / sps.
+                    tile = iq + offset + (int64_t)c * 4096 * sps: pointer + int64 + int64.  tile + s0 * sps: int, below 4096 * 64.
+                    i + (i / row) * sps, b * (row + sps) + k: int, below 4160.  parts[part0 + (int64_t)c * sps + t]: int64.
+  k_sym_time        j: int, below MAX_JOBS.  tiles = (R + 4095) / 4096: int, R <= (2^31 - 1) / 3.  parts + part0 + lane: pointer +
+                    int64 + int; T[(int64_t)c * sps]: int64.  tw + tw0: int, below 2 * 64 * 63.  state_of: base = e * sps in double,
+                    n - 3 - first: int, first <= 64.
+  k_sym_pick        j0 = (int)(blockIdx.x - pick_prefix[j]) * 4096: int, < max_out <= 2^30.  y = iq + offset: pointer + int64.
+                    out = out + out_offset + j0: pointer + int64 + int.  span = y + (first - 1) + (int64_t)(j0 + s0) * sps: int +
+                    int64, j0 + s0 < n_sym.  span + t * sps, (count - 1) * sps + 4: int, below 256 * 64.  out[s0 + t]: int, < 4096.
+                    mom[(mom0 + j0 / 4096) * 6 + t]: int64.
+  k_sym_record      tiles = min((n_sym + 4095) / 4096, tiles_max): int.  mom + mom0 * 6 + lane: pointer + int64 + int;
+                    T[(int64_t)c * 6]: int64.  records[j], counts[j]: below MAX_JOBS.
 None is a 32-bit product or sum that can pass 2^31: nothing to fix."""
 import functools
 
@@ -56,32 +89,36 @@ import correlate_model as cm
 import demod_model as dm
 import extract_model as em
 import measure_model as mm
+import psd_model as pm
 import resample_model as rm
+import symbols_model as sm
 
 SENTINEL = 0x5a5a5a5a
-PASSES = ("extract", "resample", "measure", "demod", "correlate")
-MODELS = {"extract": em, "resample": rm, "measure": mm, "demod": dm, "correlate": cm}
+PASSES = ("extract", "resample", "measure", "demod", "correlate", "psd", "symbols")
+MODELS = {"extract": em, "resample": rm, "measure": mm, "demod": dm, "correlate": cm, "psd": pm, "symbols": sm}
 MAX_JOBS = 4096
 GUARD = 3						# every model's: output elements before, between and behind the jobs' ranges
 
 
 class Case:
     """name: the pass; jobs; iq: float32 [n][2], or int16 / float16 [n][2] with fmt; taps: float32 (extract, resample); tpl:
-    float32 [n][2] or None where the templates lie in iq (correlate)"""
+    float32 [n][2] or None where the templates lie in iq (correlate); win: float32, the windows (psd)"""
 
-    def __init__(self, name, jobs, iq, taps=None, tpl=None, fmt=em.FP32):
+    def __init__(self, name, jobs, iq, taps=None, tpl=None, fmt=em.FP32, win=None):
         self.name, self.jobs, self.fmt = name, np.ascontiguousarray(jobs, MODELS[name].JOB_DTYPE), fmt
         self.iq = np.ascontiguousarray(iq, em.RAW_DTYPE[fmt]).reshape(-1, 2)
         self.taps = None if taps is None else np.ascontiguousarray(taps, np.float32)
         self.tpl = None if tpl is None else np.ascontiguousarray(tpl, np.float32).reshape(-1, 2)
+        self.win = None if win is None else np.ascontiguousarray(win, np.float32).reshape(-1)
 
     def with_jobs(self, jobs):
-        return Case(self.name, jobs, self.iq, self.taps, self.tpl, self.fmt)
+        return Case(self.name, jobs, self.iq, self.taps, self.tpl, self.fmt, self.win)
 
     def model_case(self):
         """the case as its model's functions take it"""
         return {"extract": (self.fmt, self.iq, self.jobs, self.taps), "resample": (self.iq, self.taps, self.jobs),
-                "measure": (self.iq, self.jobs), "demod": (self.iq, self.jobs), "correlate": (self.iq, self.tpl, self.jobs)}[self.name]
+                "measure": (self.iq, self.jobs), "demod": (self.iq, self.jobs), "correlate": (self.iq, self.tpl, self.jobs),
+                "psd": (self.iq, self.win, self.jobs), "symbols": (self.iq, self.jobs)}[self.name]
 
 
 def from_model(name, case):
@@ -93,13 +130,17 @@ def from_model(name, case):
         return Case(name, case[2], case[0], taps=case[1])
     if name == "correlate":
         return Case(name, case[2], case[0], tpl=case[1])
+    if name == "psd":
+        return Case(name, case[2], case[0], win=case[1])
     return Case(name, case[1], case[0])
 
 
-# ---- one view of the five passes --------------------------------------------------------------------------------------------------
+# ---- one view of the seven passes -------------------------------------------------------------------------------------------------
 
-IN_FIELD = {"extract": "first", "resample": "offset", "measure": "offset", "demod": "offset", "correlate": "offset"}
-OUT_WORDS = {"extract": 2, "resample": 2, "measure": 0, "demod": 1, "correlate": 1}	# 32-bit words of an out_offset unit
+IN_FIELD = {"extract": "first", "resample": "offset", "measure": "offset", "demod": "offset", "correlate": "offset", "psd": "offset",
+            "symbols": "offset"}
+OUT_WORDS = {"extract": 2, "resample": 2, "measure": 0, "demod": 1, "correlate": 1, "psd": 1, "symbols": 2}	# 32-bit words of an out_offset unit
+WITH_RECORDS = ("measure", "correlate", "psd", "symbols")
 
 
 def sample_bytes(case):
@@ -107,19 +148,34 @@ def sample_bytes(case):
 
 
 def n_out(name, job):
-    """the output elements of a job, in units of its out_offset"""
+    """the output elements of a job, in units of its out_offset; a symbols job reserves its max_out"""
     if name in ("extract", "resample"):
         return int(job["n_out"])
     if name == "demod":
         return dm.n_out(int(job["mode"]), int(job["n"]), int(job["avg"]))
     if name == "correlate":
         return cm.n_out(int(job["trace"]), int(job["n"]), int(job["tpl_len"]))
+    if name == "psd":
+        return pm.n_out(job)
+    if name == "symbols":
+        return sm.job_max_out(job)
     return 0
 
 
 def has_out(name, job):
-    """does out_offset of the job mean anything?  A correlate job without a trace must leave it 0"""
+    """does out_offset of the job mean anything?  A correlate or psd job without a trace must leave it 0"""
+    if name == "psd":
+        return int(job["trace"]) != pm.T_NONE
     return name != "measure" and not (name == "correlate" and int(job["trace"]) == cm.NONE)
+
+
+def has_work(name, job):
+    """does the job give a work-group something to do?"""
+    if name == "measure":
+        return int(job["n"]) > 0
+    if name == "psd":
+        return pm.job_n_seg(job) > 0
+    return n_out(name, job) > 0
 
 
 def capacity(name, jobs):
@@ -154,14 +210,25 @@ def forms(name, jobs):
         return ["wave" if mm.form(int(j["n"])) == mm.FORM_WAVE else "split" for j in jobs]
     if name == "demod":
         return ["direct" if j["avg"] == 1 else "avg" for j in jobs]
+    if name == "psd":
+        return ["group" if int(j["fft_len_log"]) > pm.WAVE_MAX_LOG else "wave" for j in jobs]
+    if name == "symbols":
+        return ["estimate" if int(j["mode"]) == sm.ESTIMATE else "fixed" for j in jobs]
     return ["tile"] * len(jobs)
 
 
-def expected_stats(name, jobs):
-    """the stats delta one successful call leaves: the forms that ran, and what they were given"""
+def expected_stats(name, jobs, records=None):
+    """the stats delta one successful call leaves: the forms that ran, and what they were given.  records: what the call wrote
+    (symbols alone: its counter of symbols is the records' n_sym, which the caller holds to the model)"""
     f = np.array(forms(name, jobs))
     if name == "resample":
         return rm.expected_stats(jobs)
+    if name == "symbols":
+        return sm.expected_stats(jobs, records)
+    if name == "psd":					# what tests/test_gpu_psd.py's Box.run asserts
+        segs = np.array([pm.job_n_seg(j) for j in jobs])
+        return dict(calls=1, k_group=int(((f == "group") & (segs > 0)).any()), k_wave=int(((f == "wave") & (segs > 0)).any()),
+                    k_combine=1, jobs=len(jobs), segments=int(segs.sum()))
     if name == "extract":
         live = jobs["n_out"] > 0
         return dict(calls=1, k_tile=int((f[live] == "tile").any()), k_wave=int((f[live] == "wave").any()),
@@ -182,8 +249,9 @@ def expected_stats(name, jobs):
 
 
 class Model:
-    """what the model says of a case, computed once: records (measure, correlate), the image of the output buffer as uint32 words
-    with SENTINEL wherever no job writes (resample, demod, correlate), or the float64 outputs and bounds per job (extract)"""
+    """what the model says of a case, computed once: records (measure, correlate, psd, symbols), the image of the output buffer as
+    uint32 words with SENTINEL wherever no job writes (resample, demod, correlate, psd, symbols), or the float64 outputs and bounds
+    per job (extract)"""
 
     def __init__(self, case):
         name, jobs = case.name, case.jobs
@@ -197,6 +265,11 @@ class Model:
             self.image = rm.image(case.model_case(), SENTINEL)
         elif name == "correlate":
             self.records, self.image = cm.image(case.model_case(), SENTINEL)
+        elif name == "psd":
+            self.records, self.image = pm.image(case.model_case(), SENTINEL)
+        elif name == "symbols":
+            self.records, image = sm.image(case.model_case(), SENTINEL)
+            self.image = image.reshape(-1)
         else:
             x = em.widen(case.iq, case.fmt)
             self.outs = [em.extract_job(x, j, case.taps) for j in jobs]
@@ -209,7 +282,7 @@ class Model:
             mm.assert_records(rec, self.records, self.tols, tag)
             return
         assert len(words) == OUT_WORDS[name] * capacity(name, jobs), tag
-        if name == "correlate":
+        if name in ("correlate", "psd", "symbols"):
             bad = [i for i in range(len(jobs)) if rec[i].tobytes() != self.records[i].tobytes()]
             assert not bad, (tag, "records differ from the model's", bad[:4], rec[bad[:2]], self.records[bad[:2]])
         if name != "extract":
@@ -251,6 +324,10 @@ def host_twin(F, case):
         views = F.demod_host(case.iq, jobs)
     elif name == "resample":
         views = F.resample_host(case.iq, jobs, case.taps)
+    elif name == "psd":
+        rec, views = F.psd_host(case.iq, jobs, case.win)
+    elif name == "symbols":
+        rec, views = F.symbols_host(case.iq, jobs)
     else:
         rec, views = F.correlate_host(case.iq, jobs, case.iq if case.tpl is None else case.tpl)
     for j, v in zip(jobs, views):
@@ -401,6 +478,47 @@ def long_resample_case():
     return Case("resample", rm.place(rows), iq, taps=taps)
 
 
+LONG_SEGS = 130 * pm.TILE + 5
+LONG_PSD_SHAPES = ((6, 1), (8, 3), (10, 7))		# (fft_len_log, hop): WAVE; GROUP below its longest transform; GROUP at it
+
+
+def psd_n_for(segs, log, hop):
+    """the shortest n that gives `segs` segments"""
+    return (1 << log) + (segs - 1) * hop if segs else (1 << log) - 1
+
+
+def long_psd_case():
+    """ordinary noise under a Hann window.  Jobs 0 .. 2: LONG_SEGS segments at LONG_PSD_SHAPES, offsets 1, 2, 1.  Job 3: the second
+    shape under FOURTH from the other parity; job 4: the first shape without a trace.  Then job 2 cut to 64 * TILE segments, a job
+    without a segment, and job 0 cut to 64 * TILE + 1 segments."""
+    bank, rows = pm.Bank(), []
+    for i, (log, hop) in enumerate(LONG_PSD_SHAPES):
+        rows.append((1 + (i & 1), bank.at(log, pm.HANN, i), psd_n_for(LONG_SEGS, log, hop), log, hop, pm.NONE, pm.T_POWER, 0.99, 1e-2))
+    (log0, hop0), (log1, hop1), (log2, hop2) = LONG_PSD_SHAPES
+    rows.append((1, bank.at(log1, pm.HANN, 1), psd_n_for(LONG_SEGS, log1, hop1), log1, hop1, pm.FOURTH, pm.T_POWER, 0.5, 1e-3))
+    rows.append((2, bank.at(log0, pm.HANN, 0), psd_n_for(LONG_SEGS, log0, hop0), log0, hop0, pm.NONE, pm.T_NONE, 0.99, 1e-2))
+    rows.append((1, bank.at(log2, pm.HANN, 2), psd_n_for(64 * pm.TILE, log2, hop2), log2, hop2, pm.NONE, pm.T_POWER, 0.99, 1e-2))
+    rows.append((3, bank.at(log1, pm.HANN, 1), psd_n_for(0, log1, hop1), log1, hop1, pm.NONE, pm.T_POWER, 0.99, 1e-2))
+    rows.append((1, bank.at(log0, pm.HANN, 0), psd_n_for(64 * pm.TILE + 1, log0, hop0), log0, hop0, pm.NONE, pm.T_POWER, 0.99, 1e-2))
+    longest = max(r[0] + r[2] for r in rows)
+    return Case("psd", pm.place(rows), pm.noise(longest, 6565), win=bank.buffer())
+
+
+LONG_SYMS = 19 * sm.TILE + 5
+
+
+def long_symbols_case():
+    """ordinary noise.  n / sps = LONG_SYMS at sps 3 and 64 under ESTIMATE, n a few samples more than a multiple of sps, so max_out
+    is LONG_SYMS as well; n_sym = LONG_SYMS at sps 2 under FIXED (tau 0.25: first = 2); a job of n = 0; sps 8 under ESTIMATE with
+    n / sps = 8 * TILE and 8 * TILE + 1.  The offsets 1, 2, 3, 0, 2, 1."""
+    R = LONG_SYMS
+    rows = [(1, 3 * R + 1, 3, sm.ESTIMATE, 0.0), (2, 64 * R + 37, 64, sm.ESTIMATE, 0.0),
+            (3, sm.n_for(R, 2, 2, extra=1), 2, sm.FIXED, 0.25), (0, 0, 5, sm.ESTIMATE, 0.0),
+            (2, 8 * (8 * sm.TILE) + 3, 8, sm.ESTIMATE, 0.0), (1, 8 * (8 * sm.TILE + 1) + 7, 8, sm.ESTIMATE, 0.0)]
+    longest = max(r[0] + r[1] for r in rows)
+    return Case("symbols", sm.place(rows), sm.noise(longest, 6566))
+
+
 # ---- the full tables ----------------------------------------------------------------------------------------------------------------
 
 def shuffled(jobs, seed):
@@ -470,13 +588,14 @@ def full_correlate_case():
 
 
 FULL = {"extract": full_extract_case, "resample": full_resample_case, "measure": full_measure_case, "demod": full_demod_case,
-        "correlate": full_correlate_case}
+        "correlate": full_correlate_case, "psd": lambda: from_model("psd", pm.full_table_case()),
+        "symbols": lambda: from_model("symbols", sm.full_table_case())}
 
 
 def one_job_of(case):
     """the first job of a full table that has work, alone: the small call before and behind the full one"""
     name = case.name
-    work = [i for i, j in enumerate(case.jobs) if (int(j["n"]) if name == "measure" else n_out(name, j)) > 0]
+    work = [i for i, j in enumerate(case.jobs) if has_work(name, j) and (name != "psd" or n_out(name, j))]	# psd: one with a trace
     return case.with_jobs(case.jobs[work[0]:work[0] + 1])
 
 
@@ -490,8 +609,13 @@ BASES_FP32 = (2 ** 29 + 16, 2 ** 31 + 16)		# in float2 samples: byte offset beyo
 BASES_16 = BASES_FP32 + (2 ** 32 + 32,)			# in 4-byte samples
 OUT_BASE = {2: 2 ** 31 + 16, 1: 2 ** 32 + 32}		# by OUT_WORDS: beyond 2^31 complex outputs, beyond 2^32 floats
 TPL_BASE = 2 ** 31 + 48
+WIN_BASE = 2 ** 32 + 64					# in floats: inside the buffer's 2^32 + 2^21
 
 RELOCATE = {
+    "psd loads": lambda: from_model("psd", pm.loads_case()),
+    "psd tiles": lambda: from_model("psd", pm.tiles_case()),
+    "symbols loads": lambda: from_model("symbols", sm.loads_case()),
+    "symbols pick": lambda: from_model("symbols", sm.pick_case()),
     "extract n_out_seams": lambda: from_model("extract", em.cases()["n_out_seams"]),
     "extract first1_fp32": lambda: from_model("extract", em.cases()["first1_fp32"]),
     "extract first3_fp16": lambda: from_model("extract", em.cases()["first3_fp16"]),
@@ -575,16 +699,128 @@ def long_extract_job(spec, out_offset):
     return job
 
 
+# ---- the long psd and symbols jobs of the far buffer: periodic input ----------------------------------------------------------------------
+
+PERIOD = 3 * 2 ** 18					# float2 samples of the noise block the far buffer repeats
+LONG_N = 2 ** 31 - 1
+PSD_LONG = dict(fft_len_log=10, hop=1024, offset=1, n=LONG_N)		# 2^21 - 1 segments, 2^16 tiles, 512 MiB of partials
+PSD_LONG_PARTS = dict(fft_len_log=10, hop=128, offset=1, n=LONG_N)	# 2^24 - 8 segments, 2^19 tiles, 4 GiB of partials
+# the FIXED job begins 1024 samples further in, so that it ends beyond sample 2^31 and a short job of its last symbols begins there
+SYM_LONG = {"sps 64": dict(sps=64, mode=sm.ESTIMATE, tau=0.0, offset=1, n=LONG_N),
+            "sps 3": dict(sps=3, mode=sm.FIXED, tau=0.4, offset=1025, n=LONG_N)}
+
+
+def long_psd_job(spec, out_offset=GUARD, win_offset=0):
+    return pm.make_jobs([(spec["offset"], out_offset, win_offset, spec["n"], spec["fft_len_log"], spec["hop"], pm.NONE, pm.T_POWER,
+                          0.99, 1e-2)])
+
+
+def long_symbols_job(spec, out_offset=GUARD):
+    return sm.make_jobs([(spec["offset"], out_offset, spec["n"], spec["sps"], spec["mode"], spec["tau"])])
+
+
+def advanced_symbols(job, m):
+    """the FIXED job that computes symbols m .. of `job` as its symbols 0 ..: offset advanced by m sps, n shortened by as much (the
+    phase is the job's own tau, so first and mu stay)"""
+    out = np.array(job, sm.JOB_DTYPE).copy().reshape(1)
+    assert out["mode"][0] == sm.FIXED
+    out["offset"] += m * int(job["sps"])
+    out["n"] -= m * int(job["sps"])
+    return out
+
+
+def wrapped(block, first, count):
+    """samples first .. first + count of `block` repeated for ever"""
+    return block[(first + np.arange(count, dtype=np.int64)) % len(block)]
+
+
+def serial_sum(distinct, count, last=None):
+    """rows 0, 1, .. count - 1 of `distinct` taken cyclically, then `last` if there is one, added one after the other in that order
+    from 0.0 -> float64 [K]"""
+    distinct = np.asarray(distinct, np.float64)
+    S = np.zeros(distinct.shape[1])
+    with np.errstate(all="ignore"):
+        for c in range(count):
+            S = S + distinct[c % len(distinct)]
+        if last is not None:
+            S = S + last
+    return S
+
+
+def periodic_psd(block, win, job):
+    """the psd job over `block` repeated for ever, len(block) a multiple of the tile stride TILE hop: tile c of the job is tile
+    c mod (len(block) / stride).  Those distinct full tiles and the last, partial one by psd_model's functions, added in rule 4's
+    order -> (a RECORD_DTYPE array [1], the trace float32 [L] or [0])"""
+    block, win = pm.buffers((block, win))
+    log, hop, nseg = int(job["fft_len_log"]), int(job["hop"]), pm.job_n_seg(job)
+    L, stride = 1 << log, pm.TILE * hop
+    assert len(block) % stride == 0
+    full, rest = divmod(nseg, pm.TILE)
+
+    def tile(c, segs):
+        y = wrapped(block, int(job["offset"]) + c * stride, (segs - 1) * hop + L)
+        p = pm.powers(y, win, np.arange(segs, dtype=np.int64) * hop, np.full(segs, int(job["win_offset"]), np.int64),
+                      np.full(segs, int(job["pre"])), L)
+        with np.errstate(all="ignore"):
+            return pm.ordered_sum(p)
+
+    S = None
+    if nseg:
+        distinct = [tile(c, pm.TILE) for c in range(min(len(block) // stride, full))] or np.zeros((1, L))
+        S = serial_sum(distinct, full, tile(full, rest) if rest else None)
+    record, P32 = pm.result_of(job, S, win)
+    return record, (P32 if P32 is not None and int(job["trace"]) == pm.T_POWER else np.zeros(0, np.float32))
+
+
+def periodic_symbols(block, job):
+    """the symbols job over `block` repeated for ever, len(block) a multiple of the tile stride TILE sps: fold tile and output tile
+    c are those of c mod (len(block) / stride).  The distinct full tiles and the last, partial ones by symbols_model's functions,
+    added in the order of rules 1 and 6 -> (a RECORD_DTYPE array [1], the symbols of the first len(block) / sps (or of all, if
+    there are fewer) float32 [..][2], the symbols of the last, partial output tile float32 [..][2])"""
+    block = sm.buffer((block,))
+    sps, n, off = int(job["sps"]), int(job["n"]), int(job["offset"])
+    stride = sm.TILE * sps
+    assert len(block) % stride == 0
+    cycle = len(block) // stride
+    xyz = None
+    if int(job["mode"]) == sm.ESTIMATE:
+        full, rest = divmod(n // sps, sm.TILE)
+
+        def fold(c, syms):
+            y = wrapped(block, off + c * stride, syms * sps).astype(np.float64)
+            with np.errstate(all="ignore"):
+                return sm.three_level(((y[:, 0] * y[:, 0]) + (y[:, 1] * y[:, 1])).reshape(syms, sps))
+
+        distinct = [fold(c, sm.TILE) for c in range(min(cycle, full))] or np.zeros((1, sps))
+        xyz = sm.line_of(serial_sum(distinct, full, fold(full, rest) if rest else None), sps)
+    r = sm.timing_of(job, xyz)
+    none = np.zeros((0, 2), np.float32)
+    if r["status"][0] == sm.NO_TIMING:
+        return r, none, none
+    first, mu = int(r["first"][0]), r["mu"][0]
+    full, rest = divmod(int(r["n_sym"][0]), sm.TILE)
+
+    def pick(c, syms):
+        return sm.interpolate(wrapped(block, off + c * stride, first + (syms - 1) * sps + 3), first, mu, syms, sps)
+
+    outs = [pick(c, sm.TILE) for c in range(min(cycle, full))]
+    last = pick(full, rest) if rest else none
+    m = serial_sum([sm.moments(o) for o in outs] or np.zeros((1, len(sm.MOMENTS))), full, sm.moments(last) if rest else None)
+    for k, v in zip(sm.MOMENTS, m):
+        r[k] = sm.quiet64(v)
+    return r, (np.concatenate(outs) if outs else last), last
+
+
 CASES = dict(RELOCATE)
 CASES.update({"long measure": long_measure_case, "long edges": long_edges_case, "long tie": long_tie_case,
-              "long resample": long_resample_case})
+              "long resample": long_resample_case, "long psd": long_psd_case, "long symbols": long_symbols_case})
 CASES.update({"full " + k: v for k, v in FULL.items()})
 
 
 # ---- driving the passes on the device (torch is imported where it is used: the CPU tests import this file too) ----------------------
 
 class Dev:
-    """an instance, torch views of its waterfall ring and spectrum, and the five passes through the C ABI by raw device pointers"""
+    """an instance, torch views of its waterfall ring and spectrum, and the seven passes through the C ABI by raw device pointers"""
 
     def __init__(self, amd, wf_rows=16):
         self.f = amd.Fosphor(n_bins=128, wf_rows=wf_rows)
@@ -615,9 +851,10 @@ class Dev:
         assert torch.equal(self.wf.view(torch.int32), self.saved[0]), "the waterfall was written"
         assert torch.equal(self.spec.view(torch.int32), self.saved[1]), "the spectrum lines were written"
 
-    def call(self, name, jobs, fmt, iq, n_iq, out=None, cap=0, taps=None, n_taps=0, tpl=None, n_tpl=0, rec=None, tag=""):
+    def call(self, name, jobs, fmt, iq, n_iq, out=None, cap=0, taps=None, n_taps=0, tpl=None, n_tpl=0, rec=None, win=None, n_win=0,
+             tag=""):
         """one call that must succeed, every buffer a device pointer: the ring, the waterfall and the spectrum untouched and the
-        stats delta what the jobs predict"""
+        stats delta what the jobs predict (symbols: the jobs and the n_sym of the records it wrote)"""
         import torch
         jobs = np.ascontiguousarray(jobs, MODELS[name].JOB_DTYPE)
         self.save()
@@ -632,19 +869,28 @@ class Dev:
             rv = L.fosphor_amd_measure(h, iq, n_iq, jobs.ctypes.data, len(jobs), rec)
         elif name == "demod":
             rv = L.fosphor_amd_demod(h, iq, n_iq, jobs.ctypes.data, len(jobs), out, cap)
+        elif name == "psd":
+            rv = L.fosphor_amd_psd(h, iq, n_iq, win, n_win, jobs.ctypes.data, len(jobs), rec, out, cap)
+        elif name == "symbols":
+            rv = L.fosphor_amd_symbols(h, iq, n_iq, jobs.ctypes.data, len(jobs), rec, out, cap)
         else:
             rv = L.fosphor_amd_correlate(h, iq, n_iq, tpl, n_tpl, jobs.ctypes.data, len(jobs), rec, out, cap)
         after = stats()
         self.assert_untouched()
         assert rv == 0, (tag, name, rv)
         delta = {k: after[k] - before[k] for k in after}
-        assert delta == expected_stats(name, jobs), (tag, name, delta)
+        records = None
+        if name == "symbols":
+            from gr_fosphor_amd.dist import wrap_device_array
+            records = wrap_device_array(rec, (len(jobs) * sm.RECORD_WORDS,), torch.int32).cpu().numpy().view(sm.RECORD_DTYPE)
+        assert delta == expected_stats(name, jobs, records), (tag, name, delta)
 
-    def run(self, case, tag="", iq_at=None, out_at=None, tpl_at=None):
+    def run(self, case, tag="", iq_at=None, out_at=None, tpl_at=None, win_at=None):
         """the case in sentinel-filled buffers of its own -> (records or None, the whole output buffer as uint32 words or None);
-        inputs and taps are compared with their host copies afterwards.
+        inputs, taps and windows are compared with their host copies afterwards.
         iq_at, tpl_at: (device pointer, samples there, base): the case's samples or templates lie there from `base` on already --
         the jobs' offsets are moved by base, and the caller looks after that buffer.
+        win_at: (device pointer, floats there, base): the same for psd's windows and win_offset.
         out_at: (device pointer, capacity there, base): the outputs go there, out_offset moved by base; no words are returned."""
         import torch
         name, jobs = case.name, case.jobs
@@ -656,10 +902,17 @@ class Dev:
         else:
             iq, n_iq = iq_at[0], iq_at[1]
             jobs = shifted(case, IN_FIELD[name], iq_at[2]).jobs
-        taps = n_taps = tpl = n_tpl = rec = d_rec = out = d_out = None
+        taps = n_taps = tpl = n_tpl = rec = d_rec = out = d_out = win = n_win = None
         if case.taps is not None:
             held["taps"] = (up(case.taps), case.taps)
             taps, n_taps = held["taps"][0].data_ptr(), len(case.taps)
+        if name == "psd":
+            if win_at is not None:
+                win, n_win = win_at[0], win_at[1]
+                jobs = shifted(case.with_jobs(jobs), "win_offset", win_at[2]).jobs
+            else:
+                held["win"] = (up(case.win), case.win)
+                win, n_win = held["win"][0].data_ptr(), len(case.win)
         if name == "correlate":
             if tpl_at is not None:
                 tpl, n_tpl = tpl_at[0], tpl_at[1]
@@ -671,7 +924,7 @@ class Dev:
             else:
                 held["tpl"] = (up(case.tpl), case.tpl)
                 tpl, n_tpl = held["tpl"][0].data_ptr(), len(case.tpl)
-        if name in ("measure", "correlate"):
+        if name in WITH_RECORDS:
             words = MODELS[name].RECORD_DTYPE.itemsize // 4
             d_rec = torch.full(((len(jobs) + 2 * GUARD) * words,), SENTINEL, dtype=torch.int32, device="cuda")
             rec = d_rec.data_ptr() + 4 * GUARD * words
@@ -683,7 +936,7 @@ class Dev:
             d_out = torch.full((OUT_WORDS[name] * cap + 2,), SENTINEL, dtype=torch.int32, device="cuda")
             out = d_out.data_ptr()
         self.call(name, jobs, case.fmt, iq, n_iq, out=out, cap=cap, taps=taps, n_taps=n_taps or 0, tpl=tpl, n_tpl=n_tpl or 0, rec=rec,
-                  tag=tag)
+                  win=win, n_win=n_win or 0, tag=tag)
         for k, (d, host) in held.items():
             assert d.cpu().numpy().tobytes() == host.tobytes(), (tag, "the %s buffer was written" % k)
         got = words_out = None

@@ -166,6 +166,35 @@ def buffers(case):
     return np.ascontiguousarray(case[0], np.float32).reshape(-1, 2), np.ascontiguousarray(case[1], np.float32).reshape(-1)
 
 
+def powers(iq, win, start, woff, pre, L):
+    """rules 2 and 3 and |X|^2 of the segments that begin at iq[start[s]] under the window at win[woff[s]] -> float64 [S][L]"""
+    p = np.zeros((len(start), L))
+    for a in range(0, len(start), 8192):					# bounded memory
+        sl = slice(a, a + 8192)
+        at = start[sl, None] + np.arange(L)
+        xr, xi = pre_of(pre[sl], iq[at, 0], iq[at, 1], win[woff[sl, None] + np.arange(L)])
+        Xr, Xi = fft(xr, xi)
+        with np.errstate(all="ignore"):
+            p[sl] = (Xr * Xr) + (Xi * Xi)
+    return p
+
+
+def result_of(job, S, win):
+    """the end of rule 4 and rule 5: a job's S[b] (None without a segment) -> (a RECORD_DTYPE array [1], P32 or None)"""
+    L = 1 << int(job["fft_len_log"])
+    w = win[int(job["win_offset"]):int(job["win_offset"]) + L].astype(np.float64)
+    with np.errstate(all="ignore"):
+        U = ordered_sum(w * w)
+    nseg = job_n_seg(job)
+    P32 = None
+    if nseg > 0:
+        den = np.float64(nseg) * U
+        with np.errstate(all="ignore"):
+            S = np.roll(S, L // 2)						# P32[i] is bin (i + L / 2) mod L
+            P32 = np.zeros(L, np.float32) if den == 0.0 else quiet((S / den).astype(np.float32))
+    return record_of(P32, job, nseg, U), P32
+
+
 def psd(case):
     """(records RECORD_DTYPE [n_jobs], [trace floats per job, float32 [0] or [L]], [P32 per job or None])"""
     iq, win = buffers(case)
@@ -180,14 +209,7 @@ def psd(case):
         start = np.concatenate([int(jobs[i]["offset"]) + np.arange(c, dtype=np.int64) * int(jobs[i]["hop"]) for i, c in zip(idx, counts)])
         woff = np.concatenate([np.full(c, int(jobs[i]["win_offset"]), np.int64) for i, c in zip(idx, counts)])
         pre = np.concatenate([np.full(c, int(jobs[i]["pre"])) for i, c in zip(idx, counts)])
-        p = np.zeros((len(start), L))
-        for a in range(0, len(start), 8192):					# bounded memory
-            sl = slice(a, a + 8192)
-            at = start[sl, None] + np.arange(L)
-            xr, xi = pre_of(pre[sl], iq[at, 0], iq[at, 1], win[woff[sl, None] + np.arange(L)])
-            Xr, Xi = fft(xr, xi)
-            with np.errstate(all="ignore"):
-                p[sl] = (Xr * Xr) + (Xi * Xi)
+        p = powers(iq, win, start, woff, pre, L)
         at = 0
         for i, c in zip(idx, counts):
             mine = p[at:at + c]
@@ -197,18 +219,8 @@ def psd(case):
                 S_of[i] = ordered_sum(T)
     records, traces, P32s = [], [], []
     for i, j in enumerate(jobs):
-        L = 1 << int(j["fft_len_log"])
-        w = win[int(j["win_offset"]):int(j["win_offset"]) + L].astype(np.float64)
-        with np.errstate(all="ignore"):
-            U = ordered_sum(w * w)
-        nseg = job_n_seg(j)
-        P32 = None
-        if nseg > 0:
-            den = np.float64(nseg) * U
-            with np.errstate(all="ignore"):
-                S = np.roll(S_of[i], L // 2)					# P32[i] is bin (i + L / 2) mod L
-                P32 = np.zeros(L, np.float32) if den == 0.0 else quiet((S / den).astype(np.float32))
-        records.append(record_of(P32, j, nseg, U))
+        record, P32 = result_of(j, S_of[i], win)
+        records.append(record)
         traces.append(P32 if P32 is not None and int(j["trace"]) == T_POWER else np.zeros(0, np.float32))
         P32s.append(P32)
     return np.concatenate(records), traces, P32s

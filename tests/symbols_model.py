@@ -89,8 +89,13 @@ def line(y, sps):
     R = len(y) // sps
     re, im = y[:R * sps, 0].astype(np.float64), y[:R * sps, 1].astype(np.float64)
     with np.errstate(all="ignore"):
-        A = three_level(((re * re) + (im * im)).reshape(R, sps))
-        twr, twi = twiddles(sps)
+        return line_of(three_level(((re * re) + (im * im)).reshape(R, sps)), sps)
+
+
+def line_of(A, sps):
+    """rule 2 over the folded sums A [sps] -> (Xr, Xi, a0)"""
+    twr, twi = twiddles(sps)
+    with np.errstate(all="ignore"):
         return ordered_sum(A * twr), ordered_sum(A * twi), ordered_sum(A)
 
 
@@ -142,23 +147,34 @@ def moments(s32):
         return three_level(np.stack([w, w * w, ar, ai, (ar * ar) - (ai * ai), (ar * ai) + (ar * ai)], 1))
 
 
+MOMENTS = ("m2", "m4", "z2_re", "z2_im", "z4_re", "z4_im")
+
+
+def timing_of(job, xyz):
+    """rules 3 and 4 of a job whose line is xyz = (Xr, Xi, a0), None under FIXED -> a RECORD_DTYPE array [1] that lacks only the
+    moments; status NO_TIMING where there is no phase"""
+    r = np.zeros(1, RECORD_DTYPE)
+    e = np.float64(np.float32(job["tau"]))
+    if int(job["mode"]) == ESTIMATE:
+        r["x_re"], r["x_im"], r["a0"] = quiet64(xyz[0]), quiet64(xyz[1]), quiet64(xyz[2])
+        e = phase(xyz[0], xyz[1])
+        if e is None:
+            r["status"], r["tau"] = NO_TIMING, QNAN
+            return r
+    first, mu, n_sym = place_of(e, int(job["n"]), int(job["sps"]))
+    r["n_sym"], r["first"], r["tau"], r["mu"] = n_sym, first, np.float32(e), mu
+    return r
+
+
 def symbols_job(iq, job):
     """-> (a RECORD_DTYPE array [1], the job's symbols float32 [n_sym][2])"""
     n, sps = int(job["n"]), int(job["sps"])
     y = iq[int(job["offset"]):int(job["offset"]) + n]
-    r = np.zeros(1, RECORD_DTYPE)
-    e = np.float64(np.float32(job["tau"]))
-    if int(job["mode"]) == ESTIMATE:
-        xr, xi, a0 = line(y, sps)
-        r["x_re"], r["x_im"], r["a0"] = quiet64(xr), quiet64(xi), quiet64(a0)
-        e = phase(xr, xi)
-        if e is None:
-            r["status"], r["tau"] = NO_TIMING, QNAN
-            return r, np.zeros((0, 2), np.float32)
-    first, mu, n_sym = place_of(e, n, sps)
-    out = interpolate(y, first, mu, n_sym, sps)
-    r["n_sym"], r["first"], r["tau"], r["mu"] = n_sym, first, np.float32(e), mu
-    for k, v in zip(("m2", "m4", "z2_re", "z2_im", "z4_re", "z4_im"), moments(out)):
+    r = timing_of(job, line(y, sps) if int(job["mode"]) == ESTIMATE else None)
+    if r["status"][0] == NO_TIMING:
+        return r, np.zeros((0, 2), np.float32)
+    out = interpolate(y, int(r["first"][0]), r["mu"][0], int(r["n_sym"][0]), sps)
+    for k, v in zip(MOMENTS, moments(out)):
         r[k] = quiet64(v)
     return r, out
 

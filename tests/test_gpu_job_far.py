@@ -18,14 +18,31 @@ only where less than 20 GiB of device memory is free, with both numbers in the r
                 are written, from a hash of the index that numpy recomputes.  TILE: D = 25, T = 33, base = m0 * D beyond 2^31,
                 input and output in disjoint regions of the buffer; the tiles at the ends and on both sides of 2^31 against the
                 model, every output word written (a sentinel count on the device), the last outputs bit-identical to a short
-                job advanced to there (the cut rule of extract_model.split_case)."""
+                job advanced to there (the cut rule of extract_model.split_case).
+  windows       psd's windows at WIN_BASE, beyond 2^32 floats, decoys at its aliases: bit-identical to the near run.
+  long psd      one job of n = 2^31 - 1 samples at L = 1024 over the buffer filled with one noise block of PERIOD samples, repeated
+                (jc.periodic_psd says how that makes a model possible): hop 1024 is 2^21 - 1 segments in 2^16 tiles; hop 128 is
+                2^24 - 8 segments in 2^19 tiles, whose partials take 2^32 bytes of the scratch behind the table, so the last
+                tile's lie beyond byte 2^32 of it.  Record and trace bit-identical to the model, the input unchanged (every row of
+                the buffer as [k][PERIOD] against the first, on the device).
+  long symbols  n = 2^31 - 1 at sps 64 under ESTIMATE (2^13 fold tiles) and at sps 3 under FIXED (174763 output tiles, 5.4 GiB of
+                symbols): the record bit-identical to jc.periodic_symbols, every period of the output equal to the first on the
+                device, the first period and the last tile equal to the model's, sentinels either side; the FIXED job's last 64
+                symbols from a short job that begins beyond sample 2^31.
+Measured once on an MI355X, the call alone and in brackets the whole test with its fills, its model and its comparisons:
+PSD_LONG 0.55 s (0.84 s), PSD_LONG_PARTS 3.55 s (4.29 s), symbols at sps 3 0.02 s (0.12 s), at sps 64 0.01 s (0.06 s).
+PSD_LONG_PARTS wants 4 GiB of scratch and the sps 3 job 5.4 GiB of symbols beside the buffer: each is skipped, with both numbers in
+the reason, where that much more was not free when the buffer was taken."""
 import os
+import time
 
 import numpy as np
 import pytest
 
 import extract_model as em
 import job_scale_cases as jc
+import psd_model as pm
+import symbols_model as sm
 
 pytestmark = pytest.mark.gpu
 
@@ -88,6 +105,7 @@ def far():
         pytest.skip("the far buffer takes %d bytes and wants %d free: %d of %d bytes are" % (jc.FAR_BYTES, jc.FAR_FREE_NEEDED, free, total))
     print("device memory: %d of %d bytes free; the far buffer takes %d" % (free, total, jc.FAR_BYTES))
     f = Far(torch)
+    f.free = free					# before the buffer was taken: what the tests that want more go by
     yield f
     f.words = f.big = None
     torch.cuda.empty_cache()
@@ -161,6 +179,148 @@ def test_relocated_templates(dev, far):
     got = dev.run(case, tag=key + " far templates", tpl_at=(far.ptr, jc.FAR_SAMPLES, jc.TPL_BASE))
     assert same(got, near)
     assert far.get(2 * jc.TPL_BASE, len(data)).tobytes() == data.tobytes(), "the templates were written"
+
+
+@pytest.mark.parametrize("key", ["psd loads", "psd tiles"])
+def test_relocated_windows(dev, far, key):
+    case = jc.case_of(key)
+    near = dev.run(case, tag=key)
+    data = words_of(case.win)
+    decoy = decoy_of(data)
+    assert not np.array_equal(decoy, data)
+    found = jc.aliases(jc.WIN_BASE, 4)
+    assert found
+    for a in found:
+        far.put(a, decoy)
+    far.put(jc.WIN_BASE, data)
+    got = dev.run(case, tag=key + " far windows", win_at=(far.ptr, 2 * jc.FAR_SAMPLES, jc.WIN_BASE))
+    assert same(got, near), (key, "the run with far windows differs from the near one")
+    jc.model_of(key).check(*got, tag=key)
+    assert far.get(jc.WIN_BASE, len(data)).tobytes() == data.tobytes(), "the windows were written"
+    for a in found:
+        assert far.get(a, len(decoy)).tobytes() == decoy.tobytes(), "a decoy was written"
+
+
+def fill_periodic(far, block):
+    """the far buffer as [k][PERIOD] samples, every row the block -> (the rows as int32 [k][2 PERIOD], the block on the device)"""
+    torch = far.torch
+    assert len(block) == jc.PERIOD and jc.FAR_SAMPLES % jc.PERIOD == 0
+    k = jc.FAR_SAMPLES // jc.PERIOD
+    d_block = torch.from_numpy(words_of(block).view(np.int32)).cuda()
+    rows = far.words.view(k, 2 * jc.PERIOD)
+    rows.copy_(d_block.unsqueeze(0).expand(k, -1))
+    return rows, d_block
+
+
+def assert_rows_equal(torch, rows, first, what):
+    """every row of int32 [k][..] is `first`, compared on the device a piece at a time"""
+    step = max(1, 2 ** 27 // rows.shape[1])
+    for a in range(0, rows.shape[0], step):
+        assert bool((rows[a:a + step] == first).all().item()), what
+
+
+def guarded(torch, words):
+    """a sentinel-filled int32 buffer of `words` on the device; the caller counts its guards in"""
+    return torch.full((words,), SENTINEL, dtype=torch.int32, device="cuda")
+
+
+@pytest.mark.parametrize("name", ["PSD_LONG", "PSD_LONG_PARTS"])
+def test_long_psd_job(dev, far, name):
+    """2^21 - 1 segments in 2^16 tiles, and 2^24 - 8 segments in 2^19 tiles with 4 GiB of partials.  Measured once on an MI355X:
+    the call takes 0.55 s and 3.55 s (2^24 transforms of 1024 points in double, then one wave that adds 2^19 tiles), below the 5 s
+    at which the second parameter would have been left out; the tests 0.84 s and 4.29 s."""
+    import torch
+    spec = getattr(jc, name)
+    if name == "PSD_LONG_PARTS" and far.free < jc.FAR_FREE_NEEDED + 5 * 2 ** 30:
+        pytest.skip("4 GiB of scratch beside the far buffer want %d bytes free: %d were" % (jc.FAR_FREE_NEEDED + 5 * 2 ** 30, far.free))
+    t_test = time.perf_counter()
+    block = pm.noise(jc.PERIOD, 7171)
+    rows, d_block = fill_periodic(far, block)
+    win = pm.window(pm.HANN, spec["fft_len_log"])
+    d_win = torch.from_numpy(win).cuda()
+    L, W = len(win), pm.RECORD_DTYPE.itemsize // 4
+    job = jc.long_psd_job(spec, out_offset=jc.GUARD)
+    d_out = guarded(torch, L + 2 * jc.GUARD)
+    d_rec = guarded(torch, (1 + 2 * jc.GUARD) * W)
+    t_call = time.perf_counter()
+    dev.call("psd", job, em.FP32, far.ptr, jc.FAR_SAMPLES, out=d_out.data_ptr(), cap=L + 2 * jc.GUARD, rec=d_rec.data_ptr() + 4 * W * jc.GUARD,
+             win=d_win.data_ptr(), n_win=L, tag=name)
+    t_call = time.perf_counter() - t_call
+    want_rec, want = jc.periodic_psd(block, win, job[0])
+    rec = d_rec.cpu().numpy().view(np.uint32).reshape(-1, W)
+    out = d_out.cpu().numpy().view(np.uint32)
+    assert np.all(rec[:jc.GUARD] == SENTINEL) and np.all(rec[-jc.GUARD:] == SENTINEL), "written outside the record"
+    assert np.all(out[:jc.GUARD] == SENTINEL) and np.all(out[-jc.GUARD:] == SENTINEL), "written outside the trace"
+    got_rec = rec[jc.GUARD].copy().view(pm.RECORD_DTYPE)
+    assert got_rec["n_seg"][0] == pm.job_n_seg(job[0]) and got_rec["peak_bin"][0] >= 0
+    assert got_rec.tobytes() == want_rec.tobytes(), (name, got_rec, want_rec)
+    assert out[jc.GUARD:-jc.GUARD].tobytes() == want.tobytes(), "the trace differs from the periodic model's"
+    assert torch.equal(rows[0], d_block) and d_win.cpu().numpy().tobytes() == win.tobytes(), "the input was written"
+    assert_rows_equal(torch, rows, rows[0], "the input was written")
+    print("%s: the call %.2f s, the test %.2f s" % (name, t_call, time.perf_counter() - t_test))
+
+
+@pytest.mark.parametrize("key", sorted(jc.SYM_LONG))
+def test_long_symbols_job(dev, far, key):
+    """Measured once on an MI355X: the call takes 0.02 s (sps 3, FIXED, 715827882 symbols) and 0.01 s (sps 64, ESTIMATE, 2^25
+    symbols), the tests 0.12 s and 0.06 s."""
+    import torch
+    spec = jc.SYM_LONG[key]
+    sps, W = spec["sps"], sm.RECORD_WORDS
+    job = jc.long_symbols_job(spec, out_offset=G)
+    max_out = sm.job_max_out(job[0])
+    cap = max_out + 2 * G
+    if far.free < jc.FAR_FREE_NEEDED + 8 * cap + 2 ** 30:
+        pytest.skip("%d bytes of symbols beside the far buffer want %d bytes free: %d were" % (8 * cap, jc.FAR_FREE_NEEDED + 8 * cap + 2 ** 30,
+                                                                                          far.free))
+    t_test = time.perf_counter()
+    block = sm.noise(jc.PERIOD, 7272)
+    rows, d_block = fill_periodic(far, block)
+    d_out = guarded(torch, 2 * cap)
+    d_rec = guarded(torch, (1 + 2 * jc.GUARD) * W)
+    t_call = time.perf_counter()
+    dev.call("symbols", job, em.FP32, far.ptr, jc.FAR_SAMPLES, out=d_out.data_ptr(), cap=cap, rec=d_rec.data_ptr() + 4 * W * jc.GUARD, tag=key)
+    t_call = time.perf_counter() - t_call
+    want_rec, head, last = jc.periodic_symbols(block, job[0])
+    rec = d_rec.cpu().numpy().view(np.uint32).reshape(-1, W)
+    assert np.all(rec[:jc.GUARD] == SENTINEL) and np.all(rec[-jc.GUARD:] == SENTINEL), "written outside the record"
+    got_rec = rec[jc.GUARD].copy().view(sm.RECORD_DTYPE)
+    assert got_rec.tobytes() == want_rec.tobytes(), (key, got_rec, want_rec)
+    n_sym = int(got_rec["n_sym"][0])
+    assert got_rec["status"][0] == sm.OK and max_out - 64 // sps - 1 <= n_sym <= max_out
+    # the output, on the device: sentinels before, behind n_sym (the reserved rest and the guard); every period equal to the first
+    assert bool((d_out[:2 * G] == SENTINEL).all().item()) and bool((d_out[2 * (G + n_sym):] == SENTINEL).all().item()), "written beside the symbols"
+    sym = d_out[2 * G:2 * (G + n_sym)]
+    per = jc.PERIOD // sps					# symbols of a period of the input
+    k = n_sym // per
+    assert k >= 2730 and len(head) == per
+    whole = sym[:2 * k * per].view(k, 2 * per)
+    assert_rows_equal(torch, whole, whole[0], "a period of the output differs from the first")
+    rest = sym[2 * k * per:]
+    assert torch.equal(rest, whole[0][:rest.numel()]), "the last, partial period differs from the first"
+    assert whole[0].cpu().numpy().tobytes() == head.tobytes(), "the first period differs from the periodic model's"
+    tail_tile = n_sym % sm.TILE					# the last tile: partial, or (sps 64: n_sym is 2^25) a full one of the cycle
+    assert len(last) == tail_tile
+    if not tail_tile:
+        c = (n_sym // sm.TILE - 1) % (per // sm.TILE)
+        tail_tile, last = sm.TILE, head[c * sm.TILE:(c + 1) * sm.TILE]
+    assert sym[2 * (n_sym - tail_tile):].cpu().numpy().tobytes() == last.tobytes(), "the last tile differs from the periodic model's"
+    assert torch.equal(rows[0], d_block), "the input was written"
+    assert_rows_equal(torch, rows, rows[0], "the input was written")
+    if spec["mode"] == sm.FIXED:
+        # the cut rule: the last 64 symbols as a job of their own, its offset advanced
+        tail = jc.advanced_symbols(job[0], n_sym - 64)
+        tail["out_offset"] = jc.GUARD
+        assert tail["offset"][0] > 2 ** 31
+        d_tail = guarded(torch, 2 * (64 + 2 * jc.GUARD))
+        d_trec = guarded(torch, W)
+        dev.call("symbols", tail, em.FP32, far.ptr, jc.FAR_SAMPLES, out=d_tail.data_ptr(), cap=64 + 2 * jc.GUARD, rec=d_trec.data_ptr(),
+                 tag=key + ", the tail")
+        short = d_tail.cpu().numpy().view(np.uint32).reshape(-1, 2)
+        assert np.all(short[:jc.GUARD] == SENTINEL) and np.all(short[-jc.GUARD:] == SENTINEL)
+        assert d_trec.cpu().numpy().view(sm.RECORD_DTYPE)["n_sym"][0] == 64
+        assert short[jc.GUARD:-jc.GUARD].tobytes() == sym[-128:].cpu().numpy().tobytes(), "the last 64 symbols do not depend on the cut"
+    print("%s: the call %.2f s, the test %.2f s" % (key, t_call, time.perf_counter() - t_test))
 
 
 def worst(got, want):

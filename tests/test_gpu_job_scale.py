@@ -1,20 +1,24 @@
 """The passes over burst IQ on long jobs and full tables (the input sets are tests/job_scale_cases.py; tests/test_job_scale_cpu.py
 holds the conditions on them and runs the host twins over them).
 
-The single-module tests (tests/test_gpu_extract.py, _resample, _measure, _demod, _correlate) work in buffers of a few tens of
-thousands of samples: no job there has more than four partials and no call more than 257 jobs.  Here
+The single-module tests (tests/test_gpu_extract.py, _resample, _measure, _demod, _correlate, _psd, _symbols) work in buffers of a
+few tens of thousands of samples: no job there has more than four partials and no call of the five older passes more than 257 jobs.
+Here
   long jobs    measure over 131 chunks and correlate over 131 tiles: k_measure_combine and k_correlate_combine fold 64 partials a
                round, so their second and third rounds run -- a lane that holds several partials, the seam rule at partials 64 and
                128, the peak's tie inside a lane across rounds and between lanes, best_tile chosen in a later round.  The cut rule
                of measure at the round boundary.  Resample at positions of the up-sampled rate around 2^32, in both forms.
+               psd over 131, 64 and 65 tiles, which k_psd_combine adds one after the other, at L = 64, 256 and 1024; symbols over
+               20, 8 and 9 fold and pick tiles, so the loops of k_sym_time and k_sym_record under `#pragma unroll 8` run whole
+               bodies and a remainder.
   full tables  every pass with exactly MAX_JOBS jobs in shuffled order, every 11th without work: the deepest search of the prefix
                and the largest table; and on a fresh instance a call of one job, the full table and the one job again, so the
                scratch slot of the pass grows behind a first, smaller call.
 Every call goes through the C ABI into sentinel-filled buffers that are compared whole: bit for bit with demod_model,
-correlate_model and resample_model, inside measure_model.job_tolerance and extract_model.bound for the two passes whose contracts
-leave the order of the additions open.  Inputs and taps are compared with their host copies after the call, the ring position, the
-waterfall and the spectrum with what they were before, and the stats delta with what the jobs predict.  The same call twice is
-bit-identical."""
+correlate_model, resample_model, psd_model and symbols_model, inside measure_model.job_tolerance and extract_model.bound for the two passes whose contracts
+leave the order of the additions open.  Inputs, taps and windows are compared with their host copies after the call, the ring
+position, the waterfall and the spectrum with what they were before, and the stats delta with what the jobs predict.  The same call
+twice is bit-identical."""
 import os
 
 import numpy as np
@@ -25,7 +29,7 @@ import measure_model as mm
 
 pytestmark = pytest.mark.gpu
 
-LONG = ("long measure", "long edges", "long tie", "long resample")
+LONG = ("long measure", "long edges", "long tie", "long resample", "long psd", "long symbols")
 
 
 @pytest.fixture(scope="module")

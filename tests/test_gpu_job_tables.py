@@ -1,16 +1,19 @@
-"""The job tables of the four passes over burst IQ (gr-fosphor_amd/csrc/fosphor_jobs.h) on one instance: extract, then measure,
-demod and correlate over what extract wrote, three times with tables of 3, 300 and 2 jobs -- every scratch buffer of the instance
-grows once and is then reused larger than the table needs.
+"""The job tables of six passes over burst IQ (gr-fosphor_amd/csrc/fosphor_jobs.h) on one instance: extract, then measure,
+demod, correlate, psd and symbols over what extract wrote, three times with tables of 3, 300 and 2 jobs -- every scratch buffer of
+the instance grows once and is then reused larger than the table needs.
 
 A job's length comes from what can break the shared code: nothing (between live jobs and as the last job of a table), 1, one
 work-group's worth, one more, and two work-groups' worth plus 3 -- of extract's TILE_OUT 256 and WAVE_OUT 4 outputs, measure's CHUNK
 of 8192 samples (and WAVE_MAX 4096, the longest job a wave takes), demod's TILE of 2048 trace values at avg 1 and 3, correlate's TILE
-of 1024 lags with templates of 1, 2 and 33 samples.  Offsets walk through 0, 1, 2, 3, so spans begin on and off a 16-byte boundary.
-The single-module tests (tests/test_gpu_extract.py, _measure, _demod, _correlate) hold each pass's own seams at one table size; what
+of 1024 lags with templates of 1, 2 and 33 samples.  psd's lengths are its own: nothing, L - 1 (no segment), L, L + hop, one TILE of
+32 segments, one more, and two and 3, at L = 64 (WAVE) and L = 256 (GROUP); symbols': nothing, 3 samples (no symbol), and what gives
+1, 4096, 4097 and 2 * 4096 + 3 symbols, at sps 2 under FIXED and sps 5 under ESTIMATE.  Offsets walk through 0, 1, 2, 3, so spans begin
+on and off a 16-byte boundary.
+The single-module tests (tests/test_gpu_extract.py, _measure, _demod, _correlate, _psd, _symbols) hold each pass's own seams at one table size; what
 is new here is the alternation of sizes on one instance, the chain, and jobs without work between and behind the live ones.
 
-What is compared: demod's traces and correlate's records and traces with fosphor_amd_demod_host and fosphor_amd_correlate_host over
-the same buffer, bit for bit; measure's integer fields and peak with fosphor_amd_measure_host bit for bit, its eight sums in double
+What is compared: demod's traces, correlate's and psd's records and traces and symbols' records and symbols with
+fosphor_amd_demod_host, fosphor_amd_correlate_host, fosphor_amd_psd_host and fosphor_amd_symbols_host over the same buffer, bit for bit; measure's integer fields and peak with fosphor_amd_measure_host bit for bit, its eight sums in double
 within measure_model.job_tolerance of the host's, because the header leaves the order of the additions open (rule 3) and the kernels
 use that; extract against the float64 model within extract_model.bound, as tests/test_gpu_extract.py does, because extract's host
 function is a float64 statement and no bit-exact twin.  Every stats delta is what the table predicts."""
@@ -22,11 +25,14 @@ import pytest
 import correlate_model as cm
 import demod_model as dm
 import extract_model as em
+import job_scale_cases as jc
 import measure_model as mm
+import psd_model as pm
+import symbols_model as sm
 
 pytestmark = pytest.mark.gpu
 
-LONG = 18000				# outputs of the first extract job of every table: what the other passes read
+LONG = 42000				# outputs of the first extract job of every table: what the other passes read
 TILE_DT, WAVE_DT = (2, 9), (32, 257)	# (decim, taps) of the two extract forms
 TPL = 40
 
@@ -95,6 +101,33 @@ def correlate_table(count, at):
     return jobs
 
 
+PSD_SHAPES = ((6, 16, 0), (8, 100, 64))	# (fft_len_log, hop, win_offset): WAVE and GROUP
+
+
+def psd_table(count, at):
+    kinds = []
+    for log, hop, woff in PSD_SHAPES:
+        L = 1 << log
+        for k, n in enumerate([0, L - 1, L, L + hop] + [jc.psd_n_for(c, log, hop) for c in (pm.TILE, pm.TILE + 1, 2 * pm.TILE + 3)]):
+            kinds.append((at + k % 4, woff, n, log, hop, (pm.NONE, pm.SQUARE, pm.FOURTH, pm.MAGSQ)[(k + log) % 4],
+                          pm.T_NONE if k % 3 == 2 and n != L else pm.T_POWER, 0.99, 1e-2))
+    kinds[0], kinds[2] = kinds[2], kinds[0]			# a live job first; kinds[1] has no segment
+    assert [pm.n_seg(k[2], k[3], k[4]) for k in kinds[:3]] == [1, 0, 0] and kinds[0][6] == pm.T_POWER
+    assert max(k[0] + k[2] for k in kinds) <= at + LONG
+    return pm.place(pick(kinds, count, (at + 1, 0, 63, 6, 16, pm.NONE, pm.T_POWER, 0.99, 1e-2)))
+
+
+def symbols_table(count, at):
+    kinds = []
+    for sps, mode, tau, first in ((2, sm.FIXED, 0.25, 2), (5, sm.ESTIMATE, 0.0, 5)):	# first: the latest the first symbol can lie
+        for k, n in enumerate([0, 3] + [sm.n_for(c, first, sps) for c in (1, sm.TILE, sm.TILE + 1, 2 * sm.TILE + 3)]):
+            kinds.append((at + k % 4, n, sps, mode, tau))
+    kinds[0], kinds[2] = kinds[2], kinds[0]			# a live job first; kinds[1] has no symbol
+    assert [sm.max_out(k[1], k[2]) for k in kinds[:3]] == [1, 0, 0]
+    assert max(k[0] + k[1] for k in kinds) <= at + LONG
+    return sm.place(pick(kinds, count, (at + 1, 0, 5, sm.ESTIMATE, 0.0)))
+
+
 def delta(stats, before):
     after = stats()
     return {k: after[k] - before[k] for k in after}
@@ -113,6 +146,7 @@ def test_tables_of_3_300_2_jobs(amd, stream):
     import torch
     F = amd.Fosphor
     x, taps, tpl = stream
+    win = np.concatenate([F.psd_window("hann", 6), F.psd_window("blackman_harris", 8)])
     xc = x.astype(np.float64) @ np.array([1.0, 1.0j])
     d_x, d_tpl = torch.from_numpy(x).cuda(), torch.from_numpy(tpl).cuda()
     f = F(n_bins=128, wf_rows=16)
@@ -190,5 +224,33 @@ def test_tables_of_3_300_2_jobs(amd, stream):
                 assert (g is None) == (h is None) == (jobs["trace"][i] == cm.NONE)
                 if h is not None:
                     assert g.cpu().numpy().tobytes() == h.tobytes(), (count, i, tuple(jobs[i]))
+
+            # psd
+            jobs = psd_table(count, at)
+            assert len(jobs) == count and pm.job_n_seg(jobs[-1 if count != 3 else 1]) == 0
+            before = f.psd_stats()
+            rec, got = f.psd(base, jobs, win, n_samples=cap)
+            assert delta(f.psd_stats, before) == jc.expected_stats("psd", jobs), count
+            hrec, hviews = F.psd_host(y, jobs, win)
+            assert rec.tobytes() == hrec.tobytes(), (count, [i for i in range(len(jobs)) if rec[i] != hrec[i]][:4])
+            for i, (g, h) in enumerate(zip(got, hviews)):
+                assert (g is None) == (h is None) == (pm.n_out(jobs[i]) == 0)
+                if h is not None:
+                    assert g.cpu().numpy().tobytes() == h.tobytes(), (count, i, tuple(jobs[i]))
+            if count == 300:
+                assert sorted(set(rec["n_seg"])) == [0, 1, 2, pm.TILE, pm.TILE + 1, 2 * pm.TILE + 3]
+
+            # symbols
+            jobs = symbols_table(count, at)
+            assert len(jobs) == count and sm.job_max_out(jobs[-1 if count != 3 else 1]) == 0
+            before = f.symbols_stats()
+            rec, got = f.symbols(base, jobs, n_samples=cap)
+            assert delta(f.symbols_stats, before) == sm.expected_stats(jobs, rec), count
+            hrec, hviews = F.symbols_host(y, jobs)
+            assert rec.tobytes() == hrec.tobytes(), (count, [i for i in range(len(jobs)) if rec[i] != hrec[i]][:4])
+            for i, (g, h) in enumerate(zip(got, hviews)):
+                assert len(h) == rec["n_sym"][i] and g.cpu().numpy().tobytes() == h.tobytes(), (count, i, tuple(jobs[i]))
+            if count == 300:
+                assert {1, sm.TILE, sm.TILE + 1, 2 * sm.TILE + 3} <= set(rec["n_sym"]) and np.all(rec["status"] == sm.OK)
     finally:
         f.close()
