@@ -221,6 +221,24 @@ class SymbolsValues(C.Structure):
                                           "phase4", "lock4")]
 
 
+class CarrierJob(C.Structure):
+    """struct fosphor_amd_carrier_job (include/fosphor_amd_carrier.h)"""
+    _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("n", C.c_int32), ("order", C.c_int32), ("mode", C.c_int32),
+                ("lag", C.c_int32), ("freq", C.c_double), ("phase", C.c_double)]
+
+
+class CarrierRecord(C.Structure):
+    """struct fosphor_amd_carrier_record"""
+    _fields_ = [("n", C.c_int32), ("order", C.c_int32), ("lag_used", C.c_int32), ("status", C.c_int32), ("freq", C.c_double),
+                ("phase", C.c_double), ("r1_re", C.c_double), ("r1_im", C.c_double), ("rl_re", C.c_double), ("rl_im", C.c_double),
+                ("z_re", C.c_double), ("z_im", C.c_double), ("m2", C.c_double), ("mm", C.c_double)]
+
+
+class CarrierValues(C.Structure):
+    """struct fosphor_amd_carrier_values"""
+    _fields_ = [(k, C.c_double) for k in ("freq_hz", "phase_rad", "sym_power", "lock", "lag_lock", "lagl_lock")]
+
+
 class ResampleJob(C.Structure):
     """struct fosphor_amd_resample_job (include/fosphor_amd_resample.h)"""
     _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("phase0", C.c_int64), ("n", C.c_int32), ("n_out", C.c_int32),
@@ -402,6 +420,15 @@ SIGNATURES = {
     "fosphor_amd_symbols_from_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(SymbolsJob)]),
     "fosphor_amd_symbols_derive": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(SymbolsValues)]),
     "fosphor_amd_symbols_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 9)]),
+    # include/fosphor_amd_carrier.h
+    "fosphor_amd_carrier": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
+    "fosphor_amd_carrier_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
+    "fosphor_amd_carrier_from_symbols": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                   C.POINTER(CarrierJob)]),
+    "fosphor_amd_carrier_derive": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(CarrierValues)]),
+    "fosphor_amd_carrier_cossin_turns": (C.c_int, [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "fosphor_amd_carrier_cossin_turns_n": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "fosphor_amd_carrier_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 9)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

@@ -1362,6 +1362,130 @@ class Fosphor:
         """fosphor_amd_symbols_stats as a dict: calls, launches by kernel, jobs by mode, samples, symbols (SYMBOLS_STATS)"""
         return self._stats(self.L.fosphor_amd_symbols_stats, self.SYMBOLS_STATS)
 
+    CARRIER_STATS = ("calls", "k_lag", "k_freq", "k_sum", "k_phase", "k_turn", "jobs_freq", "jobs_phase", "symbols")
+    CARRIER_MAX_JOBS = 4096				# FOSPHOR_AMD_CARRIER_MAX_JOBS (include/fosphor_amd_carrier.h)
+    CARRIER_MAX_LAG = 64				# FOSPHOR_AMD_CARRIER_MAX_LAG
+    CARRIER_BLOCK, CARRIER_TILE = 64, 4096		# FOSPHOR_AMD_CARRIER_BLOCK, FOSPHOR_AMD_CARRIER_TILE
+    CARRIER_MODES = {"estimate": 0, "freq_fixed": 1, "phase_fixed": 2, "fixed": 3}	# sums of FOSPHOR_AMD_CARRIER_FREQ_FIXED, _PHASE_FIXED
+    CARRIER_STATUS = {"ok": 0, "no_carrier": 1}		# FOSPHOR_AMD_CARRIER_OK, FOSPHOR_AMD_CARRIER_NO_CARRIER
+    CARRIER_LDS = {"lag": 15536, "freq": 0, "sum": 10400, "phase": 0, "turn": 0}	# FOSPHOR_AMD_CARRIER_LDS_*
+    CARRIER_JOB_DTYPE = np.dtype([("offset", "<i8"), ("out_offset", "<i8"), ("n", "<i4"), ("order", "<i4"), ("mode", "<i4"),
+                                  ("lag", "<i4"), ("freq", "<f8"), ("phase", "<f8")])
+    CARRIER_RECORD_DTYPE = np.dtype([("n", "<i4"), ("order", "<i4"), ("lag_used", "<i4"), ("status", "<i4"), ("freq", "<f8"),
+                                     ("phase", "<f8"), ("r1_re", "<f8"), ("r1_im", "<f8"), ("rl_re", "<f8"), ("rl_im", "<f8"),
+                                     ("z_re", "<f8"), ("z_im", "<f8"), ("m2", "<f8"), ("mm", "<f8")])
+    CARRIER_VALUES = tuple(k for k, _ in _lib.CarrierValues._fields_)
+
+    @staticmethod
+    def _carrier_mode(mode):
+        if isinstance(mode, str):
+            if mode not in Fosphor.CARRIER_MODES:
+                raise ValueError("mode must be one of %s" % ", ".join(Fosphor.CARRIER_MODES))
+            return Fosphor.CARRIER_MODES[mode]
+        return int(mode)
+
+    @staticmethod
+    def cossin_turns(t):
+        """fosphor_amd_cossin_turns as the library compiled it: (cos, sin) of t turns, element-wise over float64"""
+        t = np.asarray(t, np.float64)
+        shape = t.shape
+        t = np.ascontiguousarray(t).reshape(-1)
+        c, s = np.zeros(max(t.size, 1)), np.zeros(max(t.size, 1))
+        keep = t if t.size else np.zeros(1)
+        rv = _lib.load().fosphor_amd_carrier_cossin_turns_n(keep.ctypes.data, int(t.size), c.ctypes.data, s.ctypes.data)
+        if rv:
+            _fail("fosphor_amd_carrier_cossin_turns_n", rv, ValueError)
+        return c[:t.size].reshape(shape), s[:t.size].reshape(shape)
+
+    @staticmethod
+    def carrier_jobs(symbols_jobs, symbols_records, order, mode="estimate", lag=16, freq=0.0, phase=0.0):
+        """a CARRIER_JOB_DTYPE array from a SYMBOLS_JOB_DTYPE array and the SYMBOLS_RECORD_DTYPE array that symbols() gave for it
+        (fosphor_amd_carrier_from_symbols: each job reads what the symbols job wrote, offset = out_offset, n = n_sym), the outputs
+        placed back to back from out_offset 0 on"""
+        L = _lib.load()
+        src = np.ascontiguousarray(np.atleast_1d(symbols_jobs), dtype=Fosphor.SYMBOLS_JOB_DTYPE)
+        rec = np.ascontiguousarray(np.atleast_1d(symbols_records), dtype=Fosphor.SYMBOLS_RECORD_DTYPE)
+        if src.size != rec.size:
+            raise ValueError("one symbols record per symbols job")
+        out = np.zeros(src.size, Fosphor.CARRIER_JOB_DTYPE)
+        code = Fosphor._carrier_mode(mode)
+        at = 0
+        for i, (s, r) in enumerate(zip(src, rec)):
+            job = _lib.CarrierJob()
+            rv = L.fosphor_amd_carrier_from_symbols(s.tobytes(), r.tobytes(), int(order), code, int(lag), float(freq), float(phase),
+                                                    C.byref(job))
+            if rv:
+                _fail("fosphor_amd_carrier_from_symbols", rv, ValueError)
+            out[i] = (job.offset, at, job.n, job.order, job.mode, job.lag, job.freq, job.phase)
+            at += job.n
+        return out
+
+    @staticmethod
+    def _carrier_outs(jobs):
+        return _outs(jobs, lambda j: int(j["n"]))
+
+    def carrier(self, d_iq, jobs, n_samples=None):
+        """One record and one run of derotated symbols per job, up to 4096 jobs in one call (fosphor_amd_carrier): the residual
+        carrier frequency from the lag-1 and lag-L sums of the symbols' M-th power, the phase from the sum of the powers with that
+        frequency removed, and the symbols turned back by both, over float32 symbols that are already in device memory.  d_iq: a
+        contiguous device tensor (complex64 or float32 pairs; what symbols() wrote) or a raw device pointer with n_samples; jobs: a
+        CARRIER_JOB_DTYPE array (carrier_jobs() makes one from symbols jobs and records; out_offset is honoured, the outputs
+        must not overlap).
+        Returns (records, views): a CARRIER_RECORD_DTYPE array copied from the device, in job order, and a list with one torch
+        complex64 view per job into one device buffer, n symbols long, or empty where the record says no_carrier."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.CARRIER_JOB_DTYPE)
+        n_samples = _iq_count(d_iq, n_samples, "samples")
+        _, cap = self._carrier_outs(jobs)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 1), dtype=torch.complex64, device="cuda")
+        d_rec = torch.empty(max(jobs.size, 1) * self.CARRIER_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()			# the caller's symbols were written on torch's stream
+        rv = self.L.fosphor_amd_carrier(self.h, _ptr(d_iq), n_samples, jobs.ctypes.data, int(jobs.size), d_rec.data_ptr(),
+                                        d_out.data_ptr(), cap)
+        if rv:
+            _fail("fosphor_amd_carrier", rv, RuntimeError)
+        records = d_rec.cpu().numpy().view(self.CARRIER_RECORD_DTYPE)[:jobs.size].copy()
+        return records, [d_out[int(j["out_offset"]):int(j["out_offset"]) + (int(j["n"]) if r["status"] == 0 else 0)]
+                         for j, r in zip(jobs, records)]
+
+    @staticmethod
+    def carrier_host(iq, jobs):
+        """fosphor_amd_carrier_host: the same records and symbols on the host, no GPU.  iq: complex64 or float32 pairs.  Returns
+        (records, views), the views complex64 arrays into one buffer"""
+        iq = _float_pairs(iq)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.CARRIER_JOB_DTYPE)
+        _, cap = Fosphor._carrier_outs(jobs)
+        out = np.zeros(max(cap, 1), np.complex64)
+        records = np.zeros(max(jobs.size, 1), Fosphor.CARRIER_RECORD_DTYPE)
+        keep = _or_dummy(iq)
+        rv = _lib.load().fosphor_amd_carrier_host(keep.ctypes.data, iq.size // 2, jobs.ctypes.data, int(jobs.size),
+                                                  records.ctypes.data, out.ctypes.data, cap)
+        if rv:
+            _fail("fosphor_amd_carrier_host", rv, ValueError)
+        records = records[:jobs.size]
+        return records, [out[int(j["out_offset"]):int(j["out_offset"]) + (int(j["n"]) if r["status"] == 0 else 0)]
+                         for j, r in zip(jobs, records)]
+
+    @staticmethod
+    def carrier_derive(records, symbol_rate):
+        """fosphor_amd_carrier_derive per record: a list of dicts of CARRIER_VALUES (Hz, radians, ratios)"""
+        L = _lib.load()
+        records = np.ascontiguousarray(np.atleast_1d(records), dtype=Fosphor.CARRIER_RECORD_DTYPE)
+        out = []
+        for r in records:
+            v = _lib.CarrierValues()
+            rv = L.fosphor_amd_carrier_derive(r.tobytes(), float(symbol_rate), C.byref(v))
+            if rv:
+                _fail("fosphor_amd_carrier_derive", rv, ValueError)
+            out.append({k: getattr(v, k) for k in Fosphor.CARRIER_VALUES})
+        return out
+
+    def carrier_stats(self):
+        """fosphor_amd_carrier_stats as a dict: calls, launches by kernel, jobs that estimate frequency and phase, symbols
+        (CARRIER_STATS)"""
+        return self._stats(self.L.fosphor_amd_carrier_stats, self.CARRIER_STATS)
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

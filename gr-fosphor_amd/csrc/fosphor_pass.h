@@ -28,6 +28,7 @@ enum {
 	FOSPHOR_SCRATCH_RESAMPLE,
 	FOSPHOR_SCRATCH_PSD,
 	FOSPHOR_SCRATCH_SYMBOLS,
+	FOSPHOR_SCRATCH_CARRIER,
 	FOSPHOR_SCRATCH_COUNT
 };
 
@@ -44,6 +45,7 @@ enum {
 	FOSPHOR_COUNTERS_RESAMPLE,
 	FOSPHOR_COUNTERS_PSD,
 	FOSPHOR_COUNTERS_SYMBOLS,
+	FOSPHOR_COUNTERS_CARRIER,
 	FOSPHOR_COUNTERS_COUNT
 };
 #define FOSPHOR_COUNTERS_MAX 10		/* counters of one pass at most (FOSPHOR_AMD_BURST_STATS) */
