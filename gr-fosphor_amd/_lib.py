@@ -239,6 +239,25 @@ class CarrierValues(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("freq_hz", "phase_rad", "sym_power", "lock", "lag_lock", "lagl_lock")]
 
 
+class DecideJob(C.Structure):
+    """struct fosphor_amd_decide_job (include/fosphor_amd_decide.h)"""
+    _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("n", C.c_int32), ("order", C.c_int32), ("flags", C.c_int32),
+                ("uw_offset", C.c_int32), ("uw_len", C.c_int32), ("uw_first", C.c_int32), ("uw_count", C.c_int32),
+                ("uw_max_errors", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class DecideRecord(C.Structure):
+    """struct fosphor_amd_decide_record"""
+    _fields_ = [("n", C.c_int32), ("order", C.c_int32), ("flags", C.c_int32), ("status", C.c_int32), ("uw_pos", C.c_int32),
+                ("uw_rot", C.c_int32), ("uw_errors", C.c_int32), ("erasures", C.c_int32), ("a", C.c_double), ("b", C.c_double),
+                ("m2", C.c_double), ("hist", C.c_int32 * 8), ("reserved", C.c_int32 * 2)]
+
+
+class DecideValues(C.Structure):
+    """struct fosphor_amd_decide_values"""
+    _fields_ = [(k, C.c_double) for k in ("gain", "evm_rms", "mer_db", "phase_err_rad", "uw_error_rate")]
+
+
 class ResampleJob(C.Structure):
     """struct fosphor_amd_resample_job (include/fosphor_amd_resample.h)"""
     _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("phase0", C.c_int64), ("n", C.c_int32), ("n_out", C.c_int32),
@@ -429,6 +448,15 @@ SIGNATURES = {
     "fosphor_amd_carrier_cossin_turns": (C.c_int, [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fosphor_amd_carrier_cossin_turns_n": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "fosphor_amd_carrier_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 9)]),
+    # include/fosphor_amd_decide.h
+    "fosphor_amd_decide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_int64]),
+    "fosphor_amd_decide_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_int64]),
+    "fosphor_amd_decide_from_carrier": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(DecideJob)]),
+    "fosphor_amd_decide_derive": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(DecideValues)]),
+    "fosphor_amd_decide_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 7)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

@@ -1486,6 +1486,139 @@ class Fosphor:
         (CARRIER_STATS)"""
         return self._stats(self.L.fosphor_amd_carrier_stats, self.CARRIER_STATS)
 
+    DECIDE_STATS = ("calls", "k_hard", "k_uw", "k_job", "k_out", "jobs_uw", "symbols")
+    DECIDE_MAX_JOBS = 4096				# FOSPHOR_AMD_DECIDE_MAX_JOBS (include/fosphor_amd_decide.h)
+    DECIDE_MAX_UW, DECIDE_MAX_UW_TABLE = 64, 65536	# FOSPHOR_AMD_DECIDE_MAX_UW, FOSPHOR_AMD_DECIDE_MAX_UW_TABLE
+    DECIDE_BLOCK, DECIDE_TILE = 64, 4096		# FOSPHOR_AMD_DECIDE_BLOCK, FOSPHOR_AMD_DECIDE_TILE
+    DECIDE_UW_GROUP = 256				# FOSPHOR_AMD_DECIDE_UW_GROUP
+    DECIDE_FLAGS = {"diff": 1, "gray": 2, "uw": 4}	# FOSPHOR_AMD_DECIDE_DIFF, _GRAY, _UW
+    DECIDE_STATUS = {"ok": 0, "no_uw": 1}		# FOSPHOR_AMD_DECIDE_OK, FOSPHOR_AMD_DECIDE_NO_UW
+    DECIDE_LDS = {"hard": 7904, "uw": 752, "job": 0, "out": 0}	# FOSPHOR_AMD_DECIDE_LDS_*
+    DECIDE_JOB_DTYPE = np.dtype([("offset", "<i8"), ("out_offset", "<i8"), ("n", "<i4"), ("order", "<i4"), ("flags", "<i4"),
+                                 ("uw_offset", "<i4"), ("uw_len", "<i4"), ("uw_first", "<i4"), ("uw_count", "<i4"),
+                                 ("uw_max_errors", "<i4"), ("reserved", "<i4", (4,))])
+    DECIDE_RECORD_DTYPE = np.dtype([("n", "<i4"), ("order", "<i4"), ("flags", "<i4"), ("status", "<i4"), ("uw_pos", "<i4"),
+                                    ("uw_rot", "<i4"), ("uw_errors", "<i4"), ("erasures", "<i4"), ("a", "<f8"), ("b", "<f8"),
+                                    ("m2", "<f8"), ("hist", "<i4", (8,)), ("reserved", "<i4", (2,))])
+    DECIDE_VALUES = tuple(k for k, _ in _lib.DecideValues._fields_)
+
+    @staticmethod
+    def _decide_flags(flags):
+        """an integer, one name of DECIDE_FLAGS or several ("diff", "uw") -> the sum of the bits"""
+        if isinstance(flags, str):
+            flags = (flags,)
+        if isinstance(flags, (tuple, list, set, frozenset)):
+            for k in flags:
+                if k not in Fosphor.DECIDE_FLAGS:
+                    raise ValueError("flags must be of %s" % ", ".join(Fosphor.DECIDE_FLAGS))
+            return sum(Fosphor.DECIDE_FLAGS[k] for k in set(flags))
+        return int(flags)
+
+    @staticmethod
+    def decide_owned(n):
+        """the bytes a job of n symbols owns in d_out: 4 ceil(n / 4)"""
+        return 4 * ((int(n) + 3) // 4)
+
+    @staticmethod
+    def decide_jobs(carrier_jobs, carrier_records, flags=0, uw_offset=0, uw_len=0, uw_first=0, uw_count=0, uw_max_errors=0, gap=4):
+        """a DECIDE_JOB_DTYPE array from a CARRIER_JOB_DTYPE array and the CARRIER_RECORD_DTYPE array that carrier() gave for it
+        (fosphor_amd_decide_from_carrier: each job reads what the carrier job wrote, offset = out_offset, n and order the
+        record's, n = 0 where the record says no_carrier), the owned bytes placed from out_offset 0 on at multiples of 4 with
+        `gap` bytes (rounded up to a multiple of 4) between them"""
+        L = _lib.load()
+        src = np.ascontiguousarray(np.atleast_1d(carrier_jobs), dtype=Fosphor.CARRIER_JOB_DTYPE)
+        rec = np.ascontiguousarray(np.atleast_1d(carrier_records), dtype=Fosphor.CARRIER_RECORD_DTYPE)
+        if src.size != rec.size:
+            raise ValueError("one carrier record per carrier job")
+        if gap < 0:
+            raise ValueError("gap must be >= 0")
+        out = np.zeros(src.size, Fosphor.DECIDE_JOB_DTYPE)
+        code = Fosphor._decide_flags(flags)
+        at = 0
+        for i, (s, r) in enumerate(zip(src, rec)):
+            job = _lib.DecideJob()
+            rv = L.fosphor_amd_decide_from_carrier(s.tobytes(), r.tobytes(), code, int(uw_offset), int(uw_len), int(uw_first),
+                                                   int(uw_count), int(uw_max_errors), C.byref(job))
+            if rv:
+                _fail("fosphor_amd_decide_from_carrier", rv, ValueError)
+            out[i] = (job.offset, at, job.n, job.order, job.flags, job.uw_offset, job.uw_len, job.uw_first, job.uw_count,
+                      job.uw_max_errors, (0, 0, 0, 0))
+            at += Fosphor.decide_owned(job.n) + Fosphor.decide_owned(gap)
+        return out
+
+    @staticmethod
+    def _decide_outs(jobs):
+        return _outs(jobs, lambda j: Fosphor.decide_owned(j["n"]))
+
+    @staticmethod
+    def _decide_word(uw):
+        """the call's unique-word table -> (a contiguous uint8 array or None, its length)"""
+        if uw is None:
+            return None, 0
+        uw = np.ascontiguousarray(uw, dtype=np.uint8).reshape(-1)
+        return (uw, int(uw.size)) if uw.size else (None, 0)
+
+    def decide(self, d_iq, jobs, uw=None, n_samples=None):
+        """One record and one byte per symbol per job, up to 4096 jobs in one call (fosphor_amd_decide): the nearest of M PSK points
+        per symbol, the 1 / M ambiguity taken out by differential decoding or by the rotation under which a unique word is found,
+        optional Gray demapping, over float32 symbols that are already in device memory.  d_iq: a contiguous device tensor
+        (complex64 or float32 pairs; what carrier() wrote) or a raw device pointer with n_samples; jobs: a DECIDE_JOB_DTYPE array
+        (decide_jobs() makes one from carrier jobs and records; out_offset is honoured, the owned bytes must not overlap); uw: the
+        call's table of unique-word symbols, uint8, that the jobs' uw_offset point into.
+        Returns (records, views): a DECIDE_RECORD_DTYPE array copied from the device, in job order, and a list with one torch
+        uint8 view of n symbols per job into one device buffer."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.DECIDE_JOB_DTYPE)
+        n_samples = _iq_count(d_iq, n_samples, "samples")
+        uw, n_uw = self._decide_word(uw)
+        _, cap = self._decide_outs(jobs)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 4), dtype=torch.uint8, device="cuda")
+        d_rec = torch.empty(max(jobs.size, 1) * self.DECIDE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()			# the caller's symbols were written on torch's stream
+        rv = self.L.fosphor_amd_decide(self.h, _ptr(d_iq), n_samples, jobs.ctypes.data, int(jobs.size),
+                                       uw.ctypes.data if n_uw else None, n_uw, d_rec.data_ptr(), d_out.data_ptr(), cap)
+        if rv:
+            _fail("fosphor_amd_decide", rv, RuntimeError)
+        records = d_rec.cpu().numpy().view(self.DECIDE_RECORD_DTYPE)[:jobs.size].copy()
+        return records, [d_out[int(j["out_offset"]):int(j["out_offset"]) + int(j["n"])] for j in jobs]
+
+    @staticmethod
+    def decide_host(iq, jobs, uw=None):
+        """fosphor_amd_decide_host: the same records and bytes on the host, no GPU.  iq: complex64 or float32 pairs.  Returns
+        (records, views), the views uint8 arrays into one buffer"""
+        iq = _float_pairs(iq)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.DECIDE_JOB_DTYPE)
+        uw, n_uw = Fosphor._decide_word(uw)
+        _, cap = Fosphor._decide_outs(jobs)
+        out = np.zeros(max(cap, 4) // 4, np.uint32).view(np.uint8)
+        records = np.zeros(max(jobs.size, 1), Fosphor.DECIDE_RECORD_DTYPE)
+        keep = _or_dummy(iq)
+        rv = _lib.load().fosphor_amd_decide_host(keep.ctypes.data, iq.size // 2, jobs.ctypes.data, int(jobs.size),
+                                                 uw.ctypes.data if n_uw else None, n_uw, records.ctypes.data, out.ctypes.data, cap)
+        if rv:
+            _fail("fosphor_amd_decide_host", rv, ValueError)
+        return records[:jobs.size], [out[int(j["out_offset"]):int(j["out_offset"]) + int(j["n"])] for j in jobs]
+
+    @staticmethod
+    def decide_derive(records, uw_len=0):
+        """fosphor_amd_decide_derive per record: a list of dicts of DECIDE_VALUES (ratios, dB, radians).  uw_len: one value for all
+        the records or one per record, the jobs' (0 without a unique word)"""
+        L = _lib.load()
+        records = np.ascontiguousarray(np.atleast_1d(records), dtype=Fosphor.DECIDE_RECORD_DTYPE)
+        out = []
+        for r, u in zip(records, np.broadcast_to(np.asarray(uw_len), records.shape)):
+            v = _lib.DecideValues()
+            rv = L.fosphor_amd_decide_derive(r.tobytes(), int(u), C.byref(v))
+            if rv:
+                _fail("fosphor_amd_decide_derive", rv, ValueError)
+            out.append({k: getattr(v, k) for k in Fosphor.DECIDE_VALUES})
+        return out
+
+    def decide_stats(self):
+        """fosphor_amd_decide_stats as a dict: calls, launches by kernel, jobs with a unique word, symbols (DECIDE_STATS)"""
+        return self._stats(self.L.fosphor_amd_decide_stats, self.DECIDE_STATS)
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

@@ -29,6 +29,7 @@ enum {
 	FOSPHOR_SCRATCH_PSD,
 	FOSPHOR_SCRATCH_SYMBOLS,
 	FOSPHOR_SCRATCH_CARRIER,
+	FOSPHOR_SCRATCH_DECIDE,
 	FOSPHOR_SCRATCH_COUNT
 };
 
@@ -46,6 +47,7 @@ enum {
 	FOSPHOR_COUNTERS_PSD,
 	FOSPHOR_COUNTERS_SYMBOLS,
 	FOSPHOR_COUNTERS_CARRIER,
+	FOSPHOR_COUNTERS_DECIDE,
 	FOSPHOR_COUNTERS_COUNT
 };
 #define FOSPHOR_COUNTERS_MAX 10		/* counters of one pass at most (FOSPHOR_AMD_BURST_STATS) */
