@@ -322,7 +322,8 @@ void k_dec_uw(const Params p)
 	const int diff = (job.flags & kDiff) ? 1 : 0;				/* p0 >= 1 under DIFF */
 	const int lo = p0 - diff;						/* the first decision that is read */
 	const int span = count + job.uw_len - 1 + diff;				/* decisions lo .. lo + span - 1 <= n - 1 */
-	const int w0 = lo >> 2, words = ((lo + span + 3) >> 2) - w0;		/* <= kUwWords; the last ends within the job's tiles */
+	/* span >= 1 and lo + span <= n, so nothing here passes n: lo + span + 3 would pass 2^31 - 1 in a job of 2^31 - 3 symbols or more */
+	const int w0 = lo >> 2, words = ((lo + span - 1) >> 2) + 1 - w0;	/* <= kUwWords; the last ends within the job's tiles */
 	const uint32_t *dec = p.dec + job.tile0 * (kTile / 4);
 	if (t < words && t < kUwWords)
 		s_w[t] = dec[w0 + t];

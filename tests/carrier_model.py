@@ -111,18 +111,18 @@ def frequency(R, Le):
         return (np.float64(aL) + k) / np.float64(Le)
 
 
-def phase_sums(pr, pi, w, wm, g):
-    """rule 5 -> (Zr, Zi, m2, mm)"""
-    j = np.arange(len(pr), dtype=np.float64)
+def phase_sums(pr, pi, w, wm, g, j0=0):
+    """rule 5 -> (Zr, Zi, m2, mm); j0: the job's index of the first symbol, a multiple of TILE (the sums of the tiles from there on)"""
+    j = np.arange(j0, j0 + len(pr), dtype=np.float64)
     with np.errstate(all="ignore"):
         c, sn = cossin_turns(np.float64(g) * j)
         return three_level(np.stack([(pr * c) + (pi * sn), (pi * c) - (pr * sn), w, wm], 1))
 
 
-def derotate(y, theta, f):
-    """rule 6 over float32 y [n][2] -> float32 [n][2]"""
+def derotate(y, theta, f, j0=0):
+    """rule 6 over float32 y [n][2], the symbols j0, j0 + 1, .. of a job -> float32 [n][2]"""
     sr, si = y[:, 0].astype(np.float64), y[:, 1].astype(np.float64)
-    j = np.arange(len(y), dtype=np.float64)
+    j = np.arange(j0, j0 + len(y), dtype=np.float64)
     with np.errstate(all="ignore"):
         c, sn = cossin_turns(np.float64(theta) + (np.float64(f) * j))
         return quiet(np.stack([((sr * c) + (si * sn)).astype(np.float32), ((si * c) - (sr * sn)).astype(np.float32)], 1))

@@ -1,12 +1,14 @@
 """The burst-IQ passes at the sizes their interface is built for: the input sets tests/test_job_scale_cpu.py,
-tests/test_gpu_job_scale.py and tests/test_gpu_job_far.py share, one view of the seven passes over them, and the geometry of the far
+tests/test_gpu_job_scale.py and tests/test_gpu_job_far.py share, one view of the nine passes over them, and the geometry of the far
 buffer.
 
-A case here is a Case: the pass, its jobs and the host copies of its buffers.  The seven models stay what they are
-(tests/extract_model.py, resample_model.py, measure_model.py, demod_model.py, correlate_model.py, psd_model.py, symbols_model.py);
-this file only names, per pass, the job field that places the input, the width of an output element, the stats a call must leave
+A case here is a Case: the pass, its jobs and the host copies of its buffers.  The nine models stay what they are
+(tests/extract_model.py, resample_model.py, measure_model.py, demod_model.py, correlate_model.py, psd_model.py, symbols_model.py,
+carrier_model.py, decide_model.py; carrier's rules 5 and 6 take the index of their first symbol);
+this file only names, per pass, the job field that places the input, the width of an output element in bytes (decide's out_offset
+counts bytes, in multiples of 4, and a job owns 4 ceil(n / 4) of them), the stats a call must leave
 and the comparison the pass's contract allows: bit for bit where the contract pins the order of the operations (resample, demod,
-correlate, psd, symbols), inside measure_model.job_tolerance and extract_model.bound where it leaves the order open.
+correlate, psd, symbols, carrier, decide), inside measure_model.job_tolerance and extract_model.bound where it leaves the order open.
 
 The long cases
   measure    130 * CHUNK + 5 samples: k_measure_combine folds 64 partials a round, so three rounds.  Plants (LONG_MEASURE_PLANTS)
@@ -23,8 +25,15 @@ The long cases
   symbols    R = 19 * TILE + 5 symbols at sps 3 and 64 (ESTIMATE) and 2 (FIXED): 20 fold tiles and 20 pick tiles, which
              k_sym_time and k_sym_record add under `#pragma unroll 8` -- two unrolled bodies and a remainder of 4; sps 8 with
              8 * TILE (one body exactly) and 8 * TILE + 1 symbols; a job of n = 0 in between.
-The full tables: exactly MAX_JOBS jobs of tiny shapes in shuffled order, every 11th without work (psd's and symbols' are their
-models' own full_table_case()).
+  carrier    19 * TILE + 5 symbols (20 sum tiles, 20 lag tiles: job_sums, under `#pragma unroll 8`, runs two bodies and a
+             remainder of 4) at every order under ESTIMATE with lags 1, 16 and 64 and under the three other modes; 8 * TILE,
+             8 * TILE + 1 (9 sum tiles, 8 lag tiles: where k_car_freq and k_car_phase differ) and 8 * TILE + 2; n = 0 in between.
+  decide     19 * TILE + 5, 8 * TILE and 8 * TILE + 1 symbols at every order, every flag set without a word, DIFF over every tile
+             seam (the sum loop of k_dec_job under `#pragma unroll 8`).  "long decide words": 304 groups of k_dec_uw a job, five
+             trips of a lane of k_dec_job; the same word in the groups 3, 67, 131 (one lane) and 70; a later position with one more
+             match; a window that begins behind the first copy; one position under two rotations (long_decide_words).
+The full tables: exactly MAX_JOBS jobs of tiny shapes in shuffled order, every 11th without work (psd's, symbols', carrier's and
+decide's are their models' own full_table_case()).
 The far buffer: FAR_SAMPLES float2 samples, about 16.01 GiB; bases and their aliases below.
 The long far jobs of psd and symbols read n = 2^31 - 1 samples, which no model can hold: the far buffer is one noise block of
 PERIOD samples repeated, PERIOD a multiple of the job's tile stride (TILE hop, TILE sps), so tile c of the job sees the samples of
@@ -32,6 +41,10 @@ tile c mod (PERIOD / stride).  periodic_psd and periodic_symbols compute those P
 partial one with the models' own functions and add them in the pinned serial order: the whole record, the whole trace, and the
 symbols of the first period and of the last tile, bit for bit.  PERIOD = 3 * 2^18 divides neither 2^31 nor 2^32 (both leave
 2^18 or 2^19 samples), so a position truncated to 31 or 32 bits reads other samples.
+The long far jobs of carrier and decide (CAR_LONG, DEC_LONG) run over the same kind of buffer with 192 tiles a period.  A decision
+does not depend on j, so decide is periodic as it stands (periodic_decide).  carrier's g j and theta + f j are periodic only where
+they are exact: with freq = 37 / 2^12 and a dyadic phase they are, and repeat every TILE symbols but for whole turns, which
+fosphor_amd_cossin_turns takes off exactly (exact_products, periodic_carrier); under ESTIMATE only the lag sums, m2 and mm are.
 
 What these cases are aimed at: every expression of the kernels that forms an address or a position from offset, first, out_offset,
 tpl_offset, phase0, m0, k0, c or blockIdx.x, with the type it is evaluated in, as read in gr-fosphor_amd/csrc (all are 64-bit, or
@@ -80,12 +93,42 @@ below 2^31 because the prefix gives a job no work-group beyond its n, n_out or n
                     mom[(mom0 + j0 / 4096) * 6 + t]: int64.
   k_sym_record      tiles = min((n_sym + 4095) / 4096, tiles_max): int.  mom + mom0 * 6 + lane: pointer + int64 + int;
                     T[(int64_t)c * 6]: int64.  records[j], counts[j]: below MAX_JOBS.
-None is a 32-bit product or sum that can pass 2^31: nothing to fix."""
+  k_car_lag         c = (int)(blockIdx.x - lag_prefix[j]), j0 = c * 4096: int, < n - 1.  terms = min(n - 1 - j0, 4096), span =
+                    min(n - (j0 + s0), count + Le), count_l = min(n - Le - (j0 + s0), count): int, differences of values <= n (count_l
+                    may be negative: no term).  y = iq + offset + j0: pointer + int64 + int.  y + s0, s_p[at + t + Le]: int, below
+                    4096 + 321.  lag_parts + (lag0 + c) * 4: pointer + (int64 + int) * int.  lag_used_of: 2 * lag <= 128.
+  k_car_freq        j = blockIdx.x * 4 + wave: int, below MAX_JOBS.  tiles_of(max(n - 1, 0)): the sum n + 4095 in int64.
+                    job_sums: lag_parts + lag0 * 4 + lane: pointer + int64; T[(int64_t)c * 4]: int64.  (double)Le * a1: exact.
+  k_car_sum         j0 = c * 4096: int, < n.  syms = min(n - j0, 4096).  y = iq + offset + j0: pointer + int64 + int; y[s0 + t]: int,
+                    < 4096.  (int64_t)j0 + s0 + t: int64, < n; (double) of it exact.  sum_parts + (sum0 + c) * 4: int64.
+  k_car_phase       tiles_of(n): int64 inside.  sum_parts + sum0 * 4: pointer + int64.  records[j], turn[j]: below MAX_JOBS.
+  k_car_turn        j0 as in k_car_sum.  out = out + out_offset + j0: pointer + int64 + int.  y[s], out[s]: int, < 4096.
+                    (int64_t)j0 + s: int64; theta + f * (double)j in double.
+  k_dec_hard        j0 = c * 4096: int, < n.  y = iq + offset + j0: pointer + int64 + int.  dec = dec + (tile0 + c) * 1024: pointer +
+                    (int64 + int) * int, up to 2^19 tiles of 4 KiB in one job.  dec[(s0 + t) >> 2]: int, < 1024.  parts + (tile0 + c):
+                    int64.  the counts: 16-bit fields of at most 16, summed over 64 lanes and 4 waves.
+  k_dec_uw          g = (int)(blockIdx.x - uw_prefix[j]); p0 = p_first + g * 256: int, a candidate, so <= n - uw_len.  count =
+                    min(p_first + p_count - p0, 256): p_first + p_count <= n - uw_len + 1 <= 2^31 - 1.  lo = p0 - diff >= 0.
+                    span = count + uw_len - 1 + diff <= 320, and lo + span <= n.  words = ((lo + span - 1) >> 2) + 1 - (lo >> 2):
+                    int, nothing passes n -- it was ((lo + span + 3) >> 2) - (lo >> 2), whose sum passes 2^31 - 1 in the last
+                    work-group of a job of n >= 2^31 - 3 symbols whose candidates run to its last position (DEC_LONG["B"]); the one
+                    expression of the nine kernels that had to change.  dec + tile0 * 1024: pointer + int64; dec[w0 + t]: int,
+                    w0 < 2^29.  uw[uw_at + t]: int, below MAX_UW_TABLE.  key_of: 0x7fffffff - p with 0 <= p < 2^31, then uint64.
+                    keys[key0 + g]: int64 + int.
+  k_dec_job         j: int, below MAX_JOBS.  tiles_of(n): int64 inside.  parts + tile0: pointer + int64; parts[c]: int, < 2^19.
+                    count += parts[c].cnt[..]: int, at most n in all.  groups = ((int64_t)p_count + 255) / 256: int64, then int
+                    <= 2^23.  keys[key0 + g]: int64 + int.  records[j], rot[j]: below MAX_JOBS.
+  k_dec_out         j0 = c * 4096: int, < n.  dec + (tile0 + c) * 1024: int64.  out + (out_offset >> 2) + (j0 >> 2): pointer + int64 +
+                    int, in words.  j0 + s > 0: int, < n.  dec[w - 1]: the word before, of the tile before where w = 0 (c > 0 then).
+None other is a 32-bit product or sum that can pass 2^31 - 1 within what the rules of the headers accept."""
+import fractions
 import functools
 
 import numpy as np
 
+import carrier_model as car
 import correlate_model as cm
+import decide_model as dec
 import demod_model as dm
 import extract_model as em
 import measure_model as mm
@@ -94,31 +137,35 @@ import resample_model as rm
 import symbols_model as sm
 
 SENTINEL = 0x5a5a5a5a
-PASSES = ("extract", "resample", "measure", "demod", "correlate", "psd", "symbols")
-MODELS = {"extract": em, "resample": rm, "measure": mm, "demod": dm, "correlate": cm, "psd": pm, "symbols": sm}
+PASSES = ("extract", "resample", "measure", "demod", "correlate", "psd", "symbols", "carrier", "decide")
+MODELS = {"extract": em, "resample": rm, "measure": mm, "demod": dm, "correlate": cm, "psd": pm, "symbols": sm, "carrier": car,
+          "decide": dec}
 MAX_JOBS = 4096
 GUARD = 3						# every model's: output elements before, between and behind the jobs' ranges
 
 
 class Case:
     """name: the pass; jobs; iq: float32 [n][2], or int16 / float16 [n][2] with fmt; taps: float32 (extract, resample); tpl:
-    float32 [n][2] or None where the templates lie in iq (correlate); win: float32, the windows (psd)"""
+    float32 [n][2] or None where the templates lie in iq (correlate); win: float32, the windows (psd); uw: uint8, the call's table
+    of unique-word symbols (decide), a host buffer like the jobs"""
 
-    def __init__(self, name, jobs, iq, taps=None, tpl=None, fmt=em.FP32, win=None):
+    def __init__(self, name, jobs, iq, taps=None, tpl=None, fmt=em.FP32, win=None, uw=None):
         self.name, self.jobs, self.fmt = name, np.ascontiguousarray(jobs, MODELS[name].JOB_DTYPE), fmt
         self.iq = np.ascontiguousarray(iq, em.RAW_DTYPE[fmt]).reshape(-1, 2)
         self.taps = None if taps is None else np.ascontiguousarray(taps, np.float32)
         self.tpl = None if tpl is None else np.ascontiguousarray(tpl, np.float32).reshape(-1, 2)
         self.win = None if win is None else np.ascontiguousarray(win, np.float32).reshape(-1)
+        self.uw = None if uw is None else np.ascontiguousarray(uw, np.uint8).reshape(-1)
 
     def with_jobs(self, jobs):
-        return Case(self.name, jobs, self.iq, self.taps, self.tpl, self.fmt, self.win)
+        return Case(self.name, jobs, self.iq, self.taps, self.tpl, self.fmt, self.win, self.uw)
 
     def model_case(self):
         """the case as its model's functions take it"""
         return {"extract": (self.fmt, self.iq, self.jobs, self.taps), "resample": (self.iq, self.taps, self.jobs),
                 "measure": (self.iq, self.jobs), "demod": (self.iq, self.jobs), "correlate": (self.iq, self.tpl, self.jobs),
-                "psd": (self.iq, self.win, self.jobs), "symbols": (self.iq, self.jobs)}[self.name]
+                "psd": (self.iq, self.win, self.jobs), "symbols": (self.iq, self.jobs), "carrier": (self.iq, self.jobs),
+                "decide": (self.iq, self.jobs, self.uw)}[self.name]
 
 
 def from_model(name, case):
@@ -132,15 +179,29 @@ def from_model(name, case):
         return Case(name, case[2], case[0], tpl=case[1])
     if name == "psd":
         return Case(name, case[2], case[0], win=case[1])
+    if name == "decide":
+        return Case(name, case[1], case[0], uw=case[2])
     return Case(name, case[1], case[0])
 
 
-# ---- one view of the seven passes -------------------------------------------------------------------------------------------------
+# ---- one view of the nine passes --------------------------------------------------------------------------------------------------
 
 IN_FIELD = {"extract": "first", "resample": "offset", "measure": "offset", "demod": "offset", "correlate": "offset", "psd": "offset",
-            "symbols": "offset"}
-OUT_WORDS = {"extract": 2, "resample": 2, "measure": 0, "demod": 1, "correlate": 1, "psd": 1, "symbols": 2}	# 32-bit words of an out_offset unit
-WITH_RECORDS = ("measure", "correlate", "psd", "symbols")
+            "symbols": "offset", "carrier": "offset", "decide": "offset"}
+# bytes of an out_offset unit: complex64, float32, or -- decide -- the byte itself, at out_offsets that are multiples of 4
+OUT_BYTES = {"extract": 8, "resample": 8, "measure": 0, "demod": 4, "correlate": 4, "psd": 4, "symbols": 8, "carrier": 8, "decide": 1}
+WITH_RECORDS = ("measure", "correlate", "psd", "symbols", "carrier", "decide")
+
+
+def guard(name):
+    """output elements before, between and behind the jobs' ranges: every model's GUARD, decide's 4 bytes"""
+    return dec.GUARD if name == "decide" else GUARD
+
+
+def out_words(name, elements):
+    """the 32-bit words of `elements` units of out_offset; decide's bytes come in fours"""
+    assert (elements * OUT_BYTES[name]) % 4 == 0, (name, elements)
+    return elements * OUT_BYTES[name] // 4
 
 
 def sample_bytes(case):
@@ -148,7 +209,8 @@ def sample_bytes(case):
 
 
 def n_out(name, job):
-    """the output elements of a job, in units of its out_offset; a symbols job reserves its max_out"""
+    """the output elements of a job, in units of its out_offset; a symbols job reserves its max_out, a decide job owns
+    4 ceil(n / 4) bytes, a carrier job its n symbols also where it finds no carrier and writes none"""
     if name in ("extract", "resample"):
         return int(job["n_out"])
     if name == "demod":
@@ -159,6 +221,10 @@ def n_out(name, job):
         return pm.n_out(job)
     if name == "symbols":
         return sm.job_max_out(job)
+    if name == "carrier":
+        return int(job["n"])
+    if name == "decide":
+        return dec.owned(job["n"])
     return 0
 
 
@@ -179,8 +245,8 @@ def has_work(name, job):
 
 
 def capacity(name, jobs):
-    """output elements of a case's buffer: the last one written and GUARD behind it"""
-    return max([int(j["out_offset"]) + n_out(name, j) for j in jobs if has_out(name, j)] + [0]) + GUARD
+    """output elements of a case's buffer: the last one written and guard(name) behind it"""
+    return max([int(j["out_offset"]) + n_out(name, j) for j in jobs if has_out(name, j)] + [0]) + guard(name)
 
 
 def in_span(name, job):
@@ -214,6 +280,10 @@ def forms(name, jobs):
         return ["group" if int(j["fft_len_log"]) > pm.WAVE_MAX_LOG else "wave" for j in jobs]
     if name == "symbols":
         return ["estimate" if int(j["mode"]) == sm.ESTIMATE else "fixed" for j in jobs]
+    if name == "carrier":					# jobs_freq: does k_car_lag and k_car_freq work for the job?
+        return ["fixed" if int(j["mode"]) & car.FREQ_FIXED else "estimate" for j in jobs]
+    if name == "decide":					# jobs_uw
+        return ["word" if int(j["flags"]) & dec.UW else "plain" for j in jobs]
     return ["tile"] * len(jobs)
 
 
@@ -225,6 +295,8 @@ def expected_stats(name, jobs, records=None):
         return rm.expected_stats(jobs)
     if name == "symbols":
         return sm.expected_stats(jobs, records)
+    if name in ("carrier", "decide"):
+        return MODELS[name].expected_stats(jobs)
     if name == "psd":					# what tests/test_gpu_psd.py's Box.run asserts
         segs = np.array([pm.job_n_seg(j) for j in jobs])
         return dict(calls=1, k_group=int(((f == "group") & (segs > 0)).any()), k_wave=int(((f == "wave") & (segs > 0)).any()),
@@ -249,9 +321,10 @@ def expected_stats(name, jobs, records=None):
 
 
 class Model:
-    """what the model says of a case, computed once: records (measure, correlate, psd, symbols), the image of the output buffer as
-    uint32 words with SENTINEL wherever no job writes (resample, demod, correlate, psd, symbols), or the float64 outputs and bounds
-    per job (extract)"""
+    """what the model says of a case, computed once: records (measure, correlate, psd, symbols, carrier, decide), the image of the
+    output buffer as uint32 words with SENTINEL wherever no job writes (resample, demod, correlate, psd, symbols, carrier, decide:
+    a carrier job without a carrier writes nothing, a decide job all the bytes it owns), or the float64 outputs and bounds per job
+    (extract)"""
 
     def __init__(self, case):
         name, jobs = case.name, case.jobs
@@ -270,19 +343,25 @@ class Model:
         elif name == "symbols":
             self.records, image = sm.image(case.model_case(), SENTINEL)
             self.image = image.reshape(-1)
+        elif name == "carrier":
+            self.records, image = car.image(case.model_case(), SENTINEL)
+            self.image = image.reshape(-1)
+        elif name == "decide":
+            self.records, image = dec.image(case.model_case(), SENTINEL & 0xff)
+            self.image = image.view(np.uint32)
         else:
             x = em.widen(case.iq, case.fmt)
             self.outs = [em.extract_job(x, j, case.taps) for j in jobs]
             self.tols = [em.bound(x, j, case.taps) for j in jobs]
 
     def check(self, rec, words, tag=""):
-        """rec: the records as the pass left them, or None; words: the whole output buffer as uint32 [OUT_WORDS * capacity]"""
+        """rec: the records as the pass left them, or None; words: the whole output buffer as uint32 [out_words(capacity)]"""
         name, jobs = self.case.name, self.case.jobs
         if name == "measure":
             mm.assert_records(rec, self.records, self.tols, tag)
             return
-        assert len(words) == OUT_WORDS[name] * capacity(name, jobs), tag
-        if name in ("correlate", "psd", "symbols"):
+        assert len(words) == out_words(name, capacity(name, jobs)), tag
+        if name in ("correlate", "psd", "symbols", "carrier", "decide"):
             bad = [i for i in range(len(jobs)) if rec[i].tobytes() != self.records[i].tobytes()]
             assert not bad, (tag, "records differ from the model's", bad[:4], rec[bad[:2]], self.records[bad[:2]])
         if name != "extract":
@@ -318,7 +397,7 @@ def host_twin(F, case):
     name, jobs = case.name, case.jobs
     if name == "measure":
         return F.measure_host(case.iq, jobs), None
-    words = np.full(OUT_WORDS[name] * capacity(name, jobs), SENTINEL, np.uint32)
+    words = np.full(out_words(name, capacity(name, jobs)), SENTINEL, np.uint32)
     rec = None
     if name == "demod":
         views = F.demod_host(case.iq, jobs)
@@ -328,12 +407,18 @@ def host_twin(F, case):
         rec, views = F.psd_host(case.iq, jobs, case.win)
     elif name == "symbols":
         rec, views = F.symbols_host(case.iq, jobs)
+    elif name == "carrier":
+        rec, views = F.carrier_host(case.iq, jobs)
+    elif name == "decide":
+        rec, views = F.decide_host(case.iq, jobs, case.uw)
+        whole = views[0].base if len(views) else None	# the host's buffer: a job owns the bytes up to the next multiple of 4
+        views = [whole.view(np.uint8)[int(j["out_offset"]):int(j["out_offset"]) + dec.owned(j["n"])] for j in jobs]
     else:
         rec, views = F.correlate_host(case.iq, jobs, case.iq if case.tpl is None else case.tpl)
     for j, v in zip(jobs, views):
         if v is not None and v.size:
             w = np.ascontiguousarray(v).view(np.uint32).reshape(-1)
-            at = OUT_WORDS[name] * int(j["out_offset"])
+            at = out_words(name, int(j["out_offset"]))
             words[at:at + len(w)] = w
     return rec, words
 
@@ -519,6 +604,101 @@ def long_symbols_case():
     return Case("symbols", sm.place(rows), sm.noise(longest, 6566))
 
 
+LONG_CAR = 19 * car.TILE + 5
+LONG_CAR_F0, LONG_CAR_THETA0 = 0.004, 0.03		# turns per symbol and turns of the buffer's carrier: g = M f0 <= 0.032
+
+
+def long_carrier_case():
+    """one BPSK buffer with a carrier offset in 30 dB of noise: its M-th power is a constant turned by M f0 a symbol at M = 2, 4 and
+    8 alike, so ESTIMATE locks at every order.  Jobs 0 .. 8: LONG_CAR symbols (20 sum tiles and 20 lag tiles: two unrolled bodies
+    of job_sums and a remainder of 4) under ESTIMATE at every order with the lags 1, 16 and 64; then the same n under FREQ_FIXED,
+    PHASE_FIXED and both; a job of n = 0; and 8 TILE (8 and 8 tiles: one body exactly), 8 TILE + 1 (9 sum tiles, 8 lag tiles) and
+    8 TILE + 2 (9 and 9) under ESTIMATE.  The offsets walk through 1, 2, 3, 0."""
+    iq = car.psk(LONG_CAR + 4, 2, LONG_CAR_F0, LONG_CAR_THETA0, 6567, 30.0)
+    rows = [(LONG_CAR, M, car.ESTIMATE, lag, 0.0, 0.0) for M in car.ORDERS for lag in (1, 16, 64)]
+    rows += [(LONG_CAR, 4, car.FREQ_FIXED, 16, LONG_CAR_F0, 0.0), (LONG_CAR, 2, car.PHASE_FIXED, 64, 0.0, 0.125),
+             (LONG_CAR, 8, car.FREQ_FIXED | car.PHASE_FIXED, 1, -0.0123, -0.25), (0, 4, car.ESTIMATE, 16, 0.0, 0.0)]
+    rows += [(n, M, car.ESTIMATE, 16, 0.0, 0.0) for n, M in ((8 * car.TILE, 2), (8 * car.TILE + 1, 4), (8 * car.TILE + 2, 8))]
+    return Case("carrier", car.place([((i + 1) % 4,) + r for i, r in enumerate(rows)]), iq)
+
+
+LONG_DEC = 19 * dec.TILE + 5
+
+
+def long_decide_case():
+    """planted PSK (decide_model.three_bursts, turned by 1 / M turns).  Per order: LONG_DEC symbols (20 tiles, which k_dec_job adds
+    under `#pragma unroll 8`: two bodies and a remainder of 4) with each of the four flag sets without a word -- the two with DIFF
+    take a difference over each of the 19 tile seams --, a job of n = 0, then 8 TILE (one body exactly) and 8 TILE + 1 symbols under
+    DIFF | GRAY and DIFF.  The offsets walk through 1, 2, 3, 0."""
+    iq, at, _ = dec.three_bursts(LONG_DEC + 4, 6568)
+    rows = []
+    for M in dec.ORDERS:
+        rows += [(LONG_DEC, M, flags) for flags in dec.ALL_FLAGS]
+        rows += [(0, M, dec.GRAY), (8 * dec.TILE, M, dec.DIFF | dec.GRAY), (8 * dec.TILE + 1, M, dec.DIFF)]
+    rows = [(at[M] + (i + 1) % 4, n, M, flags) for i, (n, M, flags) in enumerate(rows)]
+    return Case("decide", dec.place(rows), iq, uw=np.zeros(0, np.uint8))
+
+
+WORD_LEN = 40
+# job-relative positions of the same WORD_LEN (and one before, for the differences) symbols: with uw_first = 0 they fall in the
+# groups 3, 67, 70 and 131 of k_dec_uw -- 3, 67 and 131 are lane 3's first, second and third trip through k_dec_job's keys, 70 is
+# lane 6's second -- and in a job whose window begins behind the first of them in the groups 64, 67 and 128: lane 0's second and
+# third trip and lane 3's second
+WORD_TIES = tuple(g * dec.UW_GROUP + k for g, k in ((3, 10), (67, 100), (70, 137), (131, 200)))
+# ... of a word whose copies at the first two positions have their last symbol turned by 1 / M turns: one error there under every
+# flag set, none at the third -- groups 5 and 69 (lane 5's first and second trip) and 133 (its third)
+WORD_LATER = tuple(g * dec.UW_GROUP + k for g, k in ((5, 20), (69, 50), (133, 90)))
+WORD_TWO_ROTATIONS = (200 * dec.UW_GROUP + 31, 2, 5)	# (position, the two rotations): an 8PSK word of 64 symbols, half under each
+
+
+@functools.lru_cache(maxsize=None)
+def long_decide_words():
+    """-> (the Case "long decide words", [(uw_pos, uw_rot, uw_errors) that rule 4 must give per job]).
+    Per order one burst of LONG_DEC symbols with the plants of WORD_TIES and WORD_LATER copied into it (long_tie_case's method: the
+    same bytes, so the same decisions), and per order and without / with DIFF three jobs over all of it, uw_first = uw_count = 0,
+    LONG_DEC - WORD_LEN + 1 candidates in 304 groups, five trips of a lane of k_dec_job:
+      the word of WORD_TIES: four positions without an error, the smallest wins;
+      the word of WORD_LATER: one error at the two earlier positions, none at the third, which wins from lane 5's third trip;
+      the word of WORD_TIES in a window that begins one position behind the first: the second position wins, from a second trip.
+    Without DIFF the words are the decisions less 1, so uw_rot = 1.  The last job, 8PSK without DIFF: a word of 64 symbols that
+    meets WORD_TWO_ROTATIONS' position with 32 matches under each of two rotations and no other position with as many: the smaller
+    rotation wins."""
+    L = WORD_LEN
+    iq, at, _ = dec.three_bursts(LONG_DEC + 4, 6569)
+    iq = iq.copy()
+    start = {M: at[M] + 1 + i for i, M in enumerate(dec.ORDERS)}		# the jobs' first symbol
+    for M in dec.ORDERS:
+        burst = iq[start[M]:start[M] + LONG_DEC]
+        for plants in (WORD_TIES, WORD_LATER):
+            for p in plants[1:]:
+                burst[p - 1:p + L] = burst[plants[0] - 1:plants[0] + L]
+        turn = np.exp(2j * np.pi / M)
+        for p in WORD_LATER[:2]:						# the last symbol of the word, turned to the next point
+            z = complex(burst[p + L - 1, 0], burst[p + L - 1, 1]) * turn
+            burst[p + L - 1] = (z.real, z.imag)
+    words, rows, want = [], [], []
+
+    def add(M, flags, word, first, max_errors, expect):
+        rows.append((start[M], LONG_DEC, M, flags | dec.UW, sum(len(w) for w in words), len(word), first, 0, max_errors))
+        words.append(np.asarray(word, np.uint8))
+        want.append(expect)
+
+    for M in dec.ORDERS:
+        k = dec.decisions(iq[start[M]:start[M] + LONG_DEC], M)[0]
+        for flags in (0, dec.DIFF):
+            d = dec.difference(k, M, flags)
+            rot = 0 if flags else 1
+            cut = lambda p: (d[p:p + L] - rot) & (M - 1)
+            add(M, flags, cut(WORD_TIES[0]), 0, 0, (WORD_TIES[0], rot, 0))
+            add(M, flags | dec.GRAY, cut(WORD_LATER[2]), 0, 0, (WORD_LATER[2], rot, 0))
+            add(M, flags, cut(WORD_TIES[0]), WORD_TIES[0] + 1, 0, (WORD_TIES[1], rot, 0))
+    p, r0, r1 = WORD_TWO_ROTATIONS
+    k = dec.decisions(iq[start[8]:start[8] + LONG_DEC], 8)[0]
+    word = np.concatenate([k[p:p + 32] - r1, k[p + 32:p + 64] - r0]) & 7
+    add(8, 0, word, 0, 32, (p, min(r0, r1), 32))
+    return Case("decide", dec.place(rows), iq, uw=np.concatenate(words)), want
+
+
 # ---- the full tables ----------------------------------------------------------------------------------------------------------------
 
 def shuffled(jobs, seed):
@@ -589,7 +769,9 @@ def full_correlate_case():
 
 FULL = {"extract": full_extract_case, "resample": full_resample_case, "measure": full_measure_case, "demod": full_demod_case,
         "correlate": full_correlate_case, "psd": lambda: from_model("psd", pm.full_table_case()),
-        "symbols": lambda: from_model("symbols", sm.full_table_case())}
+        "symbols": lambda: from_model("symbols", sm.full_table_case()),
+        "carrier": lambda: from_model("carrier", car.full_table_case()),
+        "decide": lambda: from_model("decide", dec.full_table_case())}
 
 
 def one_job_of(case):
@@ -607,7 +789,8 @@ FAR_FREE_NEEDED = 20 * 2 ** 30
 FAR_GUARD = 4096					# sentinel elements either side of a far output range
 BASES_FP32 = (2 ** 29 + 16, 2 ** 31 + 16)		# in float2 samples: byte offset beyond 2^32; sample index beyond int32
 BASES_16 = BASES_FP32 + (2 ** 32 + 32,)			# in 4-byte samples
-OUT_BASE = {2: 2 ** 31 + 16, 1: 2 ** 32 + 32}		# by OUT_WORDS: beyond 2^31 complex outputs, beyond 2^32 floats
+# by OUT_BYTES: beyond 2^31 complex outputs, beyond 2^32 floats, beyond byte 2^32 of the buffer
+OUT_BASE = {8: 2 ** 31 + 16, 4: 2 ** 32 + 32, 1: 2 ** 32 + 2 ** 16}
 TPL_BASE = 2 ** 31 + 48
 WIN_BASE = 2 ** 32 + 64					# in floats: inside the buffer's 2^32 + 2^21
 
@@ -616,6 +799,10 @@ RELOCATE = {
     "psd tiles": lambda: from_model("psd", pm.tiles_case()),
     "symbols loads": lambda: from_model("symbols", sm.loads_case()),
     "symbols pick": lambda: from_model("symbols", sm.pick_case()),
+    "carrier loads": lambda: from_model("carrier", car.loads_case()),
+    "carrier lag": lambda: from_model("carrier", car.lag_case()),
+    "decide offsets": lambda: from_model("decide", dec.offsets_case()),
+    "decide windows": lambda: from_model("decide", dec.windows_case()),
     "extract n_out_seams": lambda: from_model("extract", em.cases()["n_out_seams"]),
     "extract first1_fp32": lambda: from_model("extract", em.cases()["first1_fp32"]),
     "extract first3_fp16": lambda: from_model("extract", em.cases()["first3_fp16"]),
@@ -811,16 +998,218 @@ def periodic_symbols(block, job):
     return r, (np.concatenate(outs) if outs else last), last
 
 
+# ---- the long carrier and decide jobs of the far buffer ---------------------------------------------------------------------------------
+
+CAR_LONG_A = 37						# the fixed frequency is CAR_LONG_A / 2^12 turns a symbol, the block's own carrier
+CAR_LONG_FREQ = CAR_LONG_A / 2.0 ** 12
+CAR_LONG_PHASE = 1.0 / 8 + 1.0 / 1024
+CAR_LONG = {"C": dict(order=4, mode=car.FREQ_FIXED | car.PHASE_FIXED, lag=16, freq=CAR_LONG_FREQ, phase=CAR_LONG_PHASE, offset=1, n=LONG_N),
+            "D": dict(order=4, mode=car.FREQ_FIXED, lag=16, freq=CAR_LONG_FREQ, phase=0.0, offset=1, n=LONG_N),
+            "E": dict(order=4, mode=car.ESTIMATE, lag=16, freq=0.0, phase=0.0, offset=1, n=LONG_N)}
+CAR_E_FIELDS = ("n", "order", "lag_used", "status", "freq", "r1_re", "r1_im", "rl_re", "rl_im", "m2", "mm")	# what job E has a model of
+DEC_LONG_WORD = 16					# symbols of the far jobs' word
+DEC_LONG_AT = 100000					# where job A's word is cut from the block's first period, job-relative
+DEC_LONG = {"A": dict(order=4, flags=dec.UW, offset=1, n=LONG_N, uw_first=0),
+            "B": dict(order=4, flags=dec.UW | dec.DIFF, offset=1, n=LONG_N, uw_first=LONG_N - DEC_LONG_WORD - 600)}
+
+
+def carrier_block(order=4):
+    """PERIOD symbols of a PSK whose carrier turns by CAR_LONG_FREQ a symbol -- a whole number of turns a period, so the block
+    repeated is one continuous burst -- in 30 dB of noise"""
+    return car.psk(PERIOD, order, CAR_LONG_FREQ, 0.02, 7373, 30.0)
+
+
+def decide_block(order=4):
+    """PERIOD symbols of a planted PSK turned by 1 / M turns in 30 dB of noise"""
+    return dec.psk(PERIOD, order, 0.0, 1.0 / order + 0.01 / order, 7474, 30.0)
+
+
+def long_carrier_job(spec, out_offset=GUARD):
+    return car.make_jobs([(spec["offset"], out_offset, spec["n"], spec["order"], spec["mode"], spec["lag"], spec["freq"], spec["phase"])])
+
+
+def long_decide_job(spec, block, out_offset=dec.GUARD):
+    """-> (the job, its word).  Job A's word: the DEC_LONG_WORD decisions at DEC_LONG_AT of the first period, less 1 (uw_rot = 1).
+    Job B's: the differences at a position of the job's last group"""
+    n, M, flags, off = spec["n"], spec["order"], spec["flags"], spec["offset"]
+    L = DEC_LONG_WORD
+    p = n - L - 50 if flags & dec.DIFF else DEC_LONG_AT
+    k = dec.decisions(wrapped(block, off + p - 1, L + 1), M)[0]
+    word = ((k[1:] - k[:-1]) if flags & dec.DIFF else (k[1:] - 1)) & (M - 1)
+    return dec.make_jobs([(off, out_offset, n, M, flags, 0, L, spec["uw_first"], 0, 0)]), word.astype(np.uint8)
+
+
+def exact_products(job):
+    """are g j and theta + f j of a carrier job with fixed frequency and phase exact up to its last symbol?  Then, with g TILE a
+    whole number, both repeat every TILE symbols but for whole turns, which fosphor_amd_cossin_turns takes off exactly (t -
+    floor(t)), and the job over a periodic buffer is periodic"""
+    Fr = fractions.Fraction
+    M = int(job["order"])
+    f = Fr(float(job["freq"]))
+    g = Fr(float(np.float64(job["freq"]) * np.float64(M)))
+    ok = g == f * M and Fr(float(g / M)) == f and (g * car.TILE).denominator == 1 and (f * car.TILE).denominator == 1
+    for j in (1, car.TILE - 1, 2 ** 30 + 1, int(job["n"]) - 1):
+        ok = ok and Fr(float(np.float64(float(g)) * np.float64(j))) == g * j
+        if int(job["mode"]) & car.PHASE_FIXED:
+            th = Fr(float(job["phase"]))
+            ok = ok and Fr(float(np.float64(float(th)) + (np.float64(float(f)) * np.float64(j)))) == th + f * j
+    return bool(ok)
+
+
+def more_tiles(S, tiles):
+    """S and then every row of `tiles`, one after the other"""
+    with np.errstate(all="ignore"):
+        for t in tiles:
+            S = S + t
+    return S
+
+
+def periodic_carrier(block, job):
+    """the carrier job over `block` repeated for ever, len(block) a multiple of TILE: tile c of the lag terms and of the symbols sees
+    the samples of tile c mod (len(block) / TILE).  Lag tile c is periodic as long as all its terms of lag Le exist ((c + 1) TILE +
+    Le <= n); those tiles and every later one by carrier_model's functions, added in the order of rule 2.  The sums w and |s|^M of
+    rule 5 are periodic as they stand; its Z only where g j repeats every TILE symbols (exact_products): the tile of symbol j is
+    computed with j mod len(block), so for another g the model's z_re, z_im and phase are not the job's -- ESTIMATE at this length
+    has no model of them, and the caller compares CAR_E_FIELDS alone.
+    -> a RECORD_DTYPE array [1]"""
+    block = car.buffer((block,))
+    n, M, mode, L, off = int(job["n"]), int(job["order"]), int(job["mode"]), int(job["lag"]), int(job["offset"])
+    T, P = car.TILE, len(block)
+    assert P % T == 0
+    cycle = P // T
+    r = np.zeros(1, car.RECORD_DTYPE)
+    r["n"], r["order"] = n, M
+    if mode & car.FREQ_FIXED:
+        g = np.float64(job["freq"]) * np.float64(M)
+    else:
+        Le = car.lag_used(n, L)
+
+        def lag_tile(c):
+            """the four sums of the lag terms c TILE .. of the job"""
+            j0 = c * T
+            terms = min(n - 1 - j0, T)
+            pr, pi, _, _ = car.power(wrapped(block, off + j0, min(terms + Le, n - j0)), M)
+            t = np.zeros((terms, 4))
+            with np.errstate(all="ignore"):
+                ar, ai, br, bi = pr[1:terms + 1], pi[1:terms + 1], pr[:terms], pi[:terms]
+                t[:, 0], t[:, 1] = (ar * br) + (ai * bi), (ai * br) - (ar * bi)
+                tl = max(min(n - Le - j0, terms), 0) if Le > 1 else 0
+                ar, ai, br, bi = pr[Le:Le + tl], pi[Le:Le + tl], pr[:tl], pi[:tl]
+                t[:tl, 2], t[:tl, 3] = (ar * br) + (ai * bi), (ai * br) - (ar * bi)
+                return car.three_level(t)			# one tile: the third level adds it to 0.0
+
+        tiles = -(-max(n - 1, 0) // T)
+        whole = min(max((n - Le) // T, 0), tiles)
+        distinct = [lag_tile(c) for c in range(min(cycle, whole))] or np.zeros((1, 4))
+        R = more_tiles(serial_sum(distinct, whole), [lag_tile(c) for c in range(whole, tiles)])
+        r["lag_used"] = Le
+        r["r1_re"], r["r1_im"], r["rl_re"], r["rl_im"] = (car.quiet64(v) for v in R)
+        g = car.frequency(tuple(R), Le)
+        if g is None:
+            r["status"], r["freq"], r["phase"] = car.NO_CARRIER, car.QNAN64, car.QNAN64
+            return r
+    f = g / np.float64(M)
+    full, rest = divmod(n, T)
+
+    def sum_tile(c, syms):
+        j0 = (c % cycle) * T
+        return car.phase_sums(*car.power(wrapped(block, off + j0, syms), M), g, j0)
+
+    distinct = [sum_tile(c, T) for c in range(min(cycle, full))] or np.zeros((1, 4))
+    Z = serial_sum(distinct, full, sum_tile(full, rest) if rest else None)
+    r["z_re"], r["z_im"], r["m2"], r["mm"] = (car.quiet64(v) for v in Z)
+    if mode & car.PHASE_FIXED:
+        theta = np.float64(job["phase"])
+    else:
+        thM = dm.atan2_turns(Z[1], Z[0])
+        if np.isnan(thM):
+            r["status"], r["freq"], r["phase"] = car.NO_CARRIER, car.QNAN64, car.QNAN64
+            return r
+        theta = np.float64(thM) / np.float64(M)
+    r["freq"], r["phase"] = f, theta
+    return r
+
+
+def carrier_symbols(block, job, record, j0, count):
+    """the derotated symbols j0 .. j0 + count of the job over `block` repeated, by rule 6 with the true index j"""
+    return car.derotate(wrapped(car.buffer((block,)), int(job["offset"]) + j0, count), record["phase"][0], record["freq"][0], j0)
+
+
+def periodic_decide(block, job, uw):
+    """the decide job over `block` repeated for ever, len(block) a multiple of TILE.  A decision and its terms of rule 2 do not
+    depend on j, so tile c is tile c mod (len(block) / TILE): the distinct tiles and the last, partial one by decide_model's
+    functions, their sums added in the order of rule 2, their counts as integers.  The differences repeat from d[1] on.  The search
+    of rule 4 runs over the first len(block) candidates: a later candidate sees the decisions of the one len(block) before it,
+    which is a candidate too, so it repeats that one's key with a larger p and cannot win -- the result is exact.
+    -> (a RECORD_DTYPE array [1], bytes(j0, count): the bytes of symbols j0 .. j0 + count of the job as the record's rotation
+    leaves them, uint8)"""
+    block = dec.buffer((block,))
+    n, M, flags, off = int(job["n"]), int(job["order"]), int(job["flags"]), int(job["offset"])
+    T, P = dec.TILE, len(block)
+    assert P % T == 0
+    cycle = P // T
+    full, rest = divmod(n, T)
+
+    def tile(c, syms):
+        y = wrapped(block, off + (c % cycle) * T, syms)
+        k, erased = dec.decisions(y, M)
+        return dec.three_level(dec.terms(y, k, M)), np.concatenate([np.bincount(k, minlength=8), [int(erased.sum())]])
+
+    tiles = [tile(c, T) for c in range(min(cycle, full))]
+    last = tile(full, rest) if rest else None
+    S = serial_sum([t[0] for t in tiles] or np.zeros((1, 3)), full, last[0] if rest else None)
+    counts = np.zeros(9, np.int64)
+    if tiles:
+        per = np.array([t[1] for t in tiles], np.int64)
+        counts += (full // len(tiles)) * per.sum(0) + per[:full % len(tiles)].sum(0)
+    if rest:
+        counts += last[1]
+    r = np.zeros(1, dec.RECORD_DTYPE)
+    r["n"], r["order"], r["flags"], r["uw_pos"] = n, M, flags, -1
+    r["erasures"], r["hist"][0] = counts[8], counts[:8]
+    r["a"], r["b"], r["m2"] = (dec.quiet64(v) for v in S)
+    diff = 1 if flags & dec.DIFF else 0
+
+    def differences(j0, count):
+        """d[j0 .. j0 + count] of the job"""
+        before = 1 if diff and j0 else 0
+        k = dec.decisions(wrapped(block, off + j0 - before, count + before), M)[0]
+        if not diff:
+            return k
+        d = (k[1:] - k[:-1]) & (M - 1)
+        return d if before else np.concatenate([k[:1], d])
+
+    if flags & dec.UW:
+        L = int(job["uw_len"])
+        u = np.asarray(uw, np.int64)[int(job["uw_offset"]):int(job["uw_offset"]) + L]
+        first, count = dec.candidates(job)
+        r["uw_errors"] = L
+        if count:
+            seen = min(count, P)
+            pos, rot, matches = dec.find_word(differences(first, seen + L - 1), u, M, flags, 0, seen)
+            r["uw_pos"], r["uw_rot"], r["uw_errors"] = first + pos, rot, L - matches
+        if not count or r["uw_errors"][0] > int(job["uw_max_errors"]):
+            r["status"] = dec.NO_UW
+    rot = int(r["uw_rot"][0])
+
+    def out_bytes(j0, count):
+        q = (differences(j0, count) - rot) & (M - 1)
+        return (q ^ (q >> 1) if flags & dec.GRAY else q).astype(np.uint8)
+
+    return r, out_bytes
+
+
 CASES = dict(RELOCATE)
 CASES.update({"long measure": long_measure_case, "long edges": long_edges_case, "long tie": long_tie_case,
-              "long resample": long_resample_case, "long psd": long_psd_case, "long symbols": long_symbols_case})
+              "long resample": long_resample_case, "long psd": long_psd_case, "long symbols": long_symbols_case,
+              "long carrier": long_carrier_case, "long decide": long_decide_case, "long decide words": lambda: long_decide_words()[0]})
 CASES.update({"full " + k: v for k, v in FULL.items()})
 
 
 # ---- driving the passes on the device (torch is imported where it is used: the CPU tests import this file too) ----------------------
 
 class Dev:
-    """an instance, torch views of its waterfall ring and spectrum, and the seven passes through the C ABI by raw device pointers"""
+    """an instance, torch views of its waterfall ring and spectrum, and the nine passes through the C ABI by raw device pointers"""
 
     def __init__(self, amd, wf_rows=16):
         self.f = amd.Fosphor(n_bins=128, wf_rows=wf_rows)
@@ -852,9 +1241,10 @@ class Dev:
         assert torch.equal(self.spec.view(torch.int32), self.saved[1]), "the spectrum lines were written"
 
     def call(self, name, jobs, fmt, iq, n_iq, out=None, cap=0, taps=None, n_taps=0, tpl=None, n_tpl=0, rec=None, win=None, n_win=0,
-             tag=""):
-        """one call that must succeed, every buffer a device pointer: the ring, the waterfall and the spectrum untouched and the
-        stats delta what the jobs predict (symbols: the jobs and the n_sym of the records it wrote)"""
+             uw=None, tag=""):
+        """one call that must succeed, every buffer a device pointer (uw: decide's table, a host array): the ring, the waterfall
+        and the spectrum untouched and the stats delta what the jobs predict (symbols: the jobs and the n_sym of the records it
+        wrote)"""
         import torch
         jobs = np.ascontiguousarray(jobs, MODELS[name].JOB_DTYPE)
         self.save()
@@ -873,6 +1263,11 @@ class Dev:
             rv = L.fosphor_amd_psd(h, iq, n_iq, win, n_win, jobs.ctypes.data, len(jobs), rec, out, cap)
         elif name == "symbols":
             rv = L.fosphor_amd_symbols(h, iq, n_iq, jobs.ctypes.data, len(jobs), rec, out, cap)
+        elif name == "carrier":
+            rv = L.fosphor_amd_carrier(h, iq, n_iq, jobs.ctypes.data, len(jobs), rec, out, cap)
+        elif name == "decide":
+            n_uw = 0 if uw is None else len(uw)
+            rv = L.fosphor_amd_decide(h, iq, n_iq, jobs.ctypes.data, len(jobs), uw.ctypes.data if n_uw else None, n_uw, rec, out, cap)
         else:
             rv = L.fosphor_amd_correlate(h, iq, n_iq, tpl, n_tpl, jobs.ctypes.data, len(jobs), rec, out, cap)
         after = stats()
@@ -932,11 +1327,11 @@ class Dev:
         if out_at is not None:
             out, cap = out_at[0], out_at[1]
             jobs = shifted(case.with_jobs(jobs), "out_offset", out_at[2]).jobs
-        elif OUT_WORDS[name]:
-            d_out = torch.full((OUT_WORDS[name] * cap + 2,), SENTINEL, dtype=torch.int32, device="cuda")
+        elif OUT_BYTES[name]:
+            d_out = torch.full((out_words(name, cap) + 2,), SENTINEL, dtype=torch.int32, device="cuda")
             out = d_out.data_ptr()
         self.call(name, jobs, case.fmt, iq, n_iq, out=out, cap=cap, taps=taps, n_taps=n_taps or 0, tpl=tpl, n_tpl=n_tpl or 0, rec=rec,
-                  win=win, n_win=n_win or 0, tag=tag)
+                  win=win, n_win=n_win or 0, uw=case.uw, tag=tag)
         for k, (d, host) in held.items():
             assert d.cpu().numpy().tobytes() == host.tobytes(), (tag, "the %s buffer was written" % k)
         got = words_out = None

@@ -11,9 +11,10 @@ only where less than 20 GiB of device memory is free, with both numbers in the r
                 (jc.aliases).  The far results are bit-identical to the near ones -- also for extract and measure: their kernels
                 have no atomics, and no order of their additions depends on an address beyond its low four bits -- and the near
                 ones are held to the model as everywhere.
-  far outputs   the buffer as d_out with a small input of its own: out_offset beyond 2^31 complex outputs (extract, resample) and
-                beyond 2^32 floats (demod, correlate); FAR_GUARD sentinel elements either side of the range and the same at the
-                aliases of the output offset, all checked afterwards.  One run with the buffer as correlate's d_tpl.
+  far outputs   the buffer as d_out with a small input of its own: out_offset beyond 2^31 complex outputs (extract, resample,
+                symbols, carrier), beyond 2^32 floats (demod, correlate, psd) and beyond byte 2^32 (decide, whose out_offset counts
+                bytes); FAR_GUARD sentinel elements either side of the range and the same at the aliases of the output offset, all
+                checked afterwards.  One run with the buffer as correlate's d_tpl.
   long extract  WAVE: D = 1024, T = 3 over a span of 2^32 + 8195 sc16 samples, phase0 near 2^32; exactly the samples it reads
                 are written, from a hash of the index that numpy recomputes.  TILE: D = 25, T = 33, base = m0 * D beyond 2^31,
                 input and output in disjoint regions of the buffer; the tiles at the ends and on both sides of 2^31 against the
@@ -29,8 +30,30 @@ only where less than 20 GiB of device memory is free, with both numbers in the r
                 symbols): the record bit-identical to jc.periodic_symbols, every period of the output equal to the first on the
                 device, the first period and the last tile equal to the model's, sentinels either side; the FIXED job's last 64
                 symbols from a short job that begins beyond sample 2^31.
+  long decide   n = 2^31 - 1 planted QPSK symbols over the periodic buffer, a word of 16 symbols.  Job A: no DIFF, every position
+                a candidate (2^23 groups of k_dec_uw, 2^17 trips of a lane of k_dec_job): the record bit-identical to
+                jc.periodic_decide -- the sums of 2^19 tiles, hist, erasures, uw_pos the word's first occurrence, uw_rot 1 --,
+                every period of the output bytes equal to the first on the device, the first period and the last tile equal to
+                the model's, the one byte behind the last symbol 0, sentinels either side.  Job B: DIFF, the window is the last
+                601 positions, the word lies in the last group at a position above 2^31 - 700: the last work-group of k_dec_uw
+                has lo + span = n, where the count of words it loads was formed as (lo + span + 3) >> 2 in int before this job
+                existed (now ((lo + span - 1) >> 2) + 1; the unfixed line was never run at this length).  Byte 0 is no difference,
+                so period 0 is held to the model and the periods from 1 on to period 1.
+  long carrier  n = 2^31 - 1 QPSK symbols with a carrier of 37 / 2^12 turns a symbol over the periodic buffer, 2^19 sum tiles and
+                2^19 lag tiles.  Job C: frequency and phase fixed and dyadic, so g j and theta + f j are exact and repeat every
+                4096 symbols (jc.exact_products): the record bit-identical to jc.periodic_carrier, every period of the output
+                equal to the first, the first period and the last tile equal to the model's.  Job D: the frequency fixed, the
+                phase estimated: the record bit-identical; theta + f j rounds, so the output is not periodic: the first two tiles,
+                the two either side of j = 2^30 and the last against carrier_model.derotate with the true j.  Job E: ESTIMATE --
+                every lag tile is periodic: n, order, lag_used, status, freq, r1_*, rl_*, m2 and mm bit-identical; z_*, phase
+                and the output depend on g j with a g that is not dyadic and have no model at this length: not compared (jobs C
+                and D carry k_car_sum and k_car_turn at this length, job E is there for k_car_lag and k_car_freq).
 Measured once on an MI355X, the call alone and in brackets the whole test with its fills, its model and its comparisons:
 PSD_LONG 0.55 s (0.84 s), PSD_LONG_PARTS 3.55 s (4.29 s), symbols at sps 3 0.02 s (0.12 s), at sps 64 0.01 s (0.06 s).
+Decide A 0.21 s (0.65 s), decide B 0.15 s (0.50 s), carrier C 0.06 s (0.85 s), carrier D 0.06 s (0.32 s), carrier E 0.11 s (0.56 s):
+all far below the 5 s at which a job would have been shortened, so all five run at n = 2^31 - 1.  The decide jobs want 2 GiB of
+output and about 2.1 GiB of scratch, the carrier jobs 16 GiB of output beside the buffer; each is skipped, with both numbers in the
+reason, where that much more was not free when the buffer was taken.
 PSD_LONG_PARTS wants 4 GiB of scratch and the sps 3 job 5.4 GiB of symbols beside the buffer: each is skipped, with both numbers in
 the reason, where that much more was not free when the buffer was taken."""
 import os
@@ -39,6 +62,8 @@ import time
 import numpy as np
 import pytest
 
+import carrier_model as car
+import decide_model as dec
 import extract_model as em
 import job_scale_cases as jc
 import psd_model as pm
@@ -48,7 +73,7 @@ pytestmark = pytest.mark.gpu
 
 SENTINEL = jc.SENTINEL
 G = jc.FAR_GUARD
-WITH_OUTPUT = sorted(k for k in jc.RELOCATE if jc.OUT_WORDS[k.split()[0]])
+WITH_OUTPUT = sorted(k for k in jc.RELOCATE if jc.OUT_BYTES[k.split()[0]])
 
 
 @pytest.fixture(scope="module")
@@ -152,18 +177,19 @@ def test_relocated_output(dev, far, key):
     case = jc.case_of(key)
     near = dev.run(case, tag=key)
     jc.model_of(key).check(*near, tag=key)
-    per = jc.OUT_WORDS[case.name]				# words of an output element
-    base, cap = jc.OUT_BASE[per], jc.capacity(case.name, case.jobs)
-    spans = [(max(a - G, 0), a + cap + G) for a in jc.aliases(base, 4 * per)]
+    unit = jc.OUT_BYTES[case.name]				# bytes of an output element: 8, 4, or decide's 1
+    w = lambda elements: jc.out_words(case.name, elements)	# every base, guard and capacity here is a whole number of words
+    base, cap = jc.OUT_BASE[unit], jc.capacity(case.name, case.jobs)
+    spans = [(max(a - G, 0), a + cap + G) for a in jc.aliases(base, unit)]
     for a, b in spans + [(base - G, base + cap + G)]:
-        far.fill(a * per, (b - a) * per)
-    rec, _ = dev.run(case, tag=key + " far out", out_at=(far.ptr, jc.FAR_BYTES // (4 * per), base))
-    got = far.get((base - G) * per, (cap + 2 * G) * per)
-    assert np.all(got[:G * per] == SENTINEL) and np.all(got[-G * per:] == SENTINEL), "written beside the far range"
-    assert got[G * per:-G * per].tobytes() == near[1].tobytes(), "the far outputs differ from the near ones"
+        far.fill(w(a), w(b - a))
+    rec, _ = dev.run(case, tag=key + " far out", out_at=(far.ptr, jc.FAR_BYTES // unit, base))
+    got = far.get(w(base - G), w(cap + 2 * G))
+    assert np.all(got[:w(G)] == SENTINEL) and np.all(got[-w(G):] == SENTINEL), "written beside the far range"
+    assert got[w(G):-w(G)].tobytes() == near[1].tobytes(), "the far outputs differ from the near ones"
     assert same((rec,), near[:1])
     for a, b in spans:
-        assert far.count(a * per, (b - a) * per) == (b - a) * per, "written at an alias of the output offset"
+        assert far.count(w(a), w(b - a)) == w(b - a), "written at an alias of the output offset"
 
 
 def test_relocated_templates(dev, far):
@@ -321,6 +347,113 @@ def test_long_symbols_job(dev, far, key):
         assert d_trec.cpu().numpy().view(sm.RECORD_DTYPE)["n_sym"][0] == 64
         assert short[jc.GUARD:-jc.GUARD].tobytes() == sym[-128:].cpu().numpy().tobytes(), "the last 64 symbols do not depend on the cut"
     print("%s: the call %.2f s, the test %.2f s" % (key, t_call, time.perf_counter() - t_test))
+
+
+@pytest.mark.parametrize("name", sorted(jc.DEC_LONG))
+def test_long_decide_job(dev, far, name):
+    """2^19 tiles, which one wave of k_dec_job adds; job A's 2^23 keys, job B's last group at the end of the job.  The output is
+    2 GiB and the scratch (partial records, decisions, keys) about 2.1 GiB beside the far buffer."""
+    import torch
+    spec = jc.DEC_LONG[name]
+    n, W, T, P = spec["n"], dec.RECORD_WORDS, dec.TILE, jc.PERIOD
+    own = dec.owned(n)
+    need = jc.FAR_FREE_NEEDED + own + 3 * 2 ** 30
+    if far.free < need:
+        pytest.skip("%d bytes of output and about %d of scratch beside the far buffer want %d bytes free: %d were"
+                    % (own + 2 * G, 2 ** 31 + 2 ** 28, need, far.free))
+    t_test = time.perf_counter()
+    block = jc.decide_block(spec["order"])
+    rows, d_block = fill_periodic(far, block)
+    job, word = jc.long_decide_job(spec, block, out_offset=G)
+    cap = own + 2 * G
+    d_out = guarded(torch, cap // 4)
+    d_rec = guarded(torch, (1 + 2 * jc.GUARD) * W)
+    t_call = time.perf_counter()
+    dev.call("decide", job, em.FP32, far.ptr, jc.FAR_SAMPLES, out=d_out.data_ptr(), cap=cap, rec=d_rec.data_ptr() + 4 * W * jc.GUARD,
+             uw=word, tag="decide " + name)
+    t_call = time.perf_counter() - t_call
+    want_rec, out_bytes = jc.periodic_decide(block, job[0], word)
+    rec = d_rec.cpu().numpy().view(np.uint32).reshape(-1, W)
+    assert np.all(rec[:jc.GUARD] == SENTINEL) and np.all(rec[-jc.GUARD:] == SENTINEL), "written outside the record"
+    got_rec = rec[jc.GUARD].copy().view(dec.RECORD_DTYPE)
+    assert got_rec.tobytes() == want_rec.tobytes(), (name, got_rec, want_rec)
+    L = jc.DEC_LONG_WORD
+    want_pos = n - L - 50 if name == "B" else jc.DEC_LONG_AT
+    assert (got_rec["uw_pos"][0], got_rec["uw_rot"][0], got_rec["uw_errors"][0], got_rec["status"][0]) == (want_pos, name == "A", 0, dec.OK)
+    assert name == "A" or want_pos > 2 ** 31 - 700
+    # the bytes, on the device: sentinels before and behind what the job owns, 0 behind its last symbol
+    out = d_out.view(torch.uint8)
+    sent = SENTINEL & 0xff
+    assert bool((out[:G] == sent).all().item()) and bool((out[G + own:] == sent).all().item()), "written beside the owned bytes"
+    assert bool((out[G + n:G + own] == 0).all().item()) and own - n == 1
+    sym = out[G:G + n]
+    k = n // P
+    assert k == 2730 and n % T == T - 1
+    whole = sym[:k * P].view(k, P)
+    ref = 0 if name == "A" else 1				# under DIFF byte 0 is k[0], no difference: period 0 stands alone
+    assert_rows_equal(torch, whole[ref:], whole[ref], "a period of the output differs from period %d" % ref)
+    rest = sym[k * P:]
+    assert torch.equal(rest, whole[ref][:rest.numel()]), "the last, partial period differs"
+    for r in range(ref + 1):
+        assert whole[r].cpu().numpy().tobytes() == out_bytes(r * P, P).tobytes(), "period %d differs from the periodic model's" % r
+    assert sym[n - (T - 1):].cpu().numpy().tobytes() == out_bytes(n - (T - 1), T - 1).tobytes(), "the last tile differs from the model's"
+    assert torch.equal(rows[0], d_block), "the input was written"
+    assert_rows_equal(torch, rows, rows[0], "the input was written")
+    print("decide %s: the call %.2f s, the test %.2f s" % (name, t_call, time.perf_counter() - t_test))
+
+
+@pytest.mark.parametrize("name", sorted(jc.CAR_LONG))
+def test_long_carrier_job(dev, far, name):
+    """2^19 sum tiles and (job E) 2^19 lag tiles, which one wave of k_car_phase and of k_car_freq adds; (double)j up to 2^31 - 2 in
+    k_car_sum and k_car_turn.  The output is 16 GiB beside the far buffer.  Job E's z_re, z_im, phase and output have no model at
+    this length and are not compared."""
+    import torch
+    spec = jc.CAR_LONG[name]
+    n, W, T, P = spec["n"], car.RECORD_WORDS, car.TILE, jc.PERIOD
+    cap = n + 2 * G
+    need = jc.FAR_FREE_NEEDED + 8 * cap + 6 * 2 ** 30
+    if far.free < need:
+        pytest.skip("%d bytes of output beside the far buffer's %d want %d bytes free: %d were" % (8 * cap, jc.FAR_BYTES, need, far.free))
+    t_test = time.perf_counter()
+    block = jc.carrier_block(spec["order"])
+    rows, d_block = fill_periodic(far, block)
+    job = jc.long_carrier_job(spec, out_offset=G)
+    d_out = guarded(torch, 2 * cap)
+    d_rec = guarded(torch, (1 + 2 * jc.GUARD) * W)
+    t_call = time.perf_counter()
+    dev.call("carrier", job, em.FP32, far.ptr, jc.FAR_SAMPLES, out=d_out.data_ptr(), cap=cap, rec=d_rec.data_ptr() + 4 * W * jc.GUARD,
+             tag="carrier " + name)
+    t_call = time.perf_counter() - t_call
+    want_rec = jc.periodic_carrier(block, job[0])
+    rec = d_rec.cpu().numpy().view(np.uint32).reshape(-1, W)
+    assert np.all(rec[:jc.GUARD] == SENTINEL) and np.all(rec[-jc.GUARD:] == SENTINEL), "written outside the record"
+    got_rec = rec[jc.GUARD].copy().view(car.RECORD_DTYPE)
+    assert got_rec["status"][0] == car.OK
+    for k in (jc.CAR_E_FIELDS if name == "E" else car.RECORD_DTYPE.names):
+        assert got_rec[k].tobytes() == want_rec[k].tobytes(), (name, k, got_rec, want_rec)
+    assert bool((d_out[:2 * G] == SENTINEL).all().item()) and bool((d_out[2 * (G + n):] == SENTINEL).all().item()), "written beside the symbols"
+    sym = d_out[2 * G:2 * (G + n)]
+    piece = 2 ** 28
+    for at in range(0, 2 * n, piece):
+        assert not bool((sym[at:at + piece] == SENTINEL).any().item()), "an output word was not written"
+    tiles = lambda j0, count: sym[2 * j0:2 * (j0 + count)].cpu().numpy().tobytes()
+    model = lambda j0, count: jc.carrier_symbols(block, job[0], want_rec, j0, count).tobytes()
+    assert n % T == T - 1
+    if name == "C":
+        assert jc.exact_products(job[0])
+        k = n // P
+        whole = sym[:2 * k * P].view(k, 2 * P)
+        assert_rows_equal(torch, whole, whole[0], "a period of the output differs from the first")
+        rest = sym[2 * k * P:]
+        assert torch.equal(rest, whole[0][:rest.numel()]), "the last, partial period differs from the first"
+        assert tiles(0, P) == model(0, P), "the first period differs from the model's"
+        assert tiles(n - (T - 1), T - 1) == model(n - (T - 1), T - 1), "the last tile differs from the model's"
+    if name == "D":
+        for j0, count in ((0, 2 * T), (2 ** 30 - T, 2 * T), (n - (T - 1), T - 1)):
+            assert tiles(j0, count) == model(j0, count), ("the symbols from %d on differ from rule 6 with the true j" % j0)
+    assert torch.equal(rows[0], d_block), "the input was written"
+    assert_rows_equal(torch, rows, rows[0], "the input was written")
+    print("carrier %s: the call %.2f s, the test %.2f s" % (name, t_call, time.perf_counter() - t_test))
 
 
 def worst(got, want):

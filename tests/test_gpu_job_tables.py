@@ -1,6 +1,7 @@
-"""The job tables of six passes over burst IQ (gr-fosphor_amd/csrc/fosphor_jobs.h) on one instance: extract, then measure,
-demod, correlate, psd and symbols over what extract wrote, three times with tables of 3, 300 and 2 jobs -- every scratch buffer of
-the instance grows once and is then reused larger than the table needs.
+"""The job tables of eight passes over burst IQ (gr-fosphor_amd/csrc/fosphor_jobs.h) on one instance: extract, then measure,
+demod, correlate, psd and symbols over what extract wrote, carrier over what symbols wrote and decide over what carrier wrote, three
+times with tables of 3, 300 and 2 jobs -- every scratch buffer of the instance grows once and is then reused larger than the table
+needs.
 
 A job's length comes from what can break the shared code: nothing (between live jobs and as the last job of a table), 1, one
 work-group's worth, one more, and two work-groups' worth plus 3 -- of extract's TILE_OUT 256 and WAVE_OUT 4 outputs, measure's CHUNK
@@ -8,12 +9,18 @@ of 8192 samples (and WAVE_MAX 4096, the longest job a wave takes), demod's TILE 
 of 1024 lags with templates of 1, 2 and 33 samples.  psd's lengths are its own: nothing, L - 1 (no segment), L, L + hop, one TILE of
 32 segments, one more, and two and 3, at L = 64 (WAVE) and L = 256 (GROUP); symbols': nothing, 3 samples (no symbol), and what gives
 1, 4096, 4097 and 2 * 4096 + 3 symbols, at sps 2 under FIXED and sps 5 under ESTIMATE.  Offsets walk through 0, 1, 2, 3, so spans begin
-on and off a 16-byte boundary.
-The single-module tests (tests/test_gpu_extract.py, _measure, _demod, _correlate, _psd, _symbols) hold each pass's own seams at one table size; what
-is new here is the alternation of sizes on one instance, the chain, and jobs without work between and behind the live ones.
+on and off a 16-byte boundary.  carrier's and decide's jobs come from fosphor_amd_carrier_from_symbols and
+fosphor_amd_decide_from_carrier over the records of the pass before, so their lengths are those symbol counts (the tiles of both are
+4096 symbols); carrier takes the orders, its four modes and the lags 1, 16 and 64 in turn, decide its four flag sets, every third
+job with a word of 8 symbols cut from the decisions of the host chain.
+The single-module tests (tests/test_gpu_extract.py, _measure, _demod, _correlate, _psd, _symbols, _carrier, _decide) hold each pass's
+own seams at one table size; what is new here is the alternation of sizes on one instance, the chain, and jobs without work between and behind the live ones.
 
 What is compared: demod's traces, correlate's and psd's records and traces and symbols' records and symbols with
-fosphor_amd_demod_host, fosphor_amd_correlate_host, fosphor_amd_psd_host and fosphor_amd_symbols_host over the same buffer, bit for bit; measure's integer fields and peak with fosphor_amd_measure_host bit for bit, its eight sums in double
+fosphor_amd_demod_host, fosphor_amd_correlate_host, fosphor_amd_psd_host and fosphor_amd_symbols_host over the same buffer, bit for
+bit; carrier's records and symbols and decide's records and bytes with fosphor_amd_carrier_host and fosphor_amd_decide_host over the
+host chain (the host's symbols, then the host's derotated symbols), bit for bit; measure's integer fields and peak with
+fosphor_amd_measure_host bit for bit, its eight sums in double
 within measure_model.job_tolerance of the host's, because the header leaves the order of the additions open (rule 3) and the kernels
 use that; extract against the float64 model within extract_model.bound, as tests/test_gpu_extract.py does, because extract's host
 function is a float64 statement and no bit-exact twin.  Every stats delta is what the table predicts."""
@@ -22,7 +29,9 @@ import os
 import numpy as np
 import pytest
 
+import carrier_model as car
 import correlate_model as cm
+import decide_model as dec
 import demod_model as dm
 import extract_model as em
 import job_scale_cases as jc
@@ -126,6 +135,47 @@ def symbols_table(count, at):
     assert [sm.max_out(k[1], k[2]) for k in kinds[:3]] == [1, 0, 0]
     assert max(k[0] + k[1] for k in kinds) <= at + LONG
     return sm.place(pick(kinds, count, (at + 1, 0, 5, sm.ESTIMATE, 0.0)))
+
+
+def carrier_table(F, sjobs, srec):
+    """a carrier job per symbols job and record: the orders, the four modes and three lags in turn, the outputs one behind the
+    other with 0 or 1 symbols between them"""
+    out, at = [], 0
+    for i in range(len(sjobs)):
+        mode = i % 4
+        j = F.carrier_jobs(sjobs[i:i + 1], srec[i:i + 1], car.ORDERS[i % 3], mode=mode, lag=(1, 16, 64)[(i // 3) % 3],
+                           freq=0.01 if mode & car.FREQ_FIXED else 0.0, phase=-0.125 if mode & car.PHASE_FIXED else 0.0)
+        j["out_offset"] = at
+        at += int(j["n"][0]) + (i & 1)
+        out.append(j)
+    return np.concatenate(out)
+
+
+WORD = 8
+
+
+def decide_table(F, cjobs, crec, yc):
+    """a decide job per carrier job and record: the four flag sets in turn; every third job that is long enough looks over all its
+    positions for the WORD differences (or decisions) that fosphor_amd_decide_host finds in its middle -> (jobs, the word table)"""
+    plain = np.concatenate([F.decide_jobs(cjobs[i:i + 1], crec[i:i + 1], flags=dec.ALL_FLAGS[i % 4] & dec.DIFF) for i in range(len(cjobs))])
+    at = 0
+    for j in plain:
+        j["out_offset"] = at
+        at += dec.owned(j["n"])
+    _, d = F.decide_host(yc, plain)				# without GRAY and a word the bytes are rule 3's d
+    out, words, at = [], [], 0
+    for i in range(len(cjobs)):
+        flags, n = dec.ALL_FLAGS[i % 4], int(plain["n"][i])
+        word = {}
+        if i % 3 == 0 and n > 2 * WORD:
+            word = dict(uw_offset=WORD * len(words), uw_len=WORD)
+            words.append(np.array(d[i][n // 2:n // 2 + WORD], np.uint8))
+            flags |= dec.UW
+        j = F.decide_jobs(cjobs[i:i + 1], crec[i:i + 1], flags=flags, **word)
+        j["out_offset"] = at
+        at += dec.owned(j["n"][0]) + dec.GUARD * (1 + (i & 1))
+        out.append(j)
+    return np.concatenate(out), (np.concatenate(words) if words else np.zeros(0, np.uint8))
 
 
 def delta(stats, before):
@@ -252,5 +302,39 @@ def test_tables_of_3_300_2_jobs(amd, stream):
                 assert len(h) == rec["n_sym"][i] and g.cpu().numpy().tobytes() == h.tobytes(), (count, i, tuple(jobs[i]))
             if count == 300:
                 assert {1, sm.TILE, sm.TILE + 1, 2 * sm.TILE + 3} <= set(rec["n_sym"]) and np.all(rec["status"] == sm.OK)
+
+            # carrier, over what symbols wrote: on the device its buffer, on the host the host's
+            sym_base = got[0].data_ptr() - 8 * int(jobs["out_offset"][0])
+            ys = np.asarray(hviews[0].base).view(np.float32).reshape(-1, 2)
+            cjobs = carrier_table(F, jobs, hrec)
+            assert len(cjobs) == count and cjobs["n"][-1 if count != 3 else 1] == 0 and np.array_equal(cjobs["n"], hrec["n_sym"])
+            before = f.carrier_stats()
+            rec, got = f.carrier(sym_base, cjobs, n_samples=len(ys))
+            assert delta(f.carrier_stats, before) == car.expected_stats(cjobs), count
+            hrec, hviews = F.carrier_host(ys, cjobs)
+            assert rec.tobytes() == hrec.tobytes(), (count, [i for i in range(len(cjobs)) if rec[i] != hrec[i]][:4])
+            for i, (g, h) in enumerate(zip(got, hviews)):
+                assert len(h) == (cjobs["n"][i] if hrec["status"][i] == car.OK else 0)
+                assert g.cpu().numpy().tobytes() == h.tobytes(), (count, i, tuple(cjobs[i]))
+            if count == 300:
+                assert {1, car.TILE, car.TILE + 1, 2 * car.TILE + 3} <= set(rec["n"][rec["status"] == car.OK])
+                assert set(cjobs["mode"]) == {0, 1, 2, 3} and set(cjobs["lag"]) == {1, 16, 64} and set(cjobs["order"]) == set(car.ORDERS)
+
+            # decide, over what carrier wrote
+            car_base = got[0].data_ptr() - 8 * int(cjobs["out_offset"][0])
+            yc = np.asarray(hviews[0].base).view(np.float32).reshape(-1, 2)
+            djobs, uw = decide_table(F, cjobs, hrec, yc)
+            assert len(djobs) == count and djobs["n"][-1 if count != 3 else 1] == 0
+            before = f.decide_stats()
+            rec, got = f.decide(car_base, djobs, uw, n_samples=len(yc))
+            assert delta(f.decide_stats, before) == dec.expected_stats(djobs), count
+            hrec, hviews = F.decide_host(yc, djobs, uw)
+            assert rec.tobytes() == hrec.tobytes(), (count, [i for i in range(len(djobs)) if rec[i] != hrec[i]][:4])
+            for i, (g, h) in enumerate(zip(got, hviews)):
+                assert len(h) == djobs["n"][i] and g.cpu().numpy().tobytes() == h.tobytes(), (count, i, tuple(djobs[i]))
+            if count == 300:
+                assert {1, dec.TILE, dec.TILE + 1, 2 * dec.TILE + 3} <= set(rec["n"]) and set(djobs["flags"] & 3) == {0, 1, 2, 3}
+                with_word = (djobs["flags"] & dec.UW) != 0
+                assert with_word.sum() >= 50 and np.all(rec["status"][with_word] == dec.OK) and np.all(rec["uw_pos"][with_word] >= 0)
     finally:
         f.close()

@@ -3,11 +3,15 @@ partials, plants and ties their docstrings state, the full tables are full, the 
 must; and the long cases and full tables through fosphor_amd_*_host agree with the numpy models as each contract says, so the
 reference side alone meets every assertion the GPU tests make.  For psd and symbols also: the tile counts of their long cases, the
 cut rule of a FIXED symbols job, the periodic helpers against the whole model and the host twin on blocks short enough to
-materialise, and the geometry of the long far jobs."""
+materialise, and the geometry of the long far jobs.  For carrier and decide: the tile and group counts of their long cases, where
+the plants of "long decide words" lie and which of them rule 4 picks, the exactness that makes a carrier job with dyadic frequency
+and phase periodic, and periodic_carrier and periodic_decide against the whole models on jobs shaped like the five long far ones."""
 import numpy as np
 import pytest
 
+import carrier_model as car
 import correlate_model as cm
+import decide_model as dec
 import extract_model as em
 import job_scale_cases as jc
 import measure_model as mm
@@ -107,13 +111,13 @@ def test_full_tables_are_full(name):
     assert len(forms) == (1 if name in ("correlate", "psd") else 2), forms	# psd's table is the WAVE form's: the deepest search of one prefix
     work = np.array([jc.has_work(name, j) for j in jobs])
     assert 300 <= (~work).sum() and work.sum() >= 2000
-    if name in ("psd", "symbols"):				# the models' own tables: every 11th job of the order they were drawn in
+    if name in ("psd", "symbols", "carrier", "decide"):	# the models' own tables: every 11th job of the order they were drawn in
         assert (~work).sum() == len(range(0, jc.MAX_JOBS, 11))
         idle = jobs["n"] < 64 if name == "psd" else jobs["n"] == 0
         assert np.array_equal(idle, ~work)
     ranges = jc.out_ranges(name, jobs)
     assert jc.disjoint(ranges)
-    if name not in ("measure", "psd", "symbols"):		# the two models shuffle the jobs' shapes and place the outputs in table order
+    if name not in ("measure", "psd", "symbols", "carrier", "decide"):	# the models shuffle the jobs' shapes and place the outputs in table order
         starts = [a for a, _ in ranges]
         assert starts != sorted(starts), "outputs out of order"
     for j in jobs:
@@ -123,8 +127,8 @@ def test_full_tables_are_full(name):
     assert len(one.jobs) == 1 and sum(jc.expected_stats(name, one.jobs, records).values()) > 1
 
 
-@pytest.mark.parametrize("key", ["long measure", "long edges", "long tie", "long resample", "long psd", "long symbols"]
-                         + ["full " + k for k in jc.PASSES])
+@pytest.mark.parametrize("key", ["long measure", "long edges", "long tie", "long resample", "long psd", "long symbols", "long carrier",
+                                 "long decide", "long decide words"] + ["full " + k for k in jc.PASSES])
 def test_host_twins_meet_the_models(F, key):
     case = jc.case_of(key)
     model = jc.model_of(key)
@@ -226,6 +230,189 @@ def test_periodic_symbols_is_the_model(F, cycle, mode, tau):
     assert all(w.tobytes() == head.tobytes() for w in whole), "every period of the output is the first"
 
 
+def test_long_carrier_and_decide_tiles():
+    T = car.TILE
+    jobs, rec = jc.case_of("long carrier").jobs, jc.model_of("long carrier").records
+    n = [int(v) for v in jobs["n"]]
+    assert n == [jc.LONG_CAR] * 12 + [0, 8 * T, 8 * T + 1, 8 * T + 2] and jc.LONG_CAR == 19 * T + 5
+    est = (jobs["mode"] & car.FREQ_FIXED) == 0
+    sum_tiles = [-(-k // T) for k in n]
+    lag_tiles = [-(-max(k - 1, 0) // T) if e else 0 for k, e in zip(n, est)]
+    assert sum_tiles == [20] * 12 + [0, 8, 9, 9], "two unrolled bodies of 8 and a remainder of 4; none; one body; one body and one"
+    assert lag_tiles == [20] * 9 + [0, 20, 0, 0, 8, 8, 9], "k_car_freq and k_car_phase differ at 8 TILE + 1"
+    assert [(int(j["order"]), int(j["lag"])) for j in jobs[:9]] == [(M, L) for M in car.ORDERS for L in (1, 16, 64)]
+    assert [int(m) for m in jobs["mode"][9:12]] == [car.FREQ_FIXED, car.PHASE_FIXED, car.FREQ_FIXED | car.PHASE_FIXED]
+    assert [int(o) % 4 for o in jobs["offset"][:4]] == [1, 2, 3, 0]
+    assert np.all(rec["status"] == car.OK) and list(rec["lag_used"][:3]) == [1, 16, 64], "ESTIMATE locks at every order"
+    assert np.all(np.abs(rec["freq"][:9] - jc.LONG_CAR_F0) < 1e-5)
+
+    jobs = jc.case_of("long decide").jobs
+    T = dec.TILE
+    per_order = [jc.LONG_DEC] * 4 + [0, 8 * T, 8 * T + 1]
+    assert [int(v) for v in jobs["n"]] == per_order * 3 and [-(-k // T) for k in per_order] == [20] * 4 + [0, 8, 9]
+    assert [int(v) for v in jobs["flags"][:7]] == list(dec.ALL_FLAGS) + [dec.GRAY, dec.DIFF | dec.GRAY, dec.DIFF]
+    assert [int(v) for v in jobs["order"]] == [M for M in dec.ORDERS for _ in per_order] and not (jobs["flags"] & dec.UW).any()
+
+
+def test_long_decide_words_plants_and_winners():
+    case, want = jc.long_decide_words()
+    jobs, L, G = case.jobs, jc.WORD_LEN, dec.UW_GROUP
+    rec = jc.model_of("long decide words").records
+    assert len(jobs) == 19 == len(want) and np.all(jobs["n"] == jc.LONG_DEC) and np.all(jobs["uw_count"] == 0)
+    for j in jobs[:18]:
+        first, count = dec.candidates(j)
+        groups = -(-count // G)
+        assert groups > 300 and -(-groups // 64) == 5, "five trips of a lane through the job's keys"
+    # where the plants lie: the group of a position is (p - the first candidate) / 256
+    for first in (0, 1):					# without and with DIFF
+        g = [(p - first) // G for p in jc.WORD_TIES]
+        assert g == [3, 67, 70, 131] and g[1] % 64 == g[2] % 64 - 3 == g[3] % 64 == 3, "one lane's three trips and another lane between"
+        assert [(p - first) // G for p in jc.WORD_LATER] == [5, 69, 133], "one lane, the exact copy in its third trip"
+    behind = jc.WORD_TIES[0] + 1
+    assert [(p - behind) // G for p in jc.WORD_TIES[1:]] == [64, 67, 128], "all beyond the first trip; lane 0 twice"
+    for i, M in enumerate(dec.ORDERS):
+        at = int(jobs["offset"][6 * i])
+        assert np.all(jobs["offset"][6 * i:6 * i + 6] == at) and np.all(jobs["order"][6 * i:6 * i + 6] == M)
+        burst = case.iq[at:at + jc.LONG_DEC]
+        for plants in (jc.WORD_TIES, jc.WORD_LATER):
+            for p in plants[1:]:
+                same = burst[p - 1:p + L - 1].tobytes() == burst[plants[0] - 1:plants[0] + L - 1].tobytes()
+                assert same, "the same bytes but for the last symbol"
+        for p in jc.WORD_TIES[1:]:
+            assert burst[p + L - 1].tobytes() == burst[jc.WORD_TIES[0] + L - 1].tobytes()
+        k = dec.decisions(burst, M)[0]
+        for p in jc.WORD_LATER[:2]:
+            assert (k[p + L - 1] - k[jc.WORD_LATER[2] + L - 1]) % M == 1, "the last symbol of the two earlier copies is the next point"
+        for flags, at_job in ((0, 6 * i), (dec.DIFF, 6 * i + 3)):
+            assert [int(f) & dec.DIFF for f in jobs["flags"][at_job:at_job + 3]] == [flags] * 3
+            d = dec.difference(k, M, flags)
+            u = lambda job: case.uw[int(job["uw_offset"]):int(job["uw_offset"]) + int(job["uw_len"])].astype(np.int64)
+            rot = 0 if flags else 1
+            errors = lambda job, p: int((((d[p:p + len(u(job))] - u(job) - rot) & (M - 1)) != 0).sum())
+            assert [errors(jobs[at_job], p) for p in jc.WORD_TIES] == [0] * 4
+            assert [errors(jobs[at_job + 1], p) for p in jc.WORD_LATER] == [1, 1, 0], "a later position has one more match"
+            assert jobs["uw_first"][at_job + 2] == behind and jobs["uw_first"][at_job] == 0
+    # the winners, by the model
+    got = [(int(r["uw_pos"]), int(r["uw_rot"]), int(r["uw_errors"])) for r in rec]
+    assert got == want and np.all(rec["status"] == dec.OK)
+    assert want[0] == (jc.WORD_TIES[0], 1, 0) and want[1] == (jc.WORD_LATER[2], 1, 0) and want[2] == (jc.WORD_TIES[1], 1, 0)
+    assert want[3] == (jc.WORD_TIES[0], 0, 0) and want[4] == (jc.WORD_LATER[2], 0, 0) and want[5] == (jc.WORD_TIES[1], 0, 0)
+    # the job of two rotations: 32 matches under each at its position, fewer under every rotation anywhere else
+    p, r0, r1 = jc.WORD_TWO_ROTATIONS
+    job = jobs[18]
+    assert (int(job["order"]), int(job["flags"]), int(job["uw_len"])) == (8, dec.UW, 64) and p // G == 200
+    at = int(job["offset"])
+    k = dec.decisions(case.iq[at:at + jc.LONG_DEC], 8)[0]
+    u = case.uw[int(job["uw_offset"]):][:64].astype(np.int64)
+    win = np.lib.stride_tricks.sliding_window_view(k, 64)
+    matches = np.stack([(((win - u) & 7) == r).sum(1) for r in range(8)], 1)
+    assert sorted(np.flatnonzero(matches[p] == 32)) == sorted((r0, r1)) and matches[p].max() == 32
+    matches[p] = 0
+    assert matches.max() < 32
+    assert want[18] == (p, min(r0, r1), 32), "the smaller rotation wins"
+
+
+CAR_SHORT = 7 * car.TILE + 5
+
+
+@pytest.mark.parametrize("n", [CAR_SHORT, 7 * car.TILE + 1, 7 * car.TILE + 10, 6 * car.TILE])
+@pytest.mark.parametrize("name", sorted(jc.CAR_LONG))
+def test_periodic_carrier_is_the_model(F, name, n):
+    """a block of 3 tiles and jobs shaped like C, D and E of 7 tiles and 5 symbols from an odd offset; and with 1 and 10 symbols
+    in the last tile, where the tile before the last loses terms of lag 16, and with none"""
+    block = car.psk(3 * car.TILE, 4, jc.CAR_LONG_FREQ, 0.02, 31, 30.0)
+    job = jc.long_carrier_job(dict(jc.CAR_LONG[name], n=n, offset=5))
+    iq = np.tile(block, (4, 1))[:5 + n]
+    want_rec, want = car.carrier((iq, job))
+    host_rec, host = F.carrier_host(iq, job)
+    rec = jc.periodic_carrier(block, job[0])
+    assert want_rec["status"][0] == car.OK and want_rec.tobytes() == host_rec.tobytes()
+    if name == "E":
+        for k in jc.CAR_E_FIELDS:
+            assert rec[k].tobytes() == want_rec[k].tobytes(), k
+        return
+    assert jc.exact_products(job[0])
+    assert rec.tobytes() == want_rec.tobytes(), (rec, want_rec)
+    for j0, count in ((0, 2 * car.TILE), (3 * car.TILE - 7, 300), (n - n % car.TILE, n % car.TILE)):
+        got = jc.carrier_symbols(block, job[0], rec, j0, count)
+        assert got.tobytes() == want[0][j0:j0 + count].tobytes() == host[0].view(np.float32).reshape(-1, 2)[j0:j0 + count].tobytes()
+    if name == "C":						# every period of the output is the first
+        whole = want[0][:6 * car.TILE].reshape(2, 3 * car.TILE, 2)
+        assert whole[0].tobytes() == whole[1].tobytes()
+
+
+def test_carrier_products_are_exact():
+    """what makes jobs C and D periodic: g = freq M and f = g / M are exact, g j and theta + f j are exact up to j = 2^31 - 2, and
+    g TILE is a whole number; and a frequency that is not dyadic fails the same test"""
+    for name in ("C", "D"):
+        job = jc.long_carrier_job(jc.CAR_LONG[name])[0]
+        assert jc.exact_products(job) and int(job["n"]) - 1 == 2 ** 31 - 2
+    g = np.float64(jc.CAR_LONG_FREQ) * np.float64(4)
+    j = np.float64(2 ** 31 - 2)
+    assert (g * j) / j == g and float(g * j) == 4 * jc.CAR_LONG_A * (2 ** 31 - 2) / 4096.0
+    phi = np.float64(jc.CAR_LONG_PHASE) + (np.float64(jc.CAR_LONG_FREQ) * j)
+    assert (phi - np.float64(jc.CAR_LONG_FREQ) * j) == jc.CAR_LONG_PHASE and (g * car.TILE) % 1.0 == 0.0
+    c0, s0 = car.cossin_turns(np.float64(jc.CAR_LONG_PHASE) + np.float64(jc.CAR_LONG_FREQ) * np.float64(5))
+    c1, s1 = car.cossin_turns(np.float64(jc.CAR_LONG_PHASE) + np.float64(jc.CAR_LONG_FREQ) * np.float64(5 + 2 ** 31 - 4096))
+    assert (c0, s0) == (c1, s1), "the rotation repeats every TILE symbols"
+    off = jc.long_carrier_job(dict(jc.CAR_LONG["C"], freq=0.009))[0]
+    assert not jc.exact_products(off)
+
+
+@pytest.mark.parametrize("name", ["A", "B", "B, the word in the last group"])
+def test_periodic_decide_is_the_model(F, name):
+    """a block of 3 tiles and jobs shaped like A and B of 7 tiles and 5 symbols from an odd offset"""
+    n, L = 7 * dec.TILE + 5, jc.DEC_LONG_WORD
+    block = dec.psk(3 * dec.TILE, 4, 0.0, 0.2525, 32, 30.0)
+    spec = dict(jc.DEC_LONG[name[0]], n=n, offset=5)
+    if name[0] == "B":
+        spec["uw_first"] = n - L - 600
+    job, word = jc.long_decide_job(spec, block)
+    if name == "A":						# a word of the second tile: found there, not a period later
+        k = dec.decisions(jc.wrapped(block, 5 + 5000, L), 4)[0]
+        word = ((k - 1) & 3).astype(np.uint8)
+    iq = np.tile(block, (4, 1))[:5 + n]
+    want_rec, want = dec.decide((iq, job, word))
+    host_rec, host = F.decide_host(iq, job, word)
+    rec, out_bytes = jc.periodic_decide(block, job[0], word)
+    assert rec.tobytes() == want_rec.tobytes() == host_rec.tobytes(), (rec, want_rec)
+    assert rec["status"][0] == dec.OK and rec["uw_errors"][0] == 0
+    if name == "A":
+        assert (rec["uw_pos"][0], rec["uw_rot"][0]) == (5000, 1)
+    else:
+        first, count = dec.candidates(job[0])
+        assert count == 601 and (rec["uw_pos"][0] - first) // dec.UW_GROUP == 2 == -(-count // dec.UW_GROUP) - 1, "in the last group"
+        assert rec["uw_pos"][0] == n - L - 50 and first + count + L - 1 == n, "the last group's decisions end on the job's last"
+    assert out_bytes(0, n).tobytes() == want[0][:n].tobytes() == host[0][:n].tobytes()
+    assert out_bytes(6 * dec.TILE, dec.TILE + 5).tobytes() == want[0][6 * dec.TILE:n].tobytes()
+    P = 3 * dec.TILE
+    assert want[0][1:P].tobytes() == want[0][P + 1:2 * P].tobytes(), "every period equals the first from byte 1 on"
+
+
+def test_long_carrier_and_decide_far_geometry():
+    P, T = jc.PERIOD, car.TILE
+    assert P % T == 0 and P // T == 192
+    for spec in list(jc.CAR_LONG.values()) + list(jc.DEC_LONG.values()):
+        assert spec["n"] == 2 ** 31 - 1 and spec["offset"] % 2 == 1 and spec["offset"] + spec["n"] <= jc.FAR_SAMPLES
+    assert -(-(2 ** 31 - 1) // T) == 2 ** 19 == -(-(2 ** 31 - 2) // T), "2^19 sum tiles and 2^19 lag tiles"
+    assert (jc.CAR_LONG_FREQ * P) % 1.0 == 0.0, "the block repeated is one continuous burst"
+    assert abs(jc.CAR_LONG_FREQ * 8) <= 0.5 and abs(jc.CAR_LONG_PHASE) <= 0.5
+    block = jc.decide_block()
+    job, word = jc.long_decide_job(jc.DEC_LONG["A"], block)
+    first, count = dec.candidates(job[0])
+    assert (first, -(-count // dec.UW_GROUP)) == (0, 2 ** 23) and len(word) == 16
+    job, word = jc.long_decide_job(jc.DEC_LONG["B"], block)
+    first, count = dec.candidates(job[0])
+    n, L = 2 ** 31 - 1, jc.DEC_LONG_WORD
+    assert count == 601 and -(-count // dec.UW_GROUP) == 3 and first + count - 1 + L == n
+    # the last work-group of k_dec_uw: lo + span == n, so the unfixed ((lo + span + 3) >> 2) passed 2^31 - 1
+    p0 = first + 2 * dec.UW_GROUP
+    lo, span = p0 - 1, (first + count - p0) + L - 1 + 1
+    assert lo + span == n and lo + span + 3 > 2 ** 31 - 1 and ((lo + span - 1) >> 2) + 1 - (lo >> 2) == -(-(lo % 4 + span) // 4)
+    rec, _ = jc.periodic_decide(block, job[0], word)
+    assert rec["uw_pos"][0] == n - L - 50 > 2 ** 31 - 700 and (rec["uw_pos"][0] - first) // dec.UW_GROUP == 2 and rec["status"][0] == dec.OK
+
+
 def test_long_far_jobs_geometry():
     P = jc.PERIOD
     assert P == 3 * 2 ** 18 and jc.FAR_SAMPLES % P == 0 and 2 ** 31 % P == 2 ** 19 and 2 ** 32 % P == 2 ** 18
@@ -256,7 +443,7 @@ def test_long_far_jobs_geometry():
 
 
 def test_far_geometry():
-    total = {8: jc.FAR_SAMPLES, 4: 2 * jc.FAR_SAMPLES}
+    total = {8: jc.FAR_SAMPLES, 4: 2 * jc.FAR_SAMPLES, 1: jc.FAR_BYTES}
     assert jc.FAR_BYTES == 8 * (2 ** 31 + 2 ** 20) and total[4] == 2 ** 32 + 2 ** 21
     assert 8 * jc.BASES_FP32[0] > 2 ** 32 and jc.BASES_FP32[1] > 2 ** 31 and 8 * jc.BASES_FP32[1] > 2 ** 34 and jc.BASES_16[2] > 2 ** 32
     for key in jc.RELOCATE:
@@ -270,12 +457,12 @@ def test_far_geometry():
             assert found or base * unit < 2 ** 32, "a base beyond byte 2^32 has an alias inside the buffer"
             for a in found:
                 assert 0 <= a and a + n <= base, (key, base, a, "a decoy lies inside the buffer and before the case")
-        words = jc.OUT_WORDS[case.name]
-        if words:
-            base, cap = jc.OUT_BASE[words], jc.capacity(case.name, case.jobs)
-            unit = 4 * words
+        unit = jc.OUT_BYTES[case.name]
+        if unit:
+            base, cap = jc.OUT_BASE[unit], jc.capacity(case.name, case.jobs)
             assert base % 16 == 0 and base - jc.FAR_GUARD >= 0 and base + cap + jc.FAR_GUARD <= total[unit]
-            assert base > (2 ** 31 if words == 2 else 2 ** 32)
+            assert base > (2 ** 31 if unit == 8 else 2 ** 32)
+            assert cap * unit % 4 == 0 and jc.FAR_GUARD * unit % 4 == 0, "the ranges and their guards are whole words"
             for a in jc.aliases(base, unit):
                 assert a + cap + jc.FAR_GUARD <= base - jc.FAR_GUARD, "the alias's guards lie before the far range's"
     case = jc.case_of("correlate lag_counts")
