@@ -73,14 +73,36 @@ inline __host__ __device__ void acc_clear(Acc &a)
 		a.s[i] = 0.0;
 }
 
+/* Which NaN an operation on two NaNs hands on is the first operand's on the host's processor, and which operand is the first the
+ * compiler decides anew in every build: IEEE 754 leaves it open.  The host statement pins it (kPin): a NaN operand comes through as
+ * it is, the left one before the right one, so that a build of this source for one target gives the same bytes at every
+ * optimisation level and under instrumentation.  The kernels (kPin false) are the plain operations: `r` alone. */
+template <bool kPin, class T>
+inline __host__ __device__ T pinned(T a, T b, T r)
+{
+	if constexpr (kPin) {
+		if (a != a)
+			return a;
+		if (b != b)
+			return b;
+	}
+	return r;
+}
+
+template <bool kPin, class T> inline __host__ __device__ T op_add(T a, T b) { return pinned<kPin>(a, b, a + b); }
+template <bool kPin, class T> inline __host__ __device__ T op_sub(T a, T b) { return pinned<kPin>(a, b, a - b); }
+template <bool kPin, class T> inline __host__ __device__ T op_mul(T a, T b) { return pinned<kPin>(a, b, a * b); }
+
 /* rule 1: three rounded float32 operations (-ffp-contract=off: no fused multiply-add is formed) */
-inline __host__ __device__ float power(float2 y) { return (y.x * y.x) + (y.y * y.y); }
+template <bool kPin = false>
+inline __host__ __device__ float power(float2 y) { return op_add<kPin>(op_mul<kPin>(y.x, y.x), op_mul<kPin>(y.y, y.y)); }
 
 /* sample m of the job.  prev_above: above(m - 1), false for m == 0; next: y[m + 1] where has_next.  Every product below is of two
  * float32 values in double, hence exact; the terms of s_zz_re and r1_* round once, in their one addition or subtraction. */
+template <bool kPin = false>
 inline __host__ __device__ void acc_take(Acc &a, int m, float2 y, float thr, bool prev_above, float2 next, bool has_next)
 {
-	const float p = power(y);
+	const float p = power<kPin>(y);
 	if (p >= thr) {
 		a.n_above++;
 		a.first = m < a.first ? m : a.first;
@@ -92,16 +114,16 @@ inline __host__ __device__ void acc_take(Acc &a, int m, float2 y, float thr, boo
 		a.peak_index = m;
 	}
 	const double re = y.x, im = y.y, pd = p;
-	a.s[0] += re;
-	a.s[1] += im;
-	a.s[2] += pd;
-	a.s[3] += pd * pd;
-	a.s[4] += re * re - im * im;
-	a.s[5] += (2.0 * re) * im;
+	a.s[0] = op_add<kPin>(a.s[0], re);
+	a.s[1] = op_add<kPin>(a.s[1], im);
+	a.s[2] = op_add<kPin>(a.s[2], pd);
+	a.s[3] = op_add<kPin>(a.s[3], op_mul<kPin>(pd, pd));
+	a.s[4] = op_add<kPin>(a.s[4], op_sub<kPin>(op_mul<kPin>(re, re), op_mul<kPin>(im, im)));
+	a.s[5] = op_add<kPin>(a.s[5], op_mul<kPin>(op_mul<kPin>(2.0, re), im));
 	if (has_next) {
 		const double nr = next.x, ni = next.y;
-		a.s[6] += nr * re + ni * im;
-		a.s[7] += ni * re - nr * im;
+		a.s[6] = op_add<kPin>(a.s[6], op_add<kPin>(op_mul<kPin>(nr, re), op_mul<kPin>(ni, im)));
+		a.s[7] = op_add<kPin>(a.s[7], op_sub<kPin>(op_mul<kPin>(ni, re), op_mul<kPin>(nr, im)));
 	}
 }
 
@@ -334,8 +356,8 @@ extern "C" int fosphor_amd_measure_host(const float *iq, int64_t n_samples, cons
 		for (int m = 0; m < n; m++) {
 			const float2 v = make_float2(y[2 * m], y[2 * m + 1]);
 			const bool has_next = m + 1 < n;
-			acc_take(a, m, v, thr, prev, has_next ? make_float2(y[2 * m + 2], y[2 * m + 3]) : make_float2(0.0f, 0.0f), has_next);
-			prev = power(v) >= thr;
+			acc_take<true>(a, m, v, thr, prev, has_next ? make_float2(y[2 * m + 2], y[2 * m + 3]) : make_float2(0.0f, 0.0f), has_next);
+			prev = power<true>(v) >= thr;
 		}
 		acc_store(a, n, &records[i]);
 	}

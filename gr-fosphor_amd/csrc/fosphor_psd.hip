@@ -675,9 +675,10 @@ extern "C" int fosphor_amd_psd_derive(const struct fosphor_amd_psd_record *r, do
 	v->peak_db = 10.0 * log10((double)r->peak_power);
 	v->centroid = mean * bin;
 	v->rms_width = sqrt(var > 0.0 ? var : 0.0) * bin;
-	v->obw = (r->obw_hi - r->obw_lo + 1.0) * bin;
-	v->obw_centre = ((r->obw_lo + r->obw_hi) * 0.5 - L / 2.0) * bin;
-	v->xdb_bandwidth = (r->xdb_hi - r->xdb_lo + 1.0) * bin;
+	/* the bins in double: a record is the caller's memory, and the sum or difference of two int32 of any value is exact there */
+	v->obw = ((double)r->obw_hi - (double)r->obw_lo + 1.0) * bin;
+	v->obw_centre = (((double)r->obw_lo + (double)r->obw_hi) * 0.5 - L / 2.0) * bin;
+	v->xdb_bandwidth = ((double)r->xdb_hi - (double)r->xdb_lo + 1.0) * bin;
 	return 0;
 }
 

@@ -101,7 +101,9 @@ int fosphor_amd_measure(struct fosphor *self, const void *d_iq, int64_t n_sample
                         struct fosphor_amd_measure_record *d_records);
 
 /* HOST only, no GPU: the contract in plain C.  Same arguments with host pointers; one pass in ascending index, double sums;
- * record.form is the form the device would choose.  0; -EINVAL: what the device entry point refuses, but for self. */
+ * record.form is the form the device would choose.  Where an operation meets two NaNs the left operand's comes through, the
+ * accumulator's before the term's (this statement only, not the kernels, whose sums rule 3 holds to a bound): a build of one source
+ * for one target gives the same bytes at every optimisation level.  0; -EINVAL: what the device entry point refuses, but for self. */
 int fosphor_amd_measure_host(const float *iq, int64_t n_samples, const struct fosphor_amd_measure_job *jobs, int n_jobs,
                              struct fosphor_amd_measure_record *records);
 
