@@ -1619,6 +1619,154 @@ class Fosphor:
         """fosphor_amd_decide_stats as a dict: calls, launches by kernel, jobs with a unique word, symbols (DECIDE_STATS)"""
         return self._stats(self.L.fosphor_amd_decide_stats, self.DECIDE_STATS)
 
+    DECODE_STATS = ("calls", "k_bits", "k_acs", "k_trace", "k_rec", "jobs_crc", "steps")
+    DECODE_MAX_JOBS = 4096				# FOSPHOR_AMD_DECODE_MAX_JOBS (include/fosphor_amd_decode.h)
+    DECODE_MAX_STEPS, DECODE_MAX_CALL_STEPS = 65536, 1 << 22	# FOSPHOR_AMD_DECODE_MAX_STEPS, FOSPHOR_AMD_DECODE_MAX_CALL_STEPS
+    DECODE_BLOCK, DECODE_INF = 64, 1 << 24		# FOSPHOR_AMD_DECODE_BLOCK, FOSPHOR_AMD_DECODE_INF
+    DECODE_FLAGS = {"terminated": 1}			# FOSPHOR_AMD_DECODE_TERMINATED
+    DECODE_STATUS = {"ok": 0, "crc_fail": 1, "short": 2}	# FOSPHOR_AMD_DECODE_OK, _CRC_FAIL, _SHORT
+    DECODE_LDS = {"bits": 0, "acs": 0, "trace": 0, "rec": 0}	# FOSPHOR_AMD_DECODE_LDS_*
+    DECODE_JOB_DTYPE = np.dtype([("offset", "<i8"), ("out_offset", "<i8"), ("n", "<i4"), ("order", "<i4"), ("steps", "<i4"),
+                                 ("flags", "<i4"), ("k", "u1"), ("n_poly", "u1"), ("period", "u1"), ("crc_width", "u1"),
+                                 ("polys", "<u2", (3,)), ("punct", "<u2", (3,)), ("crc_poly", "<u4"), ("crc_init", "<u4"),
+                                 ("crc_xorout", "<u4"), ("reserved", "<u4")])
+    DECODE_RECORD_DTYPE = np.dtype([("n_steps", "<i4"), ("n_bits", "<i4"), ("n_coded", "<i4"), ("status", "<i4"),
+                                    ("end_state", "<i4"), ("metric", "<i4"), ("best_state", "<i4"), ("best_metric", "<i4"),
+                                    ("crc_calc", "<u4"), ("crc_recv", "<u4"), ("k", "<i4"), ("flags", "<i4"),
+                                    ("reserved", "<i4", (4,))])
+    DECODE_VALUES = tuple(k for k, _ in _lib.DecodeValues._fields_)
+
+    @staticmethod
+    def decode_steps(n, order, n_poly=2, period=1, punct=(1, 1, 0)):
+        """fosphor_amd_decode_steps: the trellis steps that n symbols of order M hold under the puncture masks (rule 2's T for
+        steps = 0)"""
+        p = np.ascontiguousarray(punct, dtype=np.uint16)
+        if p.size != 3:
+            raise ValueError("punct holds three masks")
+        rv = _lib.load().fosphor_amd_decode_steps(int(n), int(order), int(n_poly), int(period), p.ctypes.data)
+        if rv < 0:
+            _fail("fosphor_amd_decode_steps", rv, ValueError)
+        return rv
+
+    @staticmethod
+    def _decode_shape(j):
+        """(T, n_bits) of a job as rules 2 and 5 give them; raises ValueError where rule 9 refuses the pattern"""
+        T = int(j["steps"]) or Fosphor.decode_steps(j["n"], j["order"], j["n_poly"], j["period"], j["punct"])
+        return T, (max(T - (int(j["k"]) - 1), 0) if int(j["flags"]) & 1 else T)
+
+    @staticmethod
+    def decode_owned(n_bits):
+        """the bytes a job of n_bits decoded bits owns in d_out: 8 ceil(n_bits / 64)"""
+        return 8 * ((int(n_bits) + 63) // 64)
+
+    @staticmethod
+    def decode_jobs(decide_jobs, decide_records, uw_len, n_payload=0, k=7, polys=(0o171, 0o133, 0), period=1, punct=(1, 1, 0),
+                    steps=0, flags=0, crc_width=0, crc_poly=0, crc_init=0, crc_xorout=0, gap=8):
+        """a DECODE_JOB_DTYPE array from a DECIDE_JOB_DTYPE array and the DECIDE_RECORD_DTYPE array that decide() gave for it
+        (fosphor_amd_decode_from_decide: each job reads what the decide job wrote behind its unique word, n = n_payload symbols
+        or all of them, n = 0 where the record says no_uw), the code, the puncture masks and the CRC the same for every job, the
+        owned bytes placed from out_offset 0 on at multiples of 8 with `gap` bytes (rounded up to a multiple of 8) between them"""
+        L = _lib.load()
+        src = np.ascontiguousarray(np.atleast_1d(decide_jobs), dtype=Fosphor.DECIDE_JOB_DTYPE)
+        rec = np.ascontiguousarray(np.atleast_1d(decide_records), dtype=Fosphor.DECIDE_RECORD_DTYPE)
+        if src.size != rec.size:
+            raise ValueError("one decide record per decide job")
+        if gap < 0:
+            raise ValueError("gap must be >= 0")
+        if isinstance(flags, str):
+            if flags not in Fosphor.DECODE_FLAGS:
+                raise ValueError("flags must be of %s" % ", ".join(Fosphor.DECODE_FLAGS))
+            flags = Fosphor.DECODE_FLAGS[flags]
+        out = np.zeros(src.size, Fosphor.DECODE_JOB_DTYPE)
+        n_poly = 3 if len(polys) > 2 and polys[2] else 2
+        at = 0
+        for i, (s, r) in enumerate(zip(src, rec)):
+            job = _lib.DecodeJob()
+            rv = L.fosphor_amd_decode_from_decide(s.tobytes(), r.tobytes(), int(uw_len), int(n_payload), C.byref(job))
+            if rv:
+                _fail("fosphor_amd_decode_from_decide", rv, ValueError)
+            o = out[i]
+            o["offset"], o["out_offset"], o["n"], o["order"], o["steps"], o["flags"] = job.offset, at, job.n, job.order, steps, flags
+            o["k"], o["n_poly"], o["period"], o["crc_width"] = k, n_poly, period, crc_width
+            o["polys"], o["punct"] = tuple(polys) + (0,) * (3 - len(polys)), tuple(punct) + (0,) * (3 - len(punct))
+            o["crc_poly"], o["crc_init"], o["crc_xorout"] = crc_poly, crc_init, crc_xorout
+            at += Fosphor.decode_owned(Fosphor._decode_shape(o)[1]) + 8 * ((int(gap) + 7) // 8)
+        return out
+
+    @staticmethod
+    def _decode_outs(jobs):
+        """(n_bits per job, the capacity the jobs need); a job that rule 9 will refuse counts as owning nothing"""
+        def bits(j):
+            try:
+                return Fosphor._decode_shape(j)[1]
+            except ValueError:
+                return 0
+        n_bits = [bits(j) for j in jobs]
+        return n_bits, max([int(j["out_offset"]) + Fosphor.decode_owned(b) for j, b in zip(jobs, n_bits)] + [0])
+
+    def decode(self, d_sym, jobs, n_bytes=None):
+        """One record and the decoded bits per job, up to 4096 jobs in one call (fosphor_amd_decode): the symbols' bits
+        depunctured, a Viterbi decoder over the whole frame with one lane per state, the decoded bits packed MSB first and a CRC
+        over them, over one byte per symbol that is already in device memory.  d_sym: a contiguous uint8 device tensor (what
+        decide() wrote) or a raw device pointer with n_bytes; jobs: a DECODE_JOB_DTYPE array (decode_jobs() makes one from decide
+        jobs and records; out_offset is honoured, the owned bytes must not overlap).
+        Returns (records, views): a DECODE_RECORD_DTYPE array copied from the device, in job order, and a list with one torch
+        uint8 view of ceil(n_bits / 8) bytes per job into one device buffer."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.DECODE_JOB_DTYPE)
+        if n_bytes is None:
+            if not hasattr(d_sym, "numel"):
+                raise ValueError("a raw device pointer needs n_bytes")
+            if str(d_sym.dtype) != "torch.uint8" or not d_sym.is_contiguous():
+                raise ValueError("d_sym must be a contiguous uint8 tensor")
+            n_bytes = d_sym.numel()
+        _, cap = self._decode_outs(jobs)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 8) // 8, dtype=torch.int64, device="cuda").view(torch.uint8)
+        d_rec = torch.empty(max(jobs.size, 1) * self.DECODE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()			# the caller's bytes were written on torch's stream
+        rv = self.L.fosphor_amd_decode(self.h, _ptr(d_sym), int(n_bytes), jobs.ctypes.data, int(jobs.size), d_rec.data_ptr(),
+                                       d_out.data_ptr(), cap)
+        if rv:
+            _fail("fosphor_amd_decode", rv, RuntimeError)
+        records = d_rec.cpu().numpy().view(self.DECODE_RECORD_DTYPE)[:jobs.size].copy()
+        return records, [d_out[int(j["out_offset"]):int(j["out_offset"]) + (int(r["n_bits"]) + 7) // 8] for j, r in zip(jobs, records)]
+
+    @staticmethod
+    def decode_host(sym, jobs):
+        """fosphor_amd_decode_host: the same records and bits on the host, no GPU.  sym: uint8, one symbol a byte.  Returns
+        (records, views), the views uint8 arrays of ceil(n_bits / 8) bytes into one buffer"""
+        sym = np.ascontiguousarray(sym, dtype=np.uint8).reshape(-1)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.DECODE_JOB_DTYPE)
+        _, cap = Fosphor._decode_outs(jobs)
+        out = np.zeros(max(cap, 8) // 8, np.uint64).view(np.uint8)
+        records = np.zeros(max(jobs.size, 1), Fosphor.DECODE_RECORD_DTYPE)
+        keep = sym if sym.size else np.zeros(8, np.uint8)
+        rv = _lib.load().fosphor_amd_decode_host(keep.ctypes.data, int(sym.size), jobs.ctypes.data, int(jobs.size),
+                                                 records.ctypes.data, out.ctypes.data, cap)
+        if rv:
+            _fail("fosphor_amd_decode_host", rv, ValueError)
+        records = records[:jobs.size]
+        return records, [out[int(j["out_offset"]):int(j["out_offset"]) + (int(r["n_bits"]) + 7) // 8] for j, r in zip(jobs, records)]
+
+    @staticmethod
+    def decode_derive(records):
+        """fosphor_amd_decode_derive per record: a list of dicts of DECODE_VALUES (ratios)"""
+        L = _lib.load()
+        records = np.ascontiguousarray(np.atleast_1d(records), dtype=Fosphor.DECODE_RECORD_DTYPE)
+        out = []
+        for r in records:
+            v = _lib.DecodeValues()
+            rv = L.fosphor_amd_decode_derive(r.tobytes(), C.byref(v))
+            if rv:
+                _fail("fosphor_amd_decode_derive", rv, ValueError)
+            out.append({k: getattr(v, k) for k in Fosphor.DECODE_VALUES})
+        return out
+
+    def decode_stats(self):
+        """fosphor_amd_decode_stats as a dict: calls, launches by kernel, jobs with a CRC, steps (DECODE_STATS)"""
+        return self._stats(self.L.fosphor_amd_decode_stats, self.DECODE_STATS)
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

@@ -1294,7 +1294,7 @@ extern "C" void fosphor_amd_priv_power(struct fosphor *self, float *scale, float
 
 /* The scratch buffers that only grow, by FOSPHOR_SCRATCH_* (fosphor_pass.h): one each for fosphor_detect.hip and fosphor_mask.hip (of a
  * size fixed for the life of the instance: allocated on first use, never again), the two of fosphor_burst.hip, and one each for the
- * job tables and partials of fosphor_extract / _measure / _demod / _correlate / _resample / _psd / _symbols / _carrier / _decide.hip.  Every user has drained the stream of the
+ * job tables and partials of fosphor_extract / _measure / _demod / _correlate / _resample / _psd / _symbols / _carrier / _decide / _decode.hip.  Every user has drained the stream of the
  * launches that used the old buffer before it asks for a larger one. */
 extern "C" int fosphor_amd_priv_scratch(struct fosphor *self, int which, size_t bytes, void **d_scratch)
 {
