@@ -279,6 +279,27 @@ class DecodeValues(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("channel_ber", "rate", "crc_ok")]
 
 
+class SoftJob(C.Structure):
+    """struct fosphor_amd_soft_job (include/fosphor_amd_soft.h)"""
+    _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("n", C.c_int32), ("order", C.c_int16), ("flags", C.c_int16),
+                ("steps", C.c_int32), ("k", C.c_uint8), ("n_poly", C.c_uint8), ("period", C.c_uint8), ("crc_width", C.c_uint8),
+                ("polys", C.c_uint16 * 3), ("punct", C.c_uint16 * 3), ("crc_poly", C.c_uint32), ("crc_init", C.c_uint32),
+                ("crc_xorout", C.c_uint32), ("rot", C.c_int32), ("scale", C.c_float)]
+
+
+class SoftRecord(C.Structure):
+    """struct fosphor_amd_soft_record"""
+    _fields_ = [("n_steps", C.c_int32), ("n_bits", C.c_int32), ("n_coded", C.c_int32), ("status", C.c_int32),
+                ("end_state", C.c_int32), ("metric", C.c_int32), ("best_state", C.c_int32), ("best_metric", C.c_int32),
+                ("crc_calc", C.c_uint32), ("crc_recv", C.c_uint32), ("k", C.c_int32), ("flags", C.c_int32),
+                ("erasures", C.c_int32), ("saturated", C.c_int32), ("abs_sum", C.c_int64)]
+
+
+class SoftValues(C.Structure):
+    """struct fosphor_amd_soft_values"""
+    _fields_ = [(k, C.c_double) for k in ("mean_abs", "corrected_share", "rate", "crc_ok")]
+
+
 class ResampleJob(C.Structure):
     """struct fosphor_amd_resample_job (include/fosphor_amd_resample.h)"""
     _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("phase0", C.c_int64), ("n", C.c_int32), ("n_out", C.c_int32),
@@ -485,6 +506,12 @@ SIGNATURES = {
     "fosphor_amd_decode_from_decide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DecodeJob)]),
     "fosphor_amd_decode_derive": (C.c_int, [C.c_void_p, C.POINTER(DecodeValues)]),
     "fosphor_amd_decode_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 7)]),
+    # include/fosphor_amd_soft.h
+    "fosphor_amd_soft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
+    "fosphor_amd_soft_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
+    "fosphor_amd_soft_from_decide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(SoftJob)]),
+    "fosphor_amd_soft_derive": (C.c_int, [C.c_void_p, C.POINTER(SoftValues)]),
+    "fosphor_amd_soft_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 7)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

@@ -1767,6 +1767,129 @@ class Fosphor:
         """fosphor_amd_decode_stats as a dict: calls, launches by kernel, jobs with a CRC, steps (DECODE_STATS)"""
         return self._stats(self.L.fosphor_amd_decode_stats, self.DECODE_STATS)
 
+    SOFT_STATS = ("calls", "k_bits", "k_acs", "k_trace", "k_rec", "jobs_crc", "steps")
+    SOFT_MAX_JOBS = 4096				# FOSPHOR_AMD_SOFT_MAX_JOBS (include/fosphor_amd_soft.h)
+    SOFT_MAX_STEPS, SOFT_MAX_CALL_STEPS = 65536, 1 << 22	# FOSPHOR_AMD_SOFT_MAX_STEPS, FOSPHOR_AMD_SOFT_MAX_CALL_STEPS
+    SOFT_BLOCK, SOFT_GROUP = 64, 256			# FOSPHOR_AMD_SOFT_BLOCK, FOSPHOR_AMD_SOFT_GROUP
+    SOFT_MAX_VALUE, SOFT_INF = 127, 1 << 25		# FOSPHOR_AMD_SOFT_MAX_VALUE, FOSPHOR_AMD_SOFT_INF
+    SOFT_FLAGS = {"terminated": 1, "gray": 2}		# FOSPHOR_AMD_SOFT_TERMINATED, FOSPHOR_AMD_SOFT_GRAY
+    SOFT_STATUS = {"ok": 0, "crc_fail": 1, "short": 2}	# FOSPHOR_AMD_SOFT_OK, _CRC_FAIL, _SHORT
+    SOFT_LDS = {"bits": 32, "acs": 0, "trace": 0, "rec": 0}	# FOSPHOR_AMD_SOFT_LDS_*
+    SOFT_JOB_DTYPE = np.dtype([("offset", "<i8"), ("out_offset", "<i8"), ("n", "<i4"), ("order", "<i2"), ("flags", "<i2"),
+                               ("steps", "<i4"), ("k", "u1"), ("n_poly", "u1"), ("period", "u1"), ("crc_width", "u1"),
+                               ("polys", "<u2", (3,)), ("punct", "<u2", (3,)), ("crc_poly", "<u4"), ("crc_init", "<u4"),
+                               ("crc_xorout", "<u4"), ("rot", "<i4"), ("scale", "<f4")])
+    SOFT_RECORD_DTYPE = np.dtype([("n_steps", "<i4"), ("n_bits", "<i4"), ("n_coded", "<i4"), ("status", "<i4"),
+                                  ("end_state", "<i4"), ("metric", "<i4"), ("best_state", "<i4"), ("best_metric", "<i4"),
+                                  ("crc_calc", "<u4"), ("crc_recv", "<u4"), ("k", "<i4"), ("flags", "<i4"),
+                                  ("erasures", "<i4"), ("saturated", "<i4"), ("abs_sum", "<i8")])
+    SOFT_VALUES = tuple(k for k, _ in _lib.SoftValues._fields_)
+
+    @staticmethod
+    def _soft_flags(flags):
+        """an integer, one name of SOFT_FLAGS or several ("terminated", "gray") -> the sum of the bits"""
+        if isinstance(flags, str):
+            flags = (flags,)
+        if isinstance(flags, (tuple, list, set, frozenset)):
+            for k in flags:
+                if k not in Fosphor.SOFT_FLAGS:
+                    raise ValueError("flags must be of %s" % ", ".join(Fosphor.SOFT_FLAGS))
+            return sum(Fosphor.SOFT_FLAGS[k] for k in set(flags))
+        return int(flags)
+
+    @staticmethod
+    def soft_jobs(decide_jobs, decide_records, uw_len, n_payload=0, k=7, polys=(0o171, 0o133, 0), period=1, punct=(1, 1, 0),
+                  steps=0, flags=0, crc_width=0, crc_poly=0, crc_init=0, crc_xorout=0, gap=8):
+        """a SOFT_JOB_DTYPE array from a DECIDE_JOB_DTYPE array and the DECIDE_RECORD_DTYPE array that decide() gave for it
+        (fosphor_amd_soft_from_decide: each job reads the symbols that the decide job read, behind its unique word, n = n_payload
+        symbols or all of them, n = 0 where the record says no_uw; rot is the record's uw_rot, scale 16 n / a, "gray" the decide
+        job's), the code, the puncture masks and the CRC the same for every job, `flags` ("terminated") added to what the decide
+        job gives, the owned bytes placed from out_offset 0 on at multiples of 8 with `gap` bytes (rounded up to a multiple of 8)
+        between them"""
+        L = _lib.load()
+        src = np.ascontiguousarray(np.atleast_1d(decide_jobs), dtype=Fosphor.DECIDE_JOB_DTYPE)
+        rec = np.ascontiguousarray(np.atleast_1d(decide_records), dtype=Fosphor.DECIDE_RECORD_DTYPE)
+        if src.size != rec.size:
+            raise ValueError("one decide record per decide job")
+        if gap < 0:
+            raise ValueError("gap must be >= 0")
+        flags = Fosphor._soft_flags(flags)
+        out = np.zeros(src.size, Fosphor.SOFT_JOB_DTYPE)
+        n_poly = 3 if len(polys) > 2 and polys[2] else 2
+        at = 0
+        for i, (s, r) in enumerate(zip(src, rec)):
+            job = _lib.SoftJob()
+            rv = L.fosphor_amd_soft_from_decide(s.tobytes(), r.tobytes(), int(uw_len), int(n_payload), C.byref(job))
+            if rv:
+                _fail("fosphor_amd_soft_from_decide", rv, ValueError)
+            o = out[i]
+            o["offset"], o["out_offset"], o["n"], o["order"], o["steps"], o["flags"] = job.offset, at, job.n, job.order, steps, job.flags | flags
+            o["k"], o["n_poly"], o["period"], o["crc_width"] = k, n_poly, period, crc_width
+            o["polys"], o["punct"] = tuple(polys) + (0,) * (3 - len(polys)), tuple(punct) + (0,) * (3 - len(punct))
+            o["crc_poly"], o["crc_init"], o["crc_xorout"] = crc_poly, crc_init, crc_xorout
+            o["rot"], o["scale"] = job.rot, job.scale
+            at += Fosphor.decode_owned(Fosphor._decode_shape(o)[1]) + 8 * ((int(gap) + 7) // 8)
+        return out
+
+    def soft(self, d_iq, jobs, n_samples=None):
+        """One record and the decoded bits per job, up to 4096 jobs in one call (fosphor_amd_soft): one quantised soft value per
+        coded bit from the derotated symbols, depunctured, a soft-input Viterbi decoder over the whole frame with one lane per
+        state, the decoded bits packed MSB first and a CRC over them, over float32 symbols that are already in device memory.
+        d_iq: a contiguous device tensor (complex64 or float32 pairs; what carrier() wrote and decide() read) or a raw device
+        pointer with n_samples; jobs: a SOFT_JOB_DTYPE array (soft_jobs() makes one from decide jobs and records; out_offset is
+        honoured, the owned bytes must not overlap).
+        Returns (records, views): a SOFT_RECORD_DTYPE array copied from the device, in job order, and a list with one torch
+        uint8 view of ceil(n_bits / 8) bytes per job into one device buffer."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.SOFT_JOB_DTYPE)
+        n_samples = _iq_count(d_iq, n_samples, "samples")
+        _, cap = self._decode_outs(jobs)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 8) // 8, dtype=torch.int64, device="cuda").view(torch.uint8)
+        d_rec = torch.empty(max(jobs.size, 1) * self.SOFT_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()			# the caller's symbols were written on torch's stream
+        rv = self.L.fosphor_amd_soft(self.h, _ptr(d_iq), n_samples, jobs.ctypes.data, int(jobs.size), d_rec.data_ptr(),
+                                     d_out.data_ptr(), cap)
+        if rv:
+            _fail("fosphor_amd_soft", rv, RuntimeError)
+        records = d_rec.cpu().numpy().view(self.SOFT_RECORD_DTYPE)[:jobs.size].copy()
+        return records, [d_out[int(j["out_offset"]):int(j["out_offset"]) + (int(r["n_bits"]) + 7) // 8] for j, r in zip(jobs, records)]
+
+    @staticmethod
+    def soft_host(iq, jobs):
+        """fosphor_amd_soft_host: the same records and bits on the host, no GPU.  iq: complex64 or float32 pairs.  Returns
+        (records, views), the views uint8 arrays of ceil(n_bits / 8) bytes into one buffer"""
+        iq = _float_pairs(iq)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.SOFT_JOB_DTYPE)
+        _, cap = Fosphor._decode_outs(jobs)
+        out = np.zeros(max(cap, 8) // 8, np.uint64).view(np.uint8)
+        records = np.zeros(max(jobs.size, 1), Fosphor.SOFT_RECORD_DTYPE)
+        keep = _or_dummy(iq)
+        rv = _lib.load().fosphor_amd_soft_host(keep.ctypes.data, iq.size // 2, jobs.ctypes.data, int(jobs.size),
+                                               records.ctypes.data, out.ctypes.data, cap)
+        if rv:
+            _fail("fosphor_amd_soft_host", rv, ValueError)
+        records = records[:jobs.size]
+        return records, [out[int(j["out_offset"]):int(j["out_offset"]) + (int(r["n_bits"]) + 7) // 8] for j, r in zip(jobs, records)]
+
+    @staticmethod
+    def soft_derive(records):
+        """fosphor_amd_soft_derive per record: a list of dicts of SOFT_VALUES (ratios)"""
+        L = _lib.load()
+        records = np.ascontiguousarray(np.atleast_1d(records), dtype=Fosphor.SOFT_RECORD_DTYPE)
+        out = []
+        for r in records:
+            v = _lib.SoftValues()
+            rv = L.fosphor_amd_soft_derive(r.tobytes(), C.byref(v))
+            if rv:
+                _fail("fosphor_amd_soft_derive", rv, ValueError)
+            out.append({k: getattr(v, k) for k in Fosphor.SOFT_VALUES})
+        return out
+
+    def soft_stats(self):
+        """fosphor_amd_soft_stats as a dict: calls, launches by kernel, jobs with a CRC, steps (SOFT_STATS)"""
+        return self._stats(self.L.fosphor_amd_soft_stats, self.SOFT_STATS)
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

@@ -16,9 +16,12 @@
  * kind, no work-group waits for another, no LDS, every loop carries its bound in its header.
  */
 #include "fosphor_jobs.h"
+#include "fosphor_trellis.h"					/* kept_of, expected_of, bit_place, crc_of, steps_that_fit and the checks of the code */
 #include "../../include/fosphor_amd_decode.h"
 
 namespace {
+
+using namespace trellis;
 
 typedef struct fosphor_amd_decode_job Job;
 typedef struct fosphor_amd_decode_record Record;
@@ -65,15 +68,6 @@ struct Params {
 	int n_jobs;
 };
 
-inline __host__ __device__ int popc(uint32_t v) { return __builtin_popcount(v); }
-
-/* rule 2: the kept bits of the first T steps */
-inline __host__ __device__ int64_t kept_of(int64_t T, int period, const uint16_t *punct, int weight)
-{
-	const uint32_t below = (1u << (int)(T % period)) - 1u;
-	return (T / period) * weight + popc(punct[0] & below) + popc(punct[1] & below) + popc(punct[2] & below);
-}
-
 /* rules 1 and 2: the code byte of step t of a job whose symbol 0 is sym[0]: received bits in bits 0 .. 2, erased flags in 4 .. 6 */
 inline __host__ __device__ uint32_t code_of(const uint8_t *sym, int b, int n_poly, int period, const uint16_t *punct, int weight, int t)
 {
@@ -92,55 +86,11 @@ inline __host__ __device__ uint32_t code_of(const uint8_t *sym, int b, int n_pol
 	return c;
 }
 
-/* rule 3: what the encoder sends on the branch from state p with input u, stream i in bit i */
-inline __host__ __device__ uint32_t expected_of(const uint16_t *polys, int n_poly, int k, int u, int p)
-{
-	const uint32_t R = ((uint32_t)u << (k - 1)) | (uint32_t)p;
-	uint32_t e = 0;
-	for (int i = 0; i < 3 && i < n_poly; i++)
-		e |= (uint32_t)(popc(polys[i] & R) & 1) << i;
-	return e;
-}
-
 /* rule 3: the sent bits of a branch that differ from the received ones of code c */
 inline __host__ __device__ int branch_of(uint32_t e, uint32_t c) { return popc((e ^ c) & 7u & ~(c >> 4)); }
 
 /* rule 4 as one integer: the least metric, then the smallest state */
 inline __host__ __device__ uint32_t end_key(int metric, int state) { return ((uint32_t)metric << 6) | (uint32_t)state; }
-
-/* rule 6: where decoded bit i of a block of 64 lies in the block's output word, stored little-endian */
-inline __host__ __device__ int bit_place(int i) { return 8 * (i >> 3) + 7 - (i & 7); }
-
-/* rule 7 over the job's owned bytes */
-inline __host__ __device__ void crc_of(const uint8_t *out, int n_bits, int w, uint32_t poly, uint32_t init, uint32_t xorout,
-                                       uint32_t &calc, uint32_t &recv, int &status)
-{
-	calc = recv = 0;
-	status = FOSPHOR_AMD_DECODE_OK;
-	if (w == 0)
-		return;
-	if (n_bits < w) {
-		status = FOSPHOR_AMD_DECODE_SHORT;
-		return;
-	}
-	const int n_data = n_bits - w;
-	const uint32_t mask = w == 32 ? 0xffffffffu : (1u << w) - 1u;
-	uint32_t reg = init;
-	for (int t0 = 0; t0 < n_data; t0 += 8) {
-		const uint32_t byte = out[t0 >> 3];
-		for (int i = 0; i < 8 && t0 + i < n_data; i++) {
-			const uint32_t top = ((reg >> (w - 1)) ^ (byte >> (7 - i))) & 1u;
-			reg = (reg << 1) & mask;
-			if (top)
-				reg ^= poly;
-		}
-	}
-	calc = reg ^ xorout;
-	for (int t = n_data; t < n_bits && t < n_data + 32; t++)
-		recv = (recv << 1) | ((out[t >> 3] >> (7 - (t & 7))) & 1u);
-	if (calc != recv)
-		status = FOSPHOR_AMD_DECODE_CRC_FAIL;
-}
 
 /* the whole record, from rule 4's values and the job's owned bytes */
 inline __host__ __device__ void record_of(int n_steps, int n_bits, int n_coded, int k, int flags, const int *ends, const uint8_t *out,
@@ -276,36 +226,6 @@ void k_dcd_rec(const Params p)
 	if (lane == 0)
 		p.records[j] = r;
 }
-
-inline bool order_ok(int order) { return order == 2 || order == 4 || order == 8; }
-inline int bits_of(int order) { return order == 2 ? 1 : (order == 4 ? 2 : 3); }
-
-/* rule 9, of the puncture pattern alone */
-inline bool punct_ok(int n_poly, int period, const uint16_t *punct, int *weight)
-{
-	if ((n_poly != 2 && n_poly != 3) || period < 1 || period > 16 || !punct)
-		return false;
-	int w = 0;
-	for (int i = 0; i < 3; i++) {
-		if ((uint32_t)punct[i] >> period || (i >= n_poly && punct[i]))
-			return false;
-		w += popc(punct[i]);
-	}
-	*weight = w;
-	return w > 0;
-}
-
-/* rule 2: the largest T with kept(T) <= coded */
-inline int64_t steps_that_fit(int64_t coded, int period, const uint16_t *punct, int weight)
-{
-	int64_t T = (coded / weight) * period;
-	for (int i = 0; i < 16 && kept_of(T + 1, period, punct, weight) <= coded; i++)
-		T++;
-	return T;
-}
-
-/* the bytes a job owns in d_out */
-inline int64_t owned_of(int32_t n_bits) { return 8 * (((int64_t)n_bits + 63) / 64); }
 
 struct Shape {
 	int32_t n_steps, n_bits, n_coded, weight;

@@ -9,8 +9,8 @@
  * or the rotation under which a known word is found (rule 4).  Nothing a symbol's result feeds back into, so up to 4096 bursts go
  * in one call.
  *
- * Not this pass: soft decisions, other constellations than M-ary PSK, error correction, and words longer than
- * FOSPHOR_AMD_DECIDE_MAX_UW.
+ * Not this pass: other constellations than M-ary PSK, error correction, and words longer than FOSPHOR_AMD_DECIDE_MAX_UW.  Soft
+ * decisions over the same symbols are fosphor_amd_soft.h.
  *
  * Conventions, those of fosphor_amd_carrier.h: the device entry point waits for pending fosphor_process work first
  * (fosphor_amd_finish), runs on the instance's stream and returns when its outputs are complete; it writes no state of the
