@@ -38,6 +38,7 @@
 #include "fosphor_amd_cmap.h"
 #include "fosphor_amd_correlate.h"
 #include "fosphor_amd_decide.h"
+#include "fosphor_amd_decode.h"
 #include "fosphor_amd_demod.h"
 #include "fosphor_amd_detect.h"
 #include "fosphor_amd_extract.h"
@@ -45,6 +46,7 @@
 #include "fosphor_amd_measure.h"
 #include "fosphor_amd_psd.h"
 #include "fosphor_amd_resample.h"
+#include "fosphor_amd_soft.h"
 #include "fosphor_amd_symbols.h"
 #include "fosphor_amd_view.h"
 
@@ -135,21 +137,24 @@ const std::map<std::string, Entry> kEntries = {
 	ENTRY(fosphor_amd_extract_host), ENTRY(fosphor_amd_measure_host), ENTRY(fosphor_amd_demod_host),
 	ENTRY(fosphor_amd_correlate_host), ENTRY(fosphor_amd_resample_host), ENTRY(fosphor_amd_psd_host),
 	ENTRY(fosphor_amd_symbols_host), ENTRY(fosphor_amd_carrier_host), ENTRY(fosphor_amd_decide_host),
+	ENTRY(fosphor_amd_decode_host), ENTRY(fosphor_amd_soft_host),
 	ENTRY(fosphor_amd_bursts_host), ENTRY(fosphor_amd_mask_row_host), ENTRY(fosphor_amd_detect_bands_host),
 	/* the size rules */
 	ENTRY(fosphor_amd_demod_n_out), ENTRY(fosphor_amd_correlate_n_out), ENTRY(fosphor_amd_resample_n_out),
-	ENTRY(fosphor_amd_psd_n_seg), ENTRY(fosphor_amd_symbols_max_out),
+	ENTRY(fosphor_amd_psd_n_seg), ENTRY(fosphor_amd_symbols_max_out), ENTRY(fosphor_amd_decode_steps),
 	/* the constructors */
 	ENTRY(fosphor_amd_extract_from_burst), ENTRY(fosphor_amd_measure_from_extract), ENTRY(fosphor_amd_demod_from_extract),
 	ENTRY(fosphor_amd_correlate_from_extract), ENTRY(fosphor_amd_resample_from_extract), ENTRY(fosphor_amd_psd_from_extract),
 	ENTRY(fosphor_amd_symbols_from_extract), ENTRY(fosphor_amd_symbols_from_resample), ENTRY(fosphor_amd_carrier_from_symbols),
-	ENTRY(fosphor_amd_decide_from_carrier), ENTRY(fosphor_amd_view_from_render),
+	ENTRY(fosphor_amd_decide_from_carrier), ENTRY(fosphor_amd_decode_from_decide), ENTRY(fosphor_amd_soft_from_decide),
+	ENTRY(fosphor_amd_view_from_render),
 	/* the designs */
 	ENTRY(fosphor_amd_extract_design), ENTRY(fosphor_amd_resample_design), ENTRY(fosphor_amd_resample_ratio),
 	ENTRY(fosphor_amd_psd_window), ENTRY(fosphor_amd_psd_twiddles), ENTRY(fosphor_amd_symbols_twiddles),
 	/* the records as values */
 	ENTRY(fosphor_amd_measure_derive), ENTRY(fosphor_amd_correlate_derive), ENTRY(fosphor_amd_psd_derive),
 	ENTRY(fosphor_amd_symbols_derive), ENTRY(fosphor_amd_carrier_derive), ENTRY(fosphor_amd_decide_derive),
+	ENTRY(fosphor_amd_decode_derive), ENTRY(fosphor_amd_soft_derive),
 	/* the rest */
 	ENTRY(fosphor_amd_view_span), ENTRY(fosphor_amd_mask_from_points), ENTRY(fosphor_amd_detect_bin_y),
 	ENTRY(fosphor_amd_cmap_generate), ENTRY(fosphor_amd_freq_axis_build), ENTRY(fosphor_amd_freq_axis_render),

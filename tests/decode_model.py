@@ -403,6 +403,40 @@ def full_table_case():
     return sym, place(jobs)
 
 
+LIMIT_JOBS = MAX_CALL_STEPS // MAX_STEPS
+_LIMIT = []
+
+
+def call_limit_case():
+    """64 jobs of MAX_STEPS, exactly MAX_CALL_STEPS, in shuffled order with place()'s guards; two shapes, so that the model decodes
+    the jobs of a shape together: K = 7 at rate 1/2, QPSK, CRC-16, TERMINATED, and K = 5 punctured 3/4, 8PSK, CRC-32, not
+    terminated; encoded frames with a coded bit in 50 inverted, as max_steps_case().  Not in cases(): the model takes its time for
+    it.  Once a session"""
+    if _LIMIT:
+        return _LIMIT[0]
+    rng = np.random.default_rng(2828)
+    parts, jobs, at = [], [], 0
+    for i in rng.permutation(LIMIT_JOBS):
+        if i & 1:
+            code, punct, order, crc, term, n_info = K5, P_34, 8, CRC32, False, MAX_STEPS - 32
+        else:
+            code, punct, order, crc, term, n_info = K7, P_NONE, 4, CRC16, True, MAX_STEPS - 6 - 16
+        n_coded = kept(MAX_STEPS, punct[0], punct[1])
+        sym, T = frame(rng.integers(0, 2, n_info), code, punct, order, crc, term, flips=rng.choice(n_coded, n_coded // 50, replace=False))
+        assert T == MAX_STEPS
+        parts.append(sym)
+        jobs.append(make_job(at, 0, len(sym), order, code, punct, crc, T, TERMINATED if term else 0))
+        at += len(sym)
+    _LIMIT.append((np.concatenate(parts), place(jobs)))
+    return _LIMIT[0]
+
+
+def one_step_more(case):
+    """the case with one more job of one step behind its table: a step past MAX_CALL_STEPS"""
+    sym, jobs = case
+    return sym, place([jobs.copy(), make_job(0, 0, 1, 4, K3, P_NONE, CRC_NONE, 1, 0)])
+
+
 def cases():
     """name -> (sym, jobs): every set the CPU and GPU tests share"""
     return {"seams": seams_case(), "codes": codes_case(), "frames": frames_case(), "max_steps": max_steps_case(),

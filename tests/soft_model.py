@@ -50,8 +50,9 @@ def points(M, rot):
     return cm.cossin_turns(((q + int(rot)) & (M - 1)).astype(np.float64) / np.float64(M))
 
 
-def soft_values(y, M, rot, gray, scale):
-    """rules S1 and S2 over float32 y [n][2] -> (v int64 [n][b], a part is a NaN: bool [n])"""
+def soft_values(y, M, rot, gray, scale, variant=0):
+    """rules S1 and S2 over float32 y [n][2] -> (v int64 [n][b], a part is a NaN: bool [n]).  variant: 0, or a contraction of the
+    correlation (contracted_values(), finite symbols only)"""
     b = dm.bits_of(M)
     sr, si = y[:, 0].astype(np.float64), y[:, 1].astype(np.float64)
     nan = np.isnan(sr) | np.isnan(si)
@@ -68,14 +69,17 @@ def soft_values(y, M, rot, gray, scale):
             x = ((zero - one) * np.float64(np.float32(scale))) + 0.5
             v[:, i] = np.where(np.isnan(x), 0.0, np.clip(np.floor(x), -MAX_VALUE, MAX_VALUE)).astype(np.int64)
     v[nan] = 0
+    if variant:
+        for m in np.flatnonzero(~nan):
+            v[m] = contracted_values(y[m], M, rot, gray, scale, variant)
     return v, nan
 
 
-def step_values(iq, job, T):
+def step_values(iq, job, T, variant=0):
     """rules 2 and S2 -> (v int64 [T][3], 0 where a stream's bit was not sent; sent bool [T][3]; erasures)"""
     M, b, n_poly = int(job["order"]), dm.bits_of(job["order"]), int(job["n_poly"])
     at, n = int(job["offset"]), int(job["n"])
-    v, nan = soft_values(iq[at:at + n], M, job["rot"], int(job["flags"]) & GRAY, job["scale"])
+    v, nan = soft_values(iq[at:at + n], M, job["rot"], int(job["flags"]) & GRAY, job["scale"], variant)
     coded = v.reshape(-1)
     sent = dm.sent_of(T, n_poly, int(job["period"]), job["punct"])
     flat = sent.reshape(-1)
@@ -134,8 +138,8 @@ def buffer(case):
     return np.ascontiguousarray(case[0], np.float32).reshape(-1, 2)
 
 
-def decode(case):
-    """(records RECORD_DTYPE [n_jobs], [the owned bytes per job, uint8])"""
+def decode(case, variant=0):
+    """(records RECORD_DTYPE [n_jobs], [the owned bytes per job, uint8]); variant: soft_values()'s"""
     iq, jobs = buffer(case), case[1]
     records, outs = np.zeros(len(jobs), RECORD_DTYPE), [None] * len(jobs)
     groups = {}
@@ -143,7 +147,7 @@ def decode(case):
         T = shape(j)[0]
         groups.setdefault((T, int(j["k"]), tuple(int(v) for v in j["polys"]), int(j["n_poly"]), int(j["flags"]) & TERMINATED), []).append(i)
     for (T, k, polys, n_poly, term), members in groups.items():
-        steps = [step_values(iq, jobs[i], T) for i in members]
+        steps = [step_values(iq, jobs[i], T, variant) for i in members]
         ends, u = viterbi(np.stack([s[0] for s in steps]) if T else np.zeros((len(members), 0, 3), np.int64), k, polys, n_poly, term)
         for row, i in enumerate(members):
             j, r = jobs[i], records[i]
@@ -322,6 +326,226 @@ def full_table_case():
     return iq, place(jobs)
 
 
+# ---- one crafted symbol a job: the edges of rule S2, and symbols that tell a contracted correlation -----------------------------
+
+F32_MAX = float(np.finfo(np.float32).max)
+
+
+def value_job(at, order=2, rot=0, gray=0, scale=1.0):
+    """one step over the crafted symbol iq[at] whose bits it consumes exactly, so that the record carries the symbol's soft values
+    out -> (symbols of the job, the job).  BPSK: K = 3 (7, 5) at rate 1/2, and a second symbol (0, 0) that is worth nothing:
+    abs_sum is |v| and the decoded bit is 1 exactly when v < 0 (input 1 sends 11).  QPSK: the same code, one symbol.  8-PSK: K = 4
+    at rate 1/3, one symbol.  There abs_sum is the sum of the |v|, metric what the cheaper input pays, and the decoded bit says
+    which it was"""
+    code, n = {2: (dm.K3, 2), 4: (dm.K3, 1), 8: (dm.K4_THIRD, 1)}[order]
+    return n, make_job(at, 0, n, order, code, dm.P3_NONE if order == 8 else dm.P_NONE, dm.CRC_NONE, 1, GRAY if gray else 0, rot, scale)
+
+
+# BPSK at rot 0: the points are (1, +0) and (-1, -0), L = 2 sr exactly, x = 2 sr scale + 0.5.  (sr, scale, the v of rule S2)
+EDGE_VALUES = ((0.25, 1.0, 1), (0.75, 1.0, 2), (-0.25, 1.0, 0), (-0.75, 1.0, -1), (1.25, 1.0, 3), (-1.25, 1.0, -2),	# x at an integer: L at a half
+               (0.24999999, 1.0, 0), (0.75, 0.99999994, 1), (63.25, 1.0, 127), (63.0, 1.0, 126), (63.5, 1.0, 127), (1e30, 1.0, 127),
+               (-63.5, 1.0, -127), (-63.25, 1.0, -126), (-63.75, 1.0, -127), (-64.0, 1.0, -127), (-1e30, 1e30, -127),
+               (3e38, 3e38, 127), (np.inf, 1.0, 127), (-np.inf, 1.0, -127), (1e-30, 1e-30, 0), (0.0, 1e6, 0), (-0.0, 1e6, 0))
+# what a flush of float32 subnormals to zero would change: a subnormal symbol under the largest scale (L = 2e-38, x = 7.3; flushed,
+# v = 0) and a subnormal scale under a large symbol (L = 6e38, x = 1.1; flushed, the scale is 0 and v = 0)
+EDGE_SUBNORMAL = ((1e-38, F32_MAX, 7), (3e38, 1e-39, 1))
+# a NaN part: v = 0 and one erasure, whatever the other part is
+EDGE_NAN = ((np.nan, 0.0), (1.0, np.nan), (np.nan, np.nan), (np.inf, np.nan), (np.nan, -np.inf))
+# an infinite imaginary part meets the zero of the points' sines: both correlations are NaN, none is the largest,
+# L = -inf - -inf is a NaN: v = 0, and no erasure
+EDGE_INF = ((1.0, np.inf), (-1.0, -np.inf), (np.inf, np.inf))
+# 4- and 8-PSK: symbols on the axes and the diagonals, where two correlations tie or L = 0 ((1, 1) lies on a decision boundary of
+# QPSK at rot 0 and on a point of 8-PSK, (0, 1) on a point of both), and one symbol off them all; two scales, the second puts
+# L = 1 on a half
+EDGE_PSK_SYMBOLS = ((1.0, 1.0), (0.0, 1.0), (-1.0, 1.0), (-1.0, 0.0), (-1.0, -1.0), (0.0, -1.0), (1.0, -1.0), (1.0, 0.0), (0.5, 0.25))
+EDGE_PSK_SCALES = (10.0, 63.5)
+EDGE_ODD = (np.inf, -np.inf, 0.0, -0.0, 1.0, -1.0, 3e38, 1e-45, np.nan)
+EDGE_ODD_SCALES = (1e-3, 1.0, 3e38)
+
+
+def edge_rows():
+    """the one-symbol jobs of the "edges" case, in its order: (sr, si, order, rot, gray, scale, the expected v of bit 0 or None,
+    the expected erasures or None)"""
+    rows = [(sr, 0.0, 2, 0, 0, scale, want, 0) for sr, scale, want in EDGE_VALUES + EDGE_SUBNORMAL]
+    rows += [(sr, si, 2, 0, 0, 32.0, 0, 1) for sr, si in EDGE_NAN]
+    rows += [(sr, si, 2, 0, 0, 32.0, 0, 0) for sr, si in EDGE_INF]
+    for order in (4, 8):
+        for gray in (0, 1):
+            for rot in (0, order - 1):
+                for scale in EDGE_PSK_SCALES:
+                    rows += [(sr, si, order, rot, gray, scale, None, 0) for sr, si in EDGE_PSK_SYMBOLS]
+    return rows
+
+
+def edge_odd_jobs(at):
+    """36 jobs over the same 600 symbols at iq[at]: every order, labeling, rot = 0 and M - 1, three scales"""
+    return [make_job(at, 0, 600, order, dm.K5, dm.P_NONE, dm.CRC8, 0, gray * GRAY, rot, scale)
+            for order in ORDERS for gray in (0, 1) for rot in (0, order - 1) for scale in EDGE_ODD_SCALES]
+
+
+def edges_case():
+    """the numerical edges of rule S2, a job a crafted value (scale is a job field): halves that round upwards, 126 / 127 and
+    -126 / -127, x < -127, infinity minus infinity, NaN correlations beside live ones, +-0, scales from 1e-3 to 3e38, float32
+    subnormals that must survive the widening to double, 4- and 8-PSK symbols on decision boundaries and on points at rot = 0 and
+    M - 1 under both labelings; then 36 jobs over 600 symbols drawn from +-inf, +-0, +-1, 3e38, 1e-45 and NaN"""
+    rows = edge_rows()
+    parts, jobs, at = [], [], 0
+    for sr, si, order, rot, gray, scale, _, _ in rows:
+        n, job = value_job(at, order, rot, gray, scale)
+        parts.append(np.array([[sr, si], [0.0, 0.0]][:n], np.float32))
+        jobs.append(job)
+        at += n
+    rng = np.random.default_rng(5)
+    odd = np.array(EDGE_ODD, np.float32)
+    parts.append(np.stack([rng.choice(odd, 600), rng.choice(odd, 600)], 1))
+    jobs += edge_odd_jobs(at)
+    return np.concatenate(parts), place(jobs)
+
+
+# the correlation of rule S2 and the two ways a compiler may contract it
+S2, FMA_RE, FMA_IM = 0, 1, 2
+CONTRACT_DRAWS, CONTRACT_NEAR, CONTRACT_MAX_JOBS = 100000, 1e-9, 128
+_CONTRACT = {}
+
+
+def corr_variants(sr, si, c, s):
+    """(sr c) + (si s) over doubles in exact rational arithmetic, each IEEE operation rounded once (int / int rounds correctly)
+    -> [rule S2: three roundings, fma(sr, c, round(si s)), fma(si, s, round(sr c))]"""
+    from fractions import Fraction
+    a, b = Fraction(sr) * Fraction(c), Fraction(si) * Fraction(s)
+    ra, rb = Fraction(float(a)), Fraction(float(b))
+    return [float(ra + rb), float(a + rb), float(ra + b)]
+
+
+def contracted_values(y, M, rot, gray, scale, variant):
+    """soft_values() of one finite symbol y = (sr, si) with the correlations of corr_variants()[variant] -> v [b]"""
+    b = dm.bits_of(M)
+    C, S = points(M, rot)
+    corr = np.array([corr_variants(float(y[0]), float(y[1]), float(C[q]), float(S[q]))[variant] for q in range(M)])
+    lab = labels(M, gray)
+    v = []
+    for i in range(b):
+        bit = (lab >> (b - 1 - i)) & 1
+        x = ((corr[bit == 0].max() - corr[bit == 1].max()) * np.float64(np.float32(scale))) + 0.5
+        v.append(int(np.clip(np.floor(x), -MAX_VALUE, MAX_VALUE)))
+    return v
+
+
+def _scale_between(lo, hi, seed):
+    """a float32 scale with a half-integer n - 0.5, 1 <= n <= 126, between lo scale and hi scale, 0 < lo < hi: floor(x) of rule S2
+    steps there, for either sign of L.  Four n are tried, from a start that `seed` picks, and four neighbouring scales each"""
+    for n in [1 + (seed + 37 * t) % 126 for t in range(4)]:
+        scale = np.float32((n - 0.5) / hi)
+        for _ in range(4):
+            if np.floor(lo * np.float64(scale) + 0.5) != np.floor(hi * np.float64(scale) + 0.5):
+                return scale
+            scale = np.nextafter(scale, np.float32(np.inf))
+    return None
+
+
+def contract_search():
+    """-> (iq float32 [n][2], [(rot, gray, scale)]): 8-PSK symbols on which the quantised values of rule S2 differ from those of a
+    correlation contracted either way.  Seeded, CONTRACT_DRAWS draws, at most CONTRACT_MAX_JOBS kept; once a session.
+
+    Such a symbol lies within about 1e-9 (relative) of the boundary between two neighbouring points, one on an axis, whose
+    correlation is exact, and one on a diagonal, whose correlation is rounded three times by rule S2 and twice by a fused
+    multiply-add.  L is then the exact difference of the two, a few million ulps of them, and where both contractions move the
+    diagonal's correlation by an ulp to the same side, a float32 scale puts a half-integer of L scale between rule S2's L and
+    theirs.  Draw u, set w = float32(u tan(3 pi / 8)); (u, w) lies at 3/16 of a turn, and swapping and negating the parts gives the
+    other seven boundaries, which take turns with the labelings and rot = 0 and 5."""
+    if "search" in _CONTRACT:
+        return _CONTRACT["search"]
+    rng = np.random.default_rng(2727)
+    u = rng.uniform(0.25, 4.0, CONTRACT_DRAWS).astype(np.float32)
+    w = (u.astype(np.float64) * np.tan(3 * np.pi / 8)).astype(np.float32)
+    i = np.arange(CONTRACT_DRAWS)
+    swap, neg_re, neg_im = (i & 1).astype(bool), (i & 2).astype(bool), (i & 4).astype(bool)
+    re, im = np.where(swap, w, u), np.where(swap, u, w)
+    y = np.stack([np.where(neg_re, -re, re), np.where(neg_im, -im, im)], 1).astype(np.float32)
+    gray, rot = (i >> 3) & 1, np.where((i >> 4) & 1, 5, 0)
+    found_y, found = [], []
+    for r in (0, 5):
+        C, S = points(8, r)
+        sel = np.flatnonzero(rot == r)
+        sr, si = y[sel, 0].astype(np.float64), y[sel, 1].astype(np.float64)
+        corr = (sr[:, None] * C[None, :]) + (si[:, None] * S[None, :])
+        top = np.argsort(corr, 1)[:, -2:]						# the second largest, the largest
+        c2, c1 = corr[np.arange(len(sel)), top[:, 0]], corr[np.arange(len(sel)), top[:, 1]]
+        near = np.flatnonzero((c1 - c2 > 0) & (c1 - c2 < CONTRACT_NEAR * c1))
+        for m in near:
+            d = [a - b for a, b in zip(corr_variants(sr[m], si[m], C[top[m, 1]], S[top[m, 1]]),
+                                       corr_variants(sr[m], si[m], C[top[m, 0]], S[top[m, 0]]))]
+            if min(d) <= 0 or d[FMA_RE] == d[S2] or d[FMA_IM] == d[S2] or (d[FMA_RE] > d[S2]) != (d[FMA_IM] > d[S2]):
+                continue								# both contractions have to move L, to the same side
+            lo, hi = sorted((d[S2], min(d[1:]) if d[FMA_RE] > d[S2] else max(d[1:])))
+            k = int(sel[m])
+            scale = _scale_between(lo, hi, k)
+            if scale is None:
+                continue
+            v = [contracted_values(y[k], 8, r, gray[k], scale, variant) for variant in (S2, FMA_RE, FMA_IM)]
+            if v[FMA_RE] != v[S2] and v[FMA_IM] != v[S2]:
+                found_y.append(y[k])
+                found.append((k, r, int(gray[k]), float(scale)))
+    order = np.argsort([f[0] for f in found])[:CONTRACT_MAX_JOBS]			# in the order drawn
+    _CONTRACT["search"] = (np.array([found_y[o] for o in order], np.float32).reshape(-1, 2), [found[o][1:] for o in order])
+    return _CONTRACT["search"]
+
+
+def contract_case():
+    """one 8-PSK symbol a job, each a job on which rule S2's record differs from the record with the correlation contracted either
+    way, fma(sr, C_q, round(si S_q)) or fma(si, S_q, round(sr C_q)) (contract_search(), contract_records()): what a build without
+    -ffp-contract=off, a pragma or a compiler that fuses the correlation gives away.  The contraction of the last operation,
+    (L scale) + 0.5, is not covered: with these L the product is exact, and an input that separates it needs a product within
+    2^-54 below -0.5"""
+    y, found = contract_search()
+    jobs = [value_job(i, 8, rot, gray, scale)[1] for i, (rot, gray, scale) in enumerate(found)]
+    return y, place(jobs)
+
+
+def contract_records():
+    """the records of contract_case() under [rule S2, either contraction]; once a session"""
+    if "records" not in _CONTRACT:
+        _CONTRACT["records"] = [decode(contract_case(), variant)[0] for variant in (S2, FMA_RE, FMA_IM)]
+    return _CONTRACT["records"]
+
+
+# ---- a call at MAX_CALL_STEPS -----------------------------------------------------------------------------------------------------
+
+LIMIT_JOBS = MAX_CALL_STEPS // MAX_STEPS
+_LIMIT = []
+
+
+def call_limit_case():
+    """64 jobs of MAX_STEPS, exactly MAX_CALL_STEPS, in shuffled order with place()'s guards; two shapes, so that the model decodes
+    the jobs of a shape together: K = 7 at rate 1/2, QPSK, Gray, CRC-16, TERMINATED at scale 32, and K = 7 at rate 1/3, 8-PSK,
+    CRC-32 at scale 1e6, which saturates nearly every value: abs_sum and metric are the largest a job can produce.  Noisy frames at
+    the level of max_steps_case().  Not in cases(): the model takes its time for it.  Once a session"""
+    if _LIMIT:
+        return _LIMIT[0]
+    rng = np.random.default_rng(2828)
+    parts, jobs, at = [], [], 0
+    for i in rng.permutation(LIMIT_JOBS):
+        if i & 1:
+            iq, T, _ = noisy_frame(rng, MAX_STEPS - 32, dm.K7_THIRD, dm.P3_NONE, 8, dm.CRC32, False, int(i) % 8, (i >> 1) & 1, 0.45)
+            job = make_job(at, 0, len(iq), 8, dm.K7_THIRD, dm.P3_NONE, dm.CRC32, 0, GRAY if (i >> 1) & 1 else 0, int(i) % 8, 1e6)
+        else:
+            iq, T, _ = noisy_frame(rng, MAX_STEPS - 6 - 16, dm.K7, dm.P_NONE, 4, dm.CRC16, True, int(i) % 4, True, 0.45)
+            job = make_job(at, 0, len(iq), 4, dm.K7, dm.P_NONE, dm.CRC16, 0, TERMINATED | GRAY, int(i) % 4, 32.0)
+        assert T == MAX_STEPS
+        parts.append(iq)
+        jobs.append(job)
+        at += len(iq)
+    _LIMIT.append((np.concatenate(parts), place(jobs)))
+    return _LIMIT[0]
+
+
+def one_step_more(case):
+    """the case with one more job of one step behind its table: a step past MAX_CALL_STEPS"""
+    iq, jobs = case
+    return iq, place([jobs.copy(), value_job(0, 4)[1]])
+
+
 def cases():
     """name -> (iq, jobs): every set the CPU and GPU tests share"""
-    return {"seams": seams_case(), "nan": nan_case(), "max_steps": max_steps_case(), "full_table": full_table_case()}
+    return {"seams": seams_case(), "nan": nan_case(), "max_steps": max_steps_case(), "full_table": full_table_case(),
+            "edges": edges_case(), "contract": contract_case()}

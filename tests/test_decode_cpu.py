@@ -1,7 +1,7 @@
 """Host side of include/fosphor_amd_decode.h, no GPU: fosphor_amd_decode_host against the numpy statement (tests/decode_model.py),
 records and the whole output buffer bit for bit, on every input set the GPU tests use; maximum likelihood by brute force over all
 codewords of short frames; the error correction the free distance guarantees; the ties of rules 3 and 4; the CRC check values; the
-refusals; decode_jobs, decode_steps and decode_derive; that a job's bytes depend on the job alone; the chain decide -> decode on
+refusals; a call of exactly MAX_CALL_STEPS and one step more; decode_jobs, decode_steps and decode_derive; that a job's bytes depend on the job alone; the chain decide -> decode on
 the host; and the compiled kernels' resources."""
 import ctypes as C
 import errno
@@ -146,6 +146,29 @@ def test_host_against_model(lib, F, name):
     for j, r, v in zip(jobs, records, views):
         at = int(j["out_offset"])
         assert len(v) == (r["n_bits"] + 7) // 8 and v.tobytes() == want[at:at + len(v)].tobytes()
+
+
+def test_call_limit(lib):
+    """64 jobs of MAX_STEPS, exactly MAX_CALL_STEPS: the host statement against the model, bit for bit; the same table with one
+    more job of one step is refused with every byte and record at the sentinel"""
+    case = dm.call_limit_case()
+    jobs = case[1]
+    steps = [dm.shape(j)[0] for j in jobs]
+    assert len(jobs) == dm.LIMIT_JOBS == 64 and set(steps) == {dm.MAX_STEPS} and sum(steps) == dm.MAX_CALL_STEPS
+    assert len({(int(j["k"]), int(j["period"]), int(j["flags"])) for j in jobs}) == 2
+    rv, rec, got = host(lib, case)
+    assert rv == 0
+    want_rec, want = dm.image(case, SENTINEL, key="call_limit")
+    got_rec = records_of(rec, len(jobs))
+    for i in [i for i in range(len(want_rec)) if got_rec[i].tobytes() != want_rec[i].tobytes()][:6]:
+        print("job %d %s got %s want %s" % (i, jobs[i], got_rec[i], want_rec[i]))
+    assert got_rec.tobytes() == want_rec.tobytes(), "records bit-identical"
+    assert got.tobytes() == want.tobytes(), "bytes bit-identical, every other byte at the sentinel"
+    assert (got_rec["metric"] > 0).all() and (got_rec["n_steps"] == dm.MAX_STEPS).all() and {dm.OK, dm.CRC_FAIL} == set(got_rec["status"])
+    more = dm.one_step_more(case)
+    assert sum(dm.shape(j)[0] for j in more[1]) == dm.MAX_CALL_STEPS + 1 and more[1][:64].tobytes() == jobs.tobytes()
+    rv, rec, out = host(lib, more)
+    assert rv == EINVAL and np.all(out == SENTINEL) and np.all(rec == SENTINEL32), "nothing is written"
 
 
 def test_a_job_alone_among_others_and_shuffled(F):

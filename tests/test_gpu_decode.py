@@ -15,7 +15,8 @@ Seams of the kernels (the input sets are dm.cases()):
   codes         every code and pattern at every order: with M = 8 a symbol's three bits straddle the steps.
   frames        encoded frames with channel errors, every CRC width held and failing, SHORT.
   max_steps     one job of MAX_STEPS.
-  full_table    MAX_JOBS shuffled jobs with n <= 40, every 11th with n = 0."""
+  full_table    MAX_JOBS shuffled jobs with n <= 40, every 11th with n = 0.
+test_call_limit runs dm.call_limit_case(), 64 jobs of MAX_STEPS, between two small calls on an instance of its own."""
 import errno
 import os
 
@@ -253,6 +254,62 @@ def test_einval_table(box):
     d = torch.from_numpy(np.concatenate([np.zeros(7, np.uint8), sym])).cuda()
     rec2, out2 = box.run((sym, changed(good[:1], offset=1)), tag="odd pointer", cap=CAP, sym_at=(d.data_ptr() + 7, N_SYM))
     assert rec1.tobytes() == rec2.tobytes() and out1.tobytes() == out2.tobytes()
+
+
+_HOST = {}
+
+
+def host_image(amd, case, key):
+    """(records, the whole output buffer as fosphor_amd_decode_host leaves it, SENTINEL wherever no job owns a byte), once a session"""
+    if key not in _HOST:
+        jobs = case[1]
+        records, views = amd.Fosphor.decode_host(case[0], jobs)
+        out = np.full(dm.capacity(jobs), SENTINEL, np.uint8)
+        for j, r, v in zip(jobs, records, views):
+            at = int(j["out_offset"])
+            out[at:at + dm.owned(r["n_bits"])] = 0
+            out[at:at + len(v)] = v
+        _HOST[key] = (records, out)
+    return _HOST[key]
+
+
+def test_call_limit(amd):
+    """a call of exactly MAX_CALL_STEPS (dm.call_limit_case(): 64 jobs of MAX_STEPS, 32 MiB of survivor decisions, 4 MiB of codes,
+    step0 up to 2^22 - 2^16) on a fresh instance, between two small calls: the scratch grows behind a small call and is reused by
+    one.  All three are bit-identical to fosphor_amd_decode_host, the whole output and records buffers compared, at most one
+    launch a kernel; the job with the largest step0 gives the same record and bytes alone; one step more is refused, writes
+    nothing, launches nothing and counts nothing"""
+    import torch
+    free, total = torch.cuda.mem_get_info()
+    if free < 2 ** 30:
+        pytest.skip("the call wants 1 GiB of device memory free: %d of %d bytes are" % (free, total))
+    small, limit = CASES["frames"], dm.call_limit_case()
+    jobs = limit[1]
+    assert sum(dm.shape(j)[0] for j in jobs) == dm.MAX_CALL_STEPS and len(jobs) == 64
+    b = Box(amd)
+    try:
+        for tag, case, key in (("small", small, "frames"), ("limit", limit, "call_limit"), ("small again", small, "frames")):
+            want_rec, want = host_image(amd, case, key)
+            rv, raw, got, delta = b.call(case)
+            assert rv == 0, tag
+            assert np.all(raw[W * len(case[1]):] == SENTINEL32), "a record beyond the jobs' was written"
+            got_rec = raw[:W * len(case[1])].view(dm.RECORD_DTYPE)
+            assert delta == dm.expected_stats(case[1]) and all(delta[k] == 1 for k in KERNELS), (tag, delta)
+            explain(got_rec, want_rec, got, want, case[1])
+            assert got_rec.tobytes() == want_rec.tobytes(), tag + ": records bit-identical to fosphor_amd_decode_host"
+            assert got.tobytes() == want.tobytes(), tag + ": bytes bit-identical to fosphor_amd_decode_host, every other byte at the sentinel"
+            if tag == "limit":
+                limit_rec, limit_out = got_rec, got
+        last = len(jobs) - 1							# the table's last job: step0 = 63 MAX_STEPS
+        alone_rec, alone = b.run((limit[0], jobs[last:]), tag="alone")
+        assert alone_rec[0].tobytes() == limit_rec[last].tobytes()
+        assert bytes_of(alone, jobs[last]).tobytes() == bytes_of(limit_out, jobs[last]).tobytes()
+        more = dm.one_step_more(limit)
+        rv, rec, out, delta = b.call(more)
+        assert rv == EINVAL and np.all(out == SENTINEL) and np.all(rec == SENTINEL32), "nothing is written"
+        assert not any(delta.values()), (delta, "nothing is launched or counted")
+    finally:
+        b.f.close()
 
 
 FAR_BYTES = 2 ** 31 + 2 ** 20

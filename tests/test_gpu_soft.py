@@ -13,7 +13,11 @@ Seams of the kernels (the input sets are sm.cases()):
                 work-group of k_sft_bits; jobs with T = 0 and with n = 0 among them.
   nan           NaN, infinite and zero parts among live symbols; a job of NaN symbols alone.
   max_steps     one job of MAX_STEPS.
-  full_table    MAX_JOBS shuffled jobs with n <= 40, every 11th with n = 0."""
+  full_table    MAX_JOBS shuffled jobs with n <= 40, every 11th with n = 0.
+  edges         a job a crafted value on a rounding or clamp boundary of rule S2, float32 subnormals, NaN correlations, 4- and 8-PSK
+                symbols on decision boundaries: the floating-point path of k_sft_bits.
+  contract      8-PSK symbols on which a contracted correlation gives another record than rule S2.
+test_call_limit runs sm.call_limit_case(), 64 jobs of MAX_STEPS, between two small calls on an instance of its own."""
 import errno
 import os
 
@@ -188,6 +192,17 @@ def test_against_host(amd, box, name):
         assert (got_rec["n_steps"][0], got_rec["status"][0], got_rec["end_state"][0]) == (sm.MAX_STEPS, sm.OK, 0) and got_rec["metric"][0] > 0
     if name == "full_table":
         assert len(jobs) == sm.MAX_JOBS
+    if name == "edges":
+        rows = sm.edge_rows()
+        assert (got_rec["saturated"] > 0).any() and (got_rec["erasures"] > 0).any() and (got_rec["abs_sum"] == 0).any()
+        for (sr, si, order, rot, gray, scale, want, erasures), r in zip(rows, got_rec):
+            if want is not None:
+                assert (r["abs_sum"], r["saturated"], r["erasures"]) == (abs(want), int(abs(want) == 127), erasures), (sr, si, scale, r)
+    if name == "contract":
+        plain, fma_re, fma_im = sm.contract_records()
+        assert len(jobs) >= 64 and len(plain) == len(jobs), "the jobs that tell a contracted correlation are in the call"
+        for i in range(len(jobs)):
+            assert got_rec[i].tobytes() == plain[i].tobytes() and got_rec[i].tobytes() not in (fma_re[i].tobytes(), fma_im[i].tobytes()), (i, jobs[i])
 
 
 def test_which_kernels_ran(amd, box):
@@ -261,7 +276,49 @@ def test_refusals_launch_and_count_nothing(box):
         refused(changed(good[:1], **row))
     for name, by in (("records", 4), ("out", 4), ("iq", 4)):
         refused(good, skew=(name, by))
-    box.run((iq, changed(good[:1], rot=3, scale=1e-45, flags=3)), tag="nearest", cap=CAP)
+    nearest = (iq, changed(good[:1], rot=3, scale=1e-45, flags=3))
+    got_rec, got = box.run(nearest, tag="nearest", cap=CAP)
+    want_rec, views = type(box.f).soft_host(*nearest)
+    assert got_rec.tobytes() == want_rec.tobytes(), "records bit-identical to fosphor_amd_soft_host"
+    want = np.full(CAP + sm.GUARD, SENTINEL, np.uint8)
+    want[:sm.job_owned(nearest[1][0])] = 0
+    want[:len(views[0])] = views[0]
+    assert got.tobytes() == want.tobytes(), "bytes bit-identical to fosphor_amd_soft_host, every other byte at the sentinel"
+
+
+def test_call_limit(amd):
+    """a call of exactly MAX_CALL_STEPS (sm.call_limit_case(): 64 jobs of MAX_STEPS, 32 MiB of survivor decisions, 16 MiB of soft
+    words, 16384 partials, step0 up to 2^22 - 2^16) on a fresh instance, between two small calls: the scratch grows behind a small
+    call and is reused by one.  All three are bit-identical to fosphor_amd_soft_host, the whole output and records buffers
+    compared, with one launch a kernel; the job with the largest step0 gives the same record and bytes alone; one step more is
+    refused, writes nothing, launches nothing and counts nothing"""
+    import torch
+    free, total = torch.cuda.mem_get_info()
+    if free < 2 ** 30:
+        pytest.skip("the call wants 1 GiB of device memory free: %d of %d bytes are" % (free, total))
+    small, limit = CASES["nan"], sm.call_limit_case()
+    jobs = limit[1]
+    assert sum(sm.shape(j)[0] for j in jobs) == sm.MAX_CALL_STEPS and len(jobs) == 64
+    b = Box(amd)
+    try:
+        for tag, case, key in (("small", small, "nan"), ("limit", limit, "call_limit"), ("small again", small, "nan")):
+            want_rec, want = host_image(amd, case, key=key)
+            got_rec, got = b.run(case, tag=tag)
+            explain(got_rec, want_rec, got, want, case[1])
+            assert got_rec.tobytes() == want_rec.tobytes(), tag + ": records bit-identical to fosphor_amd_soft_host"
+            assert got.tobytes() == want.tobytes(), tag + ": bytes bit-identical to fosphor_amd_soft_host, every other byte at the sentinel"
+            if tag == "limit":
+                limit_rec, limit_out = got_rec, got
+        last = len(jobs) - 1							# the table's last job: step0 = 63 MAX_STEPS
+        alone_rec, alone = b.run((limit[0], jobs[last:]), tag="alone")
+        assert alone_rec[0].tobytes() == limit_rec[last].tobytes()
+        assert bytes_of(alone, jobs[last]).tobytes() == bytes_of(limit_out, jobs[last]).tobytes()
+        more = sm.one_step_more(limit)
+        rv, rec, out, delta = b.call(more)
+        assert rv == EINVAL and np.all(out == SENTINEL) and np.all(rec == SENTINEL32), "nothing is written"
+        assert not any(delta.values()), (delta, "nothing is launched or counted")
+    finally:
+        b.f.close()
 
 
 FAR_BYTES = 2 ** 31 + 2 ** 20

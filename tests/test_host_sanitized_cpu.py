@@ -13,7 +13,10 @@ the scalar arguments and, for every pointer, exactly as many bytes as the header
 test_host_against_model), the refusal tables (test_einval_table of every pass, tests/test_job_refusals_cpu.py) with the last jobs that fit, which those tables end with, the planners over
 tests/test_count_plan_cpu.py and tests/tile_walk_cases.py, and the views of tests/test_view_cpu.py.  extremes() adds the size
 rules, constructors, designs and derive functions at the ends of their ranges, with the argument tuples of
-tests/job_scale_cases.py (n = 2^31 - 1, 65536-entry tables); no host statement runs at that n.
+tests/job_scale_cases.py (n = 2^31 - 1, 65536-entry tables); no host statement runs at that n.  For decode and soft, whose host
+statements read kept(T) coded bits from ceil(n_coded / b) symbols and write 8 ceil(n_bits / 64) owned bytes, the harvest takes the
+modules' named cases, refusal tables, numerical edges and from_decide / derive tests, and extremes() adds fosphor_amd_decode_steps
+around MAX_STEPS and at n = 2^31 - 1 and both from_decide constructors over a decide job at offsets of 2^62.
 
 The rule for buffers.  The driver puts every buffer of a call into a heap allocation of its own of exactly the recorded size: the
 IQ, the job table, taps, templates, windows, the unique word, the thresholds, the records and each output.  The sanitizer's red
@@ -29,7 +32,8 @@ Not reproduced: calls in which a test skews a pointer off its 8-byte boundary to
 and ctypes all begin on one, and so does an allocation of its own): they are not recorded.  A call that claims more than
 MAX_BYTES for a buffer must be a refusal and gets an empty buffer in its place, which the refusal must not read.
 
-Dropped for time (whole named interior cases; every last-fit, refusal and extreme-argument case is kept): none.
+Dropped for time (whole named interior cases; every last-fit, refusal and extreme-argument case is kept): none.  The calls of
+MAX_CALL_STEPS of decode and soft (test_call_limit of both modules, 2^22 steps each) are in: their children end within seconds.
 
 fosphor_amd_measure_host pins, in its source, which of two NaN operands an operation hands on, so that both builds give the same
 bytes on measure_model's case "nonfinite".
@@ -67,7 +71,7 @@ BUILD_TIMEOUT = 900			# seconds, per compiler or linker
 
 sz = C.sizeof
 REC = {k: getattr(gr_fosphor_amd.Fosphor, k.upper() + "_RECORD_DTYPE").itemsize
-       for k in ("measure", "correlate", "psd", "symbols", "carrier", "decide")}
+       for k in ("measure", "correlate", "psd", "symbols", "carrier", "decide", "decode", "soft")}
 IQ_BYTES = {0: 8, 1: 4, 2: 4}		# fp32, fp16, sc16 pairs
 
 
@@ -94,6 +98,10 @@ CONTRACT = {
                                  4: (lambda a: a[3] * REC["carrier"], 1), 5: (lambda a: a[6] * 8, 1)},
     "fosphor_amd_decide_host": {0: (lambda a: a[1] * 8, 0), 2: (lambda a: a[3] * sz(L_.DecideJob), 0), 4: (lambda a: a[5], 0),
                                 6: (lambda a: a[3] * REC["decide"], 1), 7: (lambda a: a[8], 1)},
+    "fosphor_amd_decode_host": {0: (lambda a: a[1], 0), 2: (lambda a: a[3] * sz(L_.DecodeJob), 0),
+                                4: (lambda a: a[3] * REC["decode"], 1), 5: (lambda a: a[6], 1)},
+    "fosphor_amd_soft_host": {0: (lambda a: a[1] * 8, 0), 2: (lambda a: a[3] * sz(L_.SoftJob), 0),
+                              4: (lambda a: a[3] * REC["soft"], 1), 5: (lambda a: a[6], 1)},
     "fosphor_amd_bursts_host": {0: (lambda a: max(a[1], 0) * max(a[2], 0) * 4, 0), 3: (lambda a: a[2] * 4, 0),
                                 4: (lambda a: sz(L_.BurstCfg), 0), 5: (lambda a: sz(L_.BurstResult), 1),
                                 6: (lambda a: a[7] * sz(L_.Burst), 1)},
@@ -102,6 +110,7 @@ CONTRACT = {
     "fosphor_amd_detect_bands_host": {0: (lambda a: a[1] * 4, 0), 5: (lambda a: a[6] * sz(L_.Band), 1), 7: (lambda a: 4, 1)},
     "fosphor_amd_demod_n_out": {}, "fosphor_amd_correlate_n_out": {}, "fosphor_amd_resample_n_out": {},
     "fosphor_amd_psd_n_seg": {}, "fosphor_amd_symbols_max_out": {},
+    "fosphor_amd_decode_steps": {4: (lambda a: 3 * 2, 0)},				# "const uint16_t punct[3]"
     "fosphor_amd_extract_from_burst": {0: (lambda a: sz(L_.Burst), 0), 6: (lambda a: sz(L_.ExtractJob), 1), 7: (lambda a: 4, 1)},
     "fosphor_amd_measure_from_extract": {0: (lambda a: sz(L_.ExtractJob), 0), 2: (lambda a: sz(L_.MeasureJob), 1)},
     "fosphor_amd_demod_from_extract": {0: (lambda a: sz(L_.ExtractJob), 0), 3: (lambda a: sz(L_.DemodJob), 1)},
@@ -114,6 +123,10 @@ CONTRACT = {
                                          7: (lambda a: sz(L_.CarrierJob), 1)},
     "fosphor_amd_decide_from_carrier": {0: (lambda a: sz(L_.CarrierJob), 0), 1: (lambda a: REC["carrier"], 0),
                                         8: (lambda a: sz(L_.DecideJob), 1)},
+    "fosphor_amd_decode_from_decide": {0: (lambda a: sz(L_.DecideJob), 0), 1: (lambda a: REC["decide"], 0),
+                                       4: (lambda a: sz(L_.DecodeJob), 1)},
+    "fosphor_amd_soft_from_decide": {0: (lambda a: sz(L_.DecideJob), 0), 1: (lambda a: REC["decide"], 0),
+                                     4: (lambda a: sz(L_.SoftJob), 1)},
     "fosphor_amd_view_from_render": {2: (lambda a: sz(L_.Render), 0), 5: (lambda a: sz(L_.View), 1)},
     "fosphor_amd_extract_design": {3: (lambda a: a[1] * 4, 1)},
     "fosphor_amd_resample_design": {4: (lambda a: max(a[0], 0) * max(a[2], 0) * 4, 1)},
@@ -127,6 +140,8 @@ CONTRACT = {
     "fosphor_amd_symbols_derive": {0: (lambda a: REC["symbols"], 0), 3: (lambda a: sz(L_.SymbolsValues), 1)},
     "fosphor_amd_carrier_derive": {0: (lambda a: REC["carrier"], 0), 2: (lambda a: sz(L_.CarrierValues), 1)},
     "fosphor_amd_decide_derive": {0: (lambda a: REC["decide"], 0), 2: (lambda a: sz(L_.DecideValues), 1)},
+    "fosphor_amd_decode_derive": {0: (lambda a: REC["decode"], 0), 1: (lambda a: sz(L_.DecodeValues), 1)},
+    "fosphor_amd_soft_derive": {0: (lambda a: REC["soft"], 0), 1: (lambda a: sz(L_.SoftValues), 1)},
     "fosphor_amd_view_span": {3: (lambda a: 4, 1), 4: (lambda a: 4, 1)},
     "fosphor_amd_mask_from_points": {1: (lambda a: a[3] * 8, 0), 2: (lambda a: a[3] * 4, 0), 4: (lambda a: a[0] * 4, 1)},
     "fosphor_amd_detect_bin_y": {3: (lambda a: a[0] * 4, 1)},
@@ -399,6 +414,9 @@ HARVEST = {
                        "test_einval_table"],
     "test_correlate_cpu": None, "test_resample_cpu": None, "test_psd_cpu": None, "test_symbols_cpu": None,
     "test_carrier_cpu": None, "test_decide_cpu": None,
+    "test_decode_cpu": ["test_host_against_model", "test_einval_table", "test_steps_from_decide_and_derive", "test_call_limit"],
+    "test_soft_cpu": ["test_host_against_model", "test_einval_table", "test_numerical_edges", "test_from_decide_and_derive",
+                      "test_call_limit"],
     "test_burst_cpu": ["test_host_function_against_model", "test_model_by_hand", "test_host_overflows", "test_host_einval_table"],
     "test_mask_cpu": ["test_row_rule_fixed_cases", "test_row_rule_random_rows", "test_row_host_argument_errors",
                       "test_from_points_bit_for_bit", "test_from_points_random_bit_for_bit", "test_from_points_argument_errors"],
@@ -513,6 +531,7 @@ def harvest(rec):
 def extremes(L, F):
     """the size rules, constructors, designs and derive functions at the ends of their ranges; -> what the models' integer
     arithmetic says of the size rules, as (call index offset, expected) is checked right here against the plain library"""
+    import decode_model as dcm
     import demod_model as dm
     import correlate_model as cm
     import job_scale_cases as jc
@@ -559,6 +578,28 @@ def extremes(L, F):
     L.fosphor_amd_resample_from_extract(C.byref(e), rm.MAX_UP, 1, rm.MAX_UP * rm.MAX_BRANCH, C.byref(r))
     L.fosphor_amd_resample_from_extract(C.byref(e), 1, rm.MAX_DOWN, rm.MAX_BRANCH, C.byref(r))
     L.fosphor_amd_symbols_from_resample(C.byref(r), 2, sm.FIXED, 0.4, C.byref(L_.SymbolsJob()))
+    # decode and soft: rule 2's T at n = 2^31 - 1 and around MAX_STEPS, against the model's integers; the jobs over a decide job
+    # of 2^31 - 1 symbols at offsets of 2^62, the word at its start and at its very end
+    for order in dcm.ORDERS:
+        for period, punct in (dcm.P_NONE, dcm.P_34, dcm.P_78, dcm.P_16, dcm.P3_NONE, dcm.P3_16, (16, (1, 0, 0)), (16, (0xffff, 0xffff, 0xffff))):
+            masks = np.array(punct, np.uint16)
+            n_poly = 3 if punct[2] else 2
+            for count in (0, 1, n - 1, n):
+                assert L.fosphor_amd_decode_steps(count, order, n_poly, period, masks.ctypes.data) == fits(dcm.steps_that_fit(count, order, period, punct))
+            for T in (dcm.MAX_STEPS, dcm.MAX_STEPS + 1):
+                count = dcm.symbols_for(T, order, (period, punct))
+                got = L.fosphor_amd_decode_steps(count, order, n_poly, period, masks.ctypes.data)
+                assert got == dcm.steps_that_fit(count, order, period, punct) >= T
+    from decide_model import GRAY, JOB_DTYPE as DECIDE_JOB, NO_UW, OK as DECIDE_OK, RECORD_DTYPE as DECIDE_RECORD, UW
+    for flags in (0, UW, UW | GRAY):
+        for order in (2, 4, 8):
+            for uw_pos, uw_len, n_payload in ((0, 0, 0), (0, n, 0), (n - 32, 32, 0), (0, 32, n - 32), (n - 1, 1, 1), (n, 2 ** 31 - 1, 2 ** 31 - 1)):
+                for status in (DECIDE_OK, NO_UW):
+                    d, r = np.zeros(1, DECIDE_JOB), np.zeros(1, DECIDE_RECORD)
+                    d["offset"], d["out_offset"], d["n"], d["flags"] = 2 ** 62, 2 ** 62, n, flags
+                    r["n"], r["order"], r["status"], r["uw_pos"], r["uw_rot"], r["a"] = n, order, status, uw_pos, order - 1, 1e-30 * n
+                    L.fosphor_amd_decode_from_decide(d.ctypes.data, r.ctypes.data, uw_len, n_payload, C.byref(L_.DecodeJob()))
+                    L.fosphor_amd_soft_from_decide(d.ctypes.data, r.ctypes.data, uw_len, n_payload, C.byref(L_.SoftJob()))
     # a burst at the far end of a stream: newest_first_sample near 2^62, the largest row_hop an int holds, a ring of 65536 rows
     for hop in (1, 2 ** 31 - 1):
         for newest, oldest in ((0, 0), (0, 65535), (65535, 65535)):
@@ -613,7 +654,8 @@ def extremes(L, F):
     big = {"i": 2 ** 31 - 1, "u": 2 ** 32 - 1, "f": np.finfo(np.float32).max}
     for key, fn, extra in (("measure", L.fosphor_amd_measure_derive, (1e6,)), ("correlate", L.fosphor_amd_correlate_derive, (1e6,)),
                            ("psd", L.fosphor_amd_psd_derive, (1e6,)), ("symbols", L.fosphor_amd_symbols_derive, None),
-                           ("carrier", L.fosphor_amd_carrier_derive, (1e6,)), ("decide", L.fosphor_amd_decide_derive, None)):
+                           ("carrier", L.fosphor_amd_carrier_derive, (1e6,)), ("decide", L.fosphor_amd_decide_derive, None),
+                           ("decode", L.fosphor_amd_decode_derive, ()), ("soft", L.fosphor_amd_soft_derive, ())):
         dtype = getattr(F, key.upper() + "_RECORD_DTYPE")
         values = getattr(L_, key.capitalize() + "Values")
         zero, full, mixed = np.zeros(1, dtype), np.zeros(1, dtype), np.zeros(1, dtype)
@@ -668,7 +710,7 @@ def test_every_entry_point_has_cases(recorded):
     missing = [n for n in CONTRACT if n not in by]
     assert not missing, missing
     hosts = [n for n in CONTRACT if n.endswith("_host")]
-    assert len(hosts) == 12
+    assert len(hosts) == 14
     # every host statement with accepted calls and with refusals: a harvest that lost a module's refusal table, or a whole module
     # (pytest's fixture and parametrize attributes are read here as they are today), does not pass for complete
     for n in hosts:

@@ -2,8 +2,8 @@
 and the whole output buffer bit for bit, on every input set the GPU tests use and over every constraint length, stream count,
 order, labeling, rotation and puncture pattern; maximum likelihood by brute force over all inputs of short frames; a frame that the
 soft decoder reads and the hard chain decide -> decode cannot; saturated soft values against the hard decoder; the coding gain
-over noise; the numerical edges of rule S2; the refusals, each beside the nearest call that is accepted; soft_jobs and
-soft_derive; the chain carrier -> decide -> soft on the host; and the compiled kernels' resources."""
+over noise; the numerical edges of rule S2; a call of exactly MAX_CALL_STEPS and one step more; the refusals, each beside the
+nearest call that is accepted; soft_jobs and soft_derive; the chain carrier -> decide -> soft on the host; and the compiled kernels' resources."""
 import ctypes as C
 import errno
 import os
@@ -153,6 +153,33 @@ def test_the_cases_hold_what_they_promise():
     assert sm.shape(mj[0])[0] == sm.MAX_STEPS
     full = CASES["full_table"][1]
     assert len(full) == sm.MAX_JOBS and full["n"].max() <= 40 and (full["n"] == 0).sum() >= sm.MAX_JOBS // 11
+    # edges: a job a crafted value, then the 36 jobs over the odd symbols; the record carries the expected v out
+    rows, ej = sm.edge_rows(), CASES["edges"][1]
+    erec = sm.image(CASES["edges"], SENTINEL, key="edges")[0]
+    assert len(ej) == len(rows) + 36 and len(sm.EDGE_VALUES) == 23 and (ej["n"][len(rows):] == 600).all()
+    assert {(int(j["order"]), int(j["flags"]), int(j["rot"])) for j in ej[:len(rows)] if j["order"] > 2} == {
+        (M, g, r) for M in (4, 8) for g in (0, sm.GRAY) for r in (0, M - 1)}
+    for (sr, si, order, rot, gray, scale, want, erasures), r in zip(rows, erec):
+        assert (r["n_steps"], r["n_coded"], r["erasures"]) == (1, dm.bits_of(order) if order > 2 else 2, erasures), (sr, si, r)
+        if want is not None:
+            assert (r["abs_sum"], r["saturated"]) == (abs(want), int(abs(want) == 127)), (sr, scale, r)
+    for sr, scale, want in sm.EDGE_SUBNORMAL:
+        tiny = np.finfo(np.float32).tiny
+        assert want != 0 and (0 < np.float32(sr) < tiny or 0 < np.float32(scale) < tiny), "a float32 subnormal decides a value that is not 0"
+    assert (erec["saturated"] > 0).any() and (erec["erasures"] > 0).any() and (erec["saturated"][len(rows):] > 0).all()
+    # contract: every job tells rule S2 from a correlation contracted either way, from the model alone
+    cj = CASES["contract"][1]
+    plain, fma_re, fma_im = sm.contract_records()
+    assert 64 <= len(cj) <= sm.CONTRACT_MAX_JOBS and len(plain) == len(cj) and set(cj["order"]) == {8} and (cj["n"] == 1).all()
+    ciq = CASES["contract"][0]
+    for j in cj:
+        y, how = ciq[int(j["offset"]):int(j["offset"]) + 1], (8, j["rot"], int(j["flags"]) & sm.GRAY, j["scale"])
+        assert sm.contracted_values(y[0], *how, sm.S2) == list(sm.soft_values(y, *how)[0][0]), "the rational arithmetic gives numpy's values"
+    for i in range(len(cj)):
+        assert plain[i].tobytes() != fma_re[i].tobytes() and plain[i].tobytes() != fma_im[i].tobytes(), (i, cj[i])
+    sectors = {int(np.floor(np.arctan2(ciq[int(j["offset"]), 1], ciq[int(j["offset"]), 0]) / (np.pi / 4))) for j in cj}
+    print("contract: %d jobs, %d of the 8 boundaries, labelings %s, rotations %s" % (len(cj), len(sectors), sorted(set(cj["flags"])), sorted(set(cj["rot"]))))
+    assert len(sectors) > 1 and set(cj["flags"]) == {0, sm.GRAY} and len(set(cj["rot"])) > 1
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -399,10 +426,10 @@ def test_coding_gain_over_noise(F):
 # ---- the numerical edges of rule S2 -----------------------------------------------------------------------------------------------
 
 def one_value(F, sr, si, scale, order=2, rot=0, gray=0):
-    """v of bit 0 of one symbol, read back through a record: K = 3 (7, 5), one step, BPSK: the second symbol is (0, 0) and worth
-    nothing; abs_sum is |v| and the decoded bit is 1 exactly when v < 0 (input 1 sends 11).  -> (v, the record)"""
-    iq = np.array([[sr, si], [0.0, 0.0]], np.float32)
-    job = sm.make_job(0, 0, 2, order, dm.K3, dm.P_NONE, dm.CRC_NONE, 1, gray, rot, scale)
+    """v of bit 0 of one symbol, read back through a record (sm.value_job()): K = 3 (7, 5), one step, BPSK: the second symbol is
+    (0, 0) and worth nothing; abs_sum is |v| and the decoded bit is 1 exactly when v < 0 (input 1 sends 11).  -> (v, the record)"""
+    n, job = sm.value_job(0, order, rot, gray, scale)
+    iq = np.array([[sr, si], [0.0, 0.0]][:n], np.float32)
     rec, views = F.soft_host(iq, job)
     assert rec.tobytes() == sm.decode((iq, job))[0].tobytes(), (sr, si, scale)
     mag = int(rec["abs_sum"][0])
@@ -410,29 +437,48 @@ def one_value(F, sr, si, scale, order=2, rot=0, gray=0):
 
 
 def test_numerical_edges(F):
-    """BPSK at rot 0: the points are (1, +0) and (-1, -0), L = 2 sr exactly, x = 2 sr scale + 0.5"""
-    for sr, scale, want in ((0.25, 1.0, 1), (0.75, 1.0, 2), (-0.25, 1.0, 0), (-0.75, 1.0, -1), (1.25, 1.0, 3), (-1.25, 1.0, -2),	# x at an integer: L at a half
-                            (0.24999999, 1.0, 0), (0.75, 0.99999994, 1), (63.25, 1.0, 127), (63.0, 1.0, 126), (63.5, 1.0, 127), (1e30, 1.0, 127),
-                            (-63.5, 1.0, -127), (-63.25, 1.0, -126), (-63.75, 1.0, -127), (-64.0, 1.0, -127), (-1e30, 1e30, -127),
-                            (3e38, 3e38, 127), (np.inf, 1.0, 127), (-np.inf, 1.0, -127), (1e-30, 1e-30, 0), (0.0, 1e6, 0), (-0.0, 1e6, 0)):
+    """the rows of sm.edges_case(), each with the v it expects, against the host and the model.  BPSK at rot 0: the points are
+    (1, +0) and (-1, -0), L = 2 sr exactly, x = 2 sr scale + 0.5"""
+    assert len(sm.EDGE_VALUES) == 23
+    for sr, scale, want in sm.EDGE_VALUES + sm.EDGE_SUBNORMAL:
         v, r = one_value(F, sr, 0.0, scale)
         assert v == want, (sr, scale, v, want)
         assert (r["erasures"], r["saturated"], r["abs_sum"]) == (0, int(abs(want) == 127), abs(want)), (sr, scale, r)
+        assert sm.soft_values(np.array([[sr, 0.0]], np.float32), 2, 0, 0, scale)[0][0][0] == want, "the model alone"
+    # float32 subnormals survive the widening to double: flushed to zero, both rows would give 0
+    for sr, scale, want in sm.EDGE_SUBNORMAL:
+        assert want != 0
     # a NaN part: v = 0 and one erasure, whatever the other part is; an infinite imaginary part meets the zero of the points' sines:
     # both correlations are NaN, none is the largest, L = -inf - -inf is a NaN: v = 0, and no erasure
-    for sr, si in ((np.nan, 0.0), (1.0, np.nan), (np.nan, np.nan), (np.inf, np.nan), (np.nan, -np.inf)):
+    for sr, si in sm.EDGE_NAN:
         v, r = one_value(F, sr, si, 32.0)
         assert (v, r["erasures"], r["saturated"], r["abs_sum"]) == (0, 1, 0, 0), (sr, si)
-    for sr, si in ((1.0, np.inf), (-1.0, -np.inf), (np.inf, np.inf)):
+    for sr, si in sm.EDGE_INF:
         v, r = one_value(F, sr, si, 32.0)
         assert (v, r["erasures"], r["abs_sum"]) == (0, 0, 0), (sr, si)
+    # QPSK at rot 0, where the points lie on the axes and every product is exact: L_0 = sr + si for both labelings;
+    # L_1 = |sr| - |si| with the plain labels and max(sr, -si) - max(si, -sr) with Gray's.  (1, 1) lies on the boundary of bit 1: L = 0
+    for sr, si in sm.EDGE_PSK_SYMBOLS:
+        for scale in sm.EDGE_PSK_SCALES:
+            for gray in (0, 1):
+                L = (sr + si, max(sr, -si) - max(si, -sr) if gray else abs(sr) - abs(si))
+                want = [int(np.clip(np.floor(l * scale + 0.5), -127, 127)) for l in L]
+                y = np.array([[sr, si]], np.float32)
+                assert list(sm.soft_values(y, 4, 0, gray, scale)[0][0]) == want, (sr, si, scale, gray)
+                v, r = one_value(F, sr, si, scale, 4, 0, gray)
+                assert (r["abs_sum"], r["erasures"]) == (sum(abs(w) for w in want), 0), (sr, si, scale, gray, r)
+    assert list(sm.soft_values(np.array([[1.0, 1.0]], np.float32), 4, 0, 0, 63.5)[0][0]) == [127, 0]
+    # 8-PSK and rot = M - 1: against the model alone (one_value() holds the host to it)
+    for sr, si, order, rot, gray, scale, want, erasures in sm.edge_rows():
+        if order > 2:
+            one_value(F, sr, si, scale, order, rot, gray)
     # QPSK, Gray, rot 1: the point of value 0 lies at a quarter turn; (inf, 1) has one NaN correlation (inf times the zero of that
     # point's cosine) and the others decide: bit 0 separates left from right... asserted against the model alone
     rng = np.random.default_rng(5)
-    odd = np.array([np.inf, -np.inf, 0.0, -0.0, 1.0, -1.0, 3e38, 1e-45, np.nan], np.float32)
+    odd = np.array(sm.EDGE_ODD, np.float32)
     iq = np.stack([rng.choice(odd, 600), rng.choice(odd, 600)], 1)
-    jobs = sm.place([sm.make_job(0, 0, 600, order, dm.K5, dm.P_NONE, dm.CRC8, 0, gray * sm.GRAY, rot, scale)
-                     for order in sm.ORDERS for gray in (0, 1) for rot in (0, order - 1) for scale in (1e-3, 1.0, 3e38)])
+    jobs = sm.place(sm.edge_odd_jobs(0))
+    assert len(jobs) == 36 and iq.tobytes() == CASES["edges"][0][-600:].tobytes(), "the symbols of the edges case"
     rec, views = F.soft_host(iq, jobs)
     mrec, mouts = sm.decode((iq, jobs))
     assert rec.tobytes() == mrec.tobytes() and all(v.tobytes() == m[:len(v)].tobytes() for v, m in zip(views, mouts))
@@ -440,6 +486,31 @@ def test_numerical_edges(F):
     for j, r in zip(jobs, rec):
         used = (r["n_coded"] + dm.bits_of(j["order"]) - 1) // dm.bits_of(j["order"])
         assert r["erasures"] == nan[:used].sum() > 0 and r["saturated"] > 0
+
+
+def test_call_limit(lib):
+    """64 jobs of MAX_STEPS, exactly MAX_CALL_STEPS: the host statement against the model, bit for bit; the same table with one
+    more job of one step is refused with every byte and record at the sentinel"""
+    case = sm.call_limit_case()
+    jobs = case[1]
+    steps = [sm.shape(j)[0] for j in jobs]
+    assert len(jobs) == sm.LIMIT_JOBS == 64 and set(steps) == {sm.MAX_STEPS} and sum(steps) == sm.MAX_CALL_STEPS
+    assert len({(int(j["k"]), int(j["n_poly"]), int(j["flags"]) & sm.TERMINATED) for j in jobs}) == 2 and list(jobs["out_offset"]) == sorted(jobs["out_offset"])
+    rv, rec, got = host(lib, case)
+    assert rv == 0
+    want_rec, want = sm.image(case, SENTINEL, key="call_limit")
+    got_rec = records_of(rec, len(jobs))
+    for i in [i for i in range(len(want_rec)) if got_rec[i].tobytes() != want_rec[i].tobytes()][:6]:
+        print("job %d %s got %s want %s" % (i, jobs[i], got_rec[i], want_rec[i]))
+    assert got_rec.tobytes() == want_rec.tobytes(), "records bit-identical"
+    assert got.tobytes() == want.tobytes(), "bytes bit-identical, every other byte at the sentinel"
+    third = got_rec[jobs["n_poly"] == 3]
+    assert (third["saturated"] > 0.99 * third["n_coded"]).all() and (third["abs_sum"] > 0.99 * 127 * 3 * sm.MAX_STEPS).all()
+    assert (got_rec["metric"] > 0).all() and (got_rec["n_steps"] == sm.MAX_STEPS).all()
+    more = sm.one_step_more(case)
+    assert sum(sm.shape(j)[0] for j in more[1]) == sm.MAX_CALL_STEPS + 1 and more[1][:64].tobytes() == jobs.tobytes()
+    rv, rec, out = host(lib, more)
+    assert rv == EINVAL and np.all(out == SENTINEL) and np.all(rec == SENTINEL32), "nothing is written"
 
 
 # ---- the refusals -----------------------------------------------------------------------------------------------------------------
