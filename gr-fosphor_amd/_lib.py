@@ -300,6 +300,26 @@ class SoftValues(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("mean_abs", "corrected_share", "rate", "crc_ok")]
 
 
+class RsJob(C.Structure):
+    """struct fosphor_amd_rs_job (include/fosphor_amd_rs.h)"""
+    _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("flags", C.c_int32), ("gf_poly", C.c_uint16), ("fcr", C.c_uint8),
+                ("prim", C.c_uint8), ("n_roots", C.c_uint8), ("n_code", C.c_uint8), ("depth", C.c_uint8), ("scr_width", C.c_uint8),
+                ("scr_taps", C.c_uint32), ("scr_init", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class RsRecord(C.Structure):
+    """struct fosphor_amd_rs_record"""
+    _fields_ = [("n_codewords", C.c_int32), ("n_data", C.c_int32), ("status", C.c_int32), ("n_failed", C.c_int32),
+                ("n_clean", C.c_int32), ("corrected_symbols", C.c_int32), ("corrected_bits", C.c_int32), ("max_errors", C.c_int32),
+                ("failed_mask", C.c_uint32), ("errors", C.c_uint8 * 16), ("n_code", C.c_uint16), ("n_roots", C.c_uint16),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class RsValues(C.Structure):
+    """struct fosphor_amd_rs_values"""
+    _fields_ = [(k, C.c_double) for k in ("byte_error_rate", "failed_share", "ok")]
+
+
 class ResampleJob(C.Structure):
     """struct fosphor_amd_resample_job (include/fosphor_amd_resample.h)"""
     _fields_ = [("offset", C.c_int64), ("out_offset", C.c_int64), ("phase0", C.c_int64), ("n", C.c_int32), ("n_out", C.c_int32),
@@ -512,6 +532,13 @@ SIGNATURES = {
     "fosphor_amd_soft_from_decide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(SoftJob)]),
     "fosphor_amd_soft_derive": (C.c_int, [C.c_void_p, C.POINTER(SoftValues)]),
     "fosphor_amd_soft_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 7)]),
+    # include/fosphor_amd_rs.h
+    "fosphor_amd_rs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
+    "fosphor_amd_rs_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
+    "fosphor_amd_rs_encode_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    "fosphor_amd_rs_from_decode": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int, C.c_int, C.POINTER(RsJob)]),
+    "fosphor_amd_rs_derive": (C.c_int, [C.c_void_p, C.POINTER(RsValues)]),
+    "fosphor_amd_rs_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong * 8)]),
     # include/fosphor_amd_wire.h
     "fosphor_amd_wire_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "fosphor_amd_wire_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Wire)]),

@@ -1890,6 +1890,156 @@ class Fosphor:
         """fosphor_amd_soft_stats as a dict: calls, launches by kernel, jobs with a CRC, steps (SOFT_STATS)"""
         return self._stats(self.L.fosphor_amd_soft_stats, self.SOFT_STATS)
 
+    RS_STATS = ("calls", "k_syn", "k_fix", "k_out", "k_rec", "codewords", "clean", "failed")
+    RS_MAX_JOBS = 4096					# FOSPHOR_AMD_RS_MAX_JOBS (include/fosphor_amd_rs.h)
+    RS_MAX_ROOTS, RS_MAX_DEPTH = 32, 16			# FOSPHOR_AMD_RS_MAX_ROOTS, FOSPHOR_AMD_RS_MAX_DEPTH
+    RS_MAX_CALL_CODEWORDS = 65536			# FOSPHOR_AMD_RS_MAX_CALL_CODEWORDS
+    RS_FLAGS = {"descramble_in": 1, "descramble_out": 2}	# FOSPHOR_AMD_RS_DESCRAMBLE_IN, _DESCRAMBLE_OUT
+    RS_STATUS = {"ok": 0, "fail": 1}			# FOSPHOR_AMD_RS_OK, _FAIL
+    RS_FAILED = 255					# FOSPHOR_AMD_RS_FAILED
+    RS_LDS = {"syn": 0, "fix": 0, "out": 0, "rec": 0}	# FOSPHOR_AMD_RS_LDS_*
+    RS_JOB_DTYPE = np.dtype([("offset", "<i8"), ("out_offset", "<i8"), ("flags", "<i4"), ("gf_poly", "<u2"), ("fcr", "u1"),
+                             ("prim", "u1"), ("n_roots", "u1"), ("n_code", "u1"), ("depth", "u1"), ("scr_width", "u1"),
+                             ("scr_taps", "<u4"), ("scr_init", "<u4"), ("reserved", "<u4", (7,))])
+    RS_RECORD_DTYPE = np.dtype([("n_codewords", "<i4"), ("n_data", "<i4"), ("status", "<i4"), ("n_failed", "<i4"),
+                                ("n_clean", "<i4"), ("corrected_symbols", "<i4"), ("corrected_bits", "<i4"), ("max_errors", "<i4"),
+                                ("failed_mask", "<u4"), ("errors", "u1", (16,)), ("n_code", "<u2"), ("n_roots", "<u2"),
+                                ("reserved", "<u4", (2,))])
+    RS_VALUES = tuple(k for k, _ in _lib.RsValues._fields_)
+    RS_CCSDS = dict(gf_poly=0x187, fcr=112, prim=11, n_roots=32)		# RS(255,223), conventional basis
+    RS_DVB = dict(gf_poly=0x11d, fcr=0, prim=1, n_roots=16)			# RS(204,188)
+
+    @staticmethod
+    def _rs_flags(flags):
+        if isinstance(flags, str):
+            if flags not in Fosphor.RS_FLAGS:
+                raise ValueError("flags must be of %s" % ", ".join(Fosphor.RS_FLAGS))
+            return Fosphor.RS_FLAGS[flags]
+        return int(flags)
+
+    @staticmethod
+    def rs_owned(n_data):
+        """the bytes a job of n_data data bytes owns in d_out: 8 ceil(n_data / 8)"""
+        return 8 * ((int(n_data) + 7) // 8)
+
+    @staticmethod
+    def _rs_n_data(j):
+        return int(j["depth"]) * max(int(j["n_code"]) - int(j["n_roots"]), 0)
+
+    @staticmethod
+    def rs_jobs(out_offsets, n_bits, n_code, depth=1, skip_bytes=0, gf_poly=0x11d, fcr=0, prim=1, n_roots=16, flags=0, scr_width=0,
+                scr_taps=0, scr_init=0, gap=8):
+        """an RS_JOB_DTYPE array over what decode() or soft() wrote (fosphor_amd_rs_from_decode): out_offsets the decode or soft
+        jobs' out_offset, n_bits their records' n_bits; each frame of depth * n_code bytes begins skip_bytes behind its job's first
+        output byte and must be covered by n_bits.  The code (RS_CCSDS and RS_DVB hold two) and the scrambler are the same for
+        every job, the owned bytes placed from out_offset 0 on at multiples of 8 with `gap` bytes (rounded up to a multiple of 8)
+        between them"""
+        L = _lib.load()
+        offs = np.atleast_1d(np.asarray(out_offsets, dtype=np.int64))
+        bits = np.atleast_1d(np.asarray(n_bits, dtype=np.int64))
+        if offs.size != bits.size:
+            raise ValueError("one n_bits per out_offset")
+        if gap < 0:
+            raise ValueError("gap must be >= 0")
+        flags = Fosphor._rs_flags(flags)
+        out = np.zeros(offs.size, Fosphor.RS_JOB_DTYPE)
+        at = 0
+        for i, (o, b) in enumerate(zip(offs, bits)):
+            job = _lib.RsJob()
+            rv = L.fosphor_amd_rs_from_decode(int(o), int(min(b, 2 ** 31 - 1)), int(skip_bytes), int(n_code), int(depth), C.byref(job))
+            if rv:
+                _fail("fosphor_amd_rs_from_decode", rv, ValueError)
+            j = out[i]
+            j["offset"], j["out_offset"], j["flags"], j["n_code"], j["depth"] = job.offset, at, flags, job.n_code, job.depth
+            j["gf_poly"], j["fcr"], j["prim"], j["n_roots"] = gf_poly, fcr, prim, n_roots
+            j["scr_width"], j["scr_taps"], j["scr_init"] = scr_width, scr_taps, scr_init
+            at += Fosphor.rs_owned(Fosphor._rs_n_data(j)) + 8 * ((int(gap) + 7) // 8)
+        return out
+
+    @staticmethod
+    def _rs_cap(jobs):
+        return max([int(j["out_offset"]) + Fosphor.rs_owned(Fosphor._rs_n_data(j)) for j in jobs] + [0])
+
+    def rs(self, d_in, jobs, n_bytes=None):
+        """One record and the corrected data bytes per job, up to 4096 frames in one call (fosphor_amd_rs): the decoded bits of
+        decode() or soft() taken as interleaved Reed-Solomon frames over GF(2^8), descrambled, every codeword corrected up to
+        n_roots / 2 byte errors, the parity dropped, over bytes that are already in device memory.  d_in: a contiguous uint8
+        device tensor (what decode() or soft() wrote) or a raw device pointer with n_bytes; jobs: an RS_JOB_DTYPE array (rs_jobs()
+        makes one; out_offset is honoured, the owned bytes must not overlap).
+        Returns (records, views): an RS_RECORD_DTYPE array copied from the device, in job order, and a list with one torch uint8
+        view of n_data bytes per job into one device buffer."""
+        import torch
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=self.RS_JOB_DTYPE)
+        if n_bytes is None:
+            if not hasattr(d_in, "numel"):
+                raise ValueError("a raw device pointer needs n_bytes")
+            if str(d_in.dtype) != "torch.uint8" or not d_in.is_contiguous():
+                raise ValueError("d_in must be a contiguous uint8 tensor")
+            n_bytes = d_in.numel()
+        cap = self._rs_cap(jobs)
+        # torch.empty: a fill would run on torch's stream, unordered against the pass on the instance's
+        d_out = torch.empty(max(cap, 8) // 8, dtype=torch.int64, device="cuda").view(torch.uint8)
+        d_rec = torch.empty(max(jobs.size, 1) * self.RS_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()			# the caller's bytes were written on torch's stream
+        rv = self.L.fosphor_amd_rs(self.h, _ptr(d_in), int(n_bytes), jobs.ctypes.data, int(jobs.size), d_rec.data_ptr(),
+                                   d_out.data_ptr(), cap)
+        if rv:
+            _fail("fosphor_amd_rs", rv, RuntimeError)
+        records = d_rec.cpu().numpy().view(self.RS_RECORD_DTYPE)[:jobs.size].copy()
+        return records, [d_out[int(j["out_offset"]):int(j["out_offset"]) + int(r["n_data"])] for j, r in zip(jobs, records)]
+
+    @staticmethod
+    def rs_host(data, jobs):
+        """fosphor_amd_rs_host: the same records and bytes on the host, no GPU.  data: uint8.  Returns (records, views), the views
+        uint8 arrays of n_data bytes into one buffer"""
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.RS_JOB_DTYPE)
+        cap = Fosphor._rs_cap(jobs)
+        out = np.zeros(max(cap, 8) // 8, np.uint64).view(np.uint8)
+        records = np.zeros(max(jobs.size, 1), Fosphor.RS_RECORD_DTYPE)
+        keep = data if data.size else np.zeros(8, np.uint8)
+        rv = _lib.load().fosphor_amd_rs_host(keep.ctypes.data, int(data.size), jobs.ctypes.data, int(jobs.size),
+                                             records.ctypes.data, out.ctypes.data, cap)
+        if rv:
+            _fail("fosphor_amd_rs_host", rv, ValueError)
+        records = records[:jobs.size]
+        return records, [out[int(j["out_offset"]):int(j["out_offset"]) + int(r["n_data"])] for j, r in zip(jobs, records)]
+
+    @staticmethod
+    def rs_encode(data, jobs, n_bytes=None):
+        """fosphor_amd_rs_encode_host: the way back.  Job j takes its n_data bytes from data[out_offset ..), in the order rs()
+        writes them, and its frame of depth * n_code bytes, parity added and scrambled as flagged, goes to frames[offset ..).
+        Returns the frames buffer, uint8 [n_bytes] (the end of the last frame by default), zero where no frame lies"""
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        jobs = np.ascontiguousarray(np.atleast_1d(jobs), dtype=Fosphor.RS_JOB_DTYPE)
+        if n_bytes is None:
+            n_bytes = max([int(j["offset"]) + int(j["depth"]) * int(j["n_code"]) for j in jobs] + [0])
+        frames = np.zeros(max(int(n_bytes), 1), np.uint8)
+        keep = data if data.size else np.zeros(8, np.uint8)
+        rv = _lib.load().fosphor_amd_rs_encode_host(keep.ctypes.data, int(data.size), jobs.ctypes.data, int(jobs.size),
+                                                    frames.ctypes.data, int(n_bytes))
+        if rv:
+            _fail("fosphor_amd_rs_encode_host", rv, ValueError)
+        return frames[:max(int(n_bytes), 0)]
+
+    @staticmethod
+    def rs_derive(records):
+        """fosphor_amd_rs_derive per record: a list of dicts of RS_VALUES (ratios)"""
+        L = _lib.load()
+        records = np.ascontiguousarray(np.atleast_1d(records), dtype=Fosphor.RS_RECORD_DTYPE)
+        out = []
+        for r in records:
+            v = _lib.RsValues()
+            rv = L.fosphor_amd_rs_derive(r.tobytes(), C.byref(v))
+            if rv:
+                _fail("fosphor_amd_rs_derive", rv, ValueError)
+            out.append({k: getattr(v, k) for k in Fosphor.RS_VALUES})
+        return out
+
+    def rs_stats(self):
+        """fosphor_amd_rs_stats as a dict: calls, launches by kernel, codewords, clean and failed ones (RS_STATS)"""
+        return self._stats(self.L.fosphor_amd_rs_stats, self.RS_STATS)
+
     @property
     def histo_scale(self):
         return self.buffers(False).histo_scale

@@ -1,7 +1,7 @@
 /*
  * fosphor_jobs.h -- the job-table substrate of the passes over burst IQ (fosphor_extract.hip, fosphor_resample.hip,
  * fosphor_measure.hip, fosphor_demod.hip, fosphor_correlate.hip, fosphor_psd.hip, fosphor_symbols.hip, fosphor_carrier.hip,
- * fosphor_decide.hip, fosphor_decode.hip, fosphor_soft.hip); DESIGN.md, "the job-table substrate"
+ * fosphor_decide.hip, fosphor_decode.hip, fosphor_soft.hip, fosphor_rs.hip); DESIGN.md, "the job-table substrate"
  *
  * A pass checks the caller's jobs on the host, sorts them into at most two forms, and uploads per form its device jobs and a prefix
  * of their work-group counts; a work-group finds its job by a bounded binary search of that prefix and its place in the job from

@@ -32,6 +32,7 @@ enum {
 	FOSPHOR_SCRATCH_DECIDE,
 	FOSPHOR_SCRATCH_DECODE,
 	FOSPHOR_SCRATCH_SOFT,
+	FOSPHOR_SCRATCH_RS,
 	FOSPHOR_SCRATCH_COUNT
 };
 
@@ -52,6 +53,7 @@ enum {
 	FOSPHOR_COUNTERS_DECIDE,
 	FOSPHOR_COUNTERS_DECODE,
 	FOSPHOR_COUNTERS_SOFT,
+	FOSPHOR_COUNTERS_RS,
 	FOSPHOR_COUNTERS_COUNT
 };
 #define FOSPHOR_COUNTERS_MAX 10		/* counters of one pass at most (FOSPHOR_AMD_BURST_STATS) */

@@ -10,7 +10,8 @@
  * call.  K = 7 has 64 states and a wave has 64 lanes: add-compare-select is one lane per state.
  *
  * Not this pass: soft decisions (fosphor_amd_soft.h has them), tail-biting, truncated or block-parallel traceback, several
- * short-K jobs in one wave, interleavers and scramblers, reflected CRCs.
+ * short-K jobs in one wave, interleavers and scramblers (the block interleaver, the additive scrambler and the Reed-Solomon code
+ * that usually stand behind this decoder are fosphor_amd_rs.h), reflected CRCs.
  *
  * Conventions, those of fosphor_amd_decide.h: the device entry point waits for pending fosphor_process work first
  * (fosphor_amd_finish), runs on the instance's stream and returns when its outputs are complete; it writes no state of the

@@ -15,7 +15,8 @@
  * 4 (end), 5 (traceback), 6 (output) and 7 (CRC).  "Rule n" below is that header's rule n; the new rules are S1 to S3.
  *
  * Not this pass: differential decisions (a difference of two symbols has no soft value here: FOSPHOR_AMD_DECIDE_DIFF jobs stay
- * with fosphor_amd_decode), tail-biting, writing the soft values out, constellations other than 2-, 4- and 8-PSK, interleavers,
+ * with fosphor_amd_decode), tail-biting, writing the soft values out, constellations other than 2-, 4- and 8-PSK, interleavers
+ * (fosphor_amd_rs.h reads this pass's output and has the block interleaver, the scrambler and the Reed-Solomon code behind it),
  * reflected CRCs.
  */
 #ifndef FOSPHOR_AMD_SOFT_H
